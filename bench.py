@@ -7,12 +7,19 @@ What is timed is the PRODUCT loop: `sampling.sample()` -> `KSAMPLER.sample` -> `
 -> `CFGGuider` -> `sampling_function` -> the cached hipGraph denoiser (the call stack `KSampler2.sample` runs), in whole
 sampler passes until exactly K steps have been taken.
 
-One invocation reports
-  * headline `value`: BASELINE configs[2] — SD1.5 512x512, Euler-a / normal-30, batch 8 per GPU (UNet batch 16);
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, K timed steps, the
+outputs of the last timed step if `--dump-outputs DIR` is given, and the result line:
+  * headline `value`: BASELINE configs[2] — SD1.5 512x512, Euler-a / normal-30, batch 8 per GPU (UNet batch 16); `ms_per_step`.
+`--full` adds everything else, after the headline's timed steps:
+  * 5 one-pass repetitions (median ms/step) and the per-kernel `roofline` of each workload (HIP events around every launch, on the
+    launch stream);
   * `batch1`: BASELINE configs[1] — DPM++ 2M (dpmpp_2m_sde eta=0) / karras-20, batch 1;
-  * (N = 1 only) `hires`: configs[4] — the 128x128-latent Euler-a step at batch 4 and the 1024^2 VAE decode;
+  * (N = 1 only) `hires`: configs[4] — the 128x128-latent Euler-a step at batch 4 and the 1024^2 VAE decode; `hook_route`;
     `images_per_s_e2e`: 20-step txt2img at batch 8 including the VAE decode; `cpu_baseline`: the oracle on the host cores.
-each with its own `roofline` for the dominant kernel instantiation (HIP events around every launch, on the launch stream).
+
+`--dump-outputs DIR` writes DIR/samples.npy (float32): the latents `sampling.sample` returned for the last timed step of the headline
+workload (rank 0).  Weights, conditioning, latents and sampler noise are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 Multi-GPU: one rank per GPU (torchrun, or `--gpus N` alone, which starts N rank processes itself), a weight replica and an
 independent B-image loop per rank (weak scaling); the only collective is the RCCL broadcast of the conditioning.
@@ -29,7 +36,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-MFMA_PEAK_F16 = 2.5e15      # dense fp16/bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+MFMA_PEAK_F16 = 2.5e15      # dense fp16/bf16 MFMA peak of the MI355X
 HBM_PEAK = 8.0e12
 
 
@@ -139,11 +146,17 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="images per GPU of the headline run (UNet batch is 2x this under CFG)")
     ap.add_argument("--cfg", type=float, default=7.0)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip batch-1 / hires / e2e / cpu baseline (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repetitions, per-kernel rooflines, batch 1 / hires / hook route / "
+                         "VAE / e2e / cpu baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's last-step outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip batch-1 / hires / e2e / cpu baseline (profiling runs)")
     ap.add_argument("--only", default=None, choices=[None, "batch8", "batch1", "hires"], help="time just one workload (profiling runs)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--no-prime", action="store_true", help="skip the set-up pass (graph capture + one schedule pass) before the warm-up steps")
-    ap.add_argument("--reps", type=int, default=5, help="extra one-pass brackets after the timed region (median ms/step); 0 for profiling runs")
+    ap.add_argument("--reps", type=int, default=5, help="with --full: extra one-pass brackets after the timed region (median ms/step); "
+                                                         "0 for profiling runs")
     ap.add_argument("--sync-steps", action="store_true",
                     help="synchronize after every sampler step: bounds the host's run-ahead (rocprofv3 --pmc passes: profiles/README.md round 3)")
     args = ap.parse_args()
@@ -239,6 +252,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    outputs = {}        # workload tag -> {name: tensor} returned by the last timed step
+
     def run_workload(tag, B, L, sampler, scheduler, sched_steps, denoise, K, Wm, cfg_scale):
         """Time exactly K steps of the product sampler loop (whole passes over the schedule, then a partial one)."""
         ks = sampling.KSampler1(model, steps=sched_steps, device=dev, sampler=sampler, scheduler=scheduler, denoise=denoise,
@@ -251,13 +266,14 @@ def main():
         noise = torch.randn(B, 4, L, L, generator=gen)
 
         cb = (lambda d: torch.cuda.synchronize()) if args.sync_steps else None
+        last = {}
 
         def passes(nsteps):
             done = 0
             while done < nsteps:
                 n = min(run_len, nsteps - done)
-                sampling.sample(model, noise, pos, neg, cfg_scale, dev, sampling.ksampler(sampler, opts), sig[: n + 1], model.model_options,
-                                latent_image=latent, callback=cb, seed=rank)
+                last["samples"] = sampling.sample(model, noise, pos, neg, cfg_scale, dev, sampling.ksampler(sampler, opts), sig[: n + 1],
+                                                  model.model_options, latent_image=latent, callback=cb, seed=rank)
                 done += n
                 dump_maps(f"{tag}: {done} steps")
 
@@ -268,6 +284,9 @@ def main():
                 passes(run_len)
             torch.cuda.synchronize()
         passes(Wm)
+        # Euler-a draws its noise from the host's global generator (default_noise_sampler): seeded here, so that the timed steps draw
+        # the same numbers in every run with the same arguments
+        torch.manual_seed(4242 + rank)
         barrier()
         t0 = time.perf_counter()
         passes(K)
@@ -278,6 +297,15 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dist.barrier()
             elapsed = float(t.item())
+        outputs[tag] = {k: v.detach().clone() for k, v in last.items()}      # what the last timed step returned, before anything else runs
+        res = {
+            "workload": f"SD1.5 512x512 UNet CFG step, {sampler} / {scheduler}-{sched_steps}, batch {B}/GPU (UNet batch {2 * B}), latent {L}x{L}",
+            "steps_per_s": world * K / elapsed, "ms_per_step": 1e3 * elapsed / K, "steps": K,
+            "unet_evals_per_s": world * K * 2 * B / elapsed,
+        }
+        log(f"{tag}: {K} steps in {elapsed:.3f}s -> {res['steps_per_s']:.2f} steps/s ({res['unet_evals_per_s']:.0f} UNet-evals/s)")
+        if not args.full:
+            return res
         # repetitions (after the contract's bracket): 5 more brackets of one schedule pass each -> median ms/step
         reps = []
         for _ in range(args.reps):
@@ -301,20 +329,16 @@ def main():
         rows = unet.profile_launches()                              # per launch of the last profiled forward: shapes, FLOPs, kernel
         roof, roof_hbm = rooflines(rows, {k: v[0] for k, v in agg.items()}, traffic_lookup(tag))
         step_flops = unet.last_flops
-        res = {
-            "workload": f"SD1.5 512x512 UNet CFG step, {sampler} / {scheduler}-{sched_steps}, batch {B}/GPU (UNet batch {2 * B}), latent {L}x{L}",
-            "steps_per_s": world * K / elapsed, "ms_per_step": 1e3 * elapsed / K, "steps": K,
+        res.update({
             "ms_per_step_median_of_5_passes": statistics.median(reps) if reps else None, "ms_per_step_passes": [round(r, 4) for r in reps],
-            "unet_evals_per_s": world * K * 2 * B / elapsed,
             "step_tflops": step_flops / 1e12,
             "mfma_frac_whole_step": step_flops * K / elapsed / MFMA_PEAK_F16,
             "launches_per_forward": unet.last_launches,
             "kernel_class_ms_per_forward": {k: round(v[0], 4) for k, v in cls.items()},
             "kernels_ms_per_forward": {k: [round(v[0], 4), v[2]] for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])[:8]},
             "roofline": roof, "roofline_hbm": roof_hbm,
-        }
-        log(f"{tag}: {K} steps in {elapsed:.3f}s -> {res['steps_per_s']:.2f} steps/s ({res['unet_evals_per_s']:.0f} UNet-evals/s); "
-            f"dominant {roof['kernel']} {roof['achieved']:.0f} {roof['unit']} ({roof['bound']} roof, {100 * roof['frac']:.1f} %)")
+        })
+        log(f"{tag}: dominant {roof['kernel']} {roof['achieved']:.0f} {roof['unit']} ({roof['bound']} roof, {100 * roof['frac']:.1f} %)")
         return res
 
     def run_hook_route(B, L, K, Wm, cfg_scale, product_ms):
@@ -361,17 +385,25 @@ def main():
     K, Wm = args.steps, args.warmup
     out_extra = {}
     head = None
+    extras = args.full and args.only is None and not args.no_extras
     if args.only in (None, "batch8"):
         head = run_workload("batch8", args.batch, 64, "euler_ancestral", "normal", 30, None, K, Wm, args.cfg)
-    if (args.only is None and not args.no_extras) or args.only == "batch1":
+    if extras or args.only == "batch1":
         out_extra["batch1"] = run_workload("batch1", 1, 64, "dpmpp_2m_sde", "karras", 20, None, K, min(Wm, 20), args.cfg)
-    if ((args.only is None and not args.no_extras) and world == 1) or args.only == "hires":
+    if (extras and world == 1) or args.only == "hires":
         # config #5: hires-fix second pass — [4,4,128,128], 10 Euler-a steps from sigma 1.2768 (normal, denoise 0.45, cfg 8) + VAE -> 1024^2
         out_extra["hires"] = run_workload("hires", 4, 128, "euler_ancestral", "normal", 10, 0.45, 20, 10, 8.0)
     if head is None:
         head = out_extra.get("batch1") or out_extra.get("hires")
+    if args.dump_outputs and rank == 0:
+        # what the caller of the headline's timed path received from its last timed step
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in outputs[args.only or "batch8"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.to(torch.float32).cpu().numpy())
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
-    if args.only is None and not args.no_extras and world == 1:
+    if extras and world == 1:
         out_extra["hook_route"] = {"batch8": run_hook_route(args.batch, 64, K, Wm, args.cfg, head["ms_per_step"]),
                                    "batch1": run_hook_route(1, 64, K, min(Wm, 20), args.cfg, out_extra["batch1"]["ms_per_step"])}
         log(f"hook route: B={args.batch} {out_extra['hook_route']['batch8']['ms_per_step']:.3f} ms/step "
@@ -444,17 +476,20 @@ def main():
                                "of a step (same latents); step_tflops counts the FLOPs that are executed",
                    "timed_loop": "lightdiffusion_amd.sampling.sample (product call surface)"},
         "unet_evals_per_s": head["unet_evals_per_s"],
-        "step_tflops": head["step_tflops"], "mfma_frac_whole_step": head["mfma_frac_whole_step"],
-        "ms_per_step_median_of_5_passes": head["ms_per_step_median_of_5_passes"],
-        "launches_per_forward": head["launches_per_forward"],
         "cond_broadcast_ms": 1e3 * t_bcast, "weights_load_s": t_load,
-        "kernel_class_ms_per_forward": head["kernel_class_ms_per_forward"], "kernels_ms_per_forward": head["kernels_ms_per_forward"],
-        "roofline": head["roofline"], "roofline_hbm": head.get("roofline_hbm"),
     }
+    if args.full:
+        out.update({
+            "step_tflops": head["step_tflops"], "mfma_frac_whole_step": head["mfma_frac_whole_step"],
+            "ms_per_step_median_of_5_passes": head["ms_per_step_median_of_5_passes"],
+            "launches_per_forward": head["launches_per_forward"],
+            "kernel_class_ms_per_forward": head["kernel_class_ms_per_forward"], "kernels_ms_per_forward": head["kernels_ms_per_forward"],
+            "roofline": head["roofline"], "roofline_hbm": head.get("roofline_hbm"),
+        })
     out.update(out_extra)
 
     # ---- CPU baseline: the oracle (a port of the reference's CPU path) on this host's cores; rank 0, single-GPU runs only
-    if rank == 0 and world == 1 and args.only is None and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         from oracle import sd15_ref as O
         ncpu = host_cores()
         torch.set_num_threads(ncpu)

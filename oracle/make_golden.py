@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import json
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -296,16 +297,50 @@ REAL_PROMPTS = ["a photo of a cat", "masterpiece, (best quality:1.2), 1girl, ((d
 
 
 def g_tokens_real():
-    """SDTokenizer (LD.py:4936-5031) over HuggingFace's CLIPTokenizer with the vocabulary of `_internal/sd1_tokenizer/` (which stays in the
-    reference checkout: the fixture holds prompts and token ids only).  tests/test_host_cpu.py compares PromptTokenizer.from_pretrained on the
-    same directory when it is present."""
+    """SDTokenizer (LD.py:4936-5031) over HuggingFace's CLIPTokenizer with the vocabulary of `_internal/sd1_tokenizer/`: prompts and token
+    ids, plus `sd1_tokenizer/` = that vocabulary cut down to what these prompts use (tokenizer_subset).  tests/test_host_cpu.py compares
+    PromptTokenizer.from_pretrained on the cut-down directory."""
     os.environ.setdefault("HF_HUB_OFFLINE", "1")
     from transformers import CLIPTokenizer
-    tok = ref.SDTokenizer(tokenizer_path=os.path.join(os.path.dirname(REF_PATH), "_internal", "sd1_tokenizer"), tokenizer_class=CLIPTokenizer)
+    tdir = os.path.join(os.path.dirname(REF_PATH), "_internal", "sd1_tokenizer")
+    tok = ref.SDTokenizer(tokenizer_path=tdir, tokenizer_class=CLIPTokenizer)
     out = {p: tok.tokenize_with_weights(p) for p in REAL_PROMPTS}
     with open(os.path.join(OUT, "token_chunks_real.json"), "w") as f:
         json.dump(out, f)
     print("wrote token_chunks_real.json", {k[:20]: len(v) for k, v in out.items()})
+    tokenizer_subset(tdir, os.path.join(OUT, "sd1_tokenizer"), {t for chunks in out.values() for c in chunks for t, _ in c})
+
+
+def tokenizer_subset(src, dst, ids):
+    """A CLIP BPE vocabulary that tokenizes like `src` wherever the result uses only token `ids`: the 512 byte symbols, the special
+    tokens, every token in `ids` and the merges that build them (each merged token has exactly one merge), in their original order and
+    with their original ids.  Byte-pair encoding applies the lowest-ranked applicable merge; every merge it applies on the way to these
+    tokens is kept, so it picks the same one at each stage."""
+    vocab = json.load(open(os.path.join(src, "vocab.json"), encoding="utf-8"))
+    lines = open(os.path.join(src, "merges.txt"), encoding="utf-8").read().split("\n")
+    header, merges = lines[0], [m for m in lines[1:] if m]
+    made_by = {}
+    for i, m in enumerate(merges):
+        made_by.setdefault(m.replace(" ", ""), i)
+    inv = {v: k for k, v in vocab.items()}
+    keep_m, seen, stack = set(), set(), [inv[i] for i in ids]
+    while stack:
+        t = stack.pop()
+        if t in seen:
+            continue
+        seen.add(t)
+        if t in made_by:
+            keep_m.add(made_by[t])
+            stack.extend(merges[made_by[t]].split(" "))
+    keep = seen | {k for k, v in vocab.items() if v < 512 or k.startswith("<|")}
+    os.makedirs(dst, exist_ok=True)
+    with open(os.path.join(dst, "vocab.json"), "w", encoding="utf-8") as f:
+        json.dump({k: vocab[k] for k in sorted(keep, key=vocab.get)}, f, ensure_ascii=False)
+    with open(os.path.join(dst, "merges.txt"), "w", encoding="utf-8") as f:
+        f.write("\n".join([header] + [merges[i] for i in sorted(keep_m)]) + "\n")
+    for name in ("special_tokens_map.json", "tokenizer_config.json"):
+        shutil.copyfile(os.path.join(src, name), os.path.join(dst, name))
+    print("wrote sd1_tokenizer/", len(keep), "tokens,", len(keep_m), "merges")
 
 
 # ------------------------------------------------------------------ 7. bislerp

@@ -429,12 +429,11 @@ def test_bench_roofline_pricing():
 
 
 def test_real_clip_tokenizer_matches_reference():
-    """PromptTokenizer.from_pretrained on the reference checkout's CLIP vocabulary (HuggingFace CLIPTokenizer underneath, as the reference uses)
+    """PromptTokenizer.from_pretrained on the reference's CLIP vocabulary (HuggingFace CLIPTokenizer underneath, as the reference uses)
     against SDTokenizer.tokenize_with_weights on the same files: BOS / EOS ids read from the tokenizer, emphasis weights, escapes, a prompt that
-    spills into a second 77-token chunk.  The vocabulary does not travel with this repository: skipped where the checkout is absent."""
-    tdir = os.path.join(os.path.dirname(os.environ.get("LD_REFERENCE", "/root/reference/LightDiffusion.py")), "_internal", "sd1_tokenizer")
-    if not os.path.exists(os.path.join(tdir, "vocab.json")):
-        pytest.skip("reference tokenizer files not present")
+    spills into a second 77-token chunk.  tests/golden/sd1_tokenizer is that vocabulary cut down to the tokens and merges these prompts use,
+    with their original ids (oracle/make_golden.py tokens_real)."""
+    tdir = os.path.join(GOLDEN, "sd1_tokenizer")
     pytest.importorskip("transformers")
     os.environ.setdefault("HF_HUB_OFFLINE", "1")
     from lightdiffusion_amd.clip import PromptTokenizer

@@ -14,7 +14,7 @@ O=$R/gpurun_out
 cd $R
 if [ "$WHAT" != "pmc" ]; then
   for W in $LOADS; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_$W -- python3 bench.py --only $W --steps 60 --warmup 30 > $O/${TAG}_prof_$W.json 2> $O/${TAG}_prof_$W.err || { echo "kernel-trace $W failed"; tail -3 $O/${TAG}_prof_$W.err; exit 1; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_$W -- python3 bench.py --full --only $W --steps 60 --warmup 30 > $O/${TAG}_prof_$W.json 2> $O/${TAG}_prof_$W.err || { echo "kernel-trace $W failed"; tail -3 $O/${TAG}_prof_$W.err; exit 1; }
     python3 tools/prof_collect.py stats $O/${TAG}_prof_$W profiles/${TAG}_${W}_kernel_stats.csv && cp profiles/${TAG}_${W}_kernel_stats.csv $O/
     echo "kernel-trace $W done"
   done
@@ -32,13 +32,13 @@ if [ "$WHAT" != "kernel" ]; then
     [ "$W" = "batch8" ] && SETS+=("SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE")
     for C in "${SETS[@]}"; do
       n=$(echo $C | cut -d" " -f1)
-      timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $O/${TAG}_pmc_${W}_$n -- python3 bench.py --only $W --no-graph --no-prime --steps 2 --warmup 1 --reps 0 --sync-steps > $O/${TAG}_pmc_${W}_$n.log 2>&1 || { echo "pmc $W $n failed"; tail -3 $O/${TAG}_pmc_${W}_$n.log; exit 1; }
+      timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $O/${TAG}_pmc_${W}_$n -- python3 bench.py --full --only $W --no-graph --no-prime --steps 2 --warmup 1 --reps 0 --sync-steps > $O/${TAG}_pmc_${W}_$n.log 2>&1 || { echo "pmc $W $n failed"; tail -3 $O/${TAG}_pmc_${W}_$n.log; exit 1; }
       echo "pmc $W $n done"
     done
     if [ "$W" = "batch8" ]; then
       # co-execution / wait / LDS-instruction counters (round 4; a counter this rocprofiler build does not know only loses this pass)
       C="SQ_VALU_MFMA_COEXEC_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"
-      timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $O/${TAG}_pmc_${W}_SQ_VALU_MFMA_COEXEC_CYCLES -- python3 bench.py --only $W --no-graph --no-prime --steps 2 --warmup 1 --reps 0 --sync-steps > $O/${TAG}_pmc_${W}_coexec.log 2>&1 && echo "pmc $W coexec done" || { echo "pmc $W coexec pass failed (kept going)"; tail -3 $O/${TAG}_pmc_${W}_coexec.log; rm -rf $O/${TAG}_pmc_${W}_SQ_VALU_MFMA_COEXEC_CYCLES; }
+      timeout -k 10 300 rocprofv3 --pmc $C --output-format csv -d $O/${TAG}_pmc_${W}_SQ_VALU_MFMA_COEXEC_CYCLES -- python3 bench.py --full --only $W --no-graph --no-prime --steps 2 --warmup 1 --reps 0 --sync-steps > $O/${TAG}_pmc_${W}_coexec.log 2>&1 && echo "pmc $W coexec done" || { echo "pmc $W coexec pass failed (kept going)"; tail -3 $O/${TAG}_pmc_${W}_coexec.log; rm -rf $O/${TAG}_pmc_${W}_SQ_VALU_MFMA_COEXEC_CYCLES; }
     fi
     python3 tools/prof_collect.py pmc $W $O/${TAG}_${W}_pmc.csv $O/${TAG}_pmc_${W}_*/ && cp $O/${TAG}_${W}_pmc.csv profiles/
   done
