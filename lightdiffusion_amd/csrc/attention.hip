@@ -28,13 +28,6 @@
 #include <string>
 
 #include "kernels.h"
-// Ablation builds behind profiles/README.md ("no exp", "no tile sync", "1 of 4 PV MFMAs", "2 of 7 fragment reads"): -DLD_ATT_DBG=1..4.
-// They compute WRONG results on purpose (timing only) and exist in the A/B build (make ab, -DLD_AB_BUILD) only: the shipped library
-// ignores the macro.
-#if !defined(LD_AB_BUILD) || !defined(LD_ATT_DBG)
-#undef LD_ATT_DBG
-#define LD_ATT_DBG 0
-#endif
 
 namespace {
 
@@ -209,13 +202,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void flash_attn2_kernel(const AttnPar
         auto qk = [&](int sub, f32x16& s) {
 #pragma unroll
             for (int ks = 0; ks < DK; ++ks) {
-#if LD_ATT_DBG == 5
-                const half8 kf = qf[ks];
-#elif LD_ATT_DBG == 4
-                const half8 kf = as_half8(ld16(T + (KSUB == 2 ? koff[sub & (KSUB - 1)][0] : sub * 32 * d + koff[0][0])));
-#else
                 const half8 kf = as_half8(ld16(T + (KSUB == 2 ? koff[sub & (KSUB - 1)][ks] : sub * 32 * d + koff[0][ks])));
-#endif
                 if (ks == 0 && DK == 1) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[0], negm, 0, 0, 0);
                 else if (ks == 0) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(s) : "v"(kf), "v"(qf[0]), "v"(negm));
                 else s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s, 0, 0, 0);
@@ -296,11 +283,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void flash_attn2_kernel(const AttnPar
             for (int tt = 0; tt < DV; ++tt)
 #pragma unroll
                 for (int k2 = 0; k2 < 2; ++k2) {
-#if LD_ATT_DBG == 6
-                    const half8 vf = pf[k2];
-#elif LD_ATT_DBG == 4
-                    const half8 vf = as_half8(ld16(T + voff[2 * sub]));
-#else
                     half8 vf;
                     if (VROW) {
                         const half_t* vsrc = T + voffr[tt] + (32 * sub + 16 * k2) * (32 * DV);
@@ -310,7 +292,6 @@ __global__ __launch_bounds__(64 * NW, WPS) void flash_attn2_kernel(const AttnPar
                     } else {
                         vf = as_half8(ld16(T + tt * 32 * 64 + voff[2 * sub + k2]));
                     }
-#endif
                     o[tt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[k2], o[tt], 0, 0, 0);
                 }
         };

@@ -85,35 +85,11 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
     const int NTN = p.N / C8_BN, S = p.c8_S, TMS = p.M / 128;
-#ifdef LD_AB_BUILD
-    // phase clocks (tools/conv8_phases.py): waves 0 and 4 of every workgroup stamp s_memrealtime (100 MHz) at the phase boundaries
-    unsigned long long* const sbase = (p.dbg & 1) ? reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(p.partial) + p.partial_bytes - 65536) + blockIdx.x * 32 : nullptr;
-    unsigned long long* const stamps = sbase != nullptr ? sbase + (tid >= 256 ? 8 : 0) : nullptr;   // wave 0: [0..7], wave 4: [8..15]; [16..]: wait-time sums
-#define C8_STAMP(i) do { if (stamps != nullptr && (tid == 0 || tid == 256)) stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    unsigned long long acc_a = 0, acc_b = 0, tmark = 0;   // shader-clock sums of the time a wave spends in its barrier / in its vmcnt wait
-#define C8_T0() do { if (stamps != nullptr) tmark = __builtin_amdgcn_s_memtime(); } while (0)
-#define C8_TA() do { if (stamps != nullptr) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc_a += t_ - tmark; tmark = t_; } } while (0)
-#define C8_TB() do { if (stamps != nullptr) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); acc_b += t_ - tmark; tmark = t_; } } while (0)
-#else
-#define C8_STAMP(i) do { } while (0)
-#define C8_T0() do { } while (0)
-#define C8_TA() do { } while (0)
-#define C8_TB() do { } while (0)
-#endif
-    C8_STAMP(0);
     // block -> (weight slab q = (s, j), patch tm): logical id q * TMS + tm, and every XCD takes a contiguous run of logical ids (blocks b and
     // b + 8 share an XCD under round-robin placement): the patches of one slab sit on ONE XCD and stream its weights through that L2 together
     const int lid = xcd_remap(blockIdx.x, NTN * S * TMS);
     const int q = lid / TMS, tm = lid - q * TMS;
     const int j = q % NTN, s = q / NTN;
-#ifdef LD_AB_BUILD
-    if (stamps != nullptr && tid == 0) {   // which XCD runs this (slab, patch): hardware id, read for the placement check of tools/conv8_phases.py
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        stamps[6] = xcc & 15u;
-        stamps[7] = ((unsigned long long)q << 32) | (unsigned)tm;
-    }
-#endif
     const int Cin = p.C1 + p.C2;
     const int nsub = Cin >> 4;
     const int sb = (int)((long long)s * nsub / S), se = (int)((long long)(s + 1) * nsub / S);
@@ -210,7 +186,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
         if (2 < nloc) halo_load(1, hregB, U0{}, UN{});
     }
     if (halo_wave) halo_store(0, 0, hregA, U0{}, UN{});
-    C8_STAMP(1);
 
     // ------------------------------------------------------------------------------------------ main loop: 16-channel sub-slabs, one barrier per two
     // Three roles with SEPARATE code paths (one s_barrier per GROUP of two sub-slabs joins them — the ring holds two groups of weight stages, the halo
@@ -231,7 +206,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
         // The four ring slots hold two groups: group g + 1 goes out behind the barrier of group g into the slots group g - 1 was read from
         // (groups 0 and 1 went out in the prologue), and has one group of the loop to land.
         for (int k = 0; k < nloc; k += 2) {
-            C8_T0();
             if (k == 0 && nloc > 2) {                           // group 1 (one or two stages) may still be in flight
                 const bool two = nloc > 3;
                 if (wd == 0) { if (two) wait_vmcnt<14>(); else wait_vmcnt<7>(); }
@@ -239,20 +213,12 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
             } else {
                 wait_vmcnt<0>();
             }
-            C8_TB();                                            // (time in the vmcnt wait)
             __builtin_amdgcn_s_barrier();
-            C8_TA();                                            // (time in the barrier)
-#ifdef LD_AB_BUILD
-            if (p.dbg & 32) continue;
-#endif
             if (k >= 2) {
                 if (k + 2 < nloc) w_issue((k + 2) & (C8_RING - 1));
                 if (k + 3 < nloc) w_issue((k + 3) & (C8_RING - 1));
             }
         }
-#ifdef LD_AB_BUILD
-        if (sbase != nullptr && tid == 512) { sbase[18] = acc_a; sbase[19] = acc_b; }
-#endif
     } else if (wid >= 4) {    // ---- halo staging
         // (a vector-ALU wave beside an MFMA wave on the same SIMD: at equal priority their issue times ADD on this chip, with the vector wave
         // at priority 1 they overlap — tools/micro/coexec.hip, profiles/README.md)
@@ -260,17 +226,12 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
         for (int k = 0; k < nloc; ++k) {
             if (!(k & 1)) {                                     // (one barrier per group: see the weight DMA loop)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's halo writes of the group that starts here
-                C8_T0();
                 __builtin_amdgcn_s_barrier();
-                C8_TA();
             }
             const int g = k >> 1;
             // during group g: group g + 1 (loaded a group ago) goes into the other buffer — its previous contents were read before the barrier
             // that opened this group — and the loads of group g + 2 go out into the registers that just became free; first half of the
             // chunks in the group's first iteration, second half in its second one
-#ifdef LD_AB_BUILD
-            if (p.dbg & 16) continue;
-#endif
             if (2 * g + 2 < nloc) {
                 const bool more = 2 * g + 4 < nloc;
                 if (g & 1) {
@@ -319,38 +280,19 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
             for (int jj = 0; jj < 5; ++jj) fb[set][jj] = as_half8(*reinterpret_cast<const uint4*>(wst + t * 5120 + jj * 1024));
             fa[set][1] = as_half8(*reinterpret_cast<const uint4*>(hb + a_lane1 + toff[t]));
         };
-#ifdef LD_AB_BUILD
-        const unsigned long long loop_t0 = sbase != nullptr ? __builtin_amdgcn_s_memtime() : 0ull;
-#endif
         for (int k = 0; k < nloc; ++k) {
-            if (!(k & 1)) {                                     // (one barrier per group: see the weight DMA loop)
-                C8_T0();
-                __builtin_amdgcn_s_barrier();
-                C8_TA();
-            }
+            if (!(k & 1)) __builtin_amdgcn_s_barrier();         // (one barrier per group: see the weight DMA loop)
             const char* wst = wring + (k & (C8_RING - 1)) * C8_WSTAGE + b_lane;
             const char* hb = halo + ((k >> 1) & 1) * GROUP_B + (k & 1) * PLANE_B;
-#ifdef LD_AB_BUILD
-            const bool no_rd = (p.dbg & 4) != 0, no_mm = (p.dbg & 8) != 0;
-            if (!no_rd || k == 0)
-#endif
-            {
-                read_frags(wst, hb, 0, 0);
-                read_frags(wst, hb, 1, 1);
-            }
+            read_frags(wst, hb, 0, 0);
+            read_frags(wst, hb, 1, 1);
 #pragma unroll
             for (int t = 0; t < 5; ++t) {
                 // the fragments of step t are in: everything but the seven reads of step t + 1 (issued behind the MFMAs of step t - 1)
                 if (t + 1 < 5) asm volatile("s_waitcnt lgkmcnt(7)" ::: "memory");
                 else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef LD_AB_BUILD
-                if (!no_rd || k == 0)
-#endif
                 if (t + 2 < 5) read_frags(wst, hb, t + 2, (t + 2) % 3);
-#ifdef LD_AB_BUILD
-                if (!no_mm)
-#endif
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -369,15 +311,8 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifdef LD_AB_BUILD
-        if (sbase != nullptr && tid == 0) sbase[20] = __builtin_amdgcn_s_memtime() - loop_t0;
-#endif
     }
 
-    C8_STAMP(2);
-#ifdef LD_AB_BUILD
-    if (sbase != nullptr && (tid == 0 || tid == 256)) sbase[tid ? 17 : 16] = acc_a;   // barrier time of the consumer / halo wave
-#endif
     // ------------------------------------------------------------------------------------------ epilogue
     const long long tile = (long long)tm * NTN + j;
     const int cpg_o = p.N / 32;
@@ -450,7 +385,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
             if (wid < 8)
                 for (int grp = 0; grp < ngrp; ++grp) part_stats(wid, grp);   // wave w: part w
         }
-        C8_STAMP(5);
         return;
     }
 
@@ -468,7 +402,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
     }
     wait_vmcnt<0>();                                            // every storing wave drains its stores ...
     __syncthreads();                                            // ... before ONE lane signals for the workgroup
-    C8_STAMP(3);
     int* const cnt = p.sync + tile * 4;                         // [0] arrivals, [1] claims, [2] leavers
     if (tid == 0) {
         const int t = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -492,7 +425,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
     }
     __syncthreads();
     const bool take = flags[0] != 0;
-    C8_STAMP(4);
 
     // A claim = PC consecutive 16-row parts (PC = 8 / S for a split of 2 or 4: every workgroup then makes ONE round trip to the slabs).
     // Every load of the claim goes out before the first wait: the epilogue operands, then the S slabs of every item; slabs are summed in
@@ -572,7 +504,6 @@ __global__ __launch_bounds__(C8_THREADS, 3) void conv8_kernel(const GemmParams p
         else while (do_claim(I0{}, I1{})) {}
     }
     __syncthreads();
-    C8_STAMP(5);
     if (tid == 0) {   // the last workgroup of the tile to leave resets the counters for the next launch
         const int e = __hip_atomic_fetch_add(cnt + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (e == S - 1) {
@@ -656,7 +587,7 @@ bool conv8_plan(const GemmParams& p, int* S_out) {
     if (!(same || up) || p.Ho != p.Hv || p.Wo != p.Wv || p.Ho != p.Wo) return false;
     if (!(p.Wo == 8 || p.Wo == 16 || p.Wo == 32 || p.Wo == 64) || p.M % 128 || p.M % (p.Wo * p.Wo)) return false;
     // up to two images (the CFG pair of a batch-1 step): at UNet batch 16 the 8 x 8 level (8 patches x 16 N tiles, split 2) measured 0.1 ms per
-    // forward behind the general kernels (tools/ab_unet.py 4, profiles/README.md round 4)
+    // forward behind the general kernels (profiles/r04_ab_conv8.txt)
     if (p.M > 2 * p.Wo * p.Wo) return false;
     if (p.N % C8_BN || p.C1 % 32 || p.C2 % 32 || (p.N & 3) || p.ldc % 4 || (p.R != nullptr && p.ldr % 4) || (p.rowvec != nullptr && p.ldrv % 4)) return false;
     if (p.n_valid > 0 && p.n_valid < p.N) return false;
@@ -700,8 +631,8 @@ int conv8_launch(const GemmParams& pin, hipStream_t stream) {
             if (want < 1) want = 1;
             if (want > 16) want = 16;                                      // (the reducer's generic path sums up to 16 slabs)
             if (want > nsub / 2) want = nsub / 2;
+            if (tiles * want > 256) want = (int)(256 / tiles);            // (every workgroup of a tile co-resident: the in-launch reduction waits for its peers)
             while (want > 1 && (size_t)want * p.M * p.N * sizeof(float) > p.partial_bytes) --want;
-            (void)tiles;
             S = want;
         }
     }
@@ -709,8 +640,7 @@ int conv8_launch(const GemmParams& pin, hipStream_t stream) {
     p.c8_S = S;
     p.pad = 1;
 #ifdef LD_AB_BUILD
-    p.dbg = (getenv("LD_C8_STAMPS") != nullptr && p.partial_bytes > ((size_t)1 << 20) ? 1 : 0) | (getenv("LD_C8_NO_WAIT") != nullptr ? 2 : 0) |
-            (getenv("LD_C8_ABL") != nullptr ? atoi(getenv("LD_C8_ABL")) << 2 : 0);   // ablations (tools/conv8_abl.py; wrong results, timing only): 1 no fragment reads, 2 no MFMAs, 4 no halo staging, 8 no weight DMA in the loop
+    p.dbg = getenv("LD_C8_NO_WAIT") != nullptr ? 2 : 0;   // the lone-reducer route (tools/conv8_timeout_check.py)
 #endif
     if (p.bias_n == nullptr || p.rowvec == nullptr || p.R == nullptr) {
         // the zero page is a __device__ symbol: one address PER DEVICE (a process that drives several GPUs must not hand device 1 the page of

@@ -79,7 +79,7 @@ struct GemmParams {
     //   its in-launch reduction of the channel-slab partial sums needs >= 4 * (N / 80) zeroed ints that it leaves zeroed (self-resetting)
     int* sync = nullptr;
     int c8_S = 0;                // (internal) slab split chosen by conv8_plan
-    int dbg = 0;                 // A/B build only (LD_AB_BUILD): ablation switches of the v5 kernel (timing runs, wrong results)
+    int dbg = 0;                 // A/B build only (LD_AB_BUILD): bit 2 = conv8's lone-reducer route (LD_C8_NO_WAIT); the product leaves it 0
 };
 
 // conv8.hip: row-resident 3x3 convolution for the two-image (batch-1 CFG pair) 16x16 / 8x8 levels.  conv8_plan: does gemm_launch run this

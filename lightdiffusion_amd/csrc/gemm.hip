@@ -15,12 +15,6 @@
 #include <type_traits>
 
 #include "gemm.h"
-// Ablation build behind profiles/README.md: -DLD_DBG=6 makes every workgroup stream the SAME tile (all loads hit cache; wrong results,
-// timing only).  Never part of the shipped library.
-#if !defined(LD_AB_BUILD) || !defined(LD_DBG)   // (A/B build only: the shipped library ignores the macro)
-#undef LD_DBG
-#define LD_DBG 0
-#endif
 
 namespace {
 
@@ -57,7 +51,7 @@ __device__ __forceinline__ void epilogue_store8(const GemmParams& p, int z, int 
 // fused epilogue (bias, time-embedding row vector, residual) are loaded FIRST for every chunk, then consumed: the
 // loads overlap each other instead of paying one full memory latency per chunk (the accumulators are dead here, so
 // the registers are free).
-// Round 5 (tools/gemm3_abl.py, profiles/r05_gemm3_ablations.txt: at 16384 x 640 x 640 the tile epilogue took 8.7 of 23.5 us, 4.6 of them with
+// Round 5 (profiles/r05_gemm3_ablations.txt: at 16384 x 640 x 640 the tile epilogue took 8.7 of 23.5 us, 4.6 of them with
 // neither residual loads nor stores): the epilogue no longer starts a memory round trip of its own.  `bias_s` = this tile's BN bias halfs,
 // staged in LDS by the kernel's prologue (zeros when there is no bias); `pre` = the residual chunks of the first group of the plain interior
 // path, requested by the caller BEFORE the tile is staged in LDS (epi_prefetch_residual); the second group's are requested before the first
@@ -77,9 +71,6 @@ __device__ __forceinline__ EpiPre<BM, BN> epi_prefetch_residual(const GemmParams
     e.fast = (BM * CPR) % NT == 0 && m0 + BM <= p.M && n0 + BN <= p.N && p.act == 0 && p.bias_m == nullptr && bias_done;
 #pragma unroll
     for (int k = 0; k < GRP; ++k) e.r[k] = zero16();
-#ifdef LD_AB_BUILD
-    if (p.dbg & 32) return e;
-#endif
     if (e.fast && p.R != nullptr) {
         const half_t* Rb = p.R + (long long)z * p.sR + (long long)m0 * p.ldr + n0;
 #pragma unroll
@@ -162,14 +153,8 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const half_t*
         constexpr int CPR = BN / 8;
         constexpr int EIT = (BM * CPR + NT - 1) / NT;
         constexpr int GRP = EIT > 5 ? (EIT + 1) / 2 : EIT;   // two passes for the big tiles: bounds the live registers
-#ifdef LD_AB_BUILD
-        const bool hb = p.bias_n != nullptr && !pre.bias_done, hv = p.rowvec != nullptr, hr = p.R != nullptr && !(p.dbg & 32);   // ablations (tools/gemm3_abl.py): 32 no residual loads, 64 no output stores
-        const bool no_st = (p.dbg & 64) != 0;
-#else
         const bool hb = p.bias_n != nullptr && !pre.bias_done, hv = p.rowvec != nullptr, hr = p.R != nullptr;
-        constexpr bool no_st = false;
-#endif
-        // Interior tiles without an activation: a branch-free path in PACKED fp16 (round 5; tools/gemm3_abl.py: with neither residual loads
+        // Interior tiles without an activation: a branch-free path in PACKED fp16 (round 5; profiles/r05_gemm3_ablations.txt: with neither residual loads
         // nor stores the fp32 form of this path still took 4.6 of 23.5 us at 16384 x 640 x 640 — ~70 vector instructions per 16-byte chunk,
         // two workgroups per CU).  The bias is in the staged tile already (accumulator start value, or the LayerNorm-fold finish), so a chunk
         // is: tile chunk (+ time-embedding row) (+ residual) by v_pk_add_f16 — the sum of two fp16 values is exact in fp32, so ONE packed add
@@ -211,7 +196,7 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const half_t*
                     uint4 packed = cv[k];
                     if (hv) packed = add8h(packed, rv[k]);
                     if (hr) packed = add8h(packed, rres[k]);
-                    if (!no_st) st16(Cb + (long long)row * p.ldc + cc * 8, packed);
+                    st16(Cb + (long long)row * p.ldc + cc * 8, packed);
                     if (lds_scratch != nullptr) {   // LN-fold producer: row statistics of what was actually stored (the fp16 values)
                         const half2v one2 = {(half_t)1.f, (half_t)1.f};
                         const half2v h0 = __builtin_bit_cast(half2v, packed.x), h1 = __builtin_bit_cast(half2v, packed.y);
@@ -480,11 +465,7 @@ __global__ __launch_bounds__(NT, NST == 2 ? 2 : 1) void gemm3_kernel(const GemmP
         const int q = tid + i * NT;
         const int row = q >> 3;
         a_lc[i] = (q & 7) ^ (row & 7);
-#if LD_DBG == 6
-        const int m = row;            // every workgroup streams the SAME tile: all loads hit cache (latency probe)
-#else
         const int m = m0 + row;
-#endif
         a_ok[i] = m < p.M;
         a_img[i] = a_iy0[i] = a_ix0[i] = 0;
         a_ptr[i] = zp;
@@ -539,11 +520,7 @@ __global__ __launch_bounds__(NT, NST == 2 ? 2 : 1) void gemm3_kernel(const GemmP
         const int q = tid + i * NT;
         const int row = q >> 3;
         b_lc[i] = (q & 7) ^ (row & 7);
-#if LD_DBG == 6
-        const int n = row;
-#else
         const int n = n0 + row < p.n_valid ? n0 + row : p.n_valid - 1;
-#endif
         b_off[i] = (unsigned)(((long long)n * p.ldw + b_lc[i] * 8) * 2);
     }
     const half_t* b_base = Wb + (long long)kt_begin * BK3;   // wave-uniform
@@ -629,15 +606,6 @@ __global__ __launch_bounds__(NT, NST == 2 ? 2 : 1) void gemm3_kernel(const GemmP
             else wait_vmcnt<0>();
         }
     };
-#ifdef LD_AB_BUILD
-    if ((p.dbg & 0x700) && NST == 2) {   // experiment (tools/gemm3_abl.py stagger): the second co-resident workgroup of a CU (the second 256 blocks) starts (dbg >> 8) & 7 us late
-        if ((int)blockIdx.x >= 256 && (int)blockIdx.x < 512) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            const unsigned long long wait = 100ull * ((p.dbg >> 8) & 7);
-            while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-#endif
     f32x4 est_b, est_w;
     epi_stage_load<BN>(p, n0, tid, est_b, est_w);   // (before the first LDS-DMA: see epi_stage_load)
 #pragma unroll
@@ -670,39 +638,29 @@ __global__ __launch_bounds__(NT, NST == 2 ? 2 : 1) void gemm3_kernel(const GemmP
     read_frags(rd0, fa0, fb0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     int st = 0;
-#ifdef LD_AB_BUILD
-    // ablations (tools/gemm3_abl.py; wrong results, timing only): 1 no DMA behind the prologue, 2 no fragment reads in the loop, 4 no MFMAs, 8 no epilogue
-    const bool no_dma = (p.dbg & 1) != 0, no_rd = (p.dbg & 2) != 0, no_mm = (p.dbg & 4) != 0;
-    if (no_rd) read_frags(rd1, fa1, fb1);
-#else
-    constexpr bool no_dma = false, no_rd = false, no_mm = false;
-#endif
     for (int kt = kt_begin; kt < kt_end; ++kt) {
         // k-step 0 of slab kt sits in set 0; fetch k-step 1 under its MFMAs, then (slab kt+1 landed for everyone, stage st
         // free) refill st with slab kt+NST and fetch k-step 0 of slab kt+1 under the k-step-1 MFMAs
-        if (!no_rd) read_frags(rd1, fa1, fb1);
+        read_frags(rd1, fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!no_mm) mma(fa0, fb0);
+        mma(fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         wait_slab(kt + 1);
         __builtin_amdgcn_s_barrier();
-        if (!no_dma) issue(kt + NST, st);
+        issue(kt + NST, st);
         const int flip = (st == NST - 1) ? -(NST - 1) * STAGE : STAGE;   // halfs to the next stage of the ring
         rd0 += flip;
         rd1 += flip;
         st = (st + 1) & (NST - 1);
-        if (!no_rd) read_frags(rd0, fa0, fb0);
+        read_frags(rd0, fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
-        if (!no_mm) mma(fa1, fb1);
+        mma(fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
-#ifdef LD_AB_BUILD
-    if (p.dbg & 8) return;
-#endif
 
     if (splitk > 1) {
         float* part = p.partial + (long long)ks * p.M * p.N;
@@ -926,9 +884,6 @@ __global__ __launch_bounds__(2 * NT, WPS) void gemm4_kernel(const GemmParams p) 
         for (int kt = kt_begin; kt < kt_end; ++kt) {
             wait_slab(kt + 1, NST - 2);                  // issued so far: up to kt + NST - 1
             __builtin_amdgcn_s_barrier();                // BARRIER kt
-#ifdef LD_AB_BUILD
-            if (p.dbg & 1) continue;                     // ablation (tools/gemm4_abl.py; wrong results, timing only): no DMA behind the prologue's NST slabs
-#endif
             issue(kt + NST);
         }
         wait_vmcnt<0>();
@@ -987,16 +942,10 @@ __global__ __launch_bounds__(2 * NT, WPS) void gemm4_kernel(const GemmParams p) 
     read_frags(rd0, fa0, fb0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     int st = 0;
-#ifdef LD_AB_BUILD
-    const bool no_rd = (p.dbg & 2) != 0, no_mm = (p.dbg & 4) != 0;   // ablations (tools/gemm4_abl.py): no fragment reads in the loop / no MFMAs
-    if (no_rd) read_frags(rd1, fa1, fb1);
-#else
-    constexpr bool no_rd = false, no_mm = false;
-#endif
     for (int kt = kt_begin; kt < kt_end; ++kt) {
-        if (!no_rd) read_frags(rd1, fa1, fb1);
+        read_frags(rd1, fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!no_mm) mma(fa0, fb0);
+        mma(fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                    // BARRIER kt
@@ -1004,16 +953,13 @@ __global__ __launch_bounds__(2 * NT, WPS) void gemm4_kernel(const GemmParams p) 
         rd0 += flip;
         rd1 += flip;
         st = (st + 1) & (NST - 1);
-        if (!no_rd) read_frags(rd0, fa0, fb0);
+        read_frags(rd0, fa0, fb0);
         __builtin_amdgcn_sched_barrier(0);
-        if (!no_mm) mma(fa1, fb1);
+        mma(fa1, fb1);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();                        // tail: the ring is quiet, producers leave
-#ifdef LD_AB_BUILD
-    if (p.dbg & 8) return;                               // ablation: no epilogue
-#endif
 
     if (splitk > 1) {
         float* part = p.partial + (long long)ks * p.M * p.N;
@@ -1283,9 +1229,6 @@ __device__ __forceinline__ void v5_finish(const GemmParams& p, f32x4 (&acc)[4][1
     constexpr int TM = 4, TN = 10;
     const int fr = lane & 15, fq = lane >> 4;
     const int m_w = m0 + wm0, n_w = n0 + wn0;
-#ifdef LD_AB_BUILD
-    if (p.dbg & 4096) return;                                       // ablation (tools/conv6_abl.py; wrong results, timing only): no epilogue
-#endif
     if (splitk > 1) {
         float* part = p.partial + (long long)ks * p.M * p.N;
 #pragma unroll
@@ -1564,11 +1507,7 @@ __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
         tm_i = (x / gn) * bm_t + l % bm_t;
         tn_i = (x % gn) * bn_t + l / bm_t;
     }
-#ifdef LD_AB_BUILD
-    const int m0 = (p.dbg & 64) ? 0 : tm_i * V5_BM, n0 = (p.dbg & 64) ? 0 : tn_i * V5_BN;
-#else
     const int m0 = tm_i * V5_BM, n0 = tn_i * V5_BN;
-#endif
     const int KT = p.K / V5_BK;
     const int kt_begin = (int)((long long)ks * KT / splitk), kt_end = (int)((long long)(ks + 1) * KT / splitk);
     const int nk = kt_end - kt_begin;                              // >= 2 (gemm_launch)
@@ -1702,28 +1641,11 @@ __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
 
     for (int k = 0; k < nk; ++k) {
         // ------------------------------------------------ read phase (the partner wave of this SIMD is in its MFMA phase)
-#ifdef LD_AB_BUILD
-        if (p.dbg & 32) __builtin_amdgcn_s_setprio(2);
-        if (k + 3 < nk && !(p.dbg & 1) && !(p.dbg & 8)) issue();
-        if (!(p.dbg & 2) || k == 0) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = as_half8(ld16(rdB + j * 1024));
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = as_half8(ld16(rdA + i * 1024));
-        }
-        if (p.dbg & 8) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            if (k + 3 < nk && !(p.dbg & 1)) issue();
-        }
-        if (p.dbg & 32) __builtin_amdgcn_s_setprio(0);
-#else
         if (k + 3 < nk) issue();                                    // step k+3 -> the stage step k-1 left (both groups are done with it)
 #pragma unroll
         for (int j = 0; j < TN; ++j) fb[j] = as_half8(ld16(rdB + j * 1024));
 #pragma unroll
         for (int i = 0; i < TM; ++i) fa[i] = as_half8(ld16(rdA + i * 1024));
-#endif
         {
             const int d = st_read == V5_NST - 1 ? -(V5_NST - 1) * V5_STAGE_BYTES : V5_STAGE_BYTES;
             rdA += d;
@@ -1731,31 +1653,16 @@ __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
             st_read = st_read == V5_NST - 1 ? 0 : st_read + 1;
         }
         // my pieces of step k+1 have landed (steps k+2, k+3, if issued, may stay in flight); the barrier publishes them
-#ifdef LD_AB_BUILD
-        if (p.dbg & 1) wait_vmcnt<0>();
-        else
-#endif
-            wait_all_but(k + 3 < nk ? 2 : (k + 2 < nk ? 1 : 0));
+        wait_all_but(k + 3 < nk ? 2 : (k + 2 < nk ? 1 : 0));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         // ------------------------------------------------ MFMA phase (the partner reads / stages)
-#ifdef LD_AB_BUILD
-        if (!(p.dbg & 16))
-#endif
-            __builtin_amdgcn_s_setprio(1);
-#ifdef LD_AB_BUILD
-        if (p.dbg & 4) {
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[0], acc[0][j], 0, 0, 0);
-        } else
-#endif
-        {
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-        }
+            for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
@@ -2033,7 +1940,7 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
 //     group 1:  | (idle)   | MFMA j   | EPI j    | MFMA j+1 | ...           ('|' = s_barrier joining all 8 waves)
 //   step j lives in stage j & 1.  Group 0 issues its share of step j+1 in EPI j, group 1 its share of step j+2 in EPI j (the stage is
 //   free by then for both); every interval ends with the DMA retired + lgkmcnt(0), so a step is complete one barrier before its first reader.
-// The loop is LDS-bandwidth bound (tools/gemm7_phases.py: with an epilogue that staged its tile through LDS an interval took 4200
+// The loop is LDS-bandwidth bound (phase clocks, profiles/README.md round 2: with an epilogue that staged its tile through LDS an interval took 4200
 // clocks against 2000 for the fragment reads + DMA writes alone), so the epilogue stays OUT of LDS: the 16 W rows an MFMA tile
 // reads are chosen such that a lane's accumulators of two neighbouring tiles are 8 CONSECUTIVE output columns —
 //     tile jj < 4, MFMA index c  <-  W row 32 (jj >> 1) + 8 (c >> 2) + 4 (jj & 1) + (c & 3);   tile 4: row 64 + (c & 3) + 8 ((c >> 2) & 1) + 4 (c >> 3)
@@ -2049,16 +1956,6 @@ template <bool GEGLU, bool LN>
 __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
     constexpr int TM = 2, TN = 5;
     __shared__ __attribute__((aligned(16))) char smem7[2 * V7_STAGE_BYTES];
-#ifdef LD_AB_BUILD
-    // phase timestamps of waves 0 and 4 of one workgroup (tools/gemm7_phases.py): [wave group][step < 32][8 stamps], low 32 bits of s_memtime
-    __shared__ unsigned ts7[2 * 32 * 8];
-    const bool ts_on = (p.dbg & 2048) && blockIdx.x == 9 && (threadIdx.x & 255) == 0;
-    auto stamp = [&](int it_, int k) {
-        if (ts_on && it_ < 32) ts7[((threadIdx.x >> 8) * 32 + it_) * 8 + k] = (unsigned)__builtin_readcyclecounter();
-    };
-#else
-    auto stamp = [&](int, int) {};
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2196,9 +2093,6 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
         }
 #pragma unroll
         for (int ks = 0; ks < V7_KS; ++ks) {
-#ifdef LD_AB_BUILD
-            if ((p.dbg & 128) && ks > 0) break;
-#endif
             if (ks + 1 < V7_KS) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) fb[(ks + 1) & 1][j] = rd(j, ks + 1);
@@ -2222,12 +2116,6 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
     // store instructions it left as the youngest vector-memory operations of this wave.  Branch-free, every LDS / global read of a
     // phase issued as one batch: tile-by-tile read-wait-convert chains measured at twice the MFMA phase they are meant to hide behind.
     auto epilogue = [&](int it_, int j) -> int {                         // it_: position in this workgroup's walk (stage parity), j: the step
-#ifdef LD_AB_BUILD
-        if (p.dbg & 256) {
-            issue_next(it_);
-            return 0;
-        }
-#endif
         const int nb = j * V7_NB;                                        // row block of W / bias / wsum
         const int n_out = GEGLU ? (j >> 1) * V7_NB : nb;
         // The W pieces of a later step go out FIRST: they then have the whole epilogue to land, and the closing wait of the interval still
@@ -2262,7 +2150,6 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
                     vh[(i * TN + jj) * 2] = pk2h(v[0], v[1]);
                     vh[(i * TN + jj) * 2 + 1] = pk2h(v[2], v[3]);
                 }
-            stamp(it_, 3);
             return 0;
         }
         uint2 h[TM][TN];
@@ -2275,16 +2162,7 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
                 const unsigned aw[4] = {vh[jj * 2], vh[jj * 2 + 1], vh[(TN + jj) * 2], vh[(TN + jj) * 2 + 1]};
                 const f32x2 gp[4] = {{v[0][0], v[0][1]}, {v[0][2], v[0][3]}, {v[1][0], v[1][1]}, {v[1][2], v[1][3]}};
                 unsigned ow[4];
-#ifdef LD_AB_BUILD
-                if (p.dbg & 512) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const half2v ah = __builtin_bit_cast(half2v, aw[k]);
-                        ow[k] = pk2h((float)ah[0] * gp[k][0], (float)ah[1] * gp[k][1]);
-                    }
-                } else
-#endif
-                    geglu8_staged(aw, gp, ow);
+                geglu8_staged(aw, gp, ow);
                 h[0][jj] = make_uint2(ow[0], ow[1]);
                 h[1][jj] = make_uint2(ow[2], ow[3]);
             } else {
@@ -2295,13 +2173,11 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
                 }
             }
         }
-        stamp(it_, 3);
         // Vector-memory operations retire in order: the residual is waited for with the builtin (which hipcc's waitcnt pass models: it
         // then adds no wait of its own), unconditionally (under `if (R)` the model still holds the loads outstanding on the merged path
         // and parks its own waits further down).  The W pieces issued above are older and retire with it — they have had the whole
         // finish to land; the output stores below stay the youngest operations, so the interval's closing wait can leave them in flight.
         if (!GEGLU) __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0)
-        stamp(it_, 4);
         uint4 o16[TM][2];
         uint2 o8[TM];
 #pragma unroll
@@ -2340,9 +2216,6 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
                 if (fq == 0 && row_ok[i]) *reinterpret_cast<float2*>(p.stat_out + ((long long)j * p.M + mw + 16 * i + fr) * 2) = make_float2(s1, s2);
             }
         }
-#ifdef LD_AB_BUILD
-        if (p.dbg & 1024) return 0;                                      // ablation: no output stores
-#endif
         half_t* Cb = p.C + (long long)mw * p.ldc + n_out;
         if (full_tile) {                                                 // exactly 6 store instructions: the closing wait leaves them in flight
 #pragma unroll
@@ -2383,29 +2256,17 @@ __global__ __launch_bounds__(512, 2) void gemm7_kernel(const GemmParams p) {
     for (int it_ = 0; it_ < NS; ++it_) {
         int j = j0 + it_;
         if (j >= NS) j -= NS;
-        stamp(it_, 0);
         mfma_step(it_ & 1);
-        stamp(it_, 1);
         end_interval(st);                                                // my DMA share is older than the last epilogue's stores: those may stay in flight
-        stamp(it_, 2);
         // The epilogue runs at raised priority: on this chip a VALU stream and an MFMA stream of the two waves of a SIMD take the SUM of
         // their times when the MFMA wave has (equal or higher) priority — it holds the vector issue port while the matrix pipe is busy —
         // and the MAX when the VALU wave has priority (tools/micro/coexec.hip, profiles/README.md).
         __builtin_amdgcn_s_setprio(2);
         st = epilogue(it_, j);
         __builtin_amdgcn_s_setprio(0);
-        stamp(it_, 5);
         end_interval(st);
-        stamp(it_, 6);
     }
     if (!grp1) __builtin_amdgcn_s_barrier();                            // group 0 waits out group 1's last epilogue: every wave ran 2 NS + 2 barriers
-#ifdef LD_AB_BUILD
-    if ((p.dbg & 2048) && blockIdx.x == 9 && p.partial != nullptr) {
-        __syncthreads();
-        unsigned* out = reinterpret_cast<unsigned*>(p.partial);
-        for (int q = threadIdx.x; q < 2 * 32 * 8; q += 512) out[q] = ts7[q];
-    }
-#endif
 }
 
 // split-K second pass: sum the fp32 slabs and run the same epilogue
@@ -2571,12 +2432,8 @@ const char* intern_name(const std::string& s) {   // stable storage for composed
     return pool.insert(s).first->c_str();
 }
 
-static bool two_wg_ok();   // (A/B hook, below)
-static bool m_fastest_ok();
-static bool skinny_conv1_ok();
-
 // conv1_2wg: gemm_launch's decision to run a 1x1 convolution on 64 x 64 tiles UNSPLIT on the two-workgroups-per-CU producer / consumer kernel
-// (its skinny_conv1 rule and the older few-tile rule behind the same A/B switch) — decided THERE, not re-derived here
+// (its skinny_conv1 rule and the older few-tile rule) — decided THERE, not re-derived here
 template <int BM, int BN>
 void launch_cfg(const GemmParams& p, hipStream_t s, bool deep = false, bool conv1_2wg = false) {
     const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
@@ -2586,12 +2443,12 @@ void launch_cfg(const GemmParams& p, hipStream_t s, bool deep = false, bool conv
     // same box A/B); loses on convs and wherever two v3 workgroups share a CU.
     if constexpr (BM == 64 && BN == 64) {
         // skinny projections with more tiles than CUs: the producer / consumer kernel with two workgroups per CU (see gemm4_kernel, WPS).
-        // Measured per launch inside the batch-1 forward (tools/ab_launches.py 1 0 2048, profiles/r05_ab_gemm4_rings.txt): 2048 x 640 x 640
+        // Measured per launch inside the batch-1 forward (profiles/r05_ab_gemm4_rings.txt): 2048 x 640 x 640
         // (320 tiles, 10 slabs) 14.3 -> 11.7 us against the 2-stage kernel; 8192 x 320 x 320 (640 tiles, 5 slabs) 12.3 -> 14.4: short K stays.
         // An 8-stage ring for <= 256 tiles measured +-0 (512 x 1280 x 1280: 13.6 vs 13.4 us): these launches are not short of bytes in
-        // flight — an ablated kernel that only runs its prologue and barriers takes 4.7 of 8.3 us (tools/gemm4_abl.py).
+        // flight — an ablated kernel that only runs its prologue and barriers takes 4.7 of 8.3 us (same record).
         const long long blocks = (long long)tiles * sk * p.batch;
-        if (!p.conv && two_wg_ok() && blocks > V4_MAX_BLOCKS && blocks <= 512 && p.K >= 640) {
+        if (!p.conv && blocks > V4_MAX_BLOCKS && blocks <= 512 && p.K >= 640) {
             t_last_kernel = "gemm4_kernel<64,64,plain,2wg>";
             hipLaunchKernelGGL((gemm4_kernel<64, 64, false, 4, 4>), grid, dim3(2 * NT), 0, s, p);
             return;
@@ -2623,12 +2480,34 @@ void launch_cfg(const GemmParams& p, hipStream_t s, bool deep = false, bool conv
     }
 }
 
+// one halo-tile instantiation; its profile name says what differs from the 256 x 320 tile: conv6_kernel<W64,halo+groupnorm>,
+// conv6_kernel<W128,halo,128x512>, conv6_kernel<W64,halo,256,up>, ...
+template <int W, bool GN, int BN, int BM, bool UP>
+void launch_conv6_w(const GemmParams& p, dim3 grid, hipStream_t s) {
+    static const std::string name = "conv6_kernel<W" + std::to_string(W) + ",halo" + (GN ? "+groupnorm" : "") +
+                                    (BN == V5_BN ? "" : "," + std::to_string(BN) + (BM == V5_BM ? "" : "x" + std::to_string(BM))) + (UP ? ",up" : "") + ">";
+    t_last_kernel = name.c_str();
+    hipLaunchKernelGGL((conv6_kernel<W, GN, BN, BM, UP>), grid, dim3(512), 0, s, p);
+}
+// the tile widths v6_plan hands each tile: every width for the 320-column tile, 64 and 128 for the plain 256-column tile, 128 for the rest
+template <bool GN, int BN = V5_BN, int BM = V5_BM, bool UP = false>
+void launch_conv6(int wc, const GemmParams& p, dim3 grid, hipStream_t s) {
+    if constexpr (BN == V5_BN) {
+        if (wc == 16) return launch_conv6_w<16, GN, BN, BM, UP>(p, grid, s);
+        if (wc == 32) return launch_conv6_w<32, GN, BN, BM, UP>(p, grid, s);
+    }
+    if constexpr (BN == V5_BN || (BN == 256 && !GN)) {
+        if (wc == 64) return launch_conv6_w<64, GN, BN, BM, UP>(p, grid, s);
+    }
+    launch_conv6_w<128, GN, BN, BM, UP>(p, grid, s);
+}
+
 }  // namespace
 
 #ifdef LD_AB_BUILD
-// tuning hook of the A/B build (tools/gemm_sweep.py): force tile height / split-K for every following launch; 0 = automatic.
-// Not part of the shipped library: `make AB=1` builds libld_mi355x_ab.so with it.
-static int g_force_bm = 0, g_force_sk = 0, g_no_v5 = 0;
+// tuning hook of the A/B build (tools/gemm_sweep.py, tools/ab_launches.py): force tile height / split-K for every following launch; 0 = automatic.
+// Not part of the shipped library: `make ab` builds libld_mi355x_ab.so with it.
+static int g_force_bm = 0, g_force_sk = 0;
 // per-shape override (tools/ab_shape.py: candidates are timed launch by launch INSIDE the forward): M, N, K -> tile height, split
 static int g_shape_ovr[5] = {0, 0, 0, 0, 0};
 extern "C" void ld_debug_gemm_shape_override(int M, int N, int K, int bm, int splitk) {
@@ -2638,34 +2517,7 @@ extern "C" void ld_debug_gemm_override(int bm, int splitk) {
     g_force_bm = bm;
     g_force_sk = splitk;
 }
-extern "C" void ld_debug_gemm_no_v5(int off) { g_no_v5 = off; }
-static int g_v5_dbg = 0;
-extern "C" void ld_debug_gemm_v5_dbg(int bits) { g_v5_dbg = bits; }   // 1: no DMA issue in the loop, 2: no fragment reads, 4: 4 of 40 MFMAs
 #endif
-
-namespace {
-bool skinny_conv1_ok() {
-#ifdef LD_AB_BUILD
-    return (g_no_v5 & 8192) == 0;    // A/B: bit 8192 keeps the split 64 x 160 tiles for the skinny 1x1 convolutions
-#else
-    return true;
-#endif
-}
-bool m_fastest_ok() {
-#ifdef LD_AB_BUILD
-    return (g_no_v5 & 4096) == 0;    // A/B: bit 4096 keeps the N-fastest tile order everywhere
-#else
-    return true;
-#endif
-}
-bool two_wg_ok() {
-#ifdef LD_AB_BUILD
-    return (g_no_v5 & 2048) == 0;    // A/B: bit 2048 keeps round 4's 2-stage kernel for the 64 x 64 tiles beyond 256 workgroups
-#else
-    return true;
-#endif
-}
-}  // namespace
 
 // the split-K second pass of a launch: the plain reduce, or the one that also emits GroupNorm partials (GemmParams::gn_part)
 static void launch_splitk_reduce(const GemmParams& p, int bn, hipStream_t stream) {
@@ -2690,26 +2542,6 @@ static void launch_splitk_reduce(const GemmParams& p, int bn, hipStream_t stream
 bool gemm_ln_fold_available() { return true; }
 const char* gemm_last_kernel_name() { return t_last_kernel; }
 
-// Measured (tools/gemm5_ab.py AB_MODE=v7, tools/ab_launches.py; profiles/README.md): against the 128 x 160 kernel the row-panel kernel runs the
-// plain K = 320 projections 1.3..1.6x faster (27 vs 36 us at 65536 x 320 with residual, 37 vs 60 us at 65536 x 640) and, since its epilogue
-// left LDS and its GELUs are issued interleaved (common.h: geglu8_staged), the level-0 GEGLU as well.
-static bool v7_geglu_enabled() {
-#ifdef LD_AB_BUILD
-    return (g_no_v5 & 16) == 0;      // A/B: bit 16 sends GEGLU back to the 128 x 160 kernel
-#else
-    return true;
-#endif
-}
-
-// smallest K of a GEGLU the 256 x 320 kernel takes (round 4: 1280 — its strip epilogue ran the GELUs unbatched)
-static int v5_geglu_min_k() {
-#ifdef LD_AB_BUILD
-    return (g_no_v5 & 1024) ? 640 : 1280;      // A/B: bit 1024 also sends the K = 640 GEGLU (level 1) there
-#else
-    return 1280;
-#endif
-}
-
 // does this convolution run on the halo-tile kernel (v6), and with which tile (rows x columns), split over K and loader (UP)?
 struct V6Plan {
     int sk = 1, bn = 0, bm = V5_BM, wc = 0;   // wc: tile width in pixels (16 / 32 / 64 / 128; an image wider than 128 is cut into 128-pixel bands)
@@ -2725,10 +2557,6 @@ static bool v6_plan(const GemmParams& p, V6Plan* out) {
     if (p.SC1 > 0) return false;                                     // (a second K segment: the tap-major kernels)
     const int wc = (p.Wo == 16 || p.Wo == 32 || p.Wo == 64 || p.Wo == 128) ? p.Wo : (p.Wo > 128 && p.Wo % 128 == 0) ? 128 : 0;
     if (wc == 0) return false;
-#ifdef LD_AB_BUILD
-    if (g_no_v5 & 2) return false;
-    if ((g_no_v5 & 256) && (up || p.Wo > 128)) return false;      // A/B: round-2 coverage only
-#endif
     // tile: 320 columns for the UNet's N = 320 k; 256 for the VAE's N = 256 / 512 at >= 64-pixel rows (VAE decode b=8 29.9 -> 28.8 ms);
     // 512 pixels x 128 columns for its N = 128 (a 256 x 128 tile would leave a wave 16 MFMAs per phase: the step's fixed cost dominates).
     // (256 x 160 tiles for level 1 — 256 unsplit tiles instead of 128 + split — measured a net loss per launch inside the forward:
@@ -2737,17 +2565,9 @@ static bool v6_plan(const GemmParams& p, V6Plan* out) {
     int bn = 0, bm = V5_BM;
     if (p.N % V5_BN == 0) {
         bn = V5_BN;
-    } else if (p.N % 256 == 0 && wc >= 64 && (p.gn_scale == nullptr || (p.N == 256 && wc == 128 && !up))   // (fused GroupNorm: one tile wide, 128-pixel bands)
-#ifdef LD_AB_BUILD
-               && !(g_no_v5 & 64)
-#endif
-    ) {
+    } else if (p.N % 256 == 0 && wc >= 64 && (p.gn_scale == nullptr || (p.N == 256 && wc == 128 && !up))) {   // (fused GroupNorm: one tile wide, 128-pixel bands)
         bn = 256;
-    } else if (p.N % 128 == 0 && wc == 128 && (p.gn_scale == nullptr || (p.N == 128 && !up))
-#ifdef LD_AB_BUILD
-               && !(g_no_v5 & 256)
-#endif
-    ) {
+    } else if (p.N % 128 == 0 && wc == 128 && (p.gn_scale == nullptr || (p.N == 128 && !up))) {
         bn = 128;
         bm = 512;
     } else if (p.N == 32 && wc == 128 && p.gn_scale == nullptr && !up) {
@@ -2805,10 +2625,7 @@ bool gemm_conv_takes_halo_tile(const GemmParams& pin) {
 }
 
 bool gemm_conv_fuses_groupnorm(const GemmParams& p) {
-#ifdef LD_AB_BUILD
-    if (g_no_v5 & 4) return false;   // A/B: keep the two-pass GroupNorm in front of the halo kernel
-#endif
-    // Measured (tools/gnconv_ab.py, same process): fused vs two-pass GroupNorm + the same halo conv: +4 % at N = 320 (level 0, one N
+    // Measured (profiles/r02_ab_groupnorm_fusion.txt, same process): fused vs two-pass GroupNorm + the same halo conv: +4 % at N = 320 (level 0, one N
     // tile per M tile), +-0 % at N = 640, -3 % at N = 1280 — every N tile of an M tile normalises the same halo again, so the fusion
     // only pays where the output is one tile wide.
     // Round 5: also the VAE decoder's one-tile-wide stages — N = 256 at 256-pixel rows, N = 128 at 512-pixel rows (128-pixel bands) — where a
@@ -2816,9 +2633,6 @@ bool gemm_conv_fuses_groupnorm(const GemmParams& p) {
     V6Plan pl;
     if (!v6_plan(p, &pl) || pl.up) return false;
     if (p.N == V5_BN && pl.bn == V5_BN) return true;
-#ifdef LD_AB_BUILD
-    if (g_no_v5 & 16384) return false;   // A/B: the UNet's N = 320 case only
-#endif
     // (the 128 -> 3 output convolution — 8 MFMAs per phase — measured a loss with its norm_out fused: VAE decode +0.15 ms, profiles/r05_ab_vae_gn_fused.txt)
     return pl.wc == 128 && ((p.N == 256 && pl.bn == 256 && pl.bm == V5_BM) || (p.N == 128 && pl.bn == 128 && pl.bm == 512));
 }
@@ -2826,7 +2640,6 @@ bool gemm_conv_fuses_groupnorm(const GemmParams& p) {
 int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     GemmParams p = pin;
 #ifdef LD_AB_BUILD
-    p.dbg = g_v5_dbg;
     if (g_force_bm) p.bm = g_force_bm;
     if (g_force_sk) p.splitk = g_force_sk;
     if (g_shape_ovr[0] == p.M && g_shape_ovr[1] == p.N && g_shape_ovr[2] == p.K && p.batch == 1 && p.gn_scale == nullptr) {
@@ -2874,7 +2687,6 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
         p.pad = 1;
         if (bn6 != 32) p.n_valid = p.N;                              // (the 32-column tile stores only the caller's n_valid columns)
         dim3 grid((unsigned)(t6 * sk6), 1, 1);
-        const bool wide = p.Wo > 128;
         if (sk6 == 1 && p.gn_part != nullptr) {
             // the generic epilogue (v6_finish) also writes the GroupNorm partial statistics of the OUTPUT, one chunk per tile of an image
             const int cpg = p.N / 32, tiles_img = (p.Ho / (pl.bm / wc)) * (p.Wo / wc);
@@ -2886,59 +2698,23 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
                 p.gn_part = nullptr;
             }
         }
-        if (p.gn_scale != nullptr && bn6 != V5_BN) {
-            if (p.gn_shift == nullptr || pl.up || wc != 128 || p.N != bn6 || !((bn6 == 256 && pl.bm == V5_BM) || (bn6 == 128 && pl.bm == 512))) return LD_ERR_ARG;
-            if (bn6 == 256) {
-                t_last_kernel = "conv6_kernel<W128,halo+groupnorm,256>";
-                hipLaunchKernelGGL((conv6_kernel<128, true, 256>), grid, dim3(512), 0, stream, p);
-            } else {
-                t_last_kernel = "conv6_kernel<W128,halo+groupnorm,128x512>";
-                hipLaunchKernelGGL((conv6_kernel<128, true, 128, 512>), grid, dim3(512), 0, stream, p);
-            }
-        } else if (p.gn_scale != nullptr) {
+        if (p.gn_scale != nullptr) {
             if (p.gn_shift == nullptr || pl.up) return LD_ERR_ARG;
-            t_last_kernel = wc == 16 ? "conv6_kernel<W16,halo+groupnorm>" : wc == 32 ? "conv6_kernel<W32,halo+groupnorm>"
-                          : wc == 64 ? "conv6_kernel<W64,halo+groupnorm>" : "conv6_kernel<W128,halo+groupnorm>";
-            switch (wc) {
-                case 16: hipLaunchKernelGGL((conv6_kernel<16, true>), grid, dim3(512), 0, stream, p); break;
-                case 32: hipLaunchKernelGGL((conv6_kernel<32, true>), grid, dim3(512), 0, stream, p); break;
-                case 64: hipLaunchKernelGGL((conv6_kernel<64, true>), grid, dim3(512), 0, stream, p); break;
-                default: hipLaunchKernelGGL((conv6_kernel<128, true>), grid, dim3(512), 0, stream, p); break;
-            }
+            if (bn6 != V5_BN && (wc != 128 || p.N != bn6 || !((bn6 == 256 && pl.bm == V5_BM) || (bn6 == 128 && pl.bm == 512)))) return LD_ERR_ARG;
+            if (bn6 == 256) launch_conv6<true, 256>(wc, p, grid, stream);
+            else if (bn6 == 128) launch_conv6<true, 128, 512>(wc, p, grid, stream);
+            else launch_conv6<true>(wc, p, grid, stream);
         } else if (bn6 == 128) {
-            t_last_kernel = "conv6_kernel<W128,halo,128x512>";
-            hipLaunchKernelGGL((conv6_kernel<128, false, 128, 512>), grid, dim3(512), 0, stream, p);
+            launch_conv6<false, 128, 512>(wc, p, grid, stream);
         } else if (bn6 == 32) {
-            t_last_kernel = "conv6_kernel<W128,halo,32x512>";
-            hipLaunchKernelGGL((conv6_kernel<128, false, 32, 512>), grid, dim3(512), 0, stream, p);
+            launch_conv6<false, 32, 512>(wc, p, grid, stream);
         } else if (bn6 == 256) {
-            if (pl.up) {
-                t_last_kernel = wc == 64 ? "conv6_kernel<W64,halo,256,up>" : "conv6_kernel<W128,halo,256,up>";
-                if (wc == 64) hipLaunchKernelGGL((conv6_kernel<64, false, 256, V5_BM, true>), grid, dim3(512), 0, stream, p);
-                else hipLaunchKernelGGL((conv6_kernel<128, false, 256, V5_BM, true>), grid, dim3(512), 0, stream, p);
-            } else {
-                t_last_kernel = wc == 64 ? "conv6_kernel<W64,halo,256>" : "conv6_kernel<W128,halo,256>";
-                if (wc == 64) hipLaunchKernelGGL((conv6_kernel<64, false, 256>), grid, dim3(512), 0, stream, p);
-                else hipLaunchKernelGGL((conv6_kernel<128, false, 256>), grid, dim3(512), 0, stream, p);
-            }
-        } else if (pl.up) {
-            t_last_kernel = wc == 16 ? "conv6_kernel<W16,halo,up>" : wc == 32 ? "conv6_kernel<W32,halo,up>" : wc == 64 ? "conv6_kernel<W64,halo,up>" : "conv6_kernel<W128,halo,up>";
-            switch (wc) {
-                case 16: hipLaunchKernelGGL((conv6_kernel<16, false, V5_BN, V5_BM, true>), grid, dim3(512), 0, stream, p); break;
-                case 32: hipLaunchKernelGGL((conv6_kernel<32, false, V5_BN, V5_BM, true>), grid, dim3(512), 0, stream, p); break;
-                case 64: hipLaunchKernelGGL((conv6_kernel<64, false, V5_BN, V5_BM, true>), grid, dim3(512), 0, stream, p); break;
-                default: hipLaunchKernelGGL((conv6_kernel<128, false, V5_BN, V5_BM, true>), grid, dim3(512), 0, stream, p); break;
-            }
+            if (pl.up) launch_conv6<false, 256, V5_BM, true>(wc, p, grid, stream);
+            else launch_conv6<false, 256>(wc, p, grid, stream);
         } else {
-            t_last_kernel = wc == 16 ? "conv6_kernel<W16,halo>" : wc == 32 ? "conv6_kernel<W32,halo>" : wc == 64 ? "conv6_kernel<W64,halo>" : "conv6_kernel<W128,halo>";
-            switch (wc) {
-                case 16: hipLaunchKernelGGL((conv6_kernel<16, false>), grid, dim3(512), 0, stream, p); break;
-                case 32: hipLaunchKernelGGL((conv6_kernel<32, false>), grid, dim3(512), 0, stream, p); break;
-                case 64: hipLaunchKernelGGL((conv6_kernel<64, false>), grid, dim3(512), 0, stream, p); break;
-                default: hipLaunchKernelGGL((conv6_kernel<128, false>), grid, dim3(512), 0, stream, p); break;
-            }
+            if (pl.up) launch_conv6<false, V5_BN, V5_BM, true>(wc, p, grid, stream);
+            else launch_conv6<false>(wc, p, grid, stream);
         }
-        (void)wide;
         if (sk6 > 1) launch_splitk_reduce(p, 160, stream);
         return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
     }
@@ -2946,11 +2722,7 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     // ---- v7 (row-panel kernel, A fragments in registers): the K = 320 projections whose 256-row panels fill the chip
     if (!p.conv && p.K == V7_K && p.batch == 1 && !p.ln_swapped && p.bias_m == nullptr && p.rowvec == nullptr && p.bm == 0 && (p.bn == 0 || p.bn == 160) &&
         p.splitk == 0 && (p.n_valid <= 0 || p.n_valid >= p.N) && p.N % (p.act == 2 ? 160 : V7_NB) == 0 && (p.M + V7_BM - 1) / V7_BM >= 192 &&
-        (p.act == 0 || (p.act == 2 && p.bias_n != nullptr && p.stat_out == nullptr && p.R == nullptr && v7_geglu_enabled()))
-#ifdef LD_AB_BUILD
-        && !(g_no_v5 & 8)
-#endif
-    ) {
+        (p.act == 0 || (p.act == 2 && p.bias_n != nullptr && p.stat_out == nullptr && p.R == nullptr))) {
         if (p.stat_parts_out != nullptr) *p.stat_parts_out = p.N / V7_NB;
         dim3 grid((unsigned)((p.M + V7_BM - 1) / V7_BM), 1, 1);
         const bool ln = p.ln_stat != nullptr;
@@ -2973,13 +2745,9 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
         // a split over K (4096 x 1280 x 11520: the 128 x 160 kernel's own split is 3 % ahead)
         const bool conv3 = p.conv && p.ksize == 3;
         const bool shape_ok = !p.ln_swapped && p.bm == 0 && (p.bn == 0 || p.bn == 160) && p.N % V5_BN == 0 && p.K % V5_BK == 0 &&
-                              p.K >= (p.act == 2 ? v5_geglu_min_k() : conv3 ? 640 : 2560) && (p.n_valid == p.N || p.n_valid <= 0 || p.n_valid > p.N) &&
+                              p.K >= (p.act == 2 ? 1280 : conv3 ? 640 : 2560) && (p.n_valid == p.N || p.n_valid <= 0 || p.n_valid > p.N) &&
                               p.splitk == 0 && p.M >= 1024;
-#ifdef LD_AB_BUILD
-        if (shape_ok && !(g_no_v5 & 1)) {
-#else
         if (shape_ok) {
-#endif
             const long long t5 = (long long)((p.M + V5_BM - 1) / V5_BM) * (p.N / V5_BN) * p.batch;
             if (t5 >= 192 && !(p.act == 2 && p.stat_out != nullptr)) {
                 if (p.stat_parts_out != nullptr) *p.stat_parts_out = 2 * (p.N / V5_BN);
@@ -3012,9 +2780,6 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
                                 }
                             }
                         }
-#ifdef LD_AB_BUILD
-                        if (g_no_v5 & 512) p.xcd_gm = 0;
-#endif
                     }
                     if (p.act == 2) hipLaunchKernelGGL((gemm5_kernel<false, 2>), grid, dim3(512), 0, stream, p);
                     else if (ln) hipLaunchKernelGGL((gemm5_kernel<false, 1>), grid, dim3(512), 0, stream, p);
@@ -3038,12 +2803,12 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     }
     // Round 5: the batch-1 step's 1x1 contractions over two sources (ResBlock skip_connection on the concatenated input, the MLP-out fold at
     // K = 3200) take the same 64 x 64 tiles UNSPLIT on the producer / consumer kernel with two workgroups per CU, instead of 64 x 160 tiles
-    // split over K + a reduce launch.  Per shape inside the batch-1 forward (tools/ab_launches.py 1 0 8192, profiles/r05_ab_skinny_conv1.txt):
+    // split over K + a reduce launch.  Per shape inside the batch-1 forward (profiles/r05_ab_skinny_conv1.txt):
     // 2048 x 640 x 3200 32.2 -> 27.7 us, 2048 x 640 x 1920 26.1 -> 19.4, 512 x 1280 x 2560 25.3 -> 21.4; K = 6400 (100 slabs in one
     // workgroup) loses: 31.8 -> 37.1 us, and as two slices of 3200 + reduce 31.5 -> 34.4 us, so K stops at 3200.  (Without a split there are no GroupNorm partials from the reduce pass: the next
     // GroupNorm runs its own statistics pass — counted in the whole-forward A/B: 5.225 -> 5.207 ms before K was capped.)
     bool skinny_conv1 = false;
-    if (skinny_conv1_ok() && p.conv && p.ksize == 1 && p.act == 0 && p.bn == 0 && p.bm == 0 && p.splitk == 0 && p.batch == 1 && (p.N % 64) == 0 && p.SC1 == 0) {
+    if (p.conv && p.ksize == 1 && p.act == 0 && p.bn == 0 && p.bm == 0 && p.splitk == 0 && p.batch == 1 && (p.N % 64) == 0 && p.SC1 == 0) {
         const long long t64 = (long long)((p.M + 63) / 64) * (p.N / 64);
         if (t64 > 128 && t64 <= 512 && p.K >= 1280 && p.K <= 3200) {
             bn = 64;
@@ -3080,10 +2845,7 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     // run the 4-stage ring with ONE workgroup per CU and a split aimed at 256 workgroups: three slabs in flight per workgroup hide the
     // HBM latency of their cold weights better than two co-resident 2-stage workgroups (per launch inside the batch-1 forward,
     // tools/ab_launches.py: 128 x 1280 x 11520 24.3 -> 22.2 us, 8192 x 320 x 1600 32 -> 26 us; 64 .. 128 tiles with long K lose 10 %).
-    bool deep = p.conv && bm == 64 && bn == 160 && p.batch == 1 && p.splitk == 0 && (tiles <= 32 || (tiles >= 256 && tiles < 512));
-#ifdef LD_AB_BUILD
-    if (g_no_v5 & 128) deep = false;
-#endif
+    const bool deep = p.conv && bm == 64 && bn == 160 && p.batch == 1 && p.splitk == 0 && (tiles <= 32 || (tiles >= 256 && tiles < 512));
     if (sk == 0) {
         sk = 1;
         if (can_split && tiles * p.batch < 512) {
@@ -3110,12 +2872,12 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     // (profiles/pmc_traffic.json round 4: 113 MB per launch for 26 MB of weights)
     if (p.m_fastest < 0) {
         const int tiles_m = (p.M + bm - 1) / bm;
-        p.m_fastest = (!p.conv && p.batch == 1 && tiles_m >= 2 && tiles_m <= 8 && (long long)p.N * p.K * 2 >= (8ll << 20) && m_fastest_ok()) ? 1 : 0;
+        p.m_fastest = (!p.conv && p.batch == 1 && tiles_m >= 2 && tiles_m <= 8 && (long long)p.N * p.K * 2 >= (8ll << 20)) ? 1 : 0;
     }
 
     // every unsplit 1x1 convolution that ends on 64 x 64 tiles with at most two workgroups per CU takes the 2wg kernel: the skinny_conv1 shapes
-    // and the few-tile shapes of the older skinny_max rule alike; A/B bit 8192 (skinny_conv1_ok) restores round 4's route for all of them
-    const bool conv1_2wg = bn == 64 && skinny_conv1_ok() && p.conv && p.ksize == 1 && sk <= 1 && (long long)tiles * p.batch <= 512;
+    // and the few-tile shapes of the older skinny_max rule alike
+    const bool conv1_2wg = bn == 64 && p.conv && p.ksize == 1 && sk <= 1 && (long long)tiles * p.batch <= 512;
     if (bn == 64) launch_cfg<64, 64>(p, stream, false, conv1_2wg);
     else if (bm == 128 && bn == 160) launch_cfg<128, 160>(p, stream);
     else if (bm == 128 && bn == 128) launch_cfg<128, 128>(p, stream);

@@ -186,7 +186,6 @@ struct Exec {
     double flops = 0.0;
     float* splitk_ws = nullptr;
     size_t splitk_bytes = 0;
-    int ab_flags = 0;                // A/B build only (ld_debug_unet_flags): 4 = row-resident convolution (conv8.hip) off
     int* sync_ws = nullptr;          // LD_SYNC_INTS zeroed ints for the in-launch reductions (gemm.h GemmParams::sync); null: those kernels are not used
 
     void note(int st) {
@@ -225,7 +224,6 @@ struct Exec {
             p.partial_bytes = splitk_bytes;
             p.sync = sync_ws;
         }
-        if (ab_flags & 4) p.W8 = nullptr;
         launches += 1;
         if (dry || status != LD_OK) return;
         t_begin(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, fl, 1, p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"),
@@ -238,7 +236,6 @@ struct Exec {
         p.partial = splitk_ws;
         p.partial_bytes = splitk_bytes;
         p.sync = sync_ws;
-        if (ab_flags & 4) p.W8 = nullptr;
         return gemm_conv_takes_skip_segment(p);
     }
     // `ready` / `ready_P`: partial statistics the producer already wrote (gemm.h gn_part; ready_P pixel chunks per image): the statistics
@@ -265,7 +262,6 @@ struct Exec {
         p.partial_bytes = splitk_bytes;
         p.sync = sync_ws;
         if (ready_P <= 0) ready = nullptr;
-        if (ab_flags & 4) p.W8 = nullptr;
         if (gemm_conv_fuses_groupnorm(p)) {
             const int C = p.C1 + p.C2;
             const size_t m = arena->mark();

@@ -8,12 +8,6 @@
 #include "runtime.h"
 #include "../../include/ld_mi355x.h"
 
-#ifdef LD_AB_BUILD
-// A/B build only: executor-level switches for same-process A/B timing (tools/ab_unet.py); bit 0: no MLP-out fold
-static int g_unet_dbg = 0;
-extern "C" void ld_debug_unet_flags(int bits) { g_unet_dbg = bits; }
-#endif
-
 namespace {
 
 struct ResW {
@@ -380,9 +374,6 @@ struct Run {
         if (r.sk_w >= 0) {
             GemmParams probe = conv_params(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, nullptr, 0, nullptr, out);
             fold_skip = u->ln_fold && u->fold_base != nullptr && ex.conv_takes_skip_segment(probe);
-#ifdef LD_AB_BUILD
-            if (g_unet_dbg & 8) fold_skip = false;
-#endif
             half_t* sk = (!fold_skip || ex.dry) ? ar.halfs(M * r.cout) : nullptr;   // (a planning run sizes for either route: ld_unet_reserve plans before the split-K scratch exists)
             if (!fold_skip) {
                 conv3(x1, C1, x2, C2, H, W, H, W, 1, r.sk_w, r.sk_b, r.cout, nullptr, 0, nullptr, sk, nullptr, nullptr, 1);
@@ -547,11 +538,7 @@ struct Run {
             if (fold) ln_args(p, s.f_ff1_s);
             ex.gemm(p);
         }
-#ifdef LD_AB_BUILD
-        if (fold && !(g_unet_dbg & 1)) {
-#else
         if (fold) {
-#endif
             // out = x + proj_out(t + ff2(ff)) as one contraction over [ff | t] (K = 5C) against the folded [Wpo W2 | Wpo] (misc.hip)
             GemmParams p;
             p.conv = 1; p.ksize = 1;
@@ -636,9 +623,6 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     ex.splitk_ws = u->splitk_ws;
     ex.splitk_bytes = u->splitk_bytes;
     ex.sync_ws = u->sync_ws;
-#ifdef LD_AB_BUILD
-    ex.ab_flags = g_unet_dbg;
-#endif
     if (u->want_timing && !dry) {
         u->timing.reset();
         ex.timing = &u->timing;

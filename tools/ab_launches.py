@@ -1,6 +1,7 @@
-"""Per-launch A/B of the contraction dispatch inside the real UNet forward (A/B build): the forward is profiled launch by launch
-(ld_unet_profile + LD_PROFILE_DUMP) once per ld_debug_gemm_no_v5 flag set, and the launches are joined by position.
-Usage: python tools/ab_launches.py [batch=8] [flag sets, default "0 1 2 3 8 16"]   (1 no v5, 2 no v6, 8 no v7, 16 GEGLU not on v7)"""
+"""Per-launch A/B of the contraction tile height inside the real UNet forward (A/B build): the forward is profiled launch by launch
+(ld_unet_profile + LD_PROFILE_DUMP) once per setting, and the launches are joined by position.
+Usage: python tools/ab_launches.py [batch=8] [settings, default "0 1064 1128"]   (0 automatic; 1064 / 1128: tile height 64 / 128 forced on the
+128 x 160 family through ld_debug_gemm_override)"""
 import collections, os, re, sys, tempfile
 import torch
 sys.path.insert(0, '.')
@@ -10,7 +11,9 @@ from lightdiffusion_amd import weights as W
 from lightdiffusion_amd._lib import lib
 from lightdiffusion_amd.unet import synthetic_unet
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-sets = [int(a) for a in sys.argv[2:]] or [0, 1, 2, 3, 8, 16]
+sets = [int(a) for a in sys.argv[2:]] or [0, 1064, 1128]
+if any(f not in (0, 1064, 1128) for f in sets):
+    sys.exit("settings: 0, 1064 or 1128")
 hw = int(os.environ.get("AB_HW", "64"))
 L = lib()
 u = synthetic_unet(W.sd15_unet_config(), max_batch=2 * B, max_hw=(hw, hw))
@@ -18,9 +21,7 @@ u.set_context(torch.randn(2 * B, 77, 768))
 x = torch.randn(2 * B, 4, hw, hw, device='cuda'); s = torch.full((2 * B,), 3.0, device='cuda')
 runs = {}
 for f in sets:
-    tile = f in (1064, 1128)                                      # 1064 / 1128: force tile height 64 / 128 on the 128 x 160 family; anything else: ld_debug_gemm_no_v5 bits
-    L.ld_debug_gemm_no_v5(0 if tile else f)
-    L.ld_debug_gemm_override(f - 1000 if tile else 0, 0)
+    L.ld_debug_gemm_override(f - 1000 if f else 0, 0)
     for _ in range(2): u.forward(x, s)
     torch.cuda.synchronize()
     best = None
@@ -40,7 +41,6 @@ for f in sets:
         if best is None: best = rows
         else: best = [(min(a[0], b[0]),) + a[1:] for a, b in zip(best, rows)]
     runs[f] = best
-L.ld_debug_gemm_no_v5(0)
 L.ld_debug_gemm_override(0, 0)
 n = len(runs[sets[0]])
 agg = collections.OrderedDict()
@@ -53,7 +53,7 @@ for i in range(n):
     for f in sets:
         a["t"][f] += runs[f][i][0]
         a["k"][f].add(runs[f][i][6].split("_kernel")[0].replace("gemm", "g").replace("conv", "c") + ("+sk" if "splitk" in runs[f][i][6] else ""))
-print(f"B={B} hw={hw}; per-shape total us per forward under each flag set (kernel in brackets); * = best")
+print(f"B={B} hw={hw}; per-shape total us per forward under each setting (kernel in brackets); * = best")
 tot = {f: 0.0 for f in sets}
 for key, a in sorted(agg.items(), key=lambda kv: -kv[1]["t"][sets[0]]):
     bestf = min(sets, key=lambda f: a["t"][f])
