@@ -201,6 +201,10 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
 /* bislerp (LD.py:429-518, LatentUpscale.upscale 6639-6654): fp32 NCHW latents [n][c][h][w] -> [n][c][h_new][w_new];
  * tmp: n*c*h*w_new floats of scratch (the width pass runs first, as in the reference) */
 int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, void* stream);
+/* The contraction kernel instantiations (GEMM / convolution / attention, the names the profile tables use) that the calling thread's
+ * last ld_op_* call dispatched, in launch order, joined with ';' (e.g. "gemm3_kernel<64,160,conv>+splitk_reduce_kernel").  Reset at
+ * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call. */
+const char* ld_op_last_kernel(void);
 
 #ifdef __cplusplus
 }

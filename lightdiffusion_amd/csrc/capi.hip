@@ -1,5 +1,7 @@
 // Single-operator entry points of the C ABI (include/ld_mi355x.h) — thin, argument-checked wrappers over the
 // kernel launchers; used by the parity tests and by hosts that want to compose their own graphs.
+#include <string>
+
 #include "kernels.h"
 #include "../../include/ld_mi355x.h"
 
@@ -7,11 +9,26 @@ namespace {
 // scratch for ld_op_linear's GEGLU path: the op takes weights in checkpoint row order, the kernel wants them
 // tile-interleaved, so the op repacks into caller-provided workspace
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// ld_op_last_kernel: the contraction instantiations the calling thread's last ld_op_* call dispatched, in launch order, joined with ';'
+thread_local std::string t_op_kernels;
+inline void op_begin() { t_op_kernels.clear(); }
+inline int noted(int st, const char* name) {   // (the launchers reset their name on entry: empty = nothing was dispatched)
+    if (name != nullptr && *name != '\0') {
+        if (!t_op_kernels.empty()) t_op_kernels += ';';
+        t_op_kernels += name;
+    }
+    return st;
+}
+inline int gemm_op(const GemmParams& p, hipStream_t s) { return noted(gemm_launch(p, s), gemm_last_kernel_name()); }
+inline int attn_op(const AttnParams& a, hipStream_t s) { return noted(attention_launch(a, s), attention_last_kernel_name()); }
 }  // namespace
 
 extern "C" {
 
 const char* ld_version(void) { return "ld_mi355x 0.1 (gfx950)"; }
+
+const char* ld_op_last_kernel(void) { return t_op_kernels.c_str(); }
 
 const char* ld_status_string(int s) {
     switch (s) {
@@ -26,6 +43,7 @@ const char* ld_status_string(int s) {
 
 int ld_op_linear(const void* x, const void* w, const void* bias, const void* residual, void* y, int M, int N, int K, float alpha,
                  int act, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
     hipStream_t stream = (hipStream_t)stream_;
     GemmParams p;
     p.A = (const half_t*)x; p.lda = K;
@@ -59,7 +77,7 @@ int ld_op_linear(const void* x, const void* w, const void* bias, const void* res
     p.partial = (float*)wsp;
     p.partial_bytes = ws ? ws_bytes : 0;
     if (ws == nullptr) p.partial = nullptr;
-    return gemm_launch(p, stream);
+    return gemm_op(p, stream);
 }
 
 static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
@@ -104,28 +122,34 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
             if (hipMemsetAsync(ws, 0, sync_b, (hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
             const int st = conv8_repack_launch((const half_t*)wt, cout, c1 + c2, (half_t*)((char*)ws + sync_b), (hipStream_t)stream);
             if (st != LD_OK) return st;
-            return gemm_launch(c8, (hipStream_t)stream);
+            return gemm_op(c8, (hipStream_t)stream);
         }
     }
-    return gemm_launch(p, (hipStream_t)stream);
+    return gemm_op(p, (hipStream_t)stream);
 }
 
 int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
                const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
                size_t ws_bytes, void* stream) {
+    op_begin();
     return op_conv(x1, c1, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, rowvec, residual, y, cout, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
-size_t ld_op_conv_gn_partials_floats(int n, int hw) { return groupnorm_workspace_bytes(n, hw) / sizeof(float); }
+size_t ld_op_conv_gn_partials_floats(int n, int hw) {
+    op_begin();
+    return groupnorm_workspace_bytes(n, hw) / sizeof(float);
+}
 
 int ld_op_conv_gn_partials(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* bias, const void* residual,
                            void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+    op_begin();
     if (part == nullptr || chunks == nullptr) return LD_ERR_ARG;
     *chunks = 0;
     return op_conv(x, c, nullptr, 0, n, h, w, hv, wv, 1, 3, wt, bias, nullptr, residual, y, cout, ws, ws_bytes, stream, part, chunks);
 }
 
 size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int cout) {
+    op_begin();
     const size_t C = (size_t)c1 + c2, HW = (size_t)h * w;
     return align256(groupnorm_workspace_bytes(n, (int)HW)) + 2 * align256((size_t)n * C * sizeof(float)) + align256((size_t)n * HW * C * sizeof(half_t)) +
            align256(LD_SYNC_INTS * sizeof(int)) + (conv8_weight_eligible(cout, c1 + c2) ? align256(conv8_weight_bytes(cout, c1 + c2)) : 0) + ((size_t)96 << 20);
@@ -134,6 +158,7 @@ size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int co
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
                          const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws, size_t ws_bytes,
                          void* stream_) {
+    op_begin();
     // GroupNorm(32) + SiLU + 3x3 convolution (stride 1, pad 1): the reference's ResBlock1.in_layers / out_layers (LD.py:5224-5262).
     // On the halo-tile kernel with one N tile the normalisation is fused into the convolution's A operand; otherwise two-pass GroupNorm, then the conv.
     if (x1 == nullptr || gamma == nullptr || beta == nullptr || wt == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
@@ -167,7 +192,7 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
                                               scale, shift, stream);
         if (st != LD_OK) return st;
         p.gn_scale = scale; p.gn_shift = shift; p.gn_silu = 1;
-        return gemm_launch(p, stream);
+        return gemm_op(p, stream);
     }
     int st = groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, 1, g, part, stream);
     if (st != LD_OK) return st;
@@ -178,15 +203,17 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
         st = conv8_repack_launch((const half_t*)wt, cout, C, w8, stream);   // (per call here; the UNet executor keeps the copy resident)
         if (st != LD_OK) return st;
     }
-    return gemm_launch(p, stream);
+    return gemm_op(p, stream);
 }
 
 size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout) {
+    op_begin();
     return align256((size_t)cout * (9 * (size_t)c + sc1 + sc2) * sizeof(half_t)) + align256((size_t)cout * sizeof(half_t)) + ((size_t)96 << 20);
 }
 
 int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
                     const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
     if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
     if (ws_bytes < ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout)) return LD_ERR_ARG;
@@ -208,38 +235,46 @@ int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, c
     p.rowvec = (const half_t*)rowvec; p.rows_per_vec = h * w; p.ldrv = cout;
     p.C = (half_t*)y; p.ldc = cout;
     p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
-    return gemm_launch(p, stream);
+    return gemm_op(p, stream);
 }
 
 int ld_op_repack_conv(const void* src, int dtype, int cout, int cin, void* dst, void* stream) {
+    op_begin();
     return repack_conv3x3_launch(src, dtype == LD_F32, cout, cin, (half_t*)dst, (hipStream_t)stream);
 }
 
-size_t ld_op_groupnorm_ws_bytes(int n, int hw) { return groupnorm_workspace_bytes(n, hw); }
+size_t ld_op_groupnorm_ws_bytes(int n, int hw) {
+    op_begin();
+    return groupnorm_workspace_bytes(n, hw);
+}
 
 int ld_op_groupnorm(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
                     int silu, void* y, void* ws, void* stream) {
+    op_begin();
     return groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps,
                             silu, (half_t*)y, (float*)ws, (hipStream_t)stream);
 }
 
 int ld_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int c, float eps, void* stream) {
+    op_begin();
     return layernorm_launch((const half_t*)x, (const half_t*)gamma, (const half_t*)beta, (half_t*)y, rows, c, eps, (hipStream_t)stream);
 }
 
 int ld_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int b, int heads,
                     int lq, int lk, int d, float scale, int causal, void* stream) {
+    op_begin();
     AttnParams a;
     a.Q = (const half_t*)q; a.ldq = ldq; a.sQ = (long long)lq * ldq;
     a.K = (const half_t*)k; a.ldk = ldk; a.sK = (long long)lk * ldk;
     a.Vt = (const half_t*)vt; a.ldvt = ldvt; a.sV = (long long)heads * d * ldvt;
     a.O = (half_t*)o; a.ldo = ldo; a.sO = (long long)lq * ldo;
     a.B = b; a.H = heads; a.Lq = lq; a.Lk = lk; a.d = d; a.scale = scale; a.causal = causal;
-    return attention_launch(a, (hipStream_t)stream);
+    return attn_op(a, (hipStream_t)stream);
 }
 
 int ld_op_attention_rowv(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int b, int heads,
                          int lq, int lk, int d, float scale, int causal, void* stream) {
+    op_begin();
     // q, k, v as column blocks of one fused [b][l][ldq] tensor (ldq == ldk == ldv with overlapping row ranges) share ONE batch stride,
     // which the per-operand strides below only reproduce when lq == lk
     const char *qb = (const char*)q, *kb = (const char*)k, *vb = (const char*)v;
@@ -252,32 +287,38 @@ int ld_op_attention_rowv(const void* q, int ldq, const void* k, int ldk, const v
     a.V = (const half_t*)v; a.ldv = ldv; a.sV = (long long)lk * ldv;
     a.O = (half_t*)o; a.ldo = ldo; a.sO = (long long)lq * ldo;
     a.B = b; a.H = heads; a.Lq = lq; a.Lk = lk; a.d = d; a.scale = scale; a.causal = causal;
-    return attention_launch(a, (hipStream_t)stream);
+    return attn_op(a, (hipStream_t)stream);
 }
 
 int ld_op_softmax_rows(void* s, int rows, int cols, void* stream) {
+    op_begin();
     return softmax_rows_launch((half_t*)s, rows, cols, cols, (hipStream_t)stream);
 }
 
 int ld_op_timestep_embed(const float* sigma, const float* log_sigmas, int n_sigmas, int n, int dim, void* out, float* t_out, void* stream) {
+    op_begin();
     return timestep_embed_launch(sigma, log_sigmas, n_sigmas, n, dim, (half_t*)out, t_out, (hipStream_t)stream);
 }
 
 int ld_op_cfg_combine(const float* den2, float* out, float cfg, size_t n_half, void* stream) {
+    op_begin();
     return cfg_combine_launch(den2, out, cfg, n_half, (hipStream_t)stream);
 }
 
 int ld_op_hook_check(const void* a, const void* b, size_t words_ab, const void* x, size_t half_words_x, const void* sigma, int half_sigma,
                      int* flags, int epoch, void* stream) {
+    op_begin();
     return hook_check_launch(a, b, words_ab, x, half_words_x, sigma, half_sigma, flags, epoch, (hipStream_t)stream);
 }
 
 int ld_op_axpby(float* x, float a, const float* y, float b, const float* z, float c, size_t n, void* stream) {
+    op_begin();
     return axpby_launch(x, a, y, b, z, c, n, (hipStream_t)stream);
 }
 
 int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
                     const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
     // the UNet's LayerNorm fold (unet.hip, gemm.h) as a stand-alone operator pair, for parity tests:
     //   t = x · w_prod^T + b_prod         (producer: also emits per-row (sum, sum of squares) partials of the fp16 t)
     //   y = LayerNorm(t; gamma, beta, eps) · w^T + bias   computed as rstd * (t · W'^T - mu * wsum) + b' on the accumulators
@@ -304,7 +345,7 @@ int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const
     a.bias_n = (const half_t*)b_prod;
     a.C = (half_t*)t_out; a.ldc = C;
     a.stat_out = stat; a.stat_parts_out = &parts;
-    st = gemm_launch(a, stream);
+    st = gemm_op(a, stream);
     if (st != LD_OK) return st;
     GemmParams b;
     b.A = (const half_t*)t_out; b.lda = C;
@@ -315,11 +356,12 @@ int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const
     b.ln_stat = stat; b.ln_parts = parts; b.ln_rows = M;
     b.ln_inv_c = 1.0f / (float)C; b.ln_eps = eps;
     b.ln_wsum = wsum;
-    return gemm_launch(b, stream);
+    return gemm_op(b, stream);
 }
 
 int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
                           const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
     // the transformer block's MLP input as the executor runs it (unet.hip): t = x · w_prod^T + b_prod with row statistics, then
     //   y[M][N/2] = a * gelu(g),  [a | g] = LayerNorm(t) · w^T + bias     (GEGLU, LD.py:4513-4515, on the LayerNorm-folded weights)
     // w rows are repacked into the tile-interleaved [value | gate] order first, then folded (the fold is row-wise).
@@ -352,7 +394,7 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
     a.bias_n = (const half_t*)b_prod;
     a.C = (half_t*)t_out; a.ldc = C;
     a.stat_out = stat; a.stat_parts_out = &parts;
-    st = gemm_launch(a, stream);
+    st = gemm_op(a, stream);
     if (st != LD_OK) return st;
     GemmParams b;
     b.A = (const half_t*)t_out; b.lda = C;
@@ -364,10 +406,11 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
     b.ln_stat = stat; b.ln_parts = parts; b.ln_rows = M;
     b.ln_inv_c = 1.0f / (float)C; b.ln_eps = eps;
     b.ln_wsum = wsum;
-    return gemm_launch(b, stream);
+    return gemm_op(b, stream);
 }
 
 int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, void* stream) {
+    op_begin();
     return bislerp_launch(x, tmp, y, n, c, h, w, h_new, w_new, (hipStream_t)stream);
 }
 

@@ -2468,6 +2468,7 @@ void launch_cfg(const GemmParams& p, hipStream_t s, bool deep = false, bool conv
         t_last_kernel = name.c_str();
         if constexpr (BM == 64 && BN == 160) {
             if (deep) {   // 4-stage ring, one workgroup per CU (three slabs in flight): see the rule in gemm_launch
+                t_last_kernel = "gemm3_kernel<64,160,conv,deep>";
                 hipLaunchKernelGGL((gemm3_kernel<BM, BN, true, 4>), grid, dim3(NT), 0, s, p);
                 return;
             }
@@ -2639,6 +2640,7 @@ bool gemm_conv_fuses_groupnorm(const GemmParams& p) {
 
 int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     GemmParams p = pin;
+    t_last_kernel = "";   // nothing dispatched until a route below names its kernel
 #ifdef LD_AB_BUILD
     if (g_force_bm) p.bm = g_force_bm;
     if (g_force_sk) p.splitk = g_force_sk;
@@ -2727,11 +2729,11 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
         dim3 grid((unsigned)((p.M + V7_BM - 1) / V7_BM), 1, 1);
         const bool ln = p.ln_stat != nullptr;
         if (p.act == 2) {
-            t_last_kernel = "gemm7_kernel<256,K320,geglu>";
+            t_last_kernel = ln ? "gemm7_kernel<256,K320,geglu,ln>" : "gemm7_kernel<256,K320,geglu>";
             if (ln) hipLaunchKernelGGL((gemm7_kernel<true, true>), grid, dim3(512), 0, stream, p);
             else hipLaunchKernelGGL((gemm7_kernel<true, false>), grid, dim3(512), 0, stream, p);
         } else {
-            t_last_kernel = "gemm7_kernel<256,K320,plain>";
+            t_last_kernel = ln ? "gemm7_kernel<256,K320,plain,ln>" : "gemm7_kernel<256,K320,plain>";
             if (ln) hipLaunchKernelGGL((gemm7_kernel<false, true>), grid, dim3(512), 0, stream, p);
             else hipLaunchKernelGGL((gemm7_kernel<false, false>), grid, dim3(512), 0, stream, p);
         }
@@ -2763,7 +2765,7 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
                     t_last_kernel = "gemm5_kernel<256,320,conv>";
                     hipLaunchKernelGGL((gemm5_kernel<true, 0>), grid, dim3(512), 0, stream, p);
                 } else {
-                    t_last_kernel = "gemm5_kernel<256,320,plain>";
+                    t_last_kernel = p.act == 2 ? "gemm5_kernel<256,320,geglu>" : ln ? "gemm5_kernel<256,320,lnfold>" : "gemm5_kernel<256,320,plain>";
                     {   // XCD-blocked tile order (see the kernel): the split of the 8 XCDs over (M, N) that moves the fewest bytes, A once per
                         // N group and W once per M group
                         const int tm5 = (p.M + V5_BM - 1) / V5_BM, tn5 = p.N / V5_BN;

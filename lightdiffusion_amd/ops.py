@@ -26,6 +26,12 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def last_kernel() -> str:
+    """The kernel instantiations the last operator call on this thread dispatched, in launch order, joined with ';' ("" when it
+    dispatched no GEMM / convolution / attention kernel) — the names of the profile tables."""
+    return lib().ld_op_last_kernel().decode()
+
+
 _WS = {}
 
 
@@ -34,17 +40,20 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     operator seam is also the CLIP path (60+ calls per prompt), so no per-call allocation.  Reuse is stream-ordered — every op
     that takes the buffer runs on the stream the buffer is keyed by and is done with it when the next one starts — so ops
     issued on two streams never share slabs.  Under hipGraph capture nothing is cached: a buffer first grown there would live in
-    the graph's private pool (and a cached pointer baked into a graph would race with eager ops), so capture allocates per call."""
+    the graph's private pool (and a cached pointer baked into a graph would race with eager ops), so capture allocates per call.
+    The result is always exactly max(nbytes, 256) bytes long, a view of the cached buffer: the kernels size their split over K by the
+    scratch they are handed, so an op's route and its bits must not depend on how far earlier ops happened to grow the cache."""
     d = torch.device(device)
     idx = d.index if d.index is not None else torch.cuda.current_device()
+    n = max(nbytes, 256)
     if torch.cuda.is_current_stream_capturing():
-        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return torch.empty(n, dtype=torch.uint8, device=device)
     key = (idx, torch.cuda.current_stream(idx).cuda_stream)
     buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    if buf is None or buf.numel() < n:
+        buf = torch.empty(n, dtype=torch.uint8, device=device)
         _WS[key] = buf
-    return buf
+    return buf[:n]
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,

@@ -17,10 +17,12 @@ def short_name(k):
     m = re.match(r"gemm(\d)_kernel<(\d+), (\d+), (true|false)(?:, (\d+))?(?:, (\d+))?>", k)
     if m:   # (gemm4's trailing parameters: ring depth, waves per SIMD — 4 = the two-workgroups-per-CU instantiation gemm_launch names ",2wg")
         two = m.group(1) == "4" and m.group(6) == "4"
-        return f"gemm{m.group(1)}_kernel<{m.group(2)},{m.group(3)},{'conv' if m.group(4) == 'true' else 'plain'}{',2wg' if two else ''}>"
-    m = re.match(r"gemm5_kernel<(true|false)(?:, \d+)?>", k)
+        deep = m.group(1) == "3" and m.group(5) == "4"   # (gemm3's 4-stage ring: gemm_launch names it ",deep")
+        return f"gemm{m.group(1)}_kernel<{m.group(2)},{m.group(3)},{'conv' if m.group(4) == 'true' else 'plain'}{',2wg' if two else ''}{',deep' if deep else ''}>"
+    m = re.match(r"gemm5_kernel<(true|false)(?:, (\d+))?>", k)
     if m:
-        return f"gemm5_kernel<256,320,{'conv' if m.group(1) == 'true' else 'plain'}>"
+        epi = {"1": "lnfold", "2": "geglu"}.get(m.group(2), "plain")
+        return f"gemm5_kernel<256,320,{'conv' if m.group(1) == 'true' else epi}>"
     m = re.match(r"conv6_kernel<(\d+), (true|false)(?:, (\d+))?(?:, (\d+))?(?:, (true|false))?>", k)
     if m:   # the names gemm_launch gives its instantiations (bench.py prints those)
         w, gn, bn, bm, up = m.group(1), m.group(2) == "true", m.group(3) or "320", m.group(4) or "256", m.group(5) == "true"
@@ -30,9 +32,9 @@ def short_name(k):
         elif bn != "320":
             tail = f",{bn}"
         return f"conv6_kernel<W{w},{'halo+groupnorm' if gn else 'halo'}{tail}{',up' if up else ''}>"
-    m = re.match(r"gemm7_kernel<(true|false)(?:, (?:true|false))?>", k)
+    m = re.match(r"gemm7_kernel<(true|false)(?:, (true|false))?>", k)
     if m:
-        return f"gemm7_kernel<256,K320,{'geglu' if m.group(1) == 'true' else 'plain'}>"
+        return f"gemm7_kernel<256,K320,{'geglu' if m.group(1) == 'true' else 'plain'}{',ln' if m.group(2) == 'true' else ''}>"
     m = re.match(r"flash_attn2_kernel<(\d+), (true|false), (\d+), \d+(?:, (true|false))?>", k)
     if m:
         return f"flash_attn2_kernel<{m.group(1)}{',rowV' if m.group(4) == 'true' else ''},{'masked' if m.group(2) == 'true' else 'plain'},{m.group(3)}>"
