@@ -21,6 +21,29 @@ inline int noted(int st, const char* name) {   // (the launchers reset their nam
     return st;
 }
 inline int gemm_op(const GemmParams& p, hipStream_t s) { return noted(gemm_launch(p, s), gemm_last_kernel_name()); }
+inline int gemm_op(const GemmParams& p, const GemmPlan& plan, hipStream_t s) { return noted(gemm_run(p, plan, s), gemm_last_kernel_name()); }
+
+// The row-resident kernel (conv8.hip) from a caller's scratch: the head of the region holds the counters of its in-launch reduction and,
+// where the shape can have one, a copy of the weights in its layout; the split partials take what is left.
+constexpr size_t kSyncBytes = LD_SYNC_INTS * sizeof(int);
+inline size_t conv8_scratch_head(int cout, int cin) { return kSyncBytes + (conv8_weight_eligible(cout, cin) ? align256(conv8_weight_bytes(cout, cin)) : 0); }
+inline void conv8_scratch(GemmParams& p, void* ws, size_t partial_bytes) {
+    const int cin = p.C1 + p.C2;
+    p.sync = (int*)ws;
+    p.W8 = conv8_weight_eligible(p.N, cin) ? (const half_t*)((char*)ws + kSyncBytes) : nullptr;
+    p.partial = (float*)((char*)ws + conv8_scratch_head(p.N, cin));
+    p.partial_bytes = partial_bytes;
+}
+// launch p (laid out by conv8_scratch) by its plan; in front of the row-resident kernel, zero the counters (a caller's scratch: not known
+// to be zero) and repack the weights (per call here; the UNet executor keeps that copy resident)
+inline int conv8_scratch_op(const GemmParams& p, const GemmPlan& plan, const void* wt, hipStream_t stream) {
+    if (plan.route == GR_CONV8) {
+        if (hipMemsetAsync(p.sync, 0, kSyncBytes, stream) != hipSuccess) return LD_ERR_HIP;
+        const int st = conv8_repack_launch((const half_t*)wt, p.N, p.C1 + p.C2, const_cast<half_t*>(p.W8), stream);
+        if (st != LD_OK) return st;
+    }
+    return gemm_op(p, plan, stream);
+}
 inline int attn_op(const AttnParams& a, hipStream_t s) { return noted(attention_launch(a, s), attention_last_kernel_name()); }
 }  // namespace
 
@@ -108,22 +131,12 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
     p.C = (half_t*)y; p.ldc = cout;
     p.partial = (float*)ws;
     p.partial_bytes = ws ? ws_bytes : 0;
-    constexpr size_t sync_b = LD_SYNC_INTS * sizeof(int);
-    if (ws != nullptr && ksize == 3 && conv8_weight_eligible(cout, c1 + c2) && ws_bytes > sync_b + align256(conv8_weight_bytes(cout, c1 + c2)) + ((size_t)8 << 20)) {
-        // row-resident kernel (conv8.hip): the head of a roomy scratch buffer holds the (zeroed) counters of its in-launch reduction and a
-        // copy of the weights in its layout, made per call here (the UNet executor keeps that copy resident)
+    const size_t head = conv8_scratch_head(cout, c1 + c2);
+    if (ws != nullptr && ksize == 3 && conv8_weight_eligible(cout, c1 + c2) && ws_bytes > head + ((size_t)8 << 20)) {
+        // a roomy scratch buffer: the row-resident kernel where it takes the shape; the general kernels keep the whole buffer for their split
         GemmParams c8 = p;
-        const size_t w8b = align256(conv8_weight_bytes(cout, c1 + c2));
-        c8.sync = (int*)ws;
-        c8.W8 = (const half_t*)((char*)ws + sync_b);
-        c8.partial = (float*)((char*)ws + sync_b + w8b);
-        c8.partial_bytes = ws_bytes - sync_b - w8b;
-        if (conv8_plan(c8, nullptr)) {
-            if (hipMemsetAsync(ws, 0, sync_b, (hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
-            const int st = conv8_repack_launch((const half_t*)wt, cout, c1 + c2, (half_t*)((char*)ws + sync_b), (hipStream_t)stream);
-            if (st != LD_OK) return st;
-            return gemm_op(c8, (hipStream_t)stream);
-        }
+        conv8_scratch(c8, ws, ws_bytes - head);
+        if (const GemmPlan plan = gemm_plan(c8); plan.route == GR_CONV8) return conv8_scratch_op(c8, plan, wt, (hipStream_t)stream);
     }
     return gemm_op(p, (hipStream_t)stream);
 }
@@ -152,7 +165,7 @@ size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int co
     op_begin();
     const size_t C = (size_t)c1 + c2, HW = (size_t)h * w;
     return align256(groupnorm_workspace_bytes(n, (int)HW)) + 2 * align256((size_t)n * C * sizeof(float)) + align256((size_t)n * HW * C * sizeof(half_t)) +
-           align256(LD_SYNC_INTS * sizeof(int)) + (conv8_weight_eligible(cout, c1 + c2) ? align256(conv8_weight_bytes(cout, c1 + c2)) : 0) + ((size_t)96 << 20);
+           conv8_scratch_head(cout, c1 + c2) + ((size_t)96 << 20);
 }
 
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
@@ -170,12 +183,6 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
     float* scale = (float*)q; q += align256((size_t)n * C * sizeof(float));
     float* shift = (float*)q; q += align256((size_t)n * C * sizeof(float));
     half_t* g = (half_t*)q; q += align256((size_t)n * HW * C * sizeof(half_t));
-    int* sync = (int*)q; q += align256(LD_SYNC_INTS * sizeof(int));
-    half_t* w8 = nullptr;
-    if (conv8_weight_eligible(cout, C)) {
-        w8 = (half_t*)q;
-        q += align256(conv8_weight_bytes(cout, C));
-    }
     GemmParams p;
     p.conv = 1; p.ksize = 3;
     p.A = (const half_t*)x1; p.A2 = (const half_t*)x2; p.C1 = c1; p.C2 = c2;
@@ -186,24 +193,19 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
     p.rowvec = (const half_t*)rowvec; p.rows_per_vec = HW; p.ldrv = cout;
     p.R = (const half_t*)residual; p.ldr = cout;
     p.C = (half_t*)y; p.ldc = cout;
-    p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
-    if (gemm_conv_fuses_groupnorm(p)) {
+    conv8_scratch(p, q, (size_t)96 << 20);
+    const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
+    if (fused.can_fuse_groupnorm) {
         int st = groupnorm_scale_shift_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, part,
                                               scale, shift, stream);
         if (st != LD_OK) return st;
         p.gn_scale = scale; p.gn_shift = shift; p.gn_silu = 1;
-        return gemm_op(p, stream);
+        return gemm_op(p, fused, stream);
     }
     int st = groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, 1, g, part, stream);
     if (st != LD_OK) return st;
     p.A = g; p.A2 = nullptr; p.C1 = C; p.C2 = 0;
-    p.sync = sync; p.W8 = w8;
-    if (conv8_plan(p, nullptr)) {   // row-resident kernel (conv8.hip) on the normalised tensor: zeroed counters and its own weight layout
-        if (hipMemsetAsync(sync, 0, LD_SYNC_INTS * sizeof(int), stream) != hipSuccess) return LD_ERR_HIP;   // (a caller's scratch: not known to be zero)
-        st = conv8_repack_launch((const half_t*)wt, cout, C, w8, stream);   // (per call here; the UNet executor keeps the copy resident)
-        if (st != LD_OK) return st;
-    }
-    return gemm_op(p, stream);
+    return conv8_scratch_op(p, gemm_plan(p), (const half_t*)wt, stream);   // (the row-resident kernel takes the normalised tensor)
 }
 
 size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout) {
@@ -325,7 +327,6 @@ int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const
     if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || t_out == nullptr || y == nullptr ||
         ws == nullptr)
         return LD_ERR_ARG;
-    if (!gemm_ln_fold_available()) return LD_ERR_STATE;
     hipStream_t stream = (hipStream_t)stream_;
     const size_t wb = align256((size_t)N * C * sizeof(half_t)), bb = align256((size_t)N * sizeof(half_t)), sb = align256((size_t)N * sizeof(float));
     const size_t stb = align256((size_t)((C + 63) / 64) * M * 2 * sizeof(float));
@@ -368,7 +369,6 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
     if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || bias == nullptr || t_out == nullptr ||
         y == nullptr || ws == nullptr)
         return LD_ERR_ARG;
-    if (!gemm_ln_fold_available()) return LD_ERR_STATE;
     hipStream_t stream = (hipStream_t)stream_;
     const int bn = gemm_pick_bn(N);
     if ((N & 15) || (N % bn)) return LD_ERR_SHAPE;

@@ -577,6 +577,7 @@ int conv8_repack_launch(const half_t* w, int N, int Cin, half_t* dst, hipStream_
 }
 
 // Does this convolution run on the row-resident kernel?  Fills the slab split.  (The caller provides p.W8, p.partial and p.sync.)
+// Asked by gemm_plan, once per launch.
 bool conv8_plan(const GemmParams& p, int* S_out) {
     if (!(p.conv && p.ksize == 3 && p.stride == 1 && (p.pad < 0 || p.pad == 1) && p.batch == 1 && p.act == 0 && p.alpha == 1.0f && p.bias_m == nullptr &&
           p.bm == 0 && p.bn == 0 && p.splitk == 0 && p.W8 != nullptr && p.partial != nullptr && p.sync != nullptr && p.stat_out == nullptr && p.ln_stat == nullptr))
@@ -609,25 +610,12 @@ bool conv8_plan(const GemmParams& p, int* S_out) {
     while (S > 1 && (size_t)S * p.M * p.N * sizeof(float) > p.partial_bytes) --S;
     if (S < 1 || (size_t)p.M * p.N * sizeof(float) > p.partial_bytes) return false;
     if (tiles * S < 96) return false;
-    if (S_out) *S_out = S;
-    return true;
-}
-
-// number of pixel chunks per image of the GroupNorm partials the kernel emits (GemmParams::gn_part) for this shape
-int conv8_gn_chunks(const GemmParams& p) { return p.Wo * p.Wo / 16; }
-
-int conv8_launch(const GemmParams& pin, hipStream_t stream) {
-    GemmParams p = pin;
-    int S = 0;
-    if (!conv8_plan(p, &S)) return LD_ERR_ARG;
 #ifdef LD_AB_BUILD
     {   // slab-count sweep (tools/conv8_slab_sweep.py): LD_C8_S_W<width> = number of channel slabs per tile for that image width
         static const char* names[4] = {"LD_C8_S_W8", "LD_C8_S_W16", "LD_C8_S_W32", "LD_C8_S_W64"};
         const char* e = getenv(names[p.Wo == 8 ? 0 : p.Wo == 16 ? 1 : p.Wo == 32 ? 2 : 3]);
         if (e != nullptr) {
             int want = atoi(e);
-            const int nsub = (p.C1 + p.C2) / 16;
-            const long long tiles = (long long)(p.M / 128) * (p.N / C8_BN);
             if (want < 1) want = 1;
             if (want > 16) want = 16;                                      // (the reducer's generic path sums up to 16 slabs)
             if (want > nsub / 2) want = nsub / 2;
@@ -637,6 +625,14 @@ int conv8_launch(const GemmParams& pin, hipStream_t stream) {
         }
     }
 #endif
+    *S_out = S;
+    return true;
+}
+
+// the launch gemm_run makes of a convolution conv8_plan accepted, with the slab split it chose
+int conv8_launch(const GemmParams& pin, int S, hipStream_t stream) {
+    GemmParams p = pin;
+    if (S < 1) return LD_ERR_ARG;
     p.c8_S = S;
     p.pad = 1;
 #ifdef LD_AB_BUILD

@@ -19,7 +19,7 @@ struct GemmParams {
     // ---- second K segment of a convolution (tap-major kernels): a 1x1 convolution over up to two RAW NHWC sources of the OUTPUT's spatial
     //   size, appended to the K axis — K = ksize^2 (C1 + C2) + SC1 + SC2, weight rows [conv taps | skip channels].  ResBlock1's
     //   skip_connection folded into out_layers' convolution (LD.py:5267, 5273-5287): out = W2 * gn(h) + Wskip x + (b2 + bskip) is ONE
-    //   contraction; requires stride 1 and no resize.  The halo-tile and row-resident kernels decline it (gemm_conv_takes_skip_segment).
+    //   contraction; requires stride 1 and no resize.  The halo-tile and row-resident kernels decline it (GemmPlan::takes_skip_segment).
     const half_t* S1 = nullptr;
     const half_t* S2 = nullptr;
     int SC1 = 0, SC2 = 0;
@@ -52,7 +52,7 @@ struct GemmParams {
     // ---- LayerNorm folded into the contractions around it (v3 / v4 kernels, no split-K; unet.hip "ln fold"):
     //   producer (the GEMM that writes the residual stream): per output row and N tile, (sum, sum of squares) of the fp16 outputs
     float* stat_out = nullptr;       // [tiles_n][M][2] floats
-    int* stat_parts_out = nullptr;   // host int: gemm_launch stores the number of N tiles (parts) it used
+    int* stat_parts_out = nullptr;   // host int: gemm_run stores GemmPlan::stat_parts, the number of N tiles (parts) it used
     //   consumer (a projection of LN(x), with gamma folded into W and beta into the bias at load time):
     //   out = rstd_row * (acc - mu_row * wsum[n]) + bias'[n]; with ln_swapped the LN rows are this GEMM's COLUMNS (V^T = Wv · x^T)
     const float* ln_stat = nullptr;  // the producer's stat_out
@@ -62,7 +62,7 @@ struct GemmParams {
     float ln_inv_c = 0.f, ln_eps = 0.f;
     const float* ln_wsum = nullptr;  // per output feature: sum_k of the folded weight row ([N], or [M] when ln_swapped)
     int ln_swapped = 0;
-    // ---- GroupNorm(+SiLU) fused into the A operand of the halo-tile convolution (v6 only; see gemm_conv_fuses_groupnorm):
+    // ---- GroupNorm(+SiLU) fused into the A operand of the halo-tile convolution (v6 only; see GemmPlan::can_fuse_groupnorm):
     //   the conv reads the RAW tensor and applies  y = x * scale[img][c] + shift[img][c]  (then SiLU) while the halo sits in LDS
     const float* gn_scale = nullptr;   // [n_img][C1 + C2] fp32: rstd * gamma
     const float* gn_shift = nullptr;   // [n_img][C1 + C2] fp32: beta - mean * rstd * gamma
@@ -82,30 +82,48 @@ struct GemmParams {
     int dbg = 0;                 // A/B build only (LD_AB_BUILD): bit 2 = conv8's lone-reducer route (LD_C8_NO_WAIT); the product leaves it 0
 };
 
-// conv8.hip: row-resident 3x3 convolution for the two-image (batch-1 CFG pair) 16x16 / 8x8 levels.  conv8_plan: does gemm_launch run this
-// convolution there (p.partial and p.sync set)?  conv8_gn_chunks: pixel chunks per image of the GroupNorm partials it writes to gn_part
-// (also stored to *gn_part_done).
+// What gemm_launch does with one GemmParams: decided once by gemm_plan, carried out by gemm_run, read by the callers that
+// need to know before (or after) the launch.  A pure function of the parameters: no HIP call, nothing written through p's pointers.
+enum GemmRoute { GR_NONE = 0, GR_CONV8, GR_CONV6, GR_GEMM7, GR_GEMM5, GR_GEMM3, GR_GEMM4 };   // in the planner's order
+enum GemmReduce { GRD_NONE = 0, GRD_PLAIN, GRD_GROUPNORM };                                    // the split-K second pass
+struct GemmPlan {
+    int status = LD_OK;          // LD_ERR_ARG / LD_ERR_SHAPE: gemm_launch returns it and launches nothing (everything below is unset)
+    int route = GR_NONE;
+    // ---- variants of the route
+    bool conv = false, geglu = false;   // gemm3 / gemm4 / gemm5: the im2col loader; gemm5 / gemm7: the GEGLU epilogue
+    bool gn = false, up = false;        // conv6: GroupNorm (+SiLU) applied in the halo loader (gn_scale / gn_shift); conv6 / conv8: nearest-2x loader
+    bool ln = false;                    // gemm5 / gemm7: the LayerNorm-fold epilogue
+    bool deep = false, two_wg = false;  // gemm3 64 x 160 conv: 4-stage ring, one workgroup per CU; gemm4 64 x 64: two workgroups per CU
+    int bm = 0, bn = 0, wc = 0;         // tile; conv6 / conv8: tile width in pixels
+    int splitk = 1, c8_S = 0;           // slices over K; conv8: channel slabs per tile
+    int m_fastest = 0, xcd_gm = 0;      // gemm3 / gemm4 tile order; gemm5 XCD blocking
+    unsigned grid_x = 0, grid_z = 1;
+    int reduce = GRD_NONE;
+    // ---- what the callers need to know
+    int stat_parts = 0;          // LayerNorm-statistic parts per row the launch writes to stat_out (-> *stat_parts_out)
+    int gn_chunks = 0;           // pixel chunks per image of the GroupNorm partials it writes to gn_part (-> *gn_part_done); 0: none
+    bool halo_tile = false;      // runs on the halo-tile kernel
+    bool can_fuse_groupnorm = false;   // (asked with gn_offer) the halo-tile kernel takes gn_scale / gn_shift here, and the fusion pays
+    bool takes_skip_segment = false;   // a 3x3 convolution on a tap-major kernel (128 x 160 / 256 x 320 implicit GEMM): S1 / S2 can be appended
+    const char* kernel = "";     // profile name of what gemm_run dispatches, the reduce pass included
+};
+// gn_offer: the caller holds a GroupNorm (+SiLU) in front of this 3x3 convolution and sets gn_scale / gn_shift before gemm_run if
+// can_fuse_groupnorm comes back true.  The plan is that of p with both set; where the fusion is not available or does not pay, status is
+// LD_ERR_ARG (gemm_launch's answer to a gn_scale it cannot honour) and the caller plans the convolution of the normalised tensor instead.
+GemmPlan gemm_plan(const GemmParams& p, bool gn_offer = false);
+int gemm_run(const GemmParams& p, const GemmPlan& plan, hipStream_t stream);
+inline int gemm_launch(const GemmParams& p, hipStream_t stream) { return gemm_run(p, gemm_plan(p), stream); }
+const char* gemm_last_kernel_name();   // kernel instantiation the calling thread's last gemm_run dispatched ("" = none)
+
+// conv8.hip: row-resident 3x3 convolution for the two-image (batch-1 CFG pair) 16x16 / 8x8 levels.  conv8_plan: gemm_plan's question whether
+// this convolution runs there (p.W8, p.partial and p.sync set) and with which slab split; conv8_launch: gemm_run's launch with that split.
 bool conv8_plan(const GemmParams& p, int* S_out);
-int conv8_gn_chunks(const GemmParams& p);
-int conv8_launch(const GemmParams& p, hipStream_t stream);
+int conv8_launch(const GemmParams& p, int S, hipStream_t stream);
 // conv8's weight layout: [N / 80][Cin / 16][one 25 600-byte ring-stage image] from the general [O][ky][kx][I] layout
 bool conv8_weight_eligible(int N, int Cin);
 size_t conv8_weight_bytes(int N, int Cin);
 int conv8_repack_launch(const half_t* w_okki, int N, int Cin, half_t* dst, hipStream_t stream);
 #define LD_SYNC_INTS 1024        // ints a caller provides behind GemmParams::sync
 
-bool gemm_ln_fold_available();   // the kernels that implement stat_out / ln_stat are the ones gemm_launch will pick
-const char* gemm_last_kernel_name();   // kernel instantiation the calling thread's last gemm_launch dispatched
-
 // BN the GEGLU weight interleave must use for a projection with N (=2*inner) output rows
 static inline int gemm_pick_bn(int N) { return (N % 160 == 0) ? 160 : 128; }
-
-int gemm_launch(const GemmParams& p, hipStream_t stream);
-// true when gemm_launch would run this convolution on the halo-tile kernel, i.e. when it can take gn_scale / gn_shift
-// (fill every other field first; gemm_launch rejects gn_scale on any other path)
-bool gemm_conv_fuses_groupnorm(const GemmParams& p);
-// does gemm_launch run this 3x3 convolution on a kernel that walks K tap-major (the 128 x 160 / 256 x 320 implicit-GEMM kernels), i.e. one
-// that can take a second K segment (S1 / S2)?  Fill every field (partial, sync, W8 included) as for the launch itself, without the segment.
-bool gemm_conv_takes_skip_segment(const GemmParams& p);
-// does gemm_launch run this convolution on the halo-tile kernel?  (callers that need a property of it: the VAE's MFMA output conv)
-bool gemm_conv_takes_halo_tile(const GemmParams& p);

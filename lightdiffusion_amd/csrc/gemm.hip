@@ -13,6 +13,7 @@
 #include <set>
 #include <string>
 #include <type_traits>
+#include <vector>
 
 #include "gemm.h"
 
@@ -2423,74 +2424,67 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const GemmParams 
 // 768 -> 166.2, 1280 -> 164.8 steps/s)
 constexpr int V4_MAX_BLOCKS = 256;
 
-// name of the kernel instantiation the last gemm_launch on this thread dispatched (ld_unet_profile groups by it)
+// name of the kernel instantiation the last gemm_run on this thread dispatched (ld_unet_profile groups by it)
 thread_local const char* t_last_kernel = "";
-const char* intern_name(const std::string& s) {   // stable storage for composed names (a handful per process)
-    static std::mutex mu;
-    static std::set<std::string> pool;
+
+// the profile name of a plan: composed here and nowhere else, once per distinct plan and thread.  conv6's name says what differs from the
+// 256 x 320 tile: conv6_kernel<W64,halo+groupnorm>, conv6_kernel<W128,halo,128x512>, conv6_kernel<W64,halo,256,up>, ...
+const char* plan_kernel_name(const GemmPlan& pl) {
+    typedef unsigned long long u64;
+    const u64 key = (u64)pl.route | (u64)pl.reduce << 3 | (u64)pl.conv << 5 | (u64)pl.geglu << 6 | (u64)pl.gn << 7 | (u64)pl.up << 8 | (u64)pl.ln << 9 |
+                    (u64)pl.deep << 10 | (u64)pl.two_wg << 11 | (u64)pl.bm << 12 | (u64)pl.bn << 24 | (u64)pl.wc << 36;
+    thread_local std::vector<std::pair<u64, const char*>> seen;   // (a handful per process)
+    for (const auto& e : seen)
+        if (e.first == key) return e.second;
+    const std::string tile = std::to_string(pl.bm) + "," + std::to_string(pl.bn);
+    std::string s;
+    switch (pl.route) {
+        case GR_CONV8: s = "conv8_kernel<W" + std::to_string(pl.wc) + (pl.up ? ",up>" : ">"); break;
+        case GR_CONV6:
+            s = "conv6_kernel<W" + std::to_string(pl.wc) + ",halo" + (pl.gn ? "+groupnorm" : "") +
+                (pl.bn == V5_BN ? "" : "," + std::to_string(pl.bn) + (pl.bm == V5_BM ? "" : "x" + std::to_string(pl.bm))) + (pl.up ? ",up" : "") + ">";
+            break;
+        case GR_GEMM7: s = std::string("gemm7_kernel<256,K320,") + (pl.geglu ? "geglu" : "plain") + (pl.ln ? ",ln>" : ">"); break;
+        case GR_GEMM5: s = std::string("gemm5_kernel<256,320,") + (pl.conv ? "conv" : pl.geglu ? "geglu" : pl.ln ? "lnfold" : "plain") + ">"; break;
+        case GR_GEMM4: s = "gemm4_kernel<" + tile + (pl.conv ? ",conv" : ",plain") + (pl.two_wg ? ",2wg>" : ">"); break;
+        default: s = "gemm3_kernel<" + tile + (pl.conv ? ",conv" : ",plain") + (pl.deep ? ",deep>" : ">"); break;
+    }
+    if (pl.reduce != GRD_NONE) s += pl.reduce == GRD_GROUPNORM ? "+splitk_reduce_gn_kernel" : "+splitk_reduce_kernel";
+    static std::mutex mu; static std::set<std::string> pool;   // stable storage
     std::lock_guard<std::mutex> lock(mu);
-    return pool.insert(s).first->c_str();
+    const char* name = pool.insert(s).first->c_str();
+    seen.push_back({key, name});
+    return name;
 }
 
-// conv1_2wg: gemm_launch's decision to run a 1x1 convolution on 64 x 64 tiles UNSPLIT on the two-workgroups-per-CU producer / consumer kernel
-// (its skinny_conv1 rule and the older few-tile rule) — decided THERE, not re-derived here
+// the 64 x 64 / 64 x 128 / 64 x 160 / 128 x 128 / 128 x 160 tiles: the kernel the plan chose
 template <int BM, int BN>
-void launch_cfg(const GemmParams& p, hipStream_t s, bool deep = false, bool conv1_2wg = false) {
-    const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    const int sk = p.splitk > 1 ? p.splitk : 1;
-    dim3 grid(tiles * sk, 1, p.batch);
-    // producer/consumer kernel: wins where a plain GEMM leaves at most one workgroup per CU (batch-1 step: +5.6 % whole step,
-    // same box A/B); loses on convs and wherever two v3 workgroups share a CU.
-    if constexpr (BM == 64 && BN == 64) {
-        // skinny projections with more tiles than CUs: the producer / consumer kernel with two workgroups per CU (see gemm4_kernel, WPS).
-        // Measured per launch inside the batch-1 forward (profiles/r05_ab_gemm4_rings.txt): 2048 x 640 x 640
-        // (320 tiles, 10 slabs) 14.3 -> 11.7 us against the 2-stage kernel; 8192 x 320 x 320 (640 tiles, 5 slabs) 12.3 -> 14.4: short K stays.
-        // An 8-stage ring for <= 256 tiles measured +-0 (512 x 1280 x 1280: 13.6 vs 13.4 us): these launches are not short of bytes in
-        // flight — an ablated kernel that only runs its prologue and barriers takes 4.7 of 8.3 us (same record).
-        const long long blocks = (long long)tiles * sk * p.batch;
-        if (!p.conv && blocks > V4_MAX_BLOCKS && blocks <= 512 && p.K >= 640) {
-            t_last_kernel = "gemm4_kernel<64,64,plain,2wg>";
-            hipLaunchKernelGGL((gemm4_kernel<64, 64, false, 4, 4>), grid, dim3(2 * NT), 0, s, p);
-            return;
+void launch_cfg(const GemmParams& p, const GemmPlan& pl, dim3 grid, hipStream_t s) {
+    if (pl.route == GR_GEMM4) {
+        if constexpr (BM == 64 && BN == 64) {
+            if (pl.two_wg) {
+                if (!pl.conv) hipLaunchKernelGGL((gemm4_kernel<64, 64, false, 4, 4>), grid, dim3(2 * NT), 0, s, p);
+                else hipLaunchKernelGGL((gemm4_kernel<64, 64, true, 4, 4>), grid, dim3(2 * NT), 0, s, p);
+                return;
+            }
         }
-        if (conv1_2wg) {
-            t_last_kernel = "gemm4_kernel<64,64,conv,2wg>";
-            hipLaunchKernelGGL((gemm4_kernel<64, 64, true, 4, 4>), grid, dim3(2 * NT), 0, s, p);
-            return;
-        }
-    }
-    if (!p.conv && (long long)tiles * sk * p.batch <= V4_MAX_BLOCKS) {
-        static const std::string name = "gemm4_kernel<" + std::to_string(BM) + "," + std::to_string(BN) + ",plain>";
-        t_last_kernel = name.c_str();
         hipLaunchKernelGGL((gemm4_kernel<BM, BN, false>), grid, dim3(2 * NT), 0, s, p);
-    } else if (p.conv) {
-        static const std::string name = "gemm3_kernel<" + std::to_string(BM) + "," + std::to_string(BN) + ",conv>";
-        t_last_kernel = name.c_str();
+    } else if (pl.conv) {
         if constexpr (BM == 64 && BN == 160) {
-            if (deep) {   // 4-stage ring, one workgroup per CU (three slabs in flight): see the rule in gemm_launch
-                t_last_kernel = "gemm3_kernel<64,160,conv,deep>";
+            if (pl.deep) {   // 4-stage ring, one workgroup per CU (three slabs in flight): see the rule in gemm_plan
                 hipLaunchKernelGGL((gemm3_kernel<BM, BN, true, 4>), grid, dim3(NT), 0, s, p);
                 return;
             }
         }
         hipLaunchKernelGGL((gemm3_kernel<BM, BN, true, 2>), grid, dim3(NT), 0, s, p);
     } else {
-        static const std::string name = "gemm3_kernel<" + std::to_string(BM) + "," + std::to_string(BN) + ",plain>";
-        t_last_kernel = name.c_str();
         hipLaunchKernelGGL((gemm3_kernel<BM, BN, false, 2>), grid, dim3(NT), 0, s, p);
     }
 }
 
-// one halo-tile instantiation; its profile name says what differs from the 256 x 320 tile: conv6_kernel<W64,halo+groupnorm>,
-// conv6_kernel<W128,halo,128x512>, conv6_kernel<W64,halo,256,up>, ...
 template <int W, bool GN, int BN, int BM, bool UP>
-void launch_conv6_w(const GemmParams& p, dim3 grid, hipStream_t s) {
-    static const std::string name = "conv6_kernel<W" + std::to_string(W) + ",halo" + (GN ? "+groupnorm" : "") +
-                                    (BN == V5_BN ? "" : "," + std::to_string(BN) + (BM == V5_BM ? "" : "x" + std::to_string(BM))) + (UP ? ",up" : "") + ">";
-    t_last_kernel = name.c_str();
-    hipLaunchKernelGGL((conv6_kernel<W, GN, BN, BM, UP>), grid, dim3(512), 0, s, p);
-}
-// the tile widths v6_plan hands each tile: every width for the 320-column tile, 64 and 128 for the plain 256-column tile, 128 for the rest
+void launch_conv6_w(const GemmParams& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv6_kernel<W, GN, BN, BM, UP>), grid, dim3(512), 0, s, p); }
+// the tile widths gemm_plan hands each tile: every width for the 320-column tile, 64 and 128 for the plain 256-column tile, 128 for the rest
 template <bool GN, int BN = V5_BN, int BM = V5_BM, bool UP = false>
 void launch_conv6(int wc, const GemmParams& p, dim3 grid, hipStream_t s) {
     if constexpr (BN == V5_BN) {
@@ -2520,41 +2514,28 @@ extern "C" void ld_debug_gemm_override(int bm, int splitk) {
 }
 #endif
 
+const char* gemm_last_kernel_name() { return t_last_kernel; }
+
 // the split-K second pass of a launch: the plain reduce, or the one that also emits GroupNorm partials (GemmParams::gn_part)
-static void launch_splitk_reduce(const GemmParams& p, int bn, hipStream_t stream) {
+static void plan_reduce(const GemmParams& p, GemmPlan* pl) {
+    if (pl->splitk <= 1) return;
     // (N >= 256: below that gn_stats_kernel uses fewer, wider channel slabs — norm.hip gn_slabs — and this kernel's four-slab order would
     // no longer reproduce its partials bit for bit)
     const bool gn = p.gn_part != nullptr && p.act != 2 && p.batch == 1 && p.gn_P > 0 && p.gn_HW > 0 && p.M % p.gn_HW == 0 && p.N % 32 == 0 && p.N <= 8192 && p.N >= 256 &&
                     p.ldc == p.N && (p.N / 4) % 8 == 0 && p.N / 32 <= 256;
-    if (gn) {
-        hipLaunchKernelGGL(splitk_reduce_gn_kernel, dim3(p.gn_P, p.M / p.gn_HW, 4), dim3(256), 0, stream, p);
-        if (p.gn_part_done != nullptr) *p.gn_part_done = p.gn_P;
-        t_last_kernel = intern_name(std::string(t_last_kernel) + "+splitk_reduce_gn_kernel");
-        return;
-    }
-    const int out_n = p.act == 2 ? p.N / 2 : p.N;
-    const long long total = (long long)p.M * (out_n / 8);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p, bn);
-    t_last_kernel = intern_name(std::string(t_last_kernel) + "+splitk_reduce_kernel");
+    pl->reduce = gn ? GRD_GROUPNORM : GRD_PLAIN;
+    if (gn) pl->gn_chunks = p.gn_P;
 }
 
-bool gemm_ln_fold_available() { return true; }
-const char* gemm_last_kernel_name() { return t_last_kernel; }
-
-// does this convolution run on the halo-tile kernel (v6), and with which tile (rows x columns), split over K and loader (UP)?
-struct V6Plan {
-    int sk = 1, bn = 0, bm = V5_BM, wc = 0;   // wc: tile width in pixels (16 / 32 / 64 / 128; an image wider than 128 is cut into 128-pixel bands)
-    bool up = false;
-};
-static bool v6_plan(const GemmParams& p, V6Plan* out) {
+// does this convolution run on the halo-tile kernel (v6), and with which tile (rows x columns), split over K and loader (up)?
+// gn: gn_scale / gn_shift are, or will be, set.  Fills bm, bn, wc, splitk, up.
+static bool v6_plan(const GemmParams& p, bool gn, GemmPlan* out) {
     const bool same = p.Hv == p.Hs && p.Wv == p.Ws;
     const bool up = p.Hv == 2 * p.Hs && p.Wv == 2 * p.Ws;           // exact nearest 2x (Upsample: LD.py:3498-3511; Upsample1 when the skip is 2x)
     if (!(p.conv && p.ksize == 3 && p.stride == 1 && (p.pad < 0 || p.pad == 1) && (same || up) && p.Ho == p.Hv && p.Wo == p.Wv &&
           p.C1 % 32 == 0 && p.C2 % 32 == 0 && p.bm == 0 && p.bn == 0 && p.splitk == 0 && p.batch == 1 && p.act != 2))
         return false;
-    if (up && (p.C2 != 0 || p.gn_scale != nullptr)) return false;
+    if (up && (p.C2 != 0 || gn)) return false;
     if (p.SC1 > 0) return false;                                     // (a second K segment: the tap-major kernels)
     const int wc = (p.Wo == 16 || p.Wo == 32 || p.Wo == 64 || p.Wo == 128) ? p.Wo : (p.Wo > 128 && p.Wo % 128 == 0) ? 128 : 0;
     if (wc == 0) return false;
@@ -2566,12 +2547,12 @@ static bool v6_plan(const GemmParams& p, V6Plan* out) {
     int bn = 0, bm = V5_BM;
     if (p.N % V5_BN == 0) {
         bn = V5_BN;
-    } else if (p.N % 256 == 0 && wc >= 64 && (p.gn_scale == nullptr || (p.N == 256 && wc == 128 && !up))) {   // (fused GroupNorm: one tile wide, 128-pixel bands)
+    } else if (p.N % 256 == 0 && wc >= 64 && (!gn || (p.N == 256 && wc == 128 && !up))) {   // (fused GroupNorm: one tile wide, 128-pixel bands)
         bn = 256;
-    } else if (p.N % 128 == 0 && wc == 128 && (p.gn_scale == nullptr || (p.N == 128 && !up))) {
+    } else if (p.N % 128 == 0 && wc == 128 && !up && (!gn || p.N == 128)) {   // (!up: this tile has no nearest-2x loader instantiated)
         bn = 128;
         bm = 512;
-    } else if (p.N == 32 && wc == 128 && p.gn_scale == nullptr && !up) {
+    } else if (p.N == 32 && wc == 128 && !gn && !up) {
         // a <= 8-channel output convolution (the VAE's conv_out, weights zero-padded to 32 rows by the caller, n_valid = 8): 8 MFMAs per
         // wave and phase — the step's fixed cost dominates, but the halo tile is read once instead of nine times per pixel
         bn = 32;
@@ -2606,138 +2587,93 @@ static bool v6_plan(const GemmParams& p, V6Plan* out) {
         }
     }
 #endif
-    out->sk = sk6;
-    out->bn = bn;
-    out->bm = bm;
-    out->wc = wc;
-    out->up = up;
+    out->splitk = sk6; out->bn = bn; out->bm = bm; out->wc = wc; out->up = up;
+    out->grid_x = (unsigned)(t6 * sk6);
     return t6 * sk6 >= 192;
 }
 
-bool gemm_conv_takes_skip_segment(const GemmParams& p) {
-    V6Plan pl;
-    return p.conv && p.ksize == 3 && p.stride == 1 && p.Hv == p.Hs && p.Wv == p.Ws && p.SC1 == 0 && !conv8_plan(p, nullptr) && !v6_plan(p, &pl);
-}
-
-bool gemm_conv_takes_halo_tile(const GemmParams& pin) {
+GemmPlan gemm_plan(const GemmParams& pin, bool gn_offer) {
+    GemmPlan pl;
     GemmParams p = pin;
-    V6Plan pl;
-    return v6_plan(p, &pl);
-}
-
-bool gemm_conv_fuses_groupnorm(const GemmParams& p) {
-    // Measured (profiles/r02_ab_groupnorm_fusion.txt, same process): fused vs two-pass GroupNorm + the same halo conv: +4 % at N = 320 (level 0, one N
-    // tile per M tile), +-0 % at N = 640, -3 % at N = 1280 — every N tile of an M tile normalises the same halo again, so the fusion
-    // only pays where the output is one tile wide.
-    // Round 5: also the VAE decoder's one-tile-wide stages — N = 256 at 256-pixel rows, N = 128 at 512-pixel rows (128-pixel bands) — where a
-    // two-pass GroupNorm writes and re-reads 134 - 537 MB per convolution.
-    V6Plan pl;
-    if (!v6_plan(p, &pl) || pl.up) return false;
-    if (p.N == V5_BN && pl.bn == V5_BN) return true;
-    // (the 128 -> 3 output convolution — 8 MFMAs per phase — measured a loss with its norm_out fused: VAE decode +0.15 ms, profiles/r05_ab_vae_gn_fused.txt)
-    return pl.wc == 128 && ((p.N == 256 && pl.bn == 256 && pl.bm == V5_BM) || (p.N == 128 && pl.bn == 128 && pl.bm == 512));
-}
-
-int gemm_launch(const GemmParams& pin, hipStream_t stream) {
-    GemmParams p = pin;
-    t_last_kernel = "";   // nothing dispatched until a route below names its kernel
+    const bool gn = gn_offer || p.gn_scale != nullptr;
+    const auto fail = [](int st) { GemmPlan f; f.status = st; return f; };
+    const auto done = [&pl](int route) { pl.route = route; pl.kernel = plan_kernel_name(pl); return pl; };
 #ifdef LD_AB_BUILD
     if (g_force_bm) p.bm = g_force_bm;
     if (g_force_sk) p.splitk = g_force_sk;
-    if (g_shape_ovr[0] == p.M && g_shape_ovr[1] == p.N && g_shape_ovr[2] == p.K && p.batch == 1 && p.gn_scale == nullptr) {
+    if (g_shape_ovr[0] == p.M && g_shape_ovr[1] == p.N && g_shape_ovr[2] == p.K && p.batch == 1 && !gn) {
         p.bm = g_shape_ovr[3];
         p.splitk = g_shape_ovr[4];
     }
 #endif
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.A == nullptr || p.W == nullptr || p.C == nullptr) return LD_ERR_ARG;
-    if ((p.N & 7) || (p.K & 7) || (p.ldw & 7) || (p.ldc & 7)) return LD_ERR_SHAPE;
+    // ---- validate
+    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.A == nullptr || p.W == nullptr || p.C == nullptr) return fail(LD_ERR_ARG);
+    if ((p.N & 7) || (p.K & 7) || (p.ldw & 7) || (p.ldc & 7)) return fail(LD_ERR_SHAPE);
     if (p.conv) {
         const int Cin = p.C1 + p.C2;
-        if (p.ksize != 1 && p.ksize != 3) return LD_ERR_ARG;
+        if (p.ksize != 1 && p.ksize != 3) return fail(LD_ERR_ARG);
         if (p.pad < 0) p.pad = p.ksize >> 1;
-        if (p.SC1 < 0 || p.SC2 < 0 || (p.SC1 == 0 && p.SC2 != 0)) return LD_ERR_ARG;
-        if (Cin <= 0 || (p.C1 % 64) || (p.C2 % 64) || (p.SC1 % 64) || (p.SC2 % 64) || p.K != p.ksize * p.ksize * Cin + p.SC1 + p.SC2) return LD_ERR_SHAPE;
+        if (p.SC1 < 0 || p.SC2 < 0 || (p.SC1 == 0 && p.SC2 != 0)) return fail(LD_ERR_ARG);
+        if (Cin <= 0 || (p.C1 % 64) || (p.C2 % 64) || (p.SC1 % 64) || (p.SC2 % 64) || p.K != p.ksize * p.ksize * Cin + p.SC1 + p.SC2) return fail(LD_ERR_SHAPE);
         if (p.SC1 > 0) {   // second K segment (gemm.h): raw sources of the output's size, read at the output pixel itself
-            if (p.S1 == nullptr || (p.SC2 > 0 && p.S2 == nullptr)) return LD_ERR_ARG;
-            if (p.stride != 1 || p.Hv != p.Hs || p.Wv != p.Ws || p.Ho != p.Hv || p.Wo != p.Wv || p.pad != p.ksize / 2 || p.SC1 > 32768 || p.SC2 > 32768) return LD_ERR_SHAPE;
+            if (p.S1 == nullptr || (p.SC2 > 0 && p.S2 == nullptr)) return fail(LD_ERR_ARG);
+            if (p.stride != 1 || p.Hv != p.Hs || p.Wv != p.Ws || p.Ho != p.Hv || p.Wo != p.Wv || p.pad != p.ksize / 2 || p.SC1 > 32768 || p.SC2 > 32768) return fail(LD_ERR_SHAPE);
         }
-        if (p.C1 > 32768 || p.C2 > 32768) return LD_ERR_SHAPE;   // the stepped zero row (g_zero_row) covers one tap's channel run
-        if (p.C2 > 0 && p.A2 == nullptr) return LD_ERR_ARG;
-        if (p.M % (p.Ho * p.Wo)) return LD_ERR_SHAPE;
-        if (p.batch != 1) return LD_ERR_ARG;
+        if (p.C1 > 32768 || p.C2 > 32768) return fail(LD_ERR_SHAPE);   // the stepped zero row (g_zero_row) covers one tap's channel run
+        if (p.C2 > 0 && p.A2 == nullptr) return fail(LD_ERR_ARG);
+        if (p.M % (p.Ho * p.Wo)) return fail(LD_ERR_SHAPE);
+        if (p.batch != 1) return fail(LD_ERR_ARG);
     } else if (p.lda & 7) {
-        return LD_ERR_SHAPE;
+        return fail(LD_ERR_SHAPE);
     }
-    if (p.act == 2 && (p.bias_n == nullptr || (p.N & 15))) return LD_ERR_ARG;
-    if (p.R != nullptr && (p.ldr & 7)) return LD_ERR_SHAPE;
-
+    if (p.act == 2 && (p.bias_n == nullptr || (p.N & 15))) return fail(LD_ERR_ARG);
+    if (p.R != nullptr && (p.ldr & 7)) return fail(LD_ERR_SHAPE);
     if (p.n_valid <= 0 || p.n_valid > p.N) p.n_valid = p.N;
+    pl.conv = p.conv != 0; pl.geglu = p.act == 2;
+
     // ---- conv8 (row-resident, weights streamed once, in-launch slab reduction): the two-image 16x16 / 8x8 levels of a batch-1 step
-    if (conv8_plan(p, nullptr)) {
-        static const char* names[4][2] = {{"conv8_kernel<W8>", "conv8_kernel<W8,up>"}, {"conv8_kernel<W16>", "conv8_kernel<W16,up>"},
-                                          {"conv8_kernel<W32>", "conv8_kernel<W32,up>"}, {"conv8_kernel<W64>", "conv8_kernel<W64,up>"}};
-        t_last_kernel = names[p.Wo == 8 ? 0 : p.Wo == 16 ? 1 : p.Wo == 32 ? 2 : 3][p.Hv == 2 * p.Hs ? 1 : 0];
-        if (p.gn_part != nullptr && p.gn_part_done != nullptr) *p.gn_part_done = conv8_gn_chunks(p);
-        return conv8_launch(p, stream);
+    if (!gn && conv8_plan(p, &pl.c8_S)) {
+        pl.wc = p.Wo; pl.up = p.Hv == 2 * p.Hs;
+        if (p.gn_part != nullptr) pl.gn_chunks = p.Wo * p.Wo / 16;   // the kernel emits the GroupNorm partials of its output itself
+        return done(GR_CONV8);
     }
     // ---- v6 (halo-tile 3x3 convolution on the v5 skeleton): stride-1 convs whose tiles are whole image rows and fill the chip
-    V6Plan pl;
-    if (v6_plan(p, &pl)) {
-        const int sk6 = pl.sk, bn6 = pl.bn, wc = pl.wc;
-        const long long t6 = (long long)(p.M / pl.bm) * (p.N / bn6);
-        p.splitk = sk6;
-        p.pad = 1;
-        if (bn6 != 32) p.n_valid = p.N;                              // (the 32-column tile stores only the caller's n_valid columns)
-        dim3 grid((unsigned)(t6 * sk6), 1, 1);
-        if (sk6 == 1 && p.gn_part != nullptr) {
+    if (GemmPlan v6 = pl; v6_plan(p, gn, &v6)) {
+        pl = v6;
+        const int bn6 = pl.bn, wc = pl.wc;
+        if (gn) {
+            if ((p.gn_scale != nullptr && p.gn_shift == nullptr) || pl.up) return fail(LD_ERR_ARG);
+            if (bn6 != V5_BN && (wc != 128 || p.N != bn6 || !((bn6 == 256 && pl.bm == V5_BM) || (bn6 == 128 && pl.bm == 512)))) return fail(LD_ERR_ARG);
+            // Measured (profiles/r02_ab_groupnorm_fusion.txt, same process): fused vs two-pass GroupNorm + the same halo conv: +4 % at N = 320 (level 0, one N
+            // tile per M tile), +-0 % at N = 640, -3 % at N = 1280 — every N tile of an M tile normalises the same halo again, so the fusion
+            // only pays where the output is one tile wide.
+            // Round 5: also the VAE decoder's one-tile-wide stages — N = 256 at 256-pixel rows, N = 128 at 512-pixel rows (128-pixel bands) — where a
+            // two-pass GroupNorm writes and re-reads 134 - 537 MB per convolution.
+            // (the 128 -> 3 output convolution — 8 MFMAs per phase — measured a loss with its norm_out fused: VAE decode +0.15 ms, profiles/r05_ab_vae_gn_fused.txt)
+            pl.can_fuse_groupnorm = bn6 != V5_BN || p.N == V5_BN;   // (a 256- / 128-column tile got here as the whole output's width only)
+            if (gn_offer && !pl.can_fuse_groupnorm) return fail(LD_ERR_ARG);
+            pl.gn = true;
+        }
+        if (pl.splitk == 1 && p.gn_part != nullptr) {
             // the generic epilogue (v6_finish) also writes the GroupNorm partial statistics of the OUTPUT, one chunk per tile of an image
             const int cpg = p.N / 32, tiles_img = (p.Ho / (pl.bm / wc)) * (p.Wo / wc);
-            const bool ok = (bn6 == 256 || bn6 == 128) && p.N % 32 == 0 && (p.N == 128 || cpg % 8 == 0) && bn6 % cpg == 0 && p.n_valid == p.N && p.act == 0;
-            if (ok) {
-                p.gn_P = tiles_img;
-                if (p.gn_part_done != nullptr) *p.gn_part_done = tiles_img;
-            } else {
-                p.gn_part = nullptr;
-            }
+            const bool ok = (bn6 == 256 || bn6 == 128) && p.N % 32 == 0 && (p.N == 128 || cpg % 8 == 0) && bn6 % cpg == 0 && p.act == 0;
+            if (ok) pl.gn_chunks = tiles_img;
         }
-        if (p.gn_scale != nullptr) {
-            if (p.gn_shift == nullptr || pl.up) return LD_ERR_ARG;
-            if (bn6 != V5_BN && (wc != 128 || p.N != bn6 || !((bn6 == 256 && pl.bm == V5_BM) || (bn6 == 128 && pl.bm == 512)))) return LD_ERR_ARG;
-            if (bn6 == 256) launch_conv6<true, 256>(wc, p, grid, stream);
-            else if (bn6 == 128) launch_conv6<true, 128, 512>(wc, p, grid, stream);
-            else launch_conv6<true>(wc, p, grid, stream);
-        } else if (bn6 == 128) {
-            launch_conv6<false, 128, 512>(wc, p, grid, stream);
-        } else if (bn6 == 32) {
-            launch_conv6<false, 32, 512>(wc, p, grid, stream);
-        } else if (bn6 == 256) {
-            if (pl.up) launch_conv6<false, 256, V5_BM, true>(wc, p, grid, stream);
-            else launch_conv6<false, 256>(wc, p, grid, stream);
-        } else {
-            if (pl.up) launch_conv6<false, V5_BN, V5_BM, true>(wc, p, grid, stream);
-            else launch_conv6<false>(wc, p, grid, stream);
-        }
-        if (sk6 > 1) launch_splitk_reduce(p, 160, stream);
-        return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+        plan_reduce(p, &pl);
+        pl.halo_tile = true;
+        return done(GR_CONV6);
     }
-    if (p.gn_scale != nullptr) return LD_ERR_ARG;   // only the halo kernel applies a fused GroupNorm (ask gemm_conv_fuses_groupnorm first)
+    if (gn) return fail(LD_ERR_ARG);   // only the halo kernel applies a fused GroupNorm (ask with gn_offer first)
+    // every 3x3 convolution from here on walks K tap-major
+    pl.takes_skip_segment = p.conv && p.ksize == 3 && p.stride == 1 && p.Hv == p.Hs && p.Wv == p.Ws && p.SC1 == 0;
     // ---- v7 (row-panel kernel, A fragments in registers): the K = 320 projections whose 256-row panels fill the chip
     if (!p.conv && p.K == V7_K && p.batch == 1 && !p.ln_swapped && p.bias_m == nullptr && p.rowvec == nullptr && p.bm == 0 && (p.bn == 0 || p.bn == 160) &&
         p.splitk == 0 && (p.n_valid <= 0 || p.n_valid >= p.N) && p.N % (p.act == 2 ? 160 : V7_NB) == 0 && (p.M + V7_BM - 1) / V7_BM >= 192 &&
         (p.act == 0 || (p.act == 2 && p.bias_n != nullptr && p.stat_out == nullptr && p.R == nullptr))) {
-        if (p.stat_parts_out != nullptr) *p.stat_parts_out = p.N / V7_NB;
-        dim3 grid((unsigned)((p.M + V7_BM - 1) / V7_BM), 1, 1);
-        const bool ln = p.ln_stat != nullptr;
-        if (p.act == 2) {
-            t_last_kernel = ln ? "gemm7_kernel<256,K320,geglu,ln>" : "gemm7_kernel<256,K320,geglu>";
-            if (ln) hipLaunchKernelGGL((gemm7_kernel<true, true>), grid, dim3(512), 0, stream, p);
-            else hipLaunchKernelGGL((gemm7_kernel<true, false>), grid, dim3(512), 0, stream, p);
-        } else {
-            t_last_kernel = ln ? "gemm7_kernel<256,K320,plain,ln>" : "gemm7_kernel<256,K320,plain>";
-            if (ln) hipLaunchKernelGGL((gemm7_kernel<false, true>), grid, dim3(512), 0, stream, p);
-            else hipLaunchKernelGGL((gemm7_kernel<false, false>), grid, dim3(512), 0, stream, p);
-        }
-        return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+        pl.stat_parts = p.N / V7_NB;
+        pl.grid_x = (unsigned)((p.M + V7_BM - 1) / V7_BM); pl.ln = p.ln_stat != nullptr;
+        return done(GR_GEMM7);
     }
     // ---- v5 (256 x 320 tile, 8 waves, staggered wave groups): whenever its tiles (x an optional split over K) fill the chip
     {
@@ -2749,48 +2685,35 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
         const bool shape_ok = !p.ln_swapped && p.bm == 0 && (p.bn == 0 || p.bn == 160) && p.N % V5_BN == 0 && p.K % V5_BK == 0 &&
                               p.K >= (p.act == 2 ? 1280 : conv3 ? 640 : 2560) && (p.n_valid == p.N || p.n_valid <= 0 || p.n_valid > p.N) &&
                               p.splitk == 0 && p.M >= 1024;
-        if (shape_ok) {
-            const long long t5 = (long long)((p.M + V5_BM - 1) / V5_BM) * (p.N / V5_BN) * p.batch;
-            if (t5 >= 192 && !(p.act == 2 && p.stat_out != nullptr)) {
-                if (p.stat_parts_out != nullptr) *p.stat_parts_out = 2 * (p.N / V5_BN);
-                p.splitk = 1;
-                p.bn = 160;
-                if (p.n_valid <= 0 || p.n_valid > p.N) p.n_valid = p.N;
-                dim3 grid((unsigned)t5, 1, 1);
-                grid.x = (unsigned)(((p.M + V5_BM - 1) / V5_BM) * (p.N / V5_BN));
-                grid.z = (unsigned)p.batch;
-                const bool ln = p.ln_stat != nullptr || p.stat_out != nullptr;
-                if (p.conv) {
-                    if (ln || p.act == 2) return LD_ERR_ARG;          // (no caller: convolutions carry neither the LayerNorm fold nor GEGLU)
-                    t_last_kernel = "gemm5_kernel<256,320,conv>";
-                    hipLaunchKernelGGL((gemm5_kernel<true, 0>), grid, dim3(512), 0, stream, p);
-                } else {
-                    t_last_kernel = p.act == 2 ? "gemm5_kernel<256,320,geglu>" : ln ? "gemm5_kernel<256,320,lnfold>" : "gemm5_kernel<256,320,plain>";
-                    {   // XCD-blocked tile order (see the kernel): the split of the 8 XCDs over (M, N) that moves the fewest bytes, A once per
-                        // N group and W once per M group
-                        const int tm5 = (p.M + V5_BM - 1) / V5_BM, tn5 = p.N / V5_BN;
-                        p.xcd_gm = 0;
-                        if (p.batch == 1 && (tm5 * tn5) % 8 == 0 && p.M % V5_BM == 0) {
-                            double best = 0;
-                            for (int gm = 1; gm <= 8; gm <<= 1) {
-                                const int gn = 8 / gm;
-                                if (tm5 % gm || tn5 % gn) continue;
-                                const double cost = (double)p.M * gn + (double)p.N * gm;     // x K x 2 bytes
-                                if (p.xcd_gm == 0 || cost < best) {
-                                    best = cost;
-                                    p.xcd_gm = gm;
-                                }
-                            }
+        const int tm5 = (p.M + V5_BM - 1) / V5_BM, tn5 = p.N / V5_BN;
+        if (shape_ok && (long long)tm5 * tn5 * p.batch >= 192 && !(p.act == 2 && p.stat_out != nullptr)) {
+            pl.ln = p.ln_stat != nullptr || p.stat_out != nullptr;
+            if (p.conv && (pl.ln || p.act == 2)) return fail(LD_ERR_ARG);          // (no caller: convolutions carry neither the LayerNorm fold nor GEGLU)
+            pl.stat_parts = 2 * tn5;
+            pl.bm = V5_BM; pl.bn = V5_BN;
+            pl.grid_x = (unsigned)(tm5 * tn5); pl.grid_z = (unsigned)p.batch;
+            pl.xcd_gm = p.xcd_gm;
+            if (!p.conv) {
+                // XCD-blocked tile order (see the kernel): the split of the 8 XCDs over (M, N) that moves the fewest bytes, A once per
+                // N group and W once per M group
+                pl.xcd_gm = 0;
+                if (p.batch == 1 && (tm5 * tn5) % 8 == 0 && p.M % V5_BM == 0) {
+                    double best = 0;
+                    for (int gm = 1; gm <= 8; gm <<= 1) {
+                        const int gn5 = 8 / gm;
+                        if (tm5 % gm || tn5 % gn5) continue;
+                        const double cost = (double)p.M * gn5 + (double)p.N * gm;     // x K x 2 bytes
+                        if (pl.xcd_gm == 0 || cost < best) {
+                            best = cost;
+                            pl.xcd_gm = gm;
                         }
                     }
-                    if (p.act == 2) hipLaunchKernelGGL((gemm5_kernel<false, 2>), grid, dim3(512), 0, stream, p);
-                    else if (ln) hipLaunchKernelGGL((gemm5_kernel<false, 1>), grid, dim3(512), 0, stream, p);
-                    else hipLaunchKernelGGL((gemm5_kernel<false, 0>), grid, dim3(512), 0, stream, p);
                 }
-                return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
             }
+            return done(GR_GEMM5);
         }
     }
+    // ---- v3 / v4 (64 / 128-row tiles of 64 / 128 / 160 columns, optional split over K)
     int bn = p.bn ? p.bn : gemm_pick_bn(p.N);
     // Skinny plain GEMMs (the batch-1 step's M = 128..2048 projections): with <= 128 tiles of 64 x 160 most CUs idle while
     // each busy one streams 28.7 KB per slab through its one LDS-DMA path; 64 x 64 tiles spread the same work over 2.5x more CUs
@@ -2816,10 +2739,9 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
             bn = 64;
             skinny_conv1 = true;
         }
-
     }
-    if (bn != 128 && bn != 160 && bn != 64) return LD_ERR_ARG;
-    if (p.act == 2 && (p.N % bn)) return LD_ERR_SHAPE;
+    if (bn != 128 && bn != 160 && bn != 64) return fail(LD_ERR_ARG);
+    if (p.act == 2 && (p.N % bn)) return fail(LD_ERR_SHAPE);
     const int tiles_n = (p.N + bn - 1) / bn;
     const int KT = (p.K + BK - 1) / BK;          // 64-wide K slabs
     // Tile height and split-K, fitted to a per-shape sweep of every contraction of the SD1.5 UNet at UNet batch 2 and 16
@@ -2841,7 +2763,7 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
     }
     if (bn == 64) bm = 64;
     if (skinny_conv1) sk = 1;
-    if (bm != 64 && bm != 128) return LD_ERR_ARG;
+    if (bm != 64 && bm != 128) return fail(LD_ERR_ARG);
     const int tiles = ((p.M + bm - 1) / bm) * tiles_n;
     // Convolutions on 64 x 160 tiles with very few tiles (<= 32: the 8 x 8 level of a batch-1 step) or exactly one round of them (256 .. 511)
     // run the 4-stage ring with ONE workgroup per CU and a split aimed at 256 workgroups: three slabs in flight per workgroup hide the
@@ -2856,36 +2778,118 @@ int gemm_launch(const GemmParams& pin, hipStream_t stream) {
         }
     }
     if (sk > 1) {
-        if (p.batch != 1 || p.partial == nullptr) return LD_ERR_ARG;
+        if (p.batch != 1 || p.partial == nullptr) return fail(LD_ERR_ARG);
         while (sk > 1 && (size_t)sk * p.M * p.N * sizeof(float) > p.partial_bytes) --sk;
         if (sk > KT) sk = KT;
     }
     if (p.stat_out != nullptr || p.ln_stat != nullptr) {   // LN fold: v3 / v4 kernels, whole K in one workgroup
-        if (p.act == 2 && p.stat_out != nullptr) return LD_ERR_ARG;
+        if (p.act == 2 && p.stat_out != nullptr) return fail(LD_ERR_ARG);
         sk = 1;
-        if (p.stat_parts_out != nullptr) *p.stat_parts_out = tiles_n;
+        pl.stat_parts = tiles_n;
     }
-    p.splitk = sk;
-    p.bn = bn;
+    if (sk < 1) sk = 1;
+    pl.bm = bm; pl.bn = bn; pl.splitk = sk;
+    pl.grid_x = (unsigned)(tiles * sk); pl.grid_z = (unsigned)p.batch;
     // measured (profiles/r01_b): n-fastest wins on every SD1.5 shape — the 9 taps of a 3x3 conv and the N tiles of one
     // M panel re-read the same activations through the XCD's L2, which matters more than re-streaming the weights
     // Round 5: a plain GEMM with few M panels and a large weight matrix (the batch-1 step's M = 512 GEGLU: 4 panels x 26 MB) walks its tiles
     // M-fastest, so the panels of one N tile run together on one XCD and the weight tile leaves HBM once instead of once per panel
     // (profiles/pmc_traffic.json round 4: 113 MB per launch for 26 MB of weights)
+    pl.m_fastest = p.m_fastest;
     if (p.m_fastest < 0) {
         const int tiles_m = (p.M + bm - 1) / bm;
-        p.m_fastest = (!p.conv && p.batch == 1 && tiles_m >= 2 && tiles_m <= 8 && (long long)p.N * p.K * 2 >= (8ll << 20)) ? 1 : 0;
+        pl.m_fastest = (!p.conv && p.batch == 1 && tiles_m >= 2 && tiles_m <= 8 && (long long)p.N * p.K * 2 >= (8ll << 20)) ? 1 : 0;
     }
+    plan_reduce(p, &pl);
+    const long long blocks = (long long)tiles * sk * p.batch;
+    {
+        // skinny projections with more tiles than CUs: the producer / consumer kernel with two workgroups per CU (see gemm4_kernel, WPS).
+        // Measured per launch inside the batch-1 forward (profiles/r05_ab_gemm4_rings.txt): 2048 x 640 x 640
+        // (320 tiles, 10 slabs) 14.3 -> 11.7 us against the 2-stage kernel; 8192 x 320 x 320 (640 tiles, 5 slabs) 12.3 -> 14.4: short K stays.
+        // An 8-stage ring for <= 256 tiles measured +-0 (512 x 1280 x 1280: 13.6 vs 13.4 us): these launches are not short of bytes in
+        // flight — an ablated kernel that only runs its prologue and barriers takes 4.7 of 8.3 us (same record).
+        const bool plain_2wg = bn == 64 && !p.conv && blocks > V4_MAX_BLOCKS && blocks <= 512 && p.K >= 640;
+        // every unsplit 1x1 convolution that ends on 64 x 64 tiles with at most two workgroups per CU takes the 2wg kernel: the skinny_conv1 shapes
+        // and the few-tile shapes of the older skinny_max rule alike
+        const bool conv1_2wg = bn == 64 && p.conv && p.ksize == 1 && sk <= 1 && (long long)tiles * p.batch <= 512;
+        pl.two_wg = plain_2wg || conv1_2wg;
+        if (pl.two_wg) return done(GR_GEMM4);
+    }
+    // producer/consumer kernel: wins where a plain GEMM leaves at most one workgroup per CU (batch-1 step: +5.6 % whole step,
+    // same box A/B); loses on convs and wherever two v3 workgroups share a CU.
+    if (!p.conv && blocks <= V4_MAX_BLOCKS) return done(GR_GEMM4);
+    pl.deep = deep;   // (64 x 160 convolutions only, by its rule above)
+    return done(GR_GEMM3);
+}
 
-    // every unsplit 1x1 convolution that ends on 64 x 64 tiles with at most two workgroups per CU takes the 2wg kernel: the skinny_conv1 shapes
-    // and the few-tile shapes of the older skinny_max rule alike
-    const bool conv1_2wg = bn == 64 && p.conv && p.ksize == 1 && sk <= 1 && (long long)tiles * p.batch <= 512;
-    if (bn == 64) launch_cfg<64, 64>(p, stream, false, conv1_2wg);
-    else if (bm == 128 && bn == 160) launch_cfg<128, 160>(p, stream);
-    else if (bm == 128 && bn == 128) launch_cfg<128, 128>(p, stream);
-    else if (bm == 64 && bn == 160) launch_cfg<64, 160>(p, stream, deep);
-    else launch_cfg<64, 128>(p, stream);
-
-    if (sk > 1) launch_splitk_reduce(p, bn, stream);
+int gemm_run(const GemmParams& pin, const GemmPlan& pl, hipStream_t stream) {
+    t_last_kernel = "";   // nothing dispatched until the route below launches
+    if (pl.status != LD_OK) return pl.status;
+    if (pl.gn != (pin.gn_scale != nullptr) || (pl.gn && pin.gn_shift == nullptr)) return LD_ERR_ARG;   // (a plan made with gn_offer, run without the operands — or the reverse)
+    GemmParams p = pin;
+    if (p.stat_parts_out != nullptr) *p.stat_parts_out = pl.stat_parts;
+    if (p.gn_part_done != nullptr) *p.gn_part_done = pl.gn_chunks;
+    if (p.conv && p.pad < 0) p.pad = p.ksize >> 1;
+    if (p.n_valid <= 0 || p.n_valid > p.N) p.n_valid = p.N;
+    const dim3 grid(pl.grid_x, 1, pl.grid_z);
+    t_last_kernel = pl.kernel;
+    switch (pl.route) {
+        case GR_CONV8:
+            if (const int st = conv8_launch(p, pl.c8_S, stream); st != LD_OK) return st;
+            break;
+        case GR_CONV6:
+            p.splitk = pl.splitk;
+            if (pl.bn != 32) p.n_valid = p.N;                            // (the 32-column tile stores only the caller's n_valid columns)
+            if (pl.splitk == 1 && p.gn_part != nullptr) {                // the tile epilogue writes the GroupNorm partials, or nobody does
+                if (pl.gn_chunks > 0) p.gn_P = pl.gn_chunks;
+                else p.gn_part = nullptr;
+            }
+            if (pl.gn) {
+                if (pl.bn == 256) launch_conv6<true, 256>(pl.wc, p, grid, stream);
+                else if (pl.bn == 128) launch_conv6<true, 128, 512>(pl.wc, p, grid, stream);
+                else launch_conv6<true>(pl.wc, p, grid, stream);
+            } else if (pl.bn == 128) {
+                launch_conv6<false, 128, 512>(pl.wc, p, grid, stream);
+            } else if (pl.bn == 32) {
+                launch_conv6<false, 32, 512>(pl.wc, p, grid, stream);
+            } else if (pl.bn == 256) {
+                if (pl.up) launch_conv6<false, 256, V5_BM, true>(pl.wc, p, grid, stream);
+                else launch_conv6<false, 256>(pl.wc, p, grid, stream);
+            } else {
+                if (pl.up) launch_conv6<false, V5_BN, V5_BM, true>(pl.wc, p, grid, stream);
+                else launch_conv6<false>(pl.wc, p, grid, stream);
+            }
+            break;
+        case GR_GEMM7:
+            if (pl.geglu && pl.ln) hipLaunchKernelGGL((gemm7_kernel<true, true>), grid, dim3(512), 0, stream, p);
+            else if (pl.geglu) hipLaunchKernelGGL((gemm7_kernel<true, false>), grid, dim3(512), 0, stream, p);
+            else if (pl.ln) hipLaunchKernelGGL((gemm7_kernel<false, true>), grid, dim3(512), 0, stream, p);
+            else hipLaunchKernelGGL((gemm7_kernel<false, false>), grid, dim3(512), 0, stream, p);
+            break;
+        case GR_GEMM5:
+            p.splitk = 1; p.bn = 160; p.xcd_gm = pl.xcd_gm;
+            if (pl.conv) hipLaunchKernelGGL((gemm5_kernel<true, 0>), grid, dim3(512), 0, stream, p);
+            else if (pl.geglu) hipLaunchKernelGGL((gemm5_kernel<false, 2>), grid, dim3(512), 0, stream, p);
+            else if (pl.ln) hipLaunchKernelGGL((gemm5_kernel<false, 1>), grid, dim3(512), 0, stream, p);
+            else hipLaunchKernelGGL((gemm5_kernel<false, 0>), grid, dim3(512), 0, stream, p);
+            break;
+        default:
+            p.splitk = pl.splitk; p.bn = pl.bn; p.m_fastest = pl.m_fastest;
+            if (pl.bn == 64) launch_cfg<64, 64>(p, pl, grid, stream);
+            else if (pl.bm == 128 && pl.bn == 160) launch_cfg<128, 160>(p, pl, grid, stream);
+            else if (pl.bm == 128 && pl.bn == 128) launch_cfg<128, 128>(p, pl, grid, stream);
+            else if (pl.bm == 64 && pl.bn == 160) launch_cfg<64, 160>(p, pl, grid, stream);
+            else launch_cfg<64, 128>(p, pl, grid, stream);
+            break;
+    }
+    if (pl.reduce == GRD_GROUPNORM) {
+        hipLaunchKernelGGL(splitk_reduce_gn_kernel, dim3(p.gn_P, p.M / p.gn_HW, 4), dim3(256), 0, stream, p);
+    } else if (pl.reduce == GRD_PLAIN) {
+        const int out_n = p.act == 2 ? p.N / 2 : p.N;
+        const long long total = (long long)p.M * (out_n / 8);
+        int blocks = (int)((total + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p, pl.route == GR_CONV6 ? 160 : pl.bn);
+    }
     return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
 }

@@ -216,27 +216,27 @@ struct Exec {
         timing->kname.push_back(kernel_name);
     }
 
-    void gemm(GemmParams p) {
+    // the scratch every contraction of this executor launches with: set before planning, so that the plan is the launch's
+    void with_scratch(GemmParams& p) const {
+        if (p.batch != 1) return;
+        p.partial = splitk_ws; p.partial_bytes = splitk_bytes; p.sync = sync_ws;
+    }
+    // `plan`: gemm_plan of p with this executor's scratch, where the caller already asked for it
+    void gemm(GemmParams p, const GemmPlan* plan = nullptr) {
         const double fl = 2.0 * p.M * (double)p.N * p.K * p.batch;
         flops += fl;
-        if (p.batch == 1) {
-            p.partial = splitk_ws;
-            p.partial_bytes = splitk_bytes;
-            p.sync = sync_ws;
-        }
+        with_scratch(p);
         launches += 1;
         if (dry || status != LD_OK) return;
         t_begin(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, fl, 1, p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"),
                 p.M, p.N, p.K, p.batch);
-        note(gemm_launch(p, stream));
+        note(plan != nullptr ? gemm_run(p, *plan, stream) : gemm_launch(p, stream));
         t_end(gemm_last_kernel_name());
     }
     // would gemm() run this 3x3 convolution on a kernel that takes a second K segment (gemm.h S1 / S2)?
     bool conv_takes_skip_segment(GemmParams p) const {
-        p.partial = splitk_ws;
-        p.partial_bytes = splitk_bytes;
-        p.sync = sync_ws;
-        return gemm_conv_takes_skip_segment(p);
+        with_scratch(p);
+        return gemm_plan(p).takes_skip_segment;
     }
     // `ready` / `ready_P`: partial statistics the producer already wrote (gemm.h gn_part; ready_P pixel chunks per image): the statistics
     // launch is skipped
@@ -258,11 +258,10 @@ struct Exec {
     // `p`: the convolution with A / A2 = the RAW sources; returns through p.C as usual.
     // `ready` / `ready_P`: GroupNorm partial statistics of the input that its producer already wrote (see groupnorm)
     void gn_silu_conv(GemmParams p, int n_img, int HW, const half_t* gamma, const half_t* beta, float eps, half_t* g, float* ready = nullptr, int ready_P = 0) {
-        p.partial = splitk_ws;
-        p.partial_bytes = splitk_bytes;
-        p.sync = sync_ws;
+        with_scratch(p);
         if (ready_P <= 0) ready = nullptr;
-        if (gemm_conv_fuses_groupnorm(p)) {
+        const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
+        if (fused.can_fuse_groupnorm) {
             const int C = p.C1 + p.C2;
             const size_t m = arena->mark();
             float* ws = ready != nullptr ? ready : reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n_img, HW)));
@@ -277,7 +276,7 @@ struct Exec {
             p.gn_scale = scale;
             p.gn_shift = shift;
             p.gn_silu = 1;
-            gemm(p);
+            gemm(p, &fused);
             arena->release(m);
             return;
         }
@@ -287,12 +286,6 @@ struct Exec {
         p.C1 = p.C1 + p.C2;
         p.C2 = 0;
         gemm(p);
-    }
-    void layernorm(const half_t* x, const half_t* g, const half_t* b, half_t* y, int rows, int C) {
-        launches += 1;
-        t_begin(KC_LNORM, 0.0, 1, "layernorm", rows, C);
-        if (!dry && status == LD_OK) note(layernorm_launch(x, g, b, y, rows, C, 1e-5f, stream));
-        t_end("layernorm_kernel");
     }
     void attention(const AttnParams& p) {
         const double fl = 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.d;

@@ -90,7 +90,6 @@ struct ld_unet {
     char* fold_base = nullptr;     // LN-folded copies of the LN-consuming projections (see StW)
     size_t fold_bytes = 0;
     bool fold_dirty = true;        // set by every ld_unet_load_param; cleared when the fold kernels have run
-    bool ln_fold = false;          // the GEMM kernels in use implement it (and LD_UNET_NO_LN_FOLD is not set)
 };
 
 namespace {
@@ -372,8 +371,8 @@ struct Run {
         const half_t* skip = x1;
         bool fold_skip = false;
         if (r.sk_w >= 0) {
-            GemmParams probe = conv_params(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, nullptr, 0, nullptr, out);
-            fold_skip = u->ln_fold && u->fold_base != nullptr && ex.conv_takes_skip_segment(probe);
+            // (asked of out_layers' convolution as it stands before the skip joins it, as a residual or as a K segment)
+            fold_skip = u->fold_base != nullptr && ex.conv_takes_skip_segment(conv_params(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, nullptr, 0, nullptr, out));
             half_t* sk = (!fold_skip || ex.dry) ? ar.halfs(M * r.cout) : nullptr;   // (a planning run sizes for either route: ld_unet_reserve plans before the split-K scratch exists)
             if (!fold_skip) {
                 conv3(x1, C1, x2, C2, H, W, H, W, 1, r.sk_w, r.sk_b, r.cout, nullptr, 0, nullptr, sk, nullptr, nullptr, 1);
@@ -420,15 +419,13 @@ struct Run {
         half_t* g = ar.halfs(Ma * C);
         ex.groupnorm(x, C, nullptr, 0, n, L, P(s.gn_g), P(s.gn_b), 1e-6f, 0, g, in_stats, in_P);
         half_t* t = ar.halfs(Ma * C);
-        half_t* nrm = g;               // reuse (only the un-folded path materialises LN(x))
         half_t* qkv = ar.halfs(Ma * 3 * C);
         half_t* ao = ar.halfs(Ma * C);
         half_t* ff = nullptr;
-        const bool fold = u->ln_fold;
         // LN fold: the three LayerNorms disappear into the GEMMs around them.  The GEMM that WRITES the residual stream t also
         // writes per-row (sum, sum of squares) partials of t (one pair per N tile); the projections that read LN(t) run on t itself
         // with gamma folded into their weights and finish  rstd * (acc - mu * wsum) + b'  in the epilogue (gemm.h).
-        float* stat = fold ? reinterpret_cast<float*>(ar.alloc((size_t)((C + 63) / 64) * Ma * 2 * sizeof(float))) : nullptr;
+        float* stat = reinterpret_cast<float*>(ar.alloc((size_t)((C + 63) / 64) * Ma * 2 * sizeof(float)));
         int parts = 0;
         char* fb = u->fold_base;
         auto producer = [&](const half_t* x_, int lda, int wslot, int bslot, const half_t* R, int K) {   // t = x_ W^T + b (+ R), with row stats
@@ -439,10 +436,8 @@ struct Run {
             p.bias_n = P(bslot);
             p.R = R; p.ldr = C;
             p.C = t; p.ldc = C;
-            if (fold) {
-                p.stat_out = stat;
-                p.stat_parts_out = &parts;
-            }
+            p.stat_out = stat;
+            p.stat_parts_out = &parts;
             ex.gemm(p);
         };
         auto ln_args = [&](GemmParams& p, size_t wsum_off) {
@@ -452,18 +447,15 @@ struct Run {
         };
         producer(g, C, s.pin_w, s.pin_b, nullptr, C);
         // ---- self attention: x += to_out(attn(LN1(x)))
-        if (!fold) ex.layernorm(t, P(s.ln1_g), P(s.ln1_b), nrm, M, C);
         {   // [q | k | v] = LN1(t) [Wq ; Wk ; Wv]^T — one launch; the attention kernel reads V row-major (transposing LDS reads), so there
             // is no V^T projection
             GemmParams p;
-            p.A = fold ? t : nrm; p.lda = C;
-            p.W = fold ? reinterpret_cast<const half_t*>(fb + s.f_qk_w) : P(s.q1_w); p.ldw = C;
+            p.A = t; p.lda = C;
+            p.W = reinterpret_cast<const half_t*>(fb + s.f_qk_w); p.ldw = C;
             p.M = M; p.N = 3 * C; p.K = C;
             p.C = qkv; p.ldc = 3 * C;
-            if (fold) {
-                p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_qk_b);
-                ln_args(p, s.f_qk_s);
-            }
+            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_qk_b);
+            ln_args(p, s.f_qk_s);
             ex.gemm(p);
         }
         {
@@ -484,18 +476,15 @@ struct Run {
         const bool split_here = pair_pending;
         producer(ao, C, s.o1_w, s.o1_b, t, C);
         // ---- cross attention against the hoisted context K / V^T
-        if (!fold) ex.layernorm(t, P(s.ln2_g), P(s.ln2_b), nrm, M, C);
         half_t* q2 = qkv;   // reuse
         {
             GemmParams p;
-            p.A = fold ? t : nrm; p.lda = C;
-            p.W = fold ? reinterpret_cast<const half_t*>(fb + s.f_q2_w) : P(s.q2_w); p.ldw = C;
+            p.A = t; p.lda = C;
+            p.W = reinterpret_cast<const half_t*>(fb + s.f_q2_w); p.ldw = C;
             p.M = M; p.N = C; p.K = C;
             p.C = q2; p.ldc = C;
-            if (fold) {
-                p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_q2_b);
-                ln_args(p, s.f_q2_s);
-            }
+            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_q2_b);
+            ln_args(p, s.f_q2_s);
             ex.gemm(p);
         }
         if (split_here) {
@@ -525,20 +514,19 @@ struct Run {
         }
         producer(ao, C, s.o2_w, s.o2_b, t, C);
         // ---- GEGLU feed-forward: x = ff2(a * gelu(gate)) + x
-        if (!fold) ex.layernorm(t, P(s.ln3_g), P(s.ln3_b), nrm, M, C);
         ff = ar.halfs(Ma * 4 * C);
         {
             GemmParams p;
-            p.A = fold ? t : nrm; p.lda = C;
-            p.W = fold ? reinterpret_cast<const half_t*>(fb + s.f_ff1_w) : P(s.ff1_w); p.ldw = C;
+            p.A = t; p.lda = C;
+            p.W = reinterpret_cast<const half_t*>(fb + s.f_ff1_w); p.ldw = C;
             p.M = M; p.N = 8 * C; p.K = C;
-            p.bias_n = fold ? reinterpret_cast<const half_t*>(fb + s.f_ff1_b) : P(s.ff1_b);
+            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_ff1_b);
             p.act = 2; p.bn = s.bn;
             p.C = ff; p.ldc = 4 * C; p.ldr = 4 * C;
-            if (fold) ln_args(p, s.f_ff1_s);
+            ln_args(p, s.f_ff1_s);
             ex.gemm(p);
         }
-        if (fold) {
+        {
             // out = x + proj_out(t + ff2(ff)) as one contraction over [ff | t] (K = 5C) against the folded [Wpo W2 | Wpo] (misc.hip)
             GemmParams p;
             p.conv = 1; p.ksize = 1;
@@ -551,9 +539,6 @@ struct Run {
             p.C = out; p.ldc = C;
             want_stats(p, gno, L, &gno_done);
             ex.gemm(p);
-        } else {
-            linear(ff, 4 * C, s.ff2_w, s.ff2_b, t, t, M, C, 4 * C);
-            linear(t, C, s.pout_w, s.pout_b, x, out, M, C, C);
         }
         ar.release(mk);
         return {out, C, H, W, gno_done ? gno : nullptr, gno_done};
@@ -604,7 +589,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
             const int st = derive_conv8_weights(u, stream);
             if (st != LD_OK) return st;
         }
-        if (u->ln_fold) {
+        {
             const int st = fold_layernorms(u, stream);
             if (st != LD_OK) return st;
         }
@@ -777,8 +762,7 @@ int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
     u->w8_of_slot.assign(u->pt.slots.size(), -1);
     for (const ld_unet::W8& w : u->w8_list) u->w8_of_slot[w.slot] = (long long)w.off;
     if (u->w8_bytes > 0 && hipMalloc((void**)&u->w8_base, u->w8_bytes) != hipSuccess) u->w8_base = nullptr;   // (without the copies the general kernels run)
-    u->ln_fold = gemm_ln_fold_available();
-    if (u->ln_fold && u->fold_bytes > 0 && hipMalloc((void**)&u->fold_base, u->fold_bytes) != hipSuccess) {
+    if (u->fold_bytes > 0 && hipMalloc((void**)&u->fold_base, u->fold_bytes) != hipSuccess) {
         u->pt.destroy();
         delete u;
         return LD_ERR_HIP;

@@ -408,10 +408,12 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
         q.W = v->co_pad; q.ldw = 9 * C;
         q.M = b * H * W; q.N = 32; q.n_valid = 8; q.K = 9 * C;
         q.bias_n = v->co_pad != nullptr ? v->co_pad + (size_t)32 * 9 * C : nullptr;
-        q.partial = ex.splitk_ws; q.partial_bytes = ex.splitk_bytes;
-        if (v->co_pad != nullptr && c.out_ch <= 8 && gemm_conv_takes_halo_tile(q)) {
-            half_t* t8 = ar.halfs((size_t)b * H * W * 8);
-            q.C = t8; q.ldc = 8;
+        ex.with_scratch(q);
+        const size_t mk8 = ar.mark();
+        half_t* t8 = ar.halfs((size_t)b * H * W * 8);   // (the 8 stored columns: 1/16 of g; given back when the convolution does not take the halo tile)
+        q.C = t8; q.ldc = 8;
+        const GemmPlan qp = v->co_pad != nullptr && c.out_ch <= 8 ? gemm_plan(q) : GemmPlan();
+        if (qp.halo_tile) {
             if (!dry) {   // the three real rows of the weight matrix and the biases into the padded copies (stream-ordered, 7 KB)
                 const size_t wb = (size_t)c.out_ch * 9 * C * sizeof(half_t);
                 if (hipMemcpyAsync(v->co_pad, v->pt.ptr(v->co_w), wb, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
@@ -422,12 +424,13 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
             ex.launches += 2;
             ex.flops += fl;
             ex.t_begin(KC_CONV3, fl, 1, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1);
-            if (!dry && ex.status == LD_OK) ex.note(gemm_launch(q, stream));
+            if (!dry && ex.status == LD_OK) ex.note(gemm_run(q, qp, stream));
             ex.t_end(gemm_last_kernel_name());
             ex.t_begin(KC_MISC, 0.0, 1, "out_finish", (long long)b * H * W, c.out_ch, 0, 1);
             if (!dry && ex.status == LD_OK) ex.note(vae_out_finish_launch(t8, out, (long long)b * H * W, c.out_ch, stream));
             ex.t_end("vae_out_finish_kernel");
         } else {
+            ar.release(mk8);
             SmallConvOutArgs a;
             a.x = g; a.w = v->pt.ptr(v->co_w); a.b = v->pt.ptr(v->co_b);
             a.N = b; a.H = H; a.W = W; a.Cin = C; a.Cout = c.out_ch; a.mode = 1; a.out = out;
