@@ -151,6 +151,14 @@ int ld_op_repack_conv(const void* src_oihw, int dtype, int cout, int cin, void* 
 size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout);
 int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
                     const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream);
+/* Upsample1 (nearest resize to hv x wv, then 3x3 conv, stride 1, pad 1; LD.py:5141-5152) with the resize folded into the weights: for an exact
+ * 2x resize the layer is four 2x2 convolutions of the SOURCE image, one per output phase (2y + py, 2x + px), whose weights are sums of the 3x3
+ * taps.  ld_op_upconv2x_fold derives them once from wt [cout][9 cin] (ld_op_repack_conv's layout): wfold [py*2+px][cout][a*2+b][cin], 16 cout cin
+ * halfs, fp32 sums rounded to fp16 once.  ld_op_upconv2x runs the layer as the UNet executor does: on the folded weights (4/9 of the
+ * multiply-adds) when hv = 2h, wv = 2w and n > 2, otherwise exactly as ld_op_conv.  ws/ws_bytes: split-K scratch as ld_op_conv. */
+int ld_op_upconv2x_fold(const void* wt, int cout, int cin, void* wfold, void* stream);
+int ld_op_upconv2x(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* wfold, const void* bias, void* y, int cout,
+                   void* ws, size_t ws_bytes, void* stream);
 /* 3x3 stride-1 convolution (hv = 2h: behind a nearest-2x upsampling) that also returns the GroupNorm(32) partial statistics of its OUTPUT
  * where the kernel that runs the shape writes them (the halo convolution's generic epilogue, the row-resident kernel, the split-K second
  * pass) — what lets the GroupNorm that follows (ResBlock1 out_layers / the next block's in_layers, LD.py:5224-5262; the VAE's ResnetBlock,

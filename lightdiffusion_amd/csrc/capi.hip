@@ -105,7 +105,7 @@ int ld_op_linear(const void* x, const void* w, const void* bias, const void* res
 
 static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
                    const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
-                   size_t ws_bytes, void* stream, float* gn_part, int* gn_chunks) {
+                   size_t ws_bytes, void* stream, float* gn_part, int* gn_chunks, const void* wup = nullptr) {
     if (stride < 1 || (ksize != 1 && ksize != 3)) return LD_ERR_ARG;
     GemmParams p;
     if (gn_part != nullptr) {   // GroupNorm partial statistics of the output, where the kernel that runs this shape writes them (as the executors ask: unet.hip want_stats)
@@ -124,6 +124,7 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
     p.Wo = ksize == 3 ? (wv - 1) / stride + 1 : wv;
     p.K = ksize * ksize * (c1 + c2);
     p.W = (const half_t*)wt; p.ldw = p.K;
+    p.Wup = (const half_t*)wup;
     p.M = n * p.Ho * p.Wo; p.N = cout;
     p.bias_n = (const half_t*)bias;
     p.rowvec = (const half_t*)rowvec; p.rows_per_vec = p.Ho * p.Wo; p.ldrv = cout;
@@ -146,6 +147,20 @@ int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int
                size_t ws_bytes, void* stream) {
     op_begin();
     return op_conv(x1, c1, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, rowvec, residual, y, cout, ws, ws_bytes, stream, nullptr, nullptr);
+}
+
+int ld_op_upconv2x_fold(const void* wt, int cout, int cin, void* wfold, void* stream) {
+    op_begin();
+    return upconv_fold_launch((const half_t*)wt, cout, cin, (half_t*)wfold, (hipStream_t)stream);
+}
+
+int ld_op_upconv2x(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* wfold, const void* bias, void* y, int cout,
+                   void* ws, size_t ws_bytes, void* stream) {
+    op_begin();
+    // Upsample1 as the UNet executor runs it: the folded weights are an offer that the planner takes for an exact 2x resize of more than two
+    // images; every other case is ld_op_conv's route
+    if (wfold == nullptr) return LD_ERR_ARG;
+    return op_conv(x, c, nullptr, 0, n, h, w, hv, wv, 1, 3, wt, bias, nullptr, nullptr, y, cout, ws, ws_bytes, stream, nullptr, nullptr, wfold);
 }
 
 size_t ld_op_conv_gn_partials_floats(int n, int hw) {

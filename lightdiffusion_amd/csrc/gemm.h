@@ -79,13 +79,17 @@ struct GemmParams {
     //   its in-launch reduction of the channel-slab partial sums needs >= 4 * (N / 80) zeroed ints that it leaves zeroed (self-resetting)
     int* sync = nullptr;
     int c8_S = 0;                // (internal) slab split chosen by conv8_plan
+    // ---- nearest-2x upsampling folded into the weights (upconv route, gemm.hip "upconv"): the 3x3 convolution of a 2x-upsampled image is four 2x2
+    //   convolutions of the SOURCE image, one per output phase (py, px).  Wup holds the 16 phase-tap matrices [py*2+px][N][a*2+b][C1] (sums of the
+    //   3x3 taps, upconv_fold_launch); a caller that sets it offers the route, gemm_plan takes it for an exact 2x resize of one source above conv8's batch
+    const half_t* Wup = nullptr;
     int dbg = 0;                 // A/B build only (LD_AB_BUILD): bit 2 = conv8's lone-reducer route (LD_C8_NO_WAIT); the product leaves it 0
 };
 
 // What gemm_launch does with one GemmParams: decided once by gemm_plan, carried out by gemm_run, read by the callers that
 // need to know before (or after) the launch.  A pure function of the parameters: no HIP call, nothing written through p's pointers.
-enum GemmRoute { GR_NONE = 0, GR_CONV8, GR_CONV6, GR_GEMM7, GR_GEMM5, GR_GEMM3, GR_GEMM4 };   // in the planner's order
-enum GemmReduce { GRD_NONE = 0, GRD_PLAIN, GRD_GROUPNORM };                                    // the split-K second pass
+enum GemmRoute { GR_NONE = 0, GR_CONV8, GR_CONV6, GR_GEMM7, GR_GEMM5, GR_GEMM3, GR_GEMM4, GR_UPCONV };   // in the planner's order (upconv: between conv8 and conv6)
+enum GemmReduce { GRD_NONE = 0, GRD_PLAIN, GRD_GROUPNORM, GRD_UPCONV };                                 // the split-K second pass
 struct GemmPlan {
     int status = LD_OK;          // LD_ERR_ARG / LD_ERR_SHAPE: gemm_launch returns it and launches nothing (everything below is unset)
     int route = GR_NONE;
@@ -123,6 +127,9 @@ int conv8_launch(const GemmParams& p, int S, hipStream_t stream);
 bool conv8_weight_eligible(int N, int Cin);
 size_t conv8_weight_bytes(int N, int Cin);
 int conv8_repack_launch(const half_t* w_okki, int N, int Cin, half_t* dst, hipStream_t stream);
+// misc.hip: the upconv route's split-K second pass (an element-wise pass: slab sum + bias + depth-to-space store); p as the launch saw it —
+// M source pixels, N = 4 Cout columns [phase][Cout], Hs x Ws source image, splitk slabs in p.partial
+int upconv_reduce_launch(const GemmParams& p, hipStream_t stream);
 #define LD_SYNC_INTS 1024        // ints a caller provides behind GemmParams::sync
 
 // BN the GEGLU weight interleave must use for a projection with N (=2*inner) output rows

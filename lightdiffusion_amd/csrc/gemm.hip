@@ -1222,9 +1222,33 @@ __device__ __forceinline__ void v5_epilogue_strip(const GemmParams& p, half_t* C
     }
 }
 
+// upconv (gemm5_kernel<true, 0, true>): one staged 16-row x 160-column strip -> depth-to-space store.  Row m = (img, y, x) of the SOURCE image is output
+// pixel (2y + py, 2x + px); a row's 320-byte segment stays 16-byte chunks of one pixel's channels, only its base address changes (one lane per
+// row works it out, the others fetch it by shuffle).  The bias is in the staged strip already; no residual, row vector or activation here.
+__device__ __forceinline__ void v5_upconv_strip(const GemmParams& p, const half_t* Cs, int m_base, int col, int py, int px, int lane) {
+    const int m = m_base + (lane & 15);
+    const int mm = m < p.M ? m : p.M - 1;
+    const int hw = p.Hs * p.Ws, img = mm / hw, rem = mm - img * hw, y = rem / p.Ws, x = rem - y * p.Ws;
+    const int orow = (img * 2 * p.Hs + 2 * y + py) * (2 * p.Ws) + 2 * x + px;        // output pixel index (n * 4 * Hs * Ws < 2^31: gemm_plan)
+    uint4 cv[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int q = lane + k * 64;
+        const int row = q / 20, cc = q - row * 20;
+        cv[k] = ld16(Cs + row * V5_EPI_LD + cc * 8);
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int q = lane + k * 64;
+        const int row = q / 20, cc = q - row * 20;
+        const int o = __shfl(orow, row, 64);
+        if (m_base + row < p.M) st16(p.C + (long long)o * p.ldc + col + cc * 8, cv[k]);
+    }
+}
+
 // tail shared by the 256 x 320 tile kernels (v5 / v6): split-K slab store, or the staged fused epilogue (two 16-row strips at a
 // time through this wave's 10.5 KB of the — by now quiet — LDS ring)
-template <int EPI, bool LNC>   // EPI: see v5_epilogue_strip; LNC: LayerNorm-fold consumer (ln_mu / ln_rs valid)
+template <int EPI, bool LNC, bool UPF = false>   // EPI: see v5_epilogue_strip; LNC: LayerNorm-fold consumer (ln_mu / ln_rs valid); UPF: upconv (depth-to-space store)
 __device__ __forceinline__ void v5_finish(const GemmParams& p, f32x4 (&acc)[4][10], char* smem5, const float* ln_mu, const float* ln_rs, int z, int m0,
                                           int n0, int wm0, int wn0, int wid, int lane, int ks, int splitk, int tn_i) {
     constexpr int TM = 4, TN = 10;
@@ -1257,7 +1281,9 @@ __device__ __forceinline__ void v5_finish(const GemmParams& p, f32x4 (&acc)[4][1
     const bool add_b = bias_done && p.bias_n != nullptr;
     // (always a load: an absent bias reads the zero page — a select around a load makes hipcc branch and wait per load; per strip, from L1 after
     // the first: a batch held for all four strips costs 20 registers next to the 160 accumulators and spilled)
-    const half_t* bsrc = (add_b ? p.bias_n + n_w : reinterpret_cast<const half_t*>(g_zero_row)) + fq * 4;
+    // (upconv: the tile lies in one phase's column block; bias and output columns count from that block's start)
+    const int up_cout = UPF ? p.N >> 2 : 1, up_ph = UPF ? n0 / up_cout : 0, up_col = n_w - up_ph * up_cout;
+    const half_t* bsrc = (add_b ? p.bias_n + (UPF ? up_col : n_w) : reinterpret_cast<const half_t*>(g_zero_row)) + fq * 4;
     auto stage = [&](auto I, half_t* dst) {                         // literal strip index: the accumulators stay in registers
         constexpr int i = decltype(I)::value;
         // LN-fold consumer: acc <- rstd * (acc - mu * wsum) in fp32, strip by strip (keeps the live registers low)
@@ -1281,16 +1307,26 @@ __device__ __forceinline__ void v5_finish(const GemmParams& p, f32x4 (&acc)[4][1
     stage(std::integral_constant<int, 1>{}, Cs1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // same wave, in-order LDS: the strips are complete
     __builtin_amdgcn_sched_barrier(0);
-    v5_epilogue_strip<EPI>(p, Cs, z, m_w, n_w, lane, part, bias_done);
-    v5_epilogue_strip<EPI>(p, Cs1, z, m_w + 16, n_w, lane, part, bias_done);
+    if constexpr (UPF) {
+        v5_upconv_strip(p, Cs, m_w, up_col, up_ph >> 1, up_ph & 1, lane);
+        v5_upconv_strip(p, Cs1, m_w + 16, up_col, up_ph >> 1, up_ph & 1, lane);
+    } else {
+        v5_epilogue_strip<EPI>(p, Cs, z, m_w, n_w, lane, part, bias_done);
+        v5_epilogue_strip<EPI>(p, Cs1, z, m_w + 16, n_w, lane, part, bias_done);
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // strips consumed before the next pair overwrites them
     __builtin_amdgcn_sched_barrier(0);
     stage(std::integral_constant<int, 2>{}, Cs);
     stage(std::integral_constant<int, 3>{}, Cs1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    v5_epilogue_strip<EPI>(p, Cs, z, m_w + 32, n_w, lane, part, bias_done);
-    v5_epilogue_strip<EPI>(p, Cs1, z, m_w + 48, n_w, lane, part, bias_done);
+    if constexpr (UPF) {
+        v5_upconv_strip(p, Cs, m_w + 32, up_col, up_ph >> 1, up_ph & 1, lane);
+        v5_upconv_strip(p, Cs1, m_w + 48, up_col, up_ph >> 1, up_ph & 1, lane);
+    } else {
+        v5_epilogue_strip<EPI>(p, Cs, z, m_w + 32, n_w, lane, part, bias_done);
+        v5_epilogue_strip<EPI>(p, Cs1, z, m_w + 48, n_w, lane, part, bias_done);
+    }
 }
 
 // Epilogue of the halo-tile kernel's narrower tiles (256 x 256: the VAE's N = 256 / 512 convolutions; written for any width 16 TN per
@@ -1479,7 +1515,12 @@ __device__ __forceinline__ void v6_finish(const GemmParams& p, f32x4 (&acc)[TM][
     }
 }
 
-template <bool CONV, int EPI>
+// UPF (upconv, with CONV): nearest-2x upsample + 3x3 convolution as four 2x2 convolutions of the source image (gemm.h Wup).  Rows are SOURCE
+// pixels, columns [phase][Cout], K = [2x2 tap][Cin]; a column tile lies in one phase (Cout % 320 == 0), so the phase (py, px) is
+// workgroup-uniform: tap (a, b) of the implicit-im2col loader reads source pixel (y + py - 1 + a, x + px - 1 + b) — outside the image the
+// zero page, which is exactly the 3x3 convolution's padding of the upsampled image — and the epilogue stores row (img, y, x) to output pixel
+// (2y + py, 2x + px).  A separate instantiation: the others keep their code and registers.
+template <bool CONV, int EPI, bool UPF = false>
 __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
     constexpr int TM = 4, TN = 10;
     __shared__ __attribute__((aligned(16))) char smem5[V5_NST * V5_STAGE_BYTES];
@@ -1534,6 +1575,24 @@ __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
     int seg_left = 0;
     int k_issue = kt_begin * V5_BK;                                 // K index of the next step to issue
     auto conv_seek = [&](int k0) {
+        if constexpr (UPF) {
+            const int tap = k0 / Cin, c0 = k0 - tap * Cin;          // tap = a * 2 + b; past the last step (tap 4) the zero page
+            const int ph = n0 / (p.N >> 2);
+            const int dy = (ph >> 1) - 1 + (tap >> 1), dx = (ph & 1) - 1 + (tap & 1);
+            const int hw = p.Hs * p.Ws;
+            seg_left = (Cin - c0) / V5_BK;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int m = m0 + a_row0 + i * 16;
+                const int mm = m < p.M ? m : 0;
+                const int img = mm / hw, rem = mm - img * hw;
+                const int y = rem / p.Ws, x = rem - y * p.Ws;
+                const int iy = y + dy, ix = x + dx;
+                const bool ok = m < p.M && (unsigned)iy < (unsigned)p.Hs && (unsigned)ix < (unsigned)p.Ws && tap < 4;
+                a_ptr[i] = ok ? Ab + (((long long)img * p.Hs + iy) * p.Ws + ix) * Cin + c0 + lchunk * 8 : zp + lchunk * 8;
+            }
+            return;
+        }
         // (k0 beyond the taps: the second K segment — the 1x1 skip convolution's raw sources at the output pixel itself, gemm.h S1 / S2)
         const int K9 = p.ksize * p.ksize * Cin;
         const bool skp = k0 >= K9 && p.SC1 > 0;
@@ -1670,7 +1729,7 @@ __global__ __launch_bounds__(512, 2) void gemm5_kernel(const GemmParams p) {
     }
     if (!grp1) __builtin_amdgcn_s_barrier();                        // group 0 waits out group 1's last MFMA phase: every wave ran 2 nk + 2 barriers
 
-    v5_finish<EPI, EPI != 0>(p, acc, smem5, ln_mu, ln_rs, z, m0, n0, wm0, wn0, wid, lane, ks, splitk, tn_i);
+    v5_finish<EPI, EPI != 0, UPF>(p, acc, smem5, ln_mu, ln_rs, z, m0, n0, wm0, wn0, wid, lane, ks, splitk, tn_i);
 }
 
 // =====================================================================================================================
@@ -2439,6 +2498,7 @@ const char* plan_kernel_name(const GemmPlan& pl) {
     const std::string tile = std::to_string(pl.bm) + "," + std::to_string(pl.bn);
     std::string s;
     switch (pl.route) {
+        case GR_UPCONV: s = "upconv_kernel<256,320>"; break;   // (gemm5_kernel<true, 0, true>: a family name of its own, see the kernel)
         case GR_CONV8: s = "conv8_kernel<W" + std::to_string(pl.wc) + (pl.up ? ",up>" : ">"); break;
         case GR_CONV6:
             s = "conv6_kernel<W" + std::to_string(pl.wc) + ",halo" + (pl.gn ? "+groupnorm" : "") +
@@ -2449,7 +2509,7 @@ const char* plan_kernel_name(const GemmPlan& pl) {
         case GR_GEMM4: s = "gemm4_kernel<" + tile + (pl.conv ? ",conv" : ",plain") + (pl.two_wg ? ",2wg>" : ">"); break;
         default: s = "gemm3_kernel<" + tile + (pl.conv ? ",conv" : ",plain") + (pl.deep ? ",deep>" : ">"); break;
     }
-    if (pl.reduce != GRD_NONE) s += pl.reduce == GRD_GROUPNORM ? "+splitk_reduce_gn_kernel" : "+splitk_reduce_kernel";
+    if (pl.reduce != GRD_NONE) s += pl.reduce == GRD_GROUPNORM ? "+splitk_reduce_gn_kernel" : pl.reduce == GRD_UPCONV ? "+upconv_reduce_kernel" : "+splitk_reduce_kernel";
     static std::mutex mu; static std::set<std::string> pool;   // stable storage
     std::lock_guard<std::mutex> lock(mu);
     const char* name = pool.insert(s).first->c_str();
@@ -2525,6 +2585,32 @@ static void plan_reduce(const GemmParams& p, GemmPlan* pl) {
                     p.ldc == p.N && (p.N / 4) % 8 == 0 && p.N / 32 <= 256;
     pl->reduce = gn ? GRD_GROUPNORM : GRD_PLAIN;
     if (gn) pl->gn_chunks = p.gn_P;
+}
+
+// does this convolution run on the upconv route (p.Wup set), and with which split over K?  Fills bm, bn, splitk, grid_x, reduce.
+// Tiles are those of the launch's own view: M / 4 source pixels x 4 N columns, K = 4 Cin.
+static bool upconv_plan(const GemmParams& p, GemmPlan* out) {
+    if (!(p.conv && p.ksize == 3 && p.stride == 1 && p.pad == 1 && p.Hv == 2 * p.Hs && p.Wv == 2 * p.Ws && p.Ho == p.Hv && p.Wo == p.Wv && p.C2 == 0 &&
+          p.SC1 == 0 && p.C1 % V5_BK == 0 && p.N % V5_BN == 0 && p.n_valid == p.N && p.bm == 0 && p.bn == 0 && p.splitk == 0 && p.batch == 1 && p.act == 0 &&
+          p.alpha == 1.0f && p.rowvec == nullptr && p.R == nullptr && p.bias_m == nullptr && p.stat_out == nullptr && p.ln_stat == nullptr && p.ldc == p.N))
+        return false;
+    if ((long long)p.M * 4 > 0x7fffffffll) return false;             // (the epilogue's pixel index is an int)
+    if (p.M / (p.Ho * p.Wo) <= 2) return false;                      // one or two images (the batch-1 step) keep today's routes, whichever kernel takes the shape
+    const int Ms = p.M / 4, K = 4 * p.C1;
+    const long long tiles = (long long)((Ms + V5_BM - 1) / V5_BM) * (4 * p.N / V5_BN);
+    // fewer tiles than fill the chip: slices over K up to one workgroup per CU, each keeping >= 640 of K (the rule of the other split routes);
+    // the second pass is upconv_reduce_kernel
+    int sk = 1;
+    if (tiles < 192 && p.partial != nullptr) {
+        sk = (int)((256 + tiles - 1) / tiles);
+        const int cap = K / 640 < 1 ? 1 : K / 640;
+        if (sk > cap) sk = cap;
+        while (sk > 1 && (size_t)sk * Ms * 4 * p.N * sizeof(float) > p.partial_bytes) --sk;
+    }
+    out->bm = V5_BM; out->bn = V5_BN; out->splitk = sk; out->up = true;
+    out->grid_x = (unsigned)(tiles * sk); out->grid_z = 1;
+    out->reduce = sk > 1 ? GRD_UPCONV : GRD_NONE;
+    return true;
 }
 
 // does this convolution run on the halo-tile kernel (v6), and with which tile (rows x columns), split over K and loader (up)?
@@ -2637,6 +2723,9 @@ GemmPlan gemm_plan(const GemmParams& pin, bool gn_offer) {
         if (p.gn_part != nullptr) pl.gn_chunks = p.Wo * p.Wo / 16;   // the kernel emits the GroupNorm partials of its output itself
         return done(GR_CONV8);
     }
+    // ---- upconv (nearest-2x folded into 2x2 phase weights, gemm.h Wup): the caller holds the folded weights and the resize is exactly 2x.
+    // The route executes 4/9 of the multiply-adds of the 3x3 convolution it implements: M / 4 source pixels x 4 N columns x 4/9 K.
+    if (p.Wup != nullptr && !gn && upconv_plan(p, &pl)) return done(GR_UPCONV);
     // ---- v6 (halo-tile 3x3 convolution on the v5 skeleton): stride-1 convs whose tiles are whole image rows and fill the chip
     if (GemmPlan v6 = pl; v6_plan(p, gn, &v6)) {
         pl = v6;
@@ -2860,6 +2949,17 @@ int gemm_run(const GemmParams& pin, const GemmPlan& pl, hipStream_t stream) {
                 else launch_conv6<false>(pl.wc, p, grid, stream);
             }
             break;
+        case GR_UPCONV: {
+            // the launch's own view of the problem: rows = source pixels, columns [phase][Cout], K = [2x2 tap][Cin] (the caller's M, N, K stay those
+            // of the 3x3 convolution this implements)
+            p.W = p.Wup; p.K = 4 * p.C1; p.ldw = p.K; p.M = pin.M / 4; p.N = 4 * pin.N; p.n_valid = p.N;
+            p.splitk = pl.splitk; p.bn = 160; p.xcd_gm = 0;
+            hipLaunchKernelGGL((gemm5_kernel<true, 0, true>), grid, dim3(512), 0, stream, p);
+            if (pl.reduce == GRD_UPCONV) {
+                if (const int st = upconv_reduce_launch(p, stream); st != LD_OK) return st;   // (misc.hip: an element-wise pass over the slabs)
+            }
+            return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+        }
         case GR_GEMM7:
             if (pl.geglu && pl.ln) hipLaunchKernelGGL((gemm7_kernel<true, true>), grid, dim3(512), 0, stream, p);
             else if (pl.geglu) hipLaunchKernelGGL((gemm7_kernel<true, false>), grid, dim3(512), 0, stream, p);

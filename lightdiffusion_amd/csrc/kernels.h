@@ -57,6 +57,9 @@ int mlp_out_fold_launch(const half_t* Wpo, const half_t* W2, const half_t* b2, c
 // W'[N][K9 + SC] = [W2 | Wsk], b' = b2 + bsk (a ResBlock's skip_connection as a second K segment of its out_layers convolution; see misc.hip)
 int skip_fold_launch(const half_t* W2, const half_t* Wsk, const half_t* b2, const half_t* bsk, int N, int K9, int SC, half_t* Wout, half_t* bout,
                      hipStream_t stream);
+// nearest-2x upsample + 3x3 convolution as four 2x2 convolutions of the source (gemm.h Wup): W [O][ky][kx][I] -> Wout [py*2+px][O][a*2+b][I], the
+// 16 phase-tap matrices; a phase-tap is one 3x3 tap or the sum of two or four of them (fp32 sums, rounded to fp16 once; see misc.hip)
+int upconv_fold_launch(const half_t* W, int O, int I, half_t* Wout, hipStream_t stream);
 struct SmallConvInArgs {        // 3x3 pad-1 conv with <= 4 input channels from an fp32 NCHW tensor (conv_in of UNet / VAE)
     const float* x = nullptr;   // [N][Cin][H][W] fp32
     const float* scale_sigma = nullptr;  // optional [N]: input scaled by 1/sqrt(sigma^2+1) (EPS.calculate_input, LD.py:1259-1261)

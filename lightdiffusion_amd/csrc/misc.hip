@@ -631,6 +631,61 @@ __global__ __launch_bounds__(256) void skip_fold_kernel(const uint4* __restrict_
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < N) bout[t] = (half_t)((float)b2[t] + (float)bsk[t]);
 }
+// Nearest-2x upsample + 3x3 convolution (pad 1) = four 2x2 convolutions of the source image, one per output phase (py, px): output pixel
+// (2y + py, 2x + px) reads the source pixels (y + py - 1 + a, x + px - 1 + b), a, b in {0, 1}, and the 3x3 taps that fall on one source pixel are
+// added HERE instead of in the accumulator.  Per axis: phase 0 — a = 0 takes tap 0, a = 1 taps 1 + 2; phase 1 — a = 0 takes taps 0 + 1, a = 1 tap 2.
+// W [O][ky][kx][I] -> Wout [py*2+px][O][a*2+b][I]; fp32 sums in (ky, kx) order, one rounding to fp16.  One thread per 8 input channels.
+__global__ __launch_bounds__(256) void upconv_fold_kernel(const uint4* __restrict__ W, int O, int Ic, uint4* __restrict__ Wout) {
+    const long long total = 16ll * O * Ic;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(q % Ic);
+        const int t = (int)((q / Ic) & 3);
+        const int o = (int)((q / (4ll * Ic)) % O);
+        const int ph = (int)(q / (4ll * Ic * O));
+        const int py = ph >> 1, px = ph & 1, a = t >> 1, b = t & 1;
+        const int ky0 = py + a == 0 ? 0 : (py + a == 2 ? 2 : (py == 0 ? 1 : 0)), ky1 = py + a == 1 ? ky0 + 1 : ky0;
+        const int kx0 = px + b == 0 ? 0 : (px + b == 2 ? 2 : (px == 0 ? 1 : 0)), kx1 = px + b == 1 ? kx0 + 1 : kx0;
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) {
+                float v[8];
+                unpack8(W[((long long)o * 9 + ky * 3 + kx) * Ic + c], v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] += v[j];
+            }
+        Wout[q] = pack8(acc);
+    }
+}
+// split-K second pass of the upconv route (gemm.hip): sum the fp32 slabs in slab order, add the bias, depth-to-space store — row (img, y, x) of
+// the source image, column block ph = py * 2 + px, goes to output pixel (2y + py, 2x + px).
+// p is the launch's own view: M source pixels, N = 4 Cout columns [phase][Cout].
+__global__ __launch_bounds__(256) void upconv_reduce_kernel(const GemmParams p) {
+    const int cpr = p.N / 8, cout = p.N >> 2, hw = p.Hs * p.Ws;
+    const long long total = (long long)p.M * cpr;
+    const long long slab = (long long)p.M * p.N;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long long)gridDim.x * blockDim.x) {
+        const int m = (int)(q / cpr), n = (int)(q - (long long)m * cpr) * 8;
+        const int ph = n / cout, col = n - ph * cout;
+        const float* base = p.partial + (long long)m * p.N + n;
+        float v[8];
+        unpack8(p.bias_n != nullptr ? ld16(p.bias_n + col) : zero16(), v);
+        float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int s = 0; s < p.splitk; ++s) {
+            const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + s * slab), x1 = *reinterpret_cast<const f32x4*>(base + s * slab + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                a[j] += x0[j];
+                a[4 + j] += x1[j];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += a[j];
+        const int img = m / hw, rem = m - img * hw, y = rem / p.Ws, x = rem - y * p.Ws;
+        const long long orow = (long long)(img * 2 * p.Hs + 2 * y + (ph >> 1)) * (2 * p.Ws) + 2 * x + (ph & 1);
+        st16(p.C + orow * p.ldc + col, pack8(v));
+    }
+}
+
 }  // namespace
 
 int skip_fold_launch(const half_t* W2, const half_t* Wsk, const half_t* b2, const half_t* bsk, int N, int K9, int SC, half_t* Wout, half_t* bout,
@@ -644,5 +699,23 @@ int skip_fold_launch(const half_t* W2, const half_t* Wsk, const half_t* b2, cons
     if (blocks * 256 < N) blocks = (N + 255) / 256;
     hipLaunchKernelGGL(skip_fold_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const uint4*>(W2), reinterpret_cast<const uint4*>(Wsk), b2, bsk, N,
                        K9 / 8, SC / 8, reinterpret_cast<uint4*>(Wout), bout);
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
+int upconv_fold_launch(const half_t* W, int O, int I, half_t* Wout, hipStream_t stream) {
+    if (W == nullptr || Wout == nullptr || O <= 0 || I <= 0 || (I & 7)) return LD_ERR_ARG;
+    const long long total = 16ll * O * (I / 8);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(upconv_fold_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const uint4*>(W), O, I / 8, reinterpret_cast<uint4*>(Wout));
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
+int upconv_reduce_launch(const GemmParams& p, hipStream_t stream) {
+    if (p.partial == nullptr || p.C == nullptr || p.splitk < 2 || p.M <= 0 || (p.N % 32) || p.Hs <= 0 || p.Ws <= 0 || p.M % (p.Hs * p.Ws)) return LD_ERR_ARG;
+    const long long total = (long long)p.M * (p.N / 8);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(upconv_reduce_kernel, dim3(blocks), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
 }

@@ -31,6 +31,9 @@ struct StW {
 };
 struct ConvW {
     int cin = 0, cout = 0, w = -1, b = -1;
+    // Upsample1 only: the nearest-2x resize folded into the weights — the 16 phase-tap matrices [py*2+px][cout][a*2+b][cin] (gemm.h Wup), derived
+    // with the other folds; byte offset into fold_base, or -1
+    long long f_up = -1;
 };
 enum LayerKind { L_CONV_IN, L_RES, L_ST, L_DOWN, L_UP };
 struct Layer {
@@ -251,6 +254,8 @@ int build(ld_unet* u) {
             if (lvl && i == c.num_res_blocks[lvl]) {
                 L.push_back({L_UP, add_conv(u, S("output_blocks.%d.%d.conv", idx, j), ch, ch)});
                 u->want_w8(u->convs.back().w, ch, ch);
+                u->convs.back().f_up = (long long)u->fold_bytes;
+                u->fold_bytes += (16 * (size_t)ch * ch * sizeof(half_t) + 255) / 256 * 256;
             }
             u->out_blocks.push_back(L);
             ++idx;
@@ -301,7 +306,7 @@ struct Run {
 
     half_t* conv3(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int wslot, int bslot,
                   int cout, const half_t* rowvec, int ldrv, const half_t* R, half_t* out, int* Ho_, int* Wo_, int ksize = 3, float* stats = nullptr,
-                  int* stats_done = nullptr) {
+                  int* stats_done = nullptr, const half_t* wup = nullptr) {
         const int Ho = ksize == 3 ? (Hv - 1) / stride + 1 : Hv, Wo = ksize == 3 ? (Wv - 1) / stride + 1 : Wv;
         GemmParams p;
         p.conv = 1;
@@ -310,6 +315,7 @@ struct Run {
         p.Hs = Hs; p.Ws = Ws; p.Hv = Hv; p.Wv = Wv; p.Ho = Ho; p.Wo = Wo; p.stride = stride;
         p.W = P(wslot); p.ldw = ksize * ksize * (C1 + C2);
         p.W8 = ksize == 3 ? u->w8(wslot) : nullptr;
+        p.Wup = wup;
         p.M = n * Ho * Wo; p.N = cout; p.K = ksize * ksize * (C1 + C2);
         p.bias_n = P(bslot);
         p.rowvec = rowvec; p.rows_per_vec = Ho * Wo; p.ldrv = ldrv;
@@ -566,6 +572,11 @@ int fold_layernorms(ld_unet* u, hipStream_t stream) {
                                         reinterpret_cast<half_t*>(u->fold_base + r.f_c2_w), reinterpret_cast<half_t*>(u->fold_base + r.f_c2_b), stream);
         if (st != LD_OK) return st;
     }
+    for (const ConvW& c : u->convs) {
+        if (c.f_up < 0) continue;
+        const int st = upconv_fold_launch(u->pt.ptr(c.w), c.cout, c.cin, reinterpret_cast<half_t*>(u->fold_base + c.f_up), stream);
+        if (st != LD_OK) return st;
+    }
     u->fold_dirty = false;
     return LD_OK;
 }
@@ -662,7 +673,10 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                     const ConvW& cw = u->convs[L.idx];
                     const int Hv = outH > 0 ? outH : f.H * 2, Wv = outW > 0 ? outW : f.W * 2;
                     half_t* o = ar.halfs((size_t)n * Hv * Wv * cw.cout);
-                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, nullptr, 0, nullptr, o, nullptr, nullptr);
+                    // (the folded weights are an offer: gemm_plan takes them for an exact 2x resize above the row-resident kernel's batch.  The launch is
+                    // counted as the 3x3 convolution it implements — last_flops is algorithmic work — and executes 4/9 of it)
+                    const half_t* wup = (u->fold_base != nullptr && cw.f_up >= 0) ? reinterpret_cast<const half_t*>(u->fold_base + cw.f_up) : nullptr;
+                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, nullptr, 0, nullptr, o, nullptr, nullptr, 3, nullptr, nullptr, wup);
                     f = {o, cw.cout, Hv, Wv};
                     break;
                 }

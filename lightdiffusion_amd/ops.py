@@ -130,6 +130,29 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor]
     return y
 
 
+def upconv2x_fold(w_packed: torch.Tensor) -> torch.Tensor:
+    """The 16 phase-tap matrices of a nearest-2x upsample + 3x3 convolution, from w_packed [O, 9*I] (repack_conv_weight):
+    fp16 [4, O, 4*I] = [py*2+px][O][a*2+b][I], sums of the 3x3 taps that fall on one source pixel (fp32 sums, one rounding)."""
+    O = w_packed.shape[0]
+    I = w_packed.shape[1] // 9
+    out = torch.empty(4, O, 4 * I, dtype=torch.float16, device=w_packed.device)
+    check(lib().ld_op_upconv2x_fold(_p(w_packed), O, I, _p(out), _stream()), "ld_op_upconv2x_fold")
+    return out
+
+
+def upconv2x(x: torch.Tensor, w_packed: torch.Tensor, w_fold: torch.Tensor, bias: Optional[torch.Tensor], out_hw: Optional[tuple] = None) -> torch.Tensor:
+    """Upsample1 (LD.py:5141-5152) as the UNet executor runs it: nearest resize of x [N,H,W,C] to out_hw (default 2H x 2W), then the 3x3
+    convolution — on the folded weights (upconv2x_fold) for an exact 2x resize of more than two images, otherwise as conv2d."""
+    n, h, w, c = x.shape
+    hv, wv = (2 * h, 2 * w) if out_hw is None else out_hw
+    cout = w_packed.shape[0]
+    y = torch.empty(n, hv, wv, cout, dtype=torch.float16, device=x.device)
+    ws = _ws(192 << 20, x.device)
+    check(lib().ld_op_upconv2x(_p(x), c, n, h, w, hv, wv, _p(w_packed), _p(w_fold), _p(bias), _p(y), cout, _p(ws), ws.numel(), _stream()),
+          "ld_op_upconv2x")
+    return y
+
+
 def conv2d_skip(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, s1: torch.Tensor, s2: Optional[torch.Tensor], w_skip: torch.Tensor,
                 b_skip: torch.Tensor, rowvec: Optional[torch.Tensor] = None) -> torch.Tensor:
     """ResBlock1's out_layers convolution + its 1x1 skip_connection as one contraction (LD.py:5267, 5273-5287):
