@@ -79,7 +79,7 @@ struct GemmParams {
     //   its in-launch reduction of the channel-slab partial sums needs >= 4 * (N / 80) zeroed ints that it leaves zeroed (self-resetting)
     int* sync = nullptr;
     int c8_S = 0;                // (internal) slab split chosen by conv8_plan
-    // ---- nearest-2x upsampling folded into the weights (upconv route, gemm.hip "upconv"): the 3x3 convolution of a 2x-upsampled image is four 2x2
+    // ---- nearest-2x upsampling folded into the weights (upconv route, gemm5.hip "upconv"): the 3x3 convolution of a 2x-upsampled image is four 2x2
     //   convolutions of the SOURCE image, one per output phase (py, px).  Wup holds the 16 phase-tap matrices [py*2+px][N][a*2+b][C1] (sums of the
     //   3x3 taps, upconv_fold_launch); a caller that sets it offers the route, gemm_plan takes it for an exact 2x resize of one source above conv8's batch
     const half_t* Wup = nullptr;

@@ -656,7 +656,7 @@ __global__ __launch_bounds__(256) void upconv_fold_kernel(const uint4* __restric
         Wout[q] = pack8(acc);
     }
 }
-// split-K second pass of the upconv route (gemm.hip): sum the fp32 slabs in slab order, add the bias, depth-to-space store — row (img, y, x) of
+// split-K second pass of the upconv route (gemm5.hip): sum the fp32 slabs in slab order, add the bias, depth-to-space store — row (img, y, x) of
 // the source image, column block ph = py * 2 + px, goes to output pixel (2y + py, 2x + px).
 // p is the launch's own view: M source pixels, N = 4 Cout columns [phase][Cout].
 __global__ __launch_bounds__(256) void upconv_reduce_kernel(const GemmParams p) {

@@ -8,7 +8,7 @@ Rounding model (fp16 inputs, fp32 MFMA accumulation, one fp16 rounding of the ou
   * fp16 x fp16 products are exact in fp32; the matrix core accumulates them as an fp32 chain.  Its error against fp64 is c_acc(K) * sum|a b|
     (c_acc below), where sum|a b| = (|A| |W|^T) of the same row / column.
   * the GEMM epilogues stage the finished tile (alpha acc + bias) in fp16, apply the activation to the fp16 values, and add rowvec /
-    residual as packed fp16 adds (gemm.hip epilogue_tile, add8h): one fp16 rounding of alpha acc and of the pre-activation value (2^-11 each,
+    residual as packed fp16 adds (gemm_device.h epilogue_tile, add8h): one fp16 rounding of alpha acc and of the pre-activation value (2^-11 each,
     times the activation's Lipschitz constant L_act <= 1.13 for SiLU / quick-GELU / GELU), one of the activation's output before a residual,
     one per packed add (rowvec, then residual), fp32 arithmetic in between (2^-23), plus the approximation error eps_act of an activation fit.
   * the output is rounded to fp16 once more: 2^-11 |y_hat| (normal range) or 2^-25 absolute (subnormal range): the 2^-11 |y_hat| + 2^-24 terms.

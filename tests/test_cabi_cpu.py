@@ -31,7 +31,7 @@ def test_product_never_imports_oracle():
 def test_isa_check_of_untracked_loads(tmp_path):
     """the counted waits behind hand-issued loads (conv8's ld16_sc1, gemm's epi_stage_load) are only as good as the code
     hipcc generates around them.  tools/isa_check.py re-checks the assembly: here its hazard model on two synthetic kernels, then the real
-    conv8.hip (gemm.hip takes minutes: `make -C lightdiffusion_amd/csrc isa-check`)."""
+    conv8.hip (gemm3.hip, conv6.hip and the A/B build take minutes: `make -C lightdiffusion_amd/csrc isa-check`)."""
     import shutil
     import subprocess
     import sys

@@ -116,14 +116,16 @@ def test_cpu_conv_reference_matches_im2col():
 
 
 def test_every_contraction_kernel_template_has_a_route_row():
-    """A new __global__ kernel in gemm.hip / conv8.hip / attention.hip cannot land without a pinned row in tests/test_routes_gpu.py
+    """A new __global__ kernel in gemm.hip, a kernel family's source (gemm3.hip, gemm5.hip, conv6.hip, gemm7.hip, conv8.hip) or attention.hip
+    cannot land without a pinned row in tests/test_routes_gpu.py
     (conv8_repack_kernel is the weight-layout copy behind conv8, not a contraction: it has no route of its own)."""
     import test_routes_gpu as R
     csrc = os.path.join(ROOT, "lightdiffusion_amd", "csrc")
     names = set()
-    for f in ("gemm.hip", "conv8.hip", "attention.hip"):
+    for f in ("gemm.hip", "gemm3.hip", "gemm5.hip", "conv6.hip", "gemm7.hip", "conv8.hip", "attention.hip"):
         names.update(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+_kernel)\s*\(", open(os.path.join(csrc, f)).read()))
     names.discard("conv8_repack_kernel")
-    assert {"gemm3_kernel", "gemm5_kernel", "conv6_kernel", "conv8_kernel", "flash_attn2_kernel", "flash_attn512_kernel"} <= names
+    assert {"gemm3_kernel", "gemm4_kernel", "gemm5_kernel", "conv6_kernel", "gemm7_kernel", "conv8_kernel", "splitk_reduce_kernel", "splitk_reduce_gn_kernel",
+            "flash_attn2_kernel", "flash_attn512_kernel"} <= names
     pinned = {n.split("<")[0] for n in R.route_names()}
     assert not names - pinned, f"kernel templates without a route row: {sorted(names - pinned)}"

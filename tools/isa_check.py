@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Post-build ISA check for the hand-issued (untracked) vector loads of gemm.hip / conv8.hip.
+"""Post-build ISA check for the hand-issued (untracked) vector loads of gemm3.hip / conv6.hip / conv8.hip.
 
-`epi_stage_load` / `ld16_sc1` issue `global_load_dwordx4` through inline asm, so hipcc's waitcnt pass does not know that the destination
+`epi_stage_load` (gemm_device.h; its callers are gemm3_kernel and gemm4_kernel), `gn_load` (conv6.hip) and `ld16_sc1` (conv8.hip) issue
+`global_load_dword[x4]` through inline asm, so hipcc's waitcnt pass does not know that the destination
 registers are in flight; the only protection is that the counted `s_waitcnt vmcnt(N)` names those registers as read-write operands.
 This script re-checks the generated code: it assembles the source for gfx950 (device only), walks every kernel and, for every plain
 (non-LDS) global load, follows the straight-line code behind it while the load can still be in flight — modelling vmcnt as the in-order
@@ -9,7 +10,7 @@ counter it is — and fails if any instruction reads or writes one of the destin
 (a `v_mov` copy, a spill to scratch, a `v_accvgpr_write`, an early consumer).  Tracked loads pass trivially; the check stops at the
 first branch / label after a load (nothing is claimed about loads that live across one).
 
-Usage: python tools/isa_check.py [gemm.hip conv8.hip ...] [--ab]      (exit status 1 on a finding)
+Usage: python tools/isa_check.py [gemm3.hip conv6.hip conv8.hip ...] [--ab]      (exit status 1 on a finding)
 """
 import os
 import re
@@ -88,7 +89,7 @@ def check_asm(path):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     ab = "--ab" in sys.argv
-    srcs = args or ["gemm.hip", "conv8.hip"]
+    srcs = args or ["gemm3.hip", "conv6.hip", "conv8.hip"]
     bad = []
     with tempfile.TemporaryDirectory() as td:
         for s in srcs:
