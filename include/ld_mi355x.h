@@ -89,6 +89,28 @@ int ld_unet_profile_kernels(const ld_unet* u, char* buf, size_t buf_bytes);
 /* per LAUNCH of the last ld_unet_profile call, in launch order: "what<TAB>M<TAB>N<TAB>K<TAB>batch<TAB>algorithmic FLOPs<TAB>
  * microseconds<TAB>kernel" (contractions; GroupNorm rows carry images / pixels / channels / silu, attention rows batch*heads / Lq / Lk / d) */
 int ld_unet_profile_launches(const ld_unet* u, char* buf, size_t buf_bytes);
+/* LoRA patches of the RESIDENT weights — what ModelPatcher.patch_model / unpatch_model do with calculate_weight and a backup of the
+ * original tensors (LD.py:3335-3354, 3407-3437), on the device and in the slots' resident layouts.  One low-rank term of a patch:
+ * up [rows][rank], down [rank][cols], row-major device pointers, both LD_F16 or both LD_F32 (`dtype`); 1 <= rank <= 256; scale = strength * alpha / rank.
+ * For a conv, cols = Cin*kh*kw in the checkpoint's (i, ky, kx) order (flatten(start_dim=1)). */
+typedef struct { const void* up; const void* down; int dtype; int rank; float scale; } ld_lora_term;
+/* slot = round_fp16(float(backup) + sum_j scale_j up_j down_j): fp32 products and sum, ONE rounding to nearest for all terms (1 <= n_terms <= 8).
+ * The first patch of a slot snapshots its resident bytes into a device backup; every call recomputes from that backup, so re-patching is
+ * not cumulative.  LD_ERR_ARG: unknown name, slot not loaded, a vector slot (bias / norm), rank or n_terms out of range.
+ * Patch, unpatch and refresh are load-class calls: they may allocate, are ordered on `stream`, and must not be issued during stream capture
+ * (LD_ERR_STATE).  Addresses do not move: captured hipGraphs stay valid, but the derived copies must be refreshed (below) and the context set again
+ * (the resident cross-attention K / V^T were projected with attn2.to_k / to_v). */
+int ld_unet_patch_param(ld_unet* u, const char* name, const ld_lora_term* terms, int n_terms, void* stream);
+/* copy the backup back (bit-identical to before the first patch) and free it; name == NULL: every patched slot; never-patched slot: no-op.
+ * ld_unet_load_param on a patched slot drops that slot's backup instead (the new load is the new base). */
+int ld_unet_unpatch(ld_unet* u, const char* name, void* stream);
+/* one parameter back in CHECKPOINT layout (conv OIHW, linear [out,in], GEGLU rows [value | gate]), fp16: dst_f16 holds the slot's element count */
+int ld_unet_read_param(const ld_unet* u, const char* name, void* dst_f16, void* stream);
+/* re-derive every copy derived from the resident weights (LayerNorm / skip / MLP-out / upsample folds, the row-resident conv layout) if a load,
+ * patch or unpatch has happened since — what the next ld_unet_forward would do first; a replayed hipGraph does not, so call this after a batch of patches */
+int ld_unet_refresh_derived(ld_unet* u, void* stream);
+/* bytes of the patch backups currently held (not part of ld_unet_weight_bytes) */
+size_t ld_unet_patch_bytes(const ld_unet* u);
 /* number of kernel launches of the last forward, and algorithmic FLOPs of it (2*M*N*K over every contraction) */
 int ld_unet_last_launches(const ld_unet* u);
 double ld_unet_last_flops(const ld_unet* u);
@@ -213,6 +235,9 @@ int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int
  * last ld_op_* call dispatched, in launch order, joined with ';' (e.g. "gemm3_kernel<64,160,conv>+splitk_reduce_kernel").  Reset at
  * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call. */
 const char* ld_op_last_kernel(void);
+/* The merge kernel of ld_unet_patch_param on a plain row-major matrix: dst[rows][cols] = round_fp16(float(base) + sum_j scale_j up_j down_j);
+ * dst may alias base.  Also what the host's text model patches its weights with. */
+int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,10 @@ class VAEConfig(C.Structure):
                 ("num_res_blocks", C.c_int), ("out_ch", C.c_int), ("with_encoder", C.c_int)]
 
 
+class LoraTerm(C.Structure):
+    _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
+
+
 class LDError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -56,6 +60,11 @@ SIGNATURES = {
     "ld_unet_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_unet_profile_kernels": (_I, [_P, C.c_char_p, _Z]),
     "ld_unet_profile_launches": (_I, [_P, C.c_char_p, _Z]),
+    "ld_unet_patch_param": (_I, [_P, C.c_char_p, C.POINTER(LoraTerm), _I, _P]),
+    "ld_unet_unpatch": (_I, [_P, C.c_char_p, _P]),
+    "ld_unet_read_param": (_I, [_P, C.c_char_p, _P, _P]),
+    "ld_unet_refresh_derived": (_I, [_P, _P]),
+    "ld_unet_patch_bytes": (_Z, [_P]),
     "ld_unet_last_launches": (_I, [_P]),
     "ld_unet_last_flops": (C.c_double, [_P]),
     "ld_vae_create": (_I, [C.POINTER(VAEConfig), C.POINTER(_P)]),
@@ -97,6 +106,7 @@ SIGNATURES = {
     "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
+    "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),
 }
 
 

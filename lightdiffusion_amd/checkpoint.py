@@ -207,17 +207,27 @@ class LoraMergeResult(int):
     missing_down: tuple = ()
 
 
-def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], strength: float = 1.0, strength_clip: Optional[float] = None,
-               prefix: str = UNET_PREFIX, clip_prefix: str = CLIP_PREFIX) -> LoraMergeResult:
-    """Merge a LoRA file into the checkpoint state dict in place, UNet and text encoder: for every pair the key map resolves,
-    W += strength * (alpha / rank) * up @ down, in fp32, cast back to W's dtype (load_lora LD.py:549-575 + calculate_weight
-    LD.py:3407-3424; the reference patches before sampling, LD.py:3335-3354, so the HIP side only ever sees final weights).
-    `strength_clip` defaults to `strength` (load_lora_for_models takes both, LD.py:6203-6219).  LoRA modules that match
-    nothing are reported (`.unmatched`) and warned about instead of being dropped silently."""
-    import warnings
-    km = lora_key_map(sd, prefix, clip_prefix)
-    sc = strength if strength_clip is None else strength_clip
-    n_unet = n_clip = 0
+class LoraResolution(dict):
+    """{checkpoint key: (up, down, alpha or None)} — one entry per TARGET weight — with the report of what did not resolve"""
+    unmatched: tuple = ()
+    missing_down: tuple = ()
+
+    def warn(self) -> None:
+        import warnings
+        if self.missing_down:
+            warnings.warn(f"LoRA: {len(self.missing_down)} module(s) have lora_up but no lora_down weight and were not applied: "
+                          + ", ".join(self.missing_down[:4]))
+        if self.unmatched:
+            warnings.warn(f"LoRA: {len(self.unmatched)} module(s) match no layer of this checkpoint and were not applied: "
+                          + ", ".join(self.unmatched[:4]) + (" ..." if len(self.unmatched) > 4 else ""))
+
+
+def resolve_lora(keys, lora: Dict[str, torch.Tensor], prefix: str = UNET_PREFIX, clip_prefix: str = CLIP_PREFIX) -> LoraResolution:
+    """Which weights of a checkpoint a LoRA file patches, and with what: `keys` is the checkpoint's state dict (or any mapping of its keys
+    to tensors; only names and shapes are read), the result maps each patched checkpoint key to (lora_up, lora_down, alpha or None).
+    load_lora (LD.py:549-575) keyed by the target weight: `merge_lora` (host merge before upload) and `nodes.LoraLoader` (device patch of
+    the resident weights) share this resolution."""
+    km = lora_key_map(keys, prefix, clip_prefix)
     seen = set()
     modules = sorted({k[:-len(".lora_up.weight")] for k in lora if k.endswith(".lora_up.weight")})
     present = set(modules)
@@ -230,12 +240,29 @@ def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], stren
         if name in present and name + ".lora_down.weight" in lora:
             patches[key] = name
             seen.add(name)
+    res = LoraResolution()
     for key, name in patches.items():
-        up, down = lora[name + ".lora_up.weight"], lora[name + ".lora_down.weight"]
+        res[key] = (lora[name + ".lora_up.weight"], lora[name + ".lora_down.weight"], lora.get(name + ".alpha"))
+    res.unmatched = tuple(m for m in modules if m not in seen and m not in no_down)
+    res.missing_down = no_down
+    return res
+
+
+def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], strength: float = 1.0, strength_clip: Optional[float] = None,
+               prefix: str = UNET_PREFIX, clip_prefix: str = CLIP_PREFIX) -> LoraMergeResult:
+    """Merge a LoRA file into the checkpoint state dict in place, UNet and text encoder: for every pair the key map resolves,
+    W += strength * (alpha / rank) * up @ down, in fp32, cast back to W's dtype (load_lora LD.py:549-575 + calculate_weight
+    LD.py:3407-3424; the reference patches before sampling, LD.py:3335-3354, so the HIP side only ever sees final weights).
+    `strength_clip` defaults to `strength` (load_lora_for_models takes both, LD.py:6203-6219).  LoRA modules that match
+    nothing are reported (`.unmatched`) and warned about instead of being dropped silently."""
+    resolved = resolve_lora(sd, lora, prefix, clip_prefix)
+    sc = strength if strength_clip is None else strength_clip
+    n_unet = n_clip = 0
+    for key, (up, down, alpha) in resolved.items():
         is_clip = key.startswith(clip_prefix)
         scale = sc if is_clip else strength
-        if name + ".alpha" in lora:
-            scale = scale * float(lora[name + ".alpha"]) / down.shape[0]
+        if alpha is not None:
+            scale = scale * float(alpha) / down.shape[0]
         w = sd[key]
         delta = torch.mm(up.flatten(start_dim=1).float(), down.flatten(start_dim=1).float()).reshape(w.shape)
         sd[key] = (w.float() + scale * delta).to(w.dtype)
@@ -243,13 +270,9 @@ def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], stren
         n_unet += not is_clip
     res = LoraMergeResult(n_unet + n_clip)
     res.unet, res.clip = n_unet, n_clip
-    res.unmatched = tuple(m for m in modules if m not in seen and m not in no_down)
-    res.missing_down = no_down
-    if no_down:
-        warnings.warn(f"LoRA: {len(no_down)} module(s) have lora_up but no lora_down weight and were not applied: " + ", ".join(no_down[:4]))
-    if res.unmatched:
-        warnings.warn(f"LoRA: {len(res.unmatched)} module(s) match no layer of this checkpoint and were not applied: "
-                      + ", ".join(res.unmatched[:4]) + (" ..." if len(res.unmatched) > 4 else ""))
+    res.unmatched = resolved.unmatched
+    res.missing_down = resolved.missing_down
+    resolved.warn()
     return res
 
 

@@ -115,6 +115,43 @@ class PromptTokenizer:
         return chunks
 
 
+# ------------------------------------------------------------------ LoRA patch bookkeeping (shared by nodes.ModelPatcher and CLIP)
+class LoraPatches:
+    """The LoRA patches one ModelPatcher carries, and their identity: {checkpoint key: [(strength_patch, (up, down, alpha), strength_model)]}
+    and a uuid that changes with every add_patches (None: the loaded weights)."""
+
+    def __init__(self):
+        self.patches: Dict[str, list] = {}
+        self.uuid = None
+
+
+def _add_patches(owner, model_keys, patches, strength_patch: float, strength_model: float):
+    """ModelPatcher.add_patches (LD.py:3297-3307): append (strength_patch, patch, strength_model) to the list of every key of `patches` the
+    model has; a new patches_uuid; returns the matched keys.  `model_keys` is {key: shape}: a patch whose name resolves but whose factors do
+    not fit the weight (an SD2.x LoRA on this net: same block names, other widths) raises ValueError before anything is added, as the
+    load-time merge does at its reshape — the device merge indexes the factors by the weight's rows and columns and must never see them."""
+    import uuid
+    from .unet import lora_factor_mismatch
+    matched = [k for k in patches if k in model_keys]
+    for k in matched:
+        why = lora_factor_mismatch(model_keys[k], patches[k][0], patches[k][1])
+        if why is not None:
+            raise ValueError(f"LoRA does not fit this model: '{k}': {why}")
+    for k in matched:
+        owner.patches.setdefault(k, []).append((strength_patch, patches[k], strength_model))
+    owner.patches_uuid = uuid.uuid4()
+    return matched
+
+
+def patch_terms(entries) -> list:
+    """[(strength_patch, (up, down, alpha or None), strength_model)] -> [(up, down, scale)] with alpha / rank folded into the scale as
+    calculate_weight does (LD.py:3407-3424: alpha *= v[2] / mat2.shape[0]; strength_model is not read there either)."""
+    out = []
+    for strength, (up, down, alpha), _ in entries:
+        out.append((up, down, float(strength) * (float(alpha) / down.shape[0] if alpha is not None else 1.0)))
+    return out
+
+
 # ------------------------------------------------------------------ text transformer
 class CLIPTextModelHIP:
     """CLIP-L text transformer (CLIPTextModel_, LD.py:4413-4463) on the HIP kernels — the package's ONLY text model
@@ -134,6 +171,53 @@ class CLIPTextModelHIP:
             w = torch.cat([self.w[p + f"{t}_proj.weight"] for t in "qkv"]).contiguous()
             b = torch.cat([self.w[p + f"{t}_proj.bias"] for t in "qkv"]).contiguous()
             self.qkv.append((w, b))
+        self._backup: Dict[str, torch.Tensor] = {}      # device clones of the LoRA-patched tensors as they were loaded
+        self.applied_patches_uuid = None                # identity of the patch set merged into self.w (None: the loaded weights)
+
+    def param_shapes(self) -> Dict[str, tuple]:
+        return {k: tuple(v.shape) for k, v in self.w.items()}
+
+    def _sync_qkv(self, key: str) -> None:
+        """the fused [q|k|v] projection holds a copy of a patched q / k / v_proj weight: refresh its row block"""
+        import re
+        m = re.match(r"^text_model\.encoder\.layers\.(\d+)\.self_attn\.([qkv])_proj\.weight$", key)
+        if m:
+            h, j = self.cfg["hidden_size"], "qkv".index(m.group(2))
+            self.qkv[int(m.group(1))][0][j * h:(j + 1) * h].copy_(self.w[key])
+
+    def unpatch_weights(self, uuid=None) -> None:
+        """the loaded weights back, bit for bit (ModelPatcher.unpatch_model, LD.py:3426-3437)"""
+        with torch.no_grad():
+            for key, saved in self._backup.items():
+                self.w[key].copy_(saved)
+                self._sync_qkv(key)
+        self._backup = {}
+        self.applied_patches_uuid = uuid
+
+    def patch_weights(self, patches: Dict[str, list], uuid=None) -> None:
+        """ModelPatcher.patch_model (LD.py:3335-3354) on the resident fp16 tensors: `patches` {key under text_model.: [(up, down, scale), ...]};
+        w = round_fp16(loaded w + sum scale up down), the merge on the device (`ld_op_lora_merge`) from a device clone of the loaded tensor.
+        A patch that is refused (an unknown key, factors that do not fit, a rank or a number of terms out of range) raises, and leaves the
+        loaded weights in place."""
+        from ._lib import check, lib
+        from .unet import lora_terms
+        self.unpatch_weights()
+        try:
+            with torch.no_grad(), torch.cuda.device(self.device):
+                for key, terms in patches.items():
+                    w = self.w[key]
+                    if w.dim() != 2:
+                        raise ValueError(f"'{key}' is not a matrix")
+                    arr, keep = lora_terms(terms, self.device, tuple(w.shape))       # (ValueError unless w is a matrix the factors fit)
+                    self._backup[key] = w.clone()
+                    check(lib().ld_op_lora_merge(self._backup[key].data_ptr(), w.data_ptr(), w.shape[0], w.shape[1], arr, len(terms),
+                                                 torch.cuda.current_stream().cuda_stream), f"ld_op_lora_merge({key})")
+                    del keep
+                    self._sync_qkv(key)
+        except Exception:
+            self.unpatch_weights()               # restores what was merged so far from its backups; applied_patches_uuid = None
+            raise
+        self.applied_patches_uuid = uuid if uuid is not None else object()   # (a direct call: matches no patcher, so the next lazy swap restores)
 
     @torch.no_grad()
     def __call__(self, tokens: torch.Tensor, intermediate_output: Optional[int] = None):
@@ -171,9 +255,44 @@ class CLIP:
         """text_model(tokens[B, 77] long, intermediate_output=layer_idx) -> (last hidden state, hidden state at layer_idx or None, pooled):
         `CLIPTextModelHIP` in the product."""
         self.text_model, self.tokenizer, self.layer_idx = text_model, tokenizer, layer_idx
+        self.patches: Dict[str, list] = {}              # checkpoint key -> [(strength_patch, (up, down, alpha), strength_model)]
+        self.patches_uuid = None                        # None: the loaded weights
 
     def clone(self) -> "CLIP":
-        return CLIP(self.text_model, self.tokenizer, self.layer_idx)
+        n = CLIP(self.text_model, self.tokenizer, self.layer_idx)
+        n.patches = {k: list(v) for k, v in self.patches.items()}
+        n.patches_uuid = self.patches_uuid
+        return n
+
+    # -- LoRA patches (CLIP.add_patches -> ModelPatcher.add_patches, LD.py:3297-3307): bookkeeping here, the swap is lazy (patch_model)
+    KEY_PREFIX = "cond_stage_model.transformer."
+
+    def model_key_shapes(self) -> Dict[str, tuple]:
+        """{checkpoint key: shape} of the text model's parameters"""
+        return {self.KEY_PREFIX + k: s for k, s in self.text_model.param_shapes().items()}
+
+    def add_patches(self, patches, strength_patch: float = 1.0, strength_model: float = 1.0):
+        return _add_patches(self, self.model_key_shapes(), patches, strength_patch, strength_model)
+
+    def patch_model(self):
+        """Make the shared resident text model carry THIS clone's patches (where the reference calls load_models_gpu, LD.py:6262): a no-op when
+        they already are applied; an empty set restores the loaded weights."""
+        tm = self.text_model
+        if getattr(tm, "applied_patches_uuid", None) == self.patches_uuid:
+            return tm
+        if not hasattr(tm, "patch_weights"):
+            if self.patches:
+                raise RuntimeError("this text model cannot be patched (no patch_weights)")
+            return tm
+        if self.patches:
+            tm.patch_weights({k[len(self.KEY_PREFIX):]: patch_terms(v) for k, v in self.patches.items()}, self.patches_uuid)
+        else:
+            tm.unpatch_weights(self.patches_uuid)
+        return tm
+
+    def unpatch_model(self):
+        if hasattr(self.text_model, "unpatch_weights"):
+            self.text_model.unpatch_weights()
 
     def clip_layer(self, layer_idx: int) -> None:           # CLIPSetLastLayer → clip skip
         self.layer_idx = layer_idx
@@ -184,6 +303,7 @@ class CLIP:
         return {"l": self.tokenizer.tokenize_with_weights(text)}
 
     def _encode_ids(self, ids: List[List[int]]):
+        self.patch_model()
         last, inter, pooled = self.text_model(torch.tensor(ids, dtype=torch.long), intermediate_output=self.layer_idx)
         return (last if inter is None else inter).float(), pooled.float()
 

@@ -424,6 +424,24 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
     return gemm_op(b, stream);
 }
 
+int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream) {
+    op_begin();
+    if (terms == nullptr || n_terms < 1 || n_terms > LORA_MAX_TERMS) return LD_ERR_ARG;
+    LoraArgs a;
+    a.base = (const half_t*)base_f16;
+    a.dst = (half_t*)dst_f16;
+    a.lay.kind = LORA_MAT;
+    a.lay.rows = rows;
+    a.lay.cols = cols;
+    a.n_terms = n_terms;
+    for (int j = 0; j < n_terms; ++j) {
+        if (terms[j].dtype != LD_F16 && terms[j].dtype != LD_F32) return LD_ERR_ARG;
+        a.t[j].up = terms[j].up; a.t[j].down = terms[j].down; a.t[j].f32 = terms[j].dtype == LD_F32;
+        a.t[j].rank = terms[j].rank; a.t[j].scale = terms[j].scale;
+    }
+    return lora_merge_launch(a, (hipStream_t)stream);
+}
+
 int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, void* stream) {
     op_begin();
     return bislerp_launch(x, tmp, y, n, c, h, w, h_new, w_new, (hipStream_t)stream);

@@ -121,3 +121,32 @@ int hook_check_launch(const void* a, const void* b, size_t words_ab, const void*
                       int* flags, int epoch, hipStream_t stream);
 // bislerp (LD.py:429-518): fp32 NCHW [n][c][h][w] -> [n][c][h_new][w_new]; tmp holds n*c*h*w_new floats (width pass first)
 int bislerp_launch(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, hipStream_t stream);
+
+// LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
+//   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
+// (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout
+// `kind` (LORA_MAT rows as is, LORA_CONV3 [O][ky][kx][I], LORA_GEGLU the tile interleave of repack_rows_launch with geglu_bn = bn).
+enum LoraLayoutKind { LORA_MAT = 0, LORA_CONV3 = 1, LORA_GEGLU = 2 };
+struct LoraLayout {
+    int kind = LORA_MAT;
+    int rows = 0, cols = 0;
+    int bn = 0;               // LORA_GEGLU: rows per interleaved tile
+};
+constexpr int LORA_MAX_TERMS = 8, LORA_MAX_RANK = 256;
+struct LoraTerm {
+    const void* up = nullptr;      // [rows][rank] row-major
+    const void* down = nullptr;    // [rank][cols] row-major
+    int f32 = 0;                   // both factors fp32 (else fp16)
+    int rank = 0;
+    float scale = 0.f;
+};
+struct LoraArgs {
+    const half_t* base = nullptr;
+    half_t* dst = nullptr;         // may alias base
+    LoraLayout lay;
+    int n_terms = 0;
+    LoraTerm t[LORA_MAX_TERMS];
+};
+int lora_merge_launch(const LoraArgs& a, hipStream_t stream);
+// resident layout -> checkpoint layout [rows][cols] (the inverse of the load-time repack; same index map as the merge)
+int lora_read_launch(const half_t* resident, const LoraLayout& lay, half_t* dst, hipStream_t stream);

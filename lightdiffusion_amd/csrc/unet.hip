@@ -92,7 +92,18 @@ struct ld_unet {
     bool want_timing = false;
     char* fold_base = nullptr;     // LN-folded copies of the LN-consuming projections (see StW)
     size_t fold_bytes = 0;
-    bool fold_dirty = true;        // set by every ld_unet_load_param; cleared when the fold kernels have run
+    bool fold_dirty = true;        // set by every ld_unet_load_param / patch / unpatch; cleared when the fold kernels have run
+    // LoRA patches (ld_unet_patch_param): per patched slot a device snapshot of its resident bytes as they were before the first patch — a
+    // further resident copy, held only while the slot is patched.  Every merge reads the snapshot, ld_unet_unpatch copies it back.
+    std::unordered_map<int, half_t*> backups;
+    size_t patch_bytes = 0;
+    void drop_backup(int slot) {
+        auto it = backups.find(slot);
+        if (it == backups.end()) return;
+        (void)hipFree(it->second);
+        patch_bytes -= pt.slots[slot].elems * sizeof(half_t);
+        backups.erase(it);
+    }
 };
 
 namespace {
@@ -590,21 +601,27 @@ int derive_conv8_weights(ld_unet* u, hipStream_t stream) {
     return LD_OK;
 }
 
+// every copy derived from the resident weights, re-derived when a load, a patch or an unpatch has changed them (fold_dirty)
+int refresh_derived(ld_unet* u, hipStream_t stream) {
+    if (!u->fold_dirty) return LD_OK;
+    if (u->w8_base != nullptr) {
+        const int st = derive_conv8_weights(u, stream);
+        if (st != LD_OK) return st;
+    }
+    const int st = fold_layernorms(u, stream);
+    if (st != LD_OK) return st;
+    u->fold_dirty = false;
+    return LD_OK;
+}
+
 // `pair`: classifier-free-guidance pair (ld_unet_forward_pair).  x / sigma hold n / 2 samples; the batch is [uncond x n/2 ; cond x n/2] of the SAME latents
 // (what calc_cond_batch feeds the model: cat([x, x]), LD.py:2515-2547); the resident context has n rows.  The layers in front of the first
 // cross-attention run once on n / 2 samples (Run::pair_pending), everything else on n.  out: n samples.
 int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, hipStream_t stream,
                 size_t* dry_peak = nullptr, bool pair = false) {
-    if (!dry && u->fold_dirty) {
-        if (u->w8_base != nullptr) {
-            const int st = derive_conv8_weights(u, stream);
-            if (st != LD_OK) return st;
-        }
-        {
-            const int st = fold_layernorms(u, stream);
-            if (st != LD_OK) return st;
-        }
-        u->fold_dirty = false;
+    if (!dry) {
+        const int st = refresh_derived(u, stream);
+        if (st != LD_OK) return st;
     }
     if (pair && (n & 1)) return LD_ERR_SHAPE;
     Run R;
@@ -750,6 +767,27 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
 }  // namespace
 
 // ==================================================================================================== C ABI
+// LoRA patches: slot -> layout, capture guard
+namespace {
+// the logical matrix of a slot as a checkpoint stores it, and how the slot keeps it resident (ParamTable::load)
+LoraLayout slot_layout(const ParamSlot& s) {
+    LoraLayout L;
+    switch (s.kind) {
+        case PK_CONV3: L.kind = LORA_CONV3; L.rows = (int)s.shape[0]; L.cols = (int)s.shape[1] * 9; break;
+        case PK_GEGLU_W: L.kind = LORA_GEGLU; L.rows = (int)s.shape[0]; L.cols = (int)s.shape[1]; L.bn = s.geglu_bn; break;
+        case PK_GEGLU_B: L.kind = LORA_GEGLU; L.rows = (int)s.shape[0]; L.cols = 1; L.bn = s.geglu_bn; break;
+        case PK_MAT: L.kind = LORA_MAT; L.rows = (int)s.shape[0]; L.cols = (int)(s.elems / s.shape[0]); break;
+        default: L.kind = LORA_MAT; L.rows = 1; L.cols = (int)s.elems; break;
+    }
+    if (L.kind == LORA_GEGLU && L.bn <= 0) L.kind = LORA_MAT;
+    return L;
+}
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+}  // namespace
+
 extern "C" {
 
 int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
@@ -801,6 +839,7 @@ void ld_unet_destroy(ld_unet* u) {
     if (u->sync_ws) (void)hipFree(u->sync_ws);
     if (u->w8_base) (void)hipFree(u->w8_base);
     if (u->fold_base) (void)hipFree(u->fold_base);
+    for (auto& b : u->backups) (void)hipFree(b.second);
     delete u;
 }
 
@@ -819,7 +858,88 @@ int ld_unet_param_info(const ld_unet* u, int i, const char** name, int* ndim, in
 int ld_unet_load_param(ld_unet* u, const char* name, const void* src, int dtype, void* stream) {
     if (u == nullptr || name == nullptr) return LD_ERR_ARG;
     u->fold_dirty = true;   // the LN-folded copies are re-derived at the next forward
+    auto it = u->pt.index.find(name);
+    if (it != u->pt.index.end() && u->backups.count(it->second)) {   // a load onto a patched slot is the new base: its backup is dropped
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
+        u->drop_backup(it->second);
+    }
     return u->pt.load(name, src, dtype, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------------- LoRA patches (load-class calls)
+int ld_unet_patch_param(ld_unet* u, const char* name, const ld_lora_term* terms, int n_terms, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (u == nullptr || name == nullptr || terms == nullptr || n_terms < 1 || n_terms > LORA_MAX_TERMS) return LD_ERR_ARG;
+    auto it = u->pt.index.find(name);
+    if (it == u->pt.index.end()) return LD_ERR_ARG;
+    const int slot = it->second;
+    const ParamSlot& s = u->pt.slots[slot];
+    if (!s.loaded || (s.kind != PK_MAT && s.kind != PK_CONV3 && s.kind != PK_GEGLU_W)) return LD_ERR_ARG;
+    LoraArgs a;
+    a.lay = slot_layout(s);
+    a.n_terms = n_terms;
+    for (int j = 0; j < n_terms; ++j) {
+        const ld_lora_term& t = terms[j];
+        if (t.up == nullptr || t.down == nullptr || t.rank < 1 || t.rank > LORA_MAX_RANK || (t.dtype != LD_F16 && t.dtype != LD_F32)) return LD_ERR_ARG;
+        a.t[j].up = t.up; a.t[j].down = t.down; a.t[j].f32 = t.dtype == LD_F32; a.t[j].rank = t.rank; a.t[j].scale = t.scale;
+    }
+    if (capturing(stream)) return LD_ERR_STATE;
+    const size_t bytes = s.elems * sizeof(half_t);
+    auto bk = u->backups.find(slot);
+    if (bk == u->backups.end()) {   // first patch of this slot: snapshot its resident bytes
+        half_t* b = nullptr;
+        if (hipMalloc((void**)&b, bytes) != hipSuccess) return LD_ERR_HIP;
+        if (hipMemcpyAsync(b, u->pt.ptr(slot), bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+            (void)hipFree(b);
+            return LD_ERR_HIP;
+        }
+        bk = u->backups.emplace(slot, b).first;
+        u->patch_bytes += bytes;
+    }
+    a.base = bk->second;            // always from the backup: re-patching is not cumulative
+    a.dst = u->pt.ptr(slot);
+    u->fold_dirty = true;
+    return lora_merge_launch(a, stream);
+}
+
+int ld_unet_unpatch(ld_unet* u, const char* name, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (u == nullptr) return LD_ERR_ARG;
+    std::vector<int> which;
+    if (name != nullptr) {
+        auto it = u->pt.index.find(name);
+        if (it == u->pt.index.end()) return LD_ERR_ARG;
+        if (u->backups.count(it->second)) which.push_back(it->second);
+    } else {
+        for (const auto& b : u->backups) which.push_back(b.first);
+    }
+    if (which.empty()) return LD_OK;
+    if (capturing(stream)) return LD_ERR_STATE;
+    for (int slot : which)
+        if (hipMemcpyAsync(u->pt.ptr(slot), u->backups[slot], u->pt.slots[slot].elems * sizeof(half_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            return LD_ERR_HIP;
+    u->fold_dirty = true;
+    if (hipStreamSynchronize(stream) != hipSuccess) return LD_ERR_HIP;   // the copies have read the backups before they are freed
+    for (int slot : which) u->drop_backup(slot);
+    return LD_OK;
+}
+
+int ld_unet_read_param(const ld_unet* u, const char* name, void* dst_f16, void* stream) {
+    if (u == nullptr || name == nullptr || dst_f16 == nullptr) return LD_ERR_ARG;
+    auto it = u->pt.index.find(name);
+    if (it == u->pt.index.end() || !u->pt.slots[it->second].loaded) return LD_ERR_ARG;
+    return lora_read_launch(u->pt.ptr(it->second), slot_layout(u->pt.slots[it->second]), (half_t*)dst_f16, (hipStream_t)stream);
+}
+
+size_t ld_unet_patch_bytes(const ld_unet* u) { return u ? u->patch_bytes : 0; }
+
+// what a forward runs under fold_dirty, on the caller's stream: a replayed hipGraph never executes that host code, so the host layer calls
+// this after a batch of patches
+int ld_unet_refresh_derived(ld_unet* u, void* stream) {
+    if (u == nullptr) return LD_ERR_ARG;
+    if (!u->pt.all_loaded()) return LD_ERR_STATE;
+    if (u->fold_dirty && capturing((hipStream_t)stream)) return LD_ERR_STATE;
+    return refresh_derived(u, (hipStream_t)stream);
 }
 
 size_t ld_unet_workspace_bytes(const ld_unet* u) { return u ? u->ws_bytes : 0; }

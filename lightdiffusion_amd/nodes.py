@@ -13,13 +13,14 @@ and gets the HIP UNet / VAE underneath.  The UNet is attached through the refere
 from __future__ import annotations
 
 import copy
+import os
 from typing import Optional
 
 import torch
 
 from . import sampling
 from . import weights as W
-from .clip import CLIP, CLIPTextModelHIP, PromptTokenizer
+from .clip import CLIP, CLIPTextModelHIP, LoraPatches, PromptTokenizer, _add_patches, patch_terms
 from .sampling import LATENT_SCALE, common_ksampler
 from .unet import MI355XUNet, MI355XVAE
 
@@ -42,9 +43,13 @@ class SD15Model:
         self.diffusion_model = unet
         self.model_sampling = sampling.ModelSampling()
         self.latent_format = SD15LatentFormat()
+        self.lora = None                 # the LoraPatches of the ModelPatcher this view of the resident UNet belongs to (shared with it)
 
     def apply_model(self, x, t, c_crossattn=None, transformer_options=None, **kwargs):
-        """BaseModel.apply_model (LD.py:5828-5860) — routed through the same wrapper object the hook would call."""
+        """BaseModel.apply_model (LD.py:5828-5860) — routed through the same wrapper object the hook would call, with the LoRA patches
+        of the patcher this view belongs to swapped in first (clones share the resident UNet)."""
+        if self.lora is not None:
+            _swap_unet_patches(self.diffusion_model, self.lora)
         return self.diffusion_model(None, {"input": x, "timestep": t, "c": {"c_crossattn": c_crossattn}, "cond_or_uncond": [1, 0]})
 
     def process_latent_in(self, latent):
@@ -54,19 +59,65 @@ class SD15Model:
         return self.latent_format.process_out(latent)
 
 
+def _swap_unet_patches(unet, lora: LoraPatches) -> None:
+    """Lazy swap: nothing when the resident weights already carry these patches (one uuid comparison); an empty set restores the loaded
+    weights."""
+    if getattr(unet, "applied_patches_uuid", None) == lora.uuid:
+        return
+    if lora.patches:
+        unet.patch_weights({k[len(ModelPatcher.KEY_PREFIX):]: patch_terms(v) for k, v in lora.patches.items()}, lora.uuid)
+    else:
+        unet.unpatch_weights(lora.uuid)
+
+
 class ModelPatcher:
-    """ModelPatcher (LD.py:3210-3437), reduced to what the hot path uses: model_options + the UNet wrapper hook."""
+    """ModelPatcher (LD.py:3210-3437), reduced to what the hot path uses: model_options, the UNet wrapper hook, and LoRA weight patches
+    (add_patches / patch_model / unpatch_model, LD.py:3297-3354, 3426-3437).  The weights live once, resident in the MI355XUNet that every
+    clone shares; a clone carries its own patch LIST, and `patch_model` makes the resident weights those of this clone when they are not.
+    Every patcher has an `SD15Model` view of its own on the resident UNet (`clone().model is not model`; the UNet, the sigma table and the
+    latent format are shared): the view and the patcher hold the SAME `LoraPatches` object, so `model.apply_model` swaps in the right
+    patches whichever of the two outlives the other.  A patcher built on a view that already belongs to another one takes a copy."""
+
+    KEY_PREFIX = "model.diffusion_model."
 
     def __init__(self, model: SD15Model, load_device, offload_device=None):
+        self._lora = LoraPatches()
+        if isinstance(model, SD15Model):
+            if model.lora is not None:
+                model = copy.copy(model)
+            model.lora = self._lora
         self.model = model
         self.load_device = torch.device(load_device)
         self.offload_device = offload_device
         self.model_options = {"transformer_options": {}}
 
+    # checkpoint key -> [(strength_patch, (up, down, alpha), strength_model)], and the identity of that set (None: the loaded weights)
+    patches = property(lambda self: self._lora.patches, lambda self, v: setattr(self._lora, "patches", v))
+    patches_uuid = property(lambda self: self._lora.uuid, lambda self, v: setattr(self._lora, "uuid", v))
+
     def clone(self):
         n = ModelPatcher(self.model, self.load_device, self.offload_device)
         n.model_options = copy.copy(self.model_options)
+        n.patches = {k: list(v) for k, v in self.patches.items()}
+        n.patches_uuid = self.patches_uuid
         return n
+
+    def model_key_shapes(self):
+        """{checkpoint key: shape} of the UNet's parameters"""
+        return {self.KEY_PREFIX + k: s for k, s in self.model.diffusion_model.param_shapes().items()}
+
+    def add_patches(self, patches, strength_patch=1.0, strength_model=1.0):
+        return _add_patches(self, self.model_key_shapes(), patches, strength_patch, strength_model)
+
+    def patch_model(self, device_to=None, patch_weights=True):
+        """Lazy swap: nothing when the resident weights already carry this patcher's patches; an empty set restores the loaded weights."""
+        if patch_weights:
+            _swap_unet_patches(self.model.diffusion_model, self._lora)
+        return self.model
+
+    def unpatch_model(self, device_to=None, unpatch_weights=True):
+        if unpatch_weights:
+            self.model.diffusion_model.unpatch_weights()
 
     def set_model_unet_function_wrapper(self, unet_wrapper_function):
         self.model_options["model_function_wrapper"] = unet_wrapper_function
@@ -102,6 +153,32 @@ class CLIPSetLastLayer:
 class KSampler2:
     def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0):
         return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise)
+
+
+class LoraLoader:
+    """LoraLoader.load_lora (LD.py:6611-6625) = load_lora_for_models (LD.py:6203-6219): clones of the model and the clip that carry the
+    LoRA as weight patches.  Nothing is merged here — the clones share the resident UNet / text model with their originals, and the patches
+    are swapped into the resident weights on the device where a clone is next used (ModelPatcher.patch_model, CLIP.patch_model)."""
+
+    def load_lora(self, model, clip, lora_name, strength_model, strength_clip):
+        from . import checkpoint as CK
+        lora = CK.load_state_dict(os.fspath(lora_name)) if isinstance(lora_name, (str, os.PathLike)) else lora_name
+        new_model = model.clone() if model is not None else None
+        new_clip = clip.clone() if clip is not None else None
+        if strength_model == 0 and strength_clip == 0:
+            return (new_model, new_clip)
+        shapes = {}
+        for part in (model, clip):
+            if part is not None:
+                shapes.update(part.model_key_shapes())
+        keys = {k: torch.empty(s, device="meta") for k, s in shapes.items()}       # names and shapes only
+        loaded = CK.resolve_lora(keys, lora, ModelPatcher.KEY_PREFIX, CLIP.KEY_PREFIX)
+        loaded.warn()
+        if new_model is not None and strength_model != 0:
+            new_model.add_patches(loaded, strength_model)
+        if new_clip is not None and strength_clip != 0:
+            new_clip.add_patches(loaded, strength_clip)
+        return (new_model, new_clip)
 
 
 class VAEDecode:

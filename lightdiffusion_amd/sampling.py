@@ -408,7 +408,9 @@ class CFGGuider:
                                  model_options=model_options or {}, seed=seed)
 
     def sample(self, noise, latent_image, sampler, sigmas, denoise_mask=None, callback=None, disable_pbar=False, seed=None):
-        self.inner_model = self.model_patcher.model
+        # load_models_gpu's place (LD.py:2930): clones share one resident UNet, so the patcher's LoRA patches are swapped in here if they are not
+        # the ones applied (one uuid comparison otherwise)
+        self.inner_model = self.model_patcher.patch_model() if hasattr(self.model_patcher, "patch_model") else self.model_patcher.model
         device = self.model_patcher.load_device
         self.conds = {k: [dict(c, cross_attn=c["cross_attn"].to(device)) for c in v] for k, v in self.original_conds.items()}
         noise, latent_image = noise.to(device), latent_image.to(device)

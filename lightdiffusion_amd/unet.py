@@ -11,12 +11,13 @@ Both are thin: they own a C handle, feed it device pointers and the current HIP 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Callable, Dict, Optional, Union
 
 import torch
 
 from . import weights as W
-from ._lib import ERR_SHAPE, F16, F32, LDError, UNetConfig, VAEConfig, check, lib
+from ._lib import ERR_SHAPE, F16, F32, LDError, LoraTerm, UNetConfig, VAEConfig, check, lib
 
 WeightSource = Union[Dict[str, torch.Tensor], Callable[[str, tuple], torch.Tensor]]
 
@@ -48,6 +49,38 @@ def _load_params(handle, count_fn, info_fn, load_fn, src: WeightSource, device, 
         t = t.to(device).contiguous()
         check(load_fn(handle, key.encode(), t.data_ptr(), F32 if t.dtype == torch.float32 else F16, _stream()), f"load_param({key})")
     torch.cuda.synchronize(device)
+
+
+def lora_factor_mismatch(shape, up, down) -> Optional[str]:
+    """Why the LoRA factors (up, down) cannot patch a weight of `shape` (checkpoint layout), or None when they fit: the patched matrix is
+    [shape[0]][prod(shape[1:])] (calculate_weight, LD.py:3420), so up flattens to [shape[0]][rank] and down to [rank][prod(shape[1:])]."""
+    if len(shape) < 2 or up.dim() < 2 or down.dim() < 2:
+        return f"weight {tuple(shape)}, up {tuple(up.shape)}, down {tuple(down.shape)}: not matrices"
+    rows, cols = int(shape[0]), math.prod(int(d) for d in shape[1:])
+    got = (up.shape[0], math.prod(up.shape[1:]), down.shape[0], math.prod(down.shape[1:]))
+    if got[0] != rows or got[3] != cols or got[1] != got[2]:
+        return f"up {tuple(up.shape)} x down {tuple(down.shape)} is not a [{rows}][{cols}] update of a weight of shape {tuple(shape)}"
+    return None
+
+
+def lora_terms(terms, device, shape):
+    """[(up, down, scale), ...] -> (ctypes array of ld_lora_term, tensors to keep alive until the merge is queued).  Plumbing only: the
+    factors go to the device as [rows][rank] / [rank][cols] row-major (a conv's down as flatten(start_dim=1), calculate_weight LD.py:3420),
+    fp16 or fp32 as they come; the arithmetic is the kernel's.  `shape` is the patched weight's, in checkpoint layout: the C calls take raw
+    pointers and index them by the SLOT's rows and columns, so factors of any other size are refused here (ValueError)."""
+    arr = (LoraTerm * len(terms))()
+    keep = []
+    for j, (up, down, scale) in enumerate(terms):
+        why = lora_factor_mismatch(shape, up, down)
+        if why is not None:
+            raise ValueError("LoRA factors do not fit: " + why)
+        dt = torch.float16 if up.dtype == torch.float16 and down.dtype == torch.float16 else torch.float32
+        up = up.flatten(start_dim=1).to(device, dt).contiguous()
+        down = down.flatten(start_dim=1).to(device, dt).contiguous()
+        keep += [up, down]
+        arr[j].up, arr[j].down = up.data_ptr(), down.data_ptr()
+        arr[j].dtype, arr[j].rank, arr[j].scale = (F16 if dt == torch.float16 else F32), up.shape[1], float(scale)
+    return arr, keep
 
 
 def _parse_launches(fn, handle) -> list:
@@ -96,6 +129,8 @@ class MI355XUNet:
         self._hook_flags = None          # pinned host ints the device-side guards write (ld_op_hook_check)
         self._hook_event = None
         self._hook_epoch = 0
+        self.applied_patches_uuid = None  # identity of the LoRA patch set merged into the resident weights (None: the loaded weights)
+        self._param_shapes = None        # {parameter name: checkpoint shape}, read from the library on first use
 
     def reserve(self, max_batch: int, max_hw=(64, 64), max_tokens: int = 77) -> None:
         """(Re)size the activation workspace.  Growing it frees and reallocates: the context must be set again and every
@@ -126,7 +161,76 @@ class MI355XUNet:
     # -- sizes
     @property
     def weight_bytes(self) -> int:
+        """Resident weights and the copies derived from them.  The backups of LoRA-patched slots are a further resident copy, held only
+        while a patch is applied and reported separately: `patch_bytes`."""
         return lib().ld_unet_weight_bytes(self._h)
+
+    @property
+    def patch_bytes(self) -> int:
+        return lib().ld_unet_patch_bytes(self._h)
+
+    # -- parameters and LoRA patches of the resident weights
+    def param_shapes(self) -> Dict[str, tuple]:
+        """{parameter name (checkpoint key minus 'model.diffusion_model.'): shape as the checkpoint stores it}"""
+        if self._param_shapes is None:
+            name, ndim, shape = C.c_char_p(), C.c_int(), (C.c_int64 * 4)()
+            out = {}
+            for i in range(lib().ld_unet_param_count(self._h)):
+                check(lib().ld_unet_param_info(self._h, i, C.byref(name), C.byref(ndim), shape), "param_info")
+                out[name.value.decode()] = tuple(int(shape[k]) for k in range(ndim.value))
+            self._param_shapes = out
+        return dict(self._param_shapes)
+
+    def read_param(self, name: str) -> torch.Tensor:
+        """The resident value of one parameter, back in checkpoint layout (fp16, device)."""
+        shapes = self.param_shapes()
+        if name not in shapes:
+            raise KeyError(name)
+        out = torch.empty(shapes[name], dtype=torch.float16, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_read_param(self._h, name.encode(), out.data_ptr(), _stream()), f"ld_unet_read_param({name})")
+        return out
+
+    def _weights_changed(self) -> None:
+        """After a patch / unpatch: re-derive the folded copies now (a replayed hipGraph never runs the executor's own check) and forget
+        the resident context — the hoisted cross-attention K / V^T were projected with attn2.to_k / to_v, so the next call re-projects them
+        whatever token or content it carries.  Workspaces, `reserve_epoch` and captured graphs stay: no address moves."""
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_refresh_derived(self._h, _stream()), "ld_unet_refresh_derived")
+        self._ctx_ref = self._ctx_token = None
+
+    def patch_weights(self, patches: Dict[str, list], uuid=None) -> None:
+        """ModelPatcher.patch_model (LD.py:3335-3354) on the resident weights: `patches` {parameter name: [(up, down, scale), ...]}; every
+        slot becomes round_fp16(loaded weight + sum scale up down) (`ld_unet_patch_param`).  Whatever was patched before is restored first, so
+        the result never depends on the previous patch set.  A patch that is refused (an unknown name, factors that do not fit the weight,
+        a rank or a number of terms out of range) raises, and leaves the loaded weights in place."""
+        shapes = self.param_shapes()
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_unpatch(self._h, None, _stream()), "ld_unet_unpatch")
+            try:
+                for name, terms in patches.items():
+                    if name not in shapes:
+                        raise KeyError(f"the UNet has no parameter '{name}'")
+                    arr, keep = lora_terms(terms, self.device, shapes[name])
+                    check(lib().ld_unet_patch_param(self._h, name.encode(), arr, len(terms), _stream()), f"ld_unet_patch_param({name})")
+                    del keep
+            except Exception:
+                check(lib().ld_unet_unpatch(self._h, None, _stream()), "ld_unet_unpatch")
+                self.applied_patches_uuid = None
+                self._weights_changed()
+                raise
+        self.applied_patches_uuid = uuid if uuid is not None else object()   # (a direct call: matches no patcher, so the next lazy swap restores)
+        self._weights_changed()
+
+    def unpatch_weights(self, uuid=None) -> None:
+        """ModelPatcher.unpatch_model (LD.py:3426-3437): the loaded weights back, bit for bit.  `uuid`: the identity recorded as applied
+        (a patcher whose patch set is empty)."""
+        changed = self.patch_bytes > 0
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_unpatch(self._h, None, _stream()), "ld_unet_unpatch")
+        self.applied_patches_uuid = uuid
+        if changed:
+            self._weights_changed()
 
     @property
     def workspace_bytes(self) -> int:
