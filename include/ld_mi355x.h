@@ -173,6 +173,14 @@ int ld_op_repack_conv(const void* src_oihw, int dtype, int cout, int cin, void* 
 size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout);
 int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
                     const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream);
+/* The same behind out_layers' GroupNorm(32) + SiLU, as the UNet executor runs a ResBlock's second half:
+ *   y = conv3x3(SiLU(GroupNorm(x)); wt) + bias + conv1x1(cat(s1, s2); wskip) + bskip (+ rowvec per image).
+ * The skip sources enter RAW.  gamma / beta NULL: no normalisation (ld_op_conv_skip).  part / chunks (both or neither): the GroupNorm partial
+ * statistics of y, as ld_op_conv_gn_partials.  ws >= ld_op_groupnorm_conv_skip_ws_bytes(...). */
+size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int n, int h, int w);
+int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const void* gamma, const void* beta, float eps, const void* wt, const void* bias,
+                              const void* s1, int sc1, const void* s2, int sc2, const void* wskip, const void* bskip, const void* rowvec, void* y, int cout,
+                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
 /* Upsample1 (nearest resize to hv x wv, then 3x3 conv, stride 1, pad 1; LD.py:5141-5152) with the resize folded into the weights: for an exact
  * 2x resize the layer is four 2x2 convolutions of the SOURCE image, one per output phase (2y + py, 2x + px), whose weights are sums of the 3x3
  * taps.  ld_op_upconv2x_fold derives them once from wt [cout][9 cin] (ld_op_repack_conv's layout): wfold [py*2+px][cout][a*2+b][cin], 16 cout cin

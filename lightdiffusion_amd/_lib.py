@@ -90,6 +90,8 @@ SIGNATURES = {
     "ld_op_upconv2x": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_conv_skip_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "ld_op_conv_skip": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "ld_op_groupnorm_conv_skip_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "ld_op_groupnorm_conv_skip": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     "ld_op_groupnorm_ws_bytes": (_Z, [_I, _I]),
     "ld_op_groupnorm": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P]),
     "ld_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),

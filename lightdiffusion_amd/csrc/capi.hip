@@ -228,15 +228,13 @@ size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout) {
     return align256((size_t)cout * (9 * (size_t)c + sc1 + sc2) * sizeof(half_t)) + align256((size_t)cout * sizeof(half_t)) + ((size_t)96 << 20);
 }
 
-int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
-                    const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream_) {
-    op_begin();
-    if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
-    if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
-    if (ws_bytes < ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout)) return LD_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int K9 = 9 * c, SC = sc1 + sc2;
-    char* q = (char*)ws;
+// ResBlock1's out_layers as the executor runs them (unet.hip Run::resblock): [GroupNorm + SiLU of x] + 3x3 convolution + the 1x1 skip_connection over
+// s1 / s2 as a second K segment, one contraction on the folded weights.  gamma / beta null: x is taken as it is.  part / chunks (optional): the
+// GroupNorm partial statistics of the OUTPUT where the launch writes them (as ld_op_conv_gn_partials).
+static int op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
+                        const void* wskip, const void* bskip, const void* rowvec, const void* gamma, const void* beta, float eps, void* y, int cout,
+                        float* part, int* chunks, char* q, hipStream_t stream) {
+    const int K9 = 9 * c, SC = sc1 + sc2, HW = h * w;
     half_t* wf = (half_t*)q; q += align256((size_t)cout * (K9 + SC) * sizeof(half_t));
     half_t* bf = (half_t*)q; q += align256((size_t)cout * sizeof(half_t));
     int st = skip_fold_launch((const half_t*)wt, (const half_t*)wskip, (const half_t*)bias, (const half_t*)bskip, cout, K9, SC, wf, bf, stream);
@@ -247,12 +245,66 @@ int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, c
     p.Hs = p.Hv = p.Ho = h; p.Ws = p.Wv = p.Wo = w; p.stride = 1;
     p.S1 = (const half_t*)s1; p.SC1 = sc1; p.S2 = (const half_t*)s2; p.SC2 = sc2;
     p.K = K9 + SC; p.W = wf; p.ldw = p.K;
-    p.M = n * h * w; p.N = cout;
+    p.M = n * HW; p.N = cout;
     p.bias_n = bf;
-    p.rowvec = (const half_t*)rowvec; p.rows_per_vec = h * w; p.ldrv = cout;
+    p.rowvec = (const half_t*)rowvec; p.rows_per_vec = HW; p.ldrv = cout;
     p.C = (half_t*)y; p.ldc = cout;
+    if (part != nullptr) {
+        p.gn_part = part;
+        p.gn_P = gn_num_chunks(n, HW);
+        p.gn_HW = HW;
+        p.gn_ppb = (HW + p.gn_P - 1) / p.gn_P;
+        p.gn_part_done = chunks;
+    }
+    if (gamma == nullptr) {
+        p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
+        return gemm_op(p, stream);
+    }
+    float* stat = (float*)q; q += align256(groupnorm_workspace_bytes(n, HW));
+    float* scale = (float*)q; q += align256((size_t)n * c * sizeof(float));
+    float* shift = (float*)q; q += align256((size_t)n * c * sizeof(float));
+    half_t* g = (half_t*)q; q += align256((size_t)n * HW * c * sizeof(half_t));
     p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
+    const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
+    if (fused.can_fuse_groupnorm) {
+        st = groupnorm_scale_shift_launch((const half_t*)x, c, nullptr, 0, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, stat, scale, shift, stream);
+        if (st != LD_OK) return st;
+        p.gn_scale = scale; p.gn_shift = shift; p.gn_silu = 1;
+        return gemm_op(p, fused, stream);
+    }
+    st = groupnorm_launch((const half_t*)x, c, nullptr, 0, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, 1, g, stat, stream);
+    if (st != LD_OK) return st;
+    p.A = g;
     return gemm_op(p, stream);
+}
+
+int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
+                    const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
+    if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
+    if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
+    if (ws_bytes < ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout)) return LD_ERR_ARG;
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, nullptr, nullptr, 0.f, y, cout, nullptr, nullptr, (char*)ws,
+                        (hipStream_t)stream_);
+}
+
+size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int n, int h, int w) {
+    op_begin();
+    const size_t HW = (size_t)h * w;
+    return ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout) + align256(groupnorm_workspace_bytes(n, (int)HW)) + 2 * align256((size_t)n * c * sizeof(float)) +
+           align256((size_t)n * HW * c * sizeof(half_t));
+}
+
+int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const void* gamma, const void* beta, float eps, const void* wt, const void* bias,
+                              const void* s1, int sc1, const void* s2, int sc2, const void* wskip, const void* bskip, const void* rowvec, void* y, int cout,
+                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream_) {
+    op_begin();
+    if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
+    if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
+    if ((gamma == nullptr) != (beta == nullptr) || (part == nullptr) != (chunks == nullptr)) return LD_ERR_ARG;
+    if (ws_bytes < ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w)) return LD_ERR_ARG;
+    if (chunks != nullptr) *chunks = 0;
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, gamma, beta, eps, y, cout, part, chunks, (char*)ws, (hipStream_t)stream_);
 }
 
 int ld_op_repack_conv(const void* src, int dtype, int cout, int cin, void* dst, void* stream) {

@@ -21,7 +21,14 @@ namespace {
 // 128 x BN/2) gives the N = 128 convolutions of the VAE's last level 32 MFMAs per phase instead of 16, (iii) UP: the input is the
 // nearest-2x upsampling of the source (Upsample / Upsample1, LD.py:3498-3511, 5114-5152): halo pixel (y, x) comes from source pixel
 // (y >> 1, x >> 1) — only the loader's address changes.
-template <int W, bool GN, int BN = V5_BN, int BM = V5_BM, bool UP = false>
+// Skip segment (SKIP, gemm.h S1 / S2): after the last 3x3 slab of the workgroup's K range come (SC1 + SC2) / 32 (split over K: its share of
+// them) CENTRE-ONLY steps.  A skip step's A operand is the tile's own 256 output pixels x 32 channels of the RAW source: a dense 16 KB
+// image, 16 one-KB LDS-DMA pieces (two per wave) — no border, no zero page, never normalised — in a four-slot ring laid over the halo
+// buffers, rows swizzled like the B ring's (V5_SWZ) so that its fragment reads are conflict-free; its B operand is the next 32 of the
+// weight row's appended columns [O][tap][I | skip].  The image of skip step j is issued two steps ahead (B: three): the first two during
+// taps 7 and 8 of the last slab, into the slots that the halo buffer NOT holding that slab covers (whichever it is), the third at skip
+// step 0, when nobody reads a halo any more.  22.8 -> 20 + 16 = 36 pieces per skip step, against 45 for a halo slab spent on one tap.
+template <int W, bool GN, int BN = V5_BN, int BM = V5_BM, bool UP = false, bool SKIP = false>
                                             // GN: GroupNorm (+SiLU) of the input fused into the halo (separate instantiation: the plain conv keeps its
                                             // registers); BN: tile width 320 (the UNet's N = 320 k), 256 (the VAE's N = 256 / 512) or 128 (its N = 128)
 __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
@@ -36,9 +43,11 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
     constexpr int NH = ((HP + 15) / 16 + 7) / 8;                      // halo LDS-DMA pieces per wave and slab (uniform: spare pieces copy zeros)
     constexpr int HBYTES = NH * 8 * 1024;                              // one halo buffer
     constexpr int BSTAGE = BN * 64, NSTB = 4;                          // B ring: 4 stages of BN rows x 64 bytes
-    constexpr int RING0 = 2 * HBYTES;                                  // byte offset of the B ring
-    __shared__ __attribute__((aligned(16))) char smem5[2 * HBYTES + NSTB * BSTAGE];
-    static_assert(2 * HBYTES + NSTB * BSTAGE <= 163840, "LDS");
+    constexpr int SKA_BYTES = 256 * 64, SKA_SLOTS = 4;                 // skip segment: one dense A image (256 pixels x 32 channels), slots of its ring
+    static_assert(!SKIP || (W <= 64 && BN == V5_BN && BM == V5_BM && !UP), "skip segment: whole-image-width tiles of the 256 x 320 skeleton");
+    constexpr int RING0 = (SKIP && 2 * HBYTES < SKA_SLOTS * SKA_BYTES) ? SKA_SLOTS * SKA_BYTES : 2 * HBYTES;   // byte offset of the B ring
+    __shared__ __attribute__((aligned(16))) char smem5[RING0 + NSTB * BSTAGE];
+    static_assert(RING0 + NSTB * BSTAGE <= 163840, "LDS");
     static_assert(!GN || NH <= 7, "fused GroupNorm: my (<= 7) pieces of the next slab are normalised in one go in the read phase of tap 3 (28 temporaries)");
     // fused GroupNorm: every wave keeps the 32 scales + 32 shifts of the slab being normalised in 256 bytes of LDS.  Where the
     // halo buffers and the B ring already take all 160 KB (W = 128) the tables live in spare piece slots of halo buffer 0 and the
@@ -66,7 +75,11 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
     const int Cin = p.C1 + p.C2;
     const int NS = Cin / 32;                                           // channel slabs
     const int s_begin = (int)((long long)ks * NS / splitk), s_end = (int)((long long)(ks + 1) * NS / splitk);
-    const int nk = (s_end - s_begin) * 9;                              // 32-wide steps of this workgroup (>= 9)
+    // skip segment: every slice over K takes an equal share of the skip steps behind its slabs (slices stay even; the bias is the reduce pass's)
+    const int NQ = SKIP ? (p.SC1 + p.SC2) / 32 : 0;
+    const int q_begin = SKIP ? (int)((long long)ks * NQ / splitk) : 0, nq = SKIP ? (int)((long long)(ks + 1) * NQ / splitk) - q_begin : 0;
+    const int nk_main = (s_end - s_begin) * 9;
+    const int nk = nk_main + nq;                                       // 32-wide steps of this workgroup (>= 9)
 
     const half_t* zp = reinterpret_cast<const half_t*>(g_zero_row);
     // this tile = rows row0 .. row0 + TR - 1, columns col0 .. col0 + W - 1 of image img (W < 128: the image is W wide, col0 = 0)
@@ -146,13 +159,16 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
     }
     const half_t* b_base = p.W + (long long)s_begin * 32;              // step (slab s_begin, tap 0); wave-uniform
     int b_tap = 0;
+    int b_main = nk_main;                                              // (SKIP) steps of the 3x3 segment still to issue
     unsigned st_issue = 0;                                             // byte offset (inside the B ring) of the stage the next step goes to
     auto issue_b = [&]() {
         const unsigned Bs = smem_base + (unsigned)RING0 + st_issue;
 #pragma unroll
         for (int i = 0; i < NB_ALL; ++i) glds16s(b_off[i], b_base, Bs + (unsigned)(wid * NB_ALL + i) * 1024u);
         if (NB_EXTRA > 0 && b_extra) glds16s(b_off[NB_ALL], b_base, Bs + (unsigned)(8 * NB_ALL + wid) * 1024u);
-        if (b_tap == 8) {
+        if (SKIP && --b_main <= 0) {                                    // behind the last tap of the last slab: the appended columns, 32 per step
+            b_base = b_main == 0 ? p.W + 9 * Cin + q_begin * 32 : b_base + 32;
+        } else if (b_tap == 8) {
             b_tap = 0;
             b_base += 32 - 8 * Cin;
         } else {
@@ -161,9 +177,40 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
         }
         st_issue = st_issue == (unsigned)((NSTB - 1) * BSTAGE) ? 0u : st_issue + (unsigned)BSTAGE;
     };
+    // ---- skip segment loader: piece 2 wid + i of a step = tile pixels (2 wid + i) * 16 .. + 15 (consecutive pixels of the image: the tile is
+    // whole rows), lane -> (pixel, swizzled 16-byte chunk); the source switches from S1 to S2 between steps (SC1 % 32 == 0)
+    int ska_slot = 0;                                                  // ring slot of skip step 0, then of the next image to issue
+    int ska_read = 0;                                                  // byte offset of the slot the next skip step reads
+    if constexpr (SKIP) {
+        // the last slab sits in halo buffer (slabs - 1) & 1; the first two images go where the OTHER buffer (or nothing) lies
+        const bool last0 = ((s_end - s_begin - 1) & 1) == 0;
+        ska_slot = last0 ? 2 : (HBYTES < 2 * SKA_BYTES ? 3 : 0);
+        ska_read = ska_slot * SKA_BYTES;
+    }
+    auto issue_ska = [&](int q) {                                      // skip step q (32 channels of the concatenated skip sources) -> slot ska_slot
+        const int c0 = q * 32;
+        const bool second = c0 >= p.SC1;
+        const int Cs = second ? p.SC2 : p.SC1;
+        const half_t* src = (second ? p.S2 : p.S1) + ((long long)img * HWo + row0 * W + wid * 32) * Cs + (second ? c0 - p.SC1 : c0);
+        const unsigned voff = (unsigned)((prow * Cs + lchunk * 8) * 2);
+        const unsigned dst = smem_base + (unsigned)(ska_slot * SKA_BYTES) + (unsigned)wid * 2048u;
+        glds16s(voff, src, dst);
+        glds16s(voff, src + 16 * Cs, dst + 1024u);
+        ska_slot = (ska_slot + 1) & (SKA_SLOTS - 1);
+    };
     // "every LDS-DMA of mine but the n newest steps' B pieces (+ the halo pieces when they sit among those) has landed"
-    auto wait_keep = [&](int steps, bool halo) {
+    // ska: this step issued a skip image (two pieces, in front of its B pieces; never in a step that leaves halo pieces in flight) — the
+    // image issued one step earlier is among what has landed
+    auto wait_keep = [&](int steps, bool halo, bool ska = false) {
         constexpr int PX = NB_ALL + 1, PA = NB_ALL;                      // pieces per step of a wave with / without the extra piece
+        if (SKIP && ska) {
+            if (NB_EXTRA > 0 && b_extra) {
+                if (steps >= 2) wait_vmcnt<2 * PX + 2>(); else if (steps == 1) wait_vmcnt<PX + 2>(); else wait_vmcnt<0>();
+            } else {
+                if (steps >= 2) wait_vmcnt<2 * PA + 2>(); else if (steps == 1) wait_vmcnt<PA + 2>(); else wait_vmcnt<0>();
+            }
+            return;
+        }
         if (NB_EXTRA > 0 && b_extra) {
             if (steps >= 2) { if (halo) wait_vmcnt<2 * PX + NH>(); else wait_vmcnt<2 * PX>(); }
             else if (steps == 1) { if (halo) wait_vmcnt<PX + NH>(); else wait_vmcnt<PX>(); }
@@ -215,6 +262,8 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
                 issue_halo(s + 1, hb ^ 1);                             // the other buffer was last read in slab s-1: free for everyone
             }
             if (GN && t == 3 && s + 1 < s_end) gn_apply_slab(hb ^ 1);   // my table load and halo pieces of slab s+1 landed at tap 2's wait
+            const bool ska = SKIP && t >= 7 && s + 1 == s_end && t - 7 < nq;   // images of skip steps 0 and 1: the other halo buffer is free
+            if (SKIP && ska) issue_ska(q_begin + t - 7);
             if (k + 3 < nk) issue_b();
 #pragma unroll
             for (int j = 0; j < TN; ++j) fb[j] = as_half8(ld16(rdB + j * 1024));
@@ -231,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
                 st_read = st_read == NSTB - 1 ? 0 : st_read + 1;
             }
             // my B pieces of step k+1 (and, from tap 2 on, the next slab's halo pieces) have landed; the barrier publishes them
-            wait_keep(k + 3 < nk ? 2 : (k + 2 < nk ? 1 : 0), t < 2 && s + 1 < s_end);
+            wait_keep(k + 3 < nk ? 2 : (k + 2 < nk ? 1 : 0), t < 2 && s + 1 < s_end, ska);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_barrier();
@@ -241,8 +290,8 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    if (GN)   // in-place form pinned in asm: with the fused-GroupNorm code around, hipcc otherwise renames the accumulators
-                              // between the unrolled taps (D != C) and spills them inside this phase
+                    if (GN || SKIP)   // in-place form pinned in asm: with the fused-GroupNorm code (or the skip steps' second loop) around, hipcc
+                              // otherwise renames the accumulators between the unrolled taps (D != C) and spills them inside this phase
                         asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][j]) : "v"(fb[j]), "v"(fa[i]));
                     else
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[j], fa[i], acc[i][j], 0, 0, 0);
@@ -252,14 +301,48 @@ __global__ __launch_bounds__(512, 2) void conv6_kernel(const GemmParams p) {
             __builtin_amdgcn_s_barrier();
         }
     }
+    if constexpr (SKIP) {
+        // ---- the skip steps: the same two phases, the A fragments from the dense image of the step (pixel wm0 + 16 i + fr, swizzled chunk)
+        const char* rdS = smem5 + (wm0 + fr) * 64 + rchunk;
+        for (int j = 0; j < nq; ++j, ++k) {
+            const bool ska = j + 2 < nq;
+            if (ska) issue_ska(q_begin + j + 2);                        // its slot was last read two steps ago
+            if (k + 3 < nk) issue_b();
+#pragma unroll
+            for (int jn = 0; jn < TN; ++jn) fb[jn] = as_half8(ld16(rdB + jn * 1024));
+#pragma unroll
+            for (int i = 0; i < TM; ++i) fa[i] = as_half8(ld16(rdS + ska_read + i * 1024));
+            {
+                const int d = st_read == NSTB - 1 ? -(NSTB - 1) * BSTAGE : BSTAGE;
+                rdB += d;
+                st_read = st_read == NSTB - 1 ? 0 : st_read + 1;
+                ska_read = (ska_read + SKA_BYTES) & (SKA_SLOTS * SKA_BYTES - 1);
+            }
+            wait_keep(k + 3 < nk ? 2 : (k + 2 < nk ? 1 : 0), false, ska);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int jn = 0; jn < TN; ++jn) {
+                    if (GN || SKIP) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc[i][jn]) : "v"(fb[jn]), "v"(fa[i]));   // (as above)
+                    else acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fb[jn], fa[i], acc[i][jn], 0, 0, 0);
+                }
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+        }
+    }
     if (!grp1) __builtin_amdgcn_s_barrier();                            // group 0 waits out group 1's last MFMA phase
-    if (GN) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // the asm MFMAs are invisible to hipcc's hazard recogniser: let the last ones retire before VALU reads the accumulators
+    if (GN || SKIP) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");          // the asm MFMAs are invisible to hipcc's hazard recogniser: let the last ones retire before VALU reads the accumulators
     if constexpr (BN == V5_BN) v5_finish<0, false>(p, acc, smem5, nullptr, nullptr, 0, m0, n0, wm0, wn0, wid, lane, ks, splitk, tn_i);
     else v6_finish<TM, TN>(p, acc, smem5, m0, n0, wm0, wn0, wid, lane, ks, splitk, img, t_in);
 }
 
-template <int W, bool GN, int BN, int BM, bool UP>
-void launch_conv6_w(const GemmParams& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv6_kernel<W, GN, BN, BM, UP>), grid, dim3(512), 0, s, p); }
+template <int W, bool GN, int BN, int BM, bool UP, bool SKIP = false>
+void launch_conv6_w(const GemmParams& p, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((conv6_kernel<W, GN, BN, BM, UP, SKIP>), grid, dim3(512), 0, s, p); }
 // the tile widths gemm_plan hands each tile: every width for the 320-column tile, 64 and 128 for the plain 256-column tile, 128 for the rest
 template <bool GN, int BN = V5_BN, int BM = V5_BM, bool UP = false>
 void launch_conv6(int wc, const GemmParams& p, dim3 grid, hipStream_t s) {
@@ -276,7 +359,17 @@ void launch_conv6(int wc, const GemmParams& p, dim3 grid, hipStream_t s) {
 }  // namespace
 
 void conv6_launch(const GemmParams& p, const GemmPlan& pl, dim3 grid, hipStream_t s) {
-    if (pl.gn) {
+    if (pl.skip) {   // (gemm_plan: 256 x 320 tiles of whole 16- / 32- / 64-pixel rows, no resize)
+        if (pl.gn) {
+            if (pl.wc == 16) launch_conv6_w<16, true, V5_BN, V5_BM, false, true>(p, grid, s);
+            else if (pl.wc == 32) launch_conv6_w<32, true, V5_BN, V5_BM, false, true>(p, grid, s);
+            else launch_conv6_w<64, true, V5_BN, V5_BM, false, true>(p, grid, s);
+        } else {
+            if (pl.wc == 16) launch_conv6_w<16, false, V5_BN, V5_BM, false, true>(p, grid, s);
+            else if (pl.wc == 32) launch_conv6_w<32, false, V5_BN, V5_BM, false, true>(p, grid, s);
+            else launch_conv6_w<64, false, V5_BN, V5_BM, false, true>(p, grid, s);
+        }
+    } else if (pl.gn) {
         if (pl.bn == 256) launch_conv6<true, 256>(pl.wc, p, grid, s);
         else if (pl.bn == 128) launch_conv6<true, 128, 512>(pl.wc, p, grid, s);
         else launch_conv6<true>(pl.wc, p, grid, s);

@@ -16,10 +16,12 @@ struct GemmParams {
     int Hv = 0, Wv = 0;          // size the conv sees (after nearest resize; == Hs,Ws without upsample)
     int Ho = 0, Wo = 0, stride = 1;
     int C1 = 0, C2 = 0;
-    // ---- second K segment of a convolution (tap-major kernels): a 1x1 convolution over up to two RAW NHWC sources of the OUTPUT's spatial
+    // ---- second K segment of a convolution: a 1x1 convolution over up to two RAW NHWC sources of the OUTPUT's spatial
     //   size, appended to the K axis — K = ksize^2 (C1 + C2) + SC1 + SC2, weight rows [conv taps | skip channels].  ResBlock1's
     //   skip_connection folded into out_layers' convolution (LD.py:5267, 5273-5287): out = W2 * gn(h) + Wskip x + (b2 + bskip) is ONE
-    //   contraction; requires stride 1 and no resize.  The halo-tile and row-resident kernels decline it (GemmPlan::takes_skip_segment).
+    //   contraction; requires stride 1 and no resize.  The tap-major kernels walk it as further K steps; the halo-tile kernel's 256 x 320 tiles of
+    //   whole <= 64-pixel rows run it as centre-only steps behind their slabs (conv6.hip; never normalised by a fused GroupNorm).  The row-resident
+    //   kernel, the 128-pixel bands and the VAE's tiles decline it (GemmPlan::takes_skip_segment).
     const half_t* S1 = nullptr;
     const half_t* S2 = nullptr;
     int SC1 = 0, SC2 = 0;
@@ -96,6 +98,7 @@ struct GemmPlan {
     // ---- variants of the route
     bool conv = false, geglu = false;   // gemm3 / gemm4 / gemm5: the im2col loader; gemm5 / gemm7: the GEGLU epilogue
     bool gn = false, up = false;        // conv6: GroupNorm (+SiLU) applied in the halo loader (gn_scale / gn_shift); conv6 / conv8: nearest-2x loader
+    bool skip = false;                  // conv6: the launch carries a second K segment (S1 / S2): the centre-only steps
     bool ln = false;                    // gemm5 / gemm7: the LayerNorm-fold epilogue
     bool deep = false, two_wg = false;  // gemm3 64 x 160 conv: 4-stage ring, one workgroup per CU; gemm4 64 x 64: two workgroups per CU
     int bm = 0, bn = 0, wc = 0;         // tile; conv6 / conv8: tile width in pixels
@@ -108,7 +111,8 @@ struct GemmPlan {
     int gn_chunks = 0;           // pixel chunks per image of the GroupNorm partials it writes to gn_part (-> *gn_part_done); 0: none
     bool halo_tile = false;      // runs on the halo-tile kernel
     bool can_fuse_groupnorm = false;   // (asked with gn_offer) the halo-tile kernel takes gn_scale / gn_shift here, and the fusion pays
-    bool takes_skip_segment = false;   // a 3x3 convolution on a tap-major kernel (128 x 160 / 256 x 320 implicit GEMM): S1 / S2 can be appended
+    bool takes_skip_segment = false;   // a 3x3 convolution on a tap-major kernel (128 x 160 / 256 x 320 implicit GEMM) or on the halo-tile kernel's
+                                       // 256 x 320 tiles of whole <= 64-pixel rows: S1 / S2 can be appended
     const char* kernel = "";     // profile name of what gemm_run dispatches, the reduce pass included
 };
 // gn_offer: the caller holds a GroupNorm (+SiLU) in front of this 3x3 convolution and sets gn_scale / gn_shift before gemm_run if

@@ -260,7 +260,6 @@ static bool v6_plan(const GemmParams& p, bool gn, GemmPlan* out) {
           p.C1 % 32 == 0 && p.C2 % 32 == 0 && p.bm == 0 && p.bn == 0 && p.splitk == 0 && p.batch == 1 && p.act != 2))
         return false;
     if (up && (p.C2 != 0 || gn)) return false;
-    if (p.SC1 > 0) return false;                                     // (a second K segment: the tap-major kernels)
     const int wc = (p.Wo == 16 || p.Wo == 32 || p.Wo == 64 || p.Wo == 128) ? p.Wo : (p.Wo > 128 && p.Wo % 128 == 0) ? 128 : 0;
     if (wc == 0) return false;
     // tile: 320 columns for the UNet's N = 320 k; 256 for the VAE's N = 256 / 512 at >= 64-pixel rows (VAE decode b=8 29.9 -> 28.8 ms);
@@ -285,15 +284,22 @@ static bool v6_plan(const GemmParams& p, bool gn, GemmPlan* out) {
         return false;
     }
     if (p.Ho % (bm / wc) != 0 || p.M % bm != 0) return false;       // whole tiles: bm / wc image rows each
+    // a second K segment (gemm.h S1 / S2) runs as centre-only steps behind the slabs (conv6.hip): 256 x 320 tiles of whole image rows, no resize.
+    // The 128-pixel bands, the VAE's tiles and the nearest-2x loader have no such instantiation; a one-tile-wide output WITHOUT the fused GroupNorm
+    // has no caller in the UNet (level 0's out_layers always brings its norm) and stays with the 256 x 320 tap-major kernel's fold.
+    // skip_ok: this geometry takes the segment (asked with SC1 = 0 by Exec::conv_takes_skip_segment, before the GroupNorm is offered).
+    const bool skip_ok = same && wc <= 64 && bn == V5_BN && bm == V5_BM && p.stride == 1 && (p.SC1 + p.SC2) % 32 == 0;
+    if (p.SC1 > 0 && !(skip_ok && (gn || p.N != V5_BN))) return false;
     const long long tm = p.M / bm;
     const long long t6 = tm * (p.N / bn);
     const int NS = (p.C1 + p.C2) / 32;
+    const int K9 = 9 * (p.C1 + p.C2);                                // (the split rule below was measured on the 3x3 segment alone: a skip segment does not move it)
     int sk6 = 1;
     // (split over K only from K = 8640 on: per launch inside the UNet forward (tools/ab_launches.py) the split + reduce pair loses to
     // the unsplit 128 x 160 kernel at 16384 x 640 x 5760 — 133 vs 124 us — and wins from 8640 on: 171 vs 176, 208 vs 227, 285 vs 329 us)
-    if (t6 < 192 && p.partial != nullptr && p.K >= 8640) {
+    if (t6 < 192 && p.partial != nullptr && K9 >= 8640) {
         sk6 = (int)((256 + t6 - 1) / t6);
-        const int cap = p.K / 2560;
+        const int cap = K9 / 2560;
         if (sk6 > cap) sk6 = cap;
         if (sk6 > NS) sk6 = NS;
         while (sk6 > 1 && (size_t)sk6 * p.M * p.N * sizeof(float) > p.partial_bytes) --sk6;
@@ -312,6 +318,7 @@ static bool v6_plan(const GemmParams& p, bool gn, GemmPlan* out) {
     }
 #endif
     out->splitk = sk6; out->bn = bn; out->bm = bm; out->wc = wc; out->up = up;
+    out->skip = p.SC1 > 0; out->takes_skip_segment = skip_ok;
     out->grid_x = (unsigned)(t6 * sk6);
     return t6 * sk6 >= 192;
 }

@@ -382,8 +382,8 @@ struct Run {
         half_t* g1 = ar.halfs(M * r.cin);
         half_t* h1 = ar.halfs(M * r.cout);
         // The 1x1 skip_connection (LD.py:5267): folded into out_layers' convolution as a second K segment where that convolution runs on a
-        // tap-major kernel (same FLOPs at the 3x3 kernels' rate, one launch and one [M][cout] round trip less); a launch of its own in front
-        // of the halo-tile and row-resident kernels.  (On a second stream beside in_layers in a batch-1 step it measured 2.9 % SLOWER than in
+        // tap-major kernel or on the halo-tile kernel's 256 x 320 tiles (centre-only steps, conv6.hip) — same FLOPs at the 3x3 kernels' rate,
+        // one launch and one [M][cout] round trip less; a launch of its own in front of the row-resident kernel and the 128-pixel bands.  (On a second stream beside in_layers in a batch-1 step it measured 2.9 % SLOWER than in
         // order: tools/experiments/fork_join_skip_conv_r05.patch.txt.)
         const half_t* skip = x1;
         bool fold_skip = false;

@@ -169,6 +169,30 @@ def conv2d_skip(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, s1:
     return y
 
 
+def group_norm_silu_conv2d_skip(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, w_packed: torch.Tensor,
+                                bias: torch.Tensor, s1: torch.Tensor, s2: Optional[torch.Tensor], w_skip: torch.Tensor, b_skip: torch.Tensor,
+                                rowvec: Optional[torch.Tensor] = None, partials: bool = False):
+    """A ResBlock's second half as the UNet executor runs it (LD.py:5267, 5273-5287):
+    y = conv3x3(SiLU(GroupNorm32(x)); w_packed) + bias + conv1x1(cat(s1, s2); w_skip) + b_skip, the raw skip sources a second K segment of
+    the one contraction.  gamma / beta None: x is taken as it is (conv2d_skip).  partials: also return the GroupNorm(32) partial statistics
+    the launch wrote for y ([n, chunks, 32, 2] fp32, or None where this shape's kernel writes none), as conv2d_gn_partials."""
+    import ctypes
+    n, h, w, c = x.shape
+    sc1 = s1.shape[-1]
+    sc2 = 0 if s2 is None else s2.shape[-1]
+    cout = w_packed.shape[0]
+    y = torch.empty(n, h, w, cout, dtype=torch.float16, device=x.device)
+    part = torch.zeros(lib().ld_op_conv_gn_partials_floats(n, h * w), dtype=torch.float32, device=x.device) if partials else None
+    chunks = ctypes.c_int(0)
+    ws = _ws(lib().ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w), x.device)
+    check(lib().ld_op_groupnorm_conv_skip(_p(x), c, n, h, w, _p(gamma), _p(beta), eps, _p(w_packed), _p(bias), _p(s1), sc1, _p(s2), sc2, _p(w_skip),
+                                          _p(b_skip), _p(rowvec), _p(y), cout, _p(part), ctypes.byref(chunks) if partials else None, _p(ws), ws.numel(),
+                                          _stream()), "ld_op_groupnorm_conv_skip")
+    if not partials:
+        return y
+    return y, (None if chunks.value == 0 else part[: n * chunks.value * 64].view(n, chunks.value, 32, 2))
+
+
 def conv2d_gn_partials(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out_hw: Optional[tuple] = None,
                        residual: Optional[torch.Tensor] = None):
     """3x3 stride-1 NHWC conv that also returns the GroupNorm(32) partial statistics its kernel wrote for the OUTPUT:
