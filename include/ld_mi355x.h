@@ -15,6 +15,7 @@
  *                        (CrossAttention.forward LD.py:4028-4036) — step-invariant, so hoisted out of the step.
  *   ld_vae_decode        VAE.decode (LD.py:6357-6381) = post_quant_conv + Decoder.forward (3470-3473, 3857-3882)
  *                        + process_output clamp + NCHW→NHWC.
+ *   ld_esrgan_forward    RRDBNet.forward (LD.py:7025-7234), the model ImageUpscaleWithModel.upscale applies per tile (LD.py:7356-7395).
  *   ld_op_*              single operators, for parity tests: the `operations=` classes of LD.py:2342-2429
  *                        (Linear / Conv2d / GroupNorm / LayerNorm) and optimized_attention (3966-3988).
  */
@@ -147,6 +148,38 @@ int ld_vae_profile_launches(const ld_vae* v, char* buf, size_t buf_bytes);
 int ld_vae_last_launches(const ld_vae* v);
 double ld_vae_last_flops(const ld_vae* v);
 
+/* ------------------------------------------------------------------ ESRGAN upscaler (RRDBNet, LD.py:7025-7234) */
+typedef struct {
+    int in_nc, out_nc;   /* 3, 3 */
+    int nf, gc;          /* 64, 32 (the dense-block kernel's channel counts) */
+    int nb;              /* RRDB blocks (23 in RealESRGAN_x4plus) */
+    int scale;           /* 1, 2, 4 or 8: log2(scale) up-convolutions */
+} ld_esrgan_config;
+
+typedef struct ld_esrgan ld_esrgan;
+
+/* LD_ERR_SHAPE for a config the kernels do not run.  Parameter names are the old-arch ones the reference normalises to (LD.py:7044-7055,
+ * 7174-7192): model.0, model.1.sub.{b}.RDB{r}.conv{c}.0, model.1.sub.{nb}, model.{3k} (up-convolutions), model.{3n+2} (HR), model.{3n+4}
+ * (last), each .weight (OIHW) / .bias */
+int ld_esrgan_create(const ld_esrgan_config* cfg, ld_esrgan** out);
+void ld_esrgan_destroy(ld_esrgan* e);
+int ld_esrgan_param_count(const ld_esrgan* e);
+int ld_esrgan_param_info(const ld_esrgan* e, int index, const char** name, int* ndim, int64_t shape[4]);
+int ld_esrgan_load_param(ld_esrgan* e, const char* name, const void* dev_src, int dtype, void* stream);
+int ld_esrgan_reserve(ld_esrgan* e, int max_b, int max_h, int max_w);   /* input size */
+size_t ld_esrgan_workspace_bytes(const ld_esrgan* e);
+/* workspace bytes ld_esrgan_reserve(b, h, w) would allocate (host-only dry run; 0 on an invalid shape) */
+size_t ld_esrgan_plan_bytes(ld_esrgan* e, int b, int h, int w);
+/* x: [b][h][w][3] fp32 NHWC (what ld_vae_decode writes); out: [b][h*scale][w*scale][3] fp32 NHWC, NOT clamped.  Only enqueues on `stream`. */
+int ld_esrgan_forward(ld_esrgan* e, const float* x, float* out, int b, int h, int w, void* stream);
+/* ld_esrgan_forward with a HIP-event pair around every launch (synchronises the stream), and that run's per-launch table in the format of
+ * ld_unet_profile_launches */
+int ld_esrgan_profile(ld_esrgan* e, const float* x, float* out, int b, int h, int w, void* stream);
+int ld_esrgan_profile_launches(const ld_esrgan* e, char* buf, size_t buf_bytes);
+int ld_esrgan_last_launches(const ld_esrgan* e);
+/* 2 * pixels * cout * 9 cin over every convolution of the last forward, the two 3-channel ends included */
+double ld_esrgan_last_flops(const ld_esrgan* e);
+
 /* ------------------------------------------------------------------ single operators (fp16 device tensors unless noted) */
 /* y[M][N] = act(alpha * x[M][K] · w[N][K]^T + bias[N]) + residual[M][N];  act: 0 none, 1 SiLU, 3 quick-GELU, 2 GEGLU (w, bias in
  * checkpoint row order [value | gate]; y is [M][N/2]).  ws/ws_bytes: optional split-K scratch. */
@@ -239,6 +272,19 @@ int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod,
 /* bislerp (LD.py:429-518, LatentUpscale.upscale 6639-6654): fp32 NCHW latents [n][c][h][w] -> [n][c][h_new][w_new];
  * tmp: n*c*h*w_new floats of scratch (the width pass runs first, as in the reference) */
 int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, void* stream);
+/* The dense-block 3x3 convolution of RRDBNet (stride 1, pad 1) on its own kernel (ResidualDenseBlock_5C, LD.py:6905-6992):
+ *   y[n][h][w][c_off .. c_off + cout) = epilogue(conv3x3(x[..][0 .. cin); wt) + bias),
+ *   epilogue (fp32, one rounding): slope != 0: v = v > 0 ? v : slope v;  r1 != NULL: v = s1 v + r1;  r2 != NULL: v = s2 v + r2.
+ * x: NHWC with pixel pitch ldx >= cin, cin a multiple of 32 in [64, 192]; cout 32 or 64; wt [cout][9 cin] as ld_op_repack_conv writes it;
+ * r1 / r2: NHWC with pitches ldr1 / ldr2, cout channels read.  y may be x (same pointer and pitch) when c_off >= cin — the dense
+ * concatenation in place; any other overlap of y with x is LD_ERR_ARG.  (h, w) is the output size; up != 0: x is [n][h/2][w/2] and is read
+ * through a nearest-2x upsampling (upconv_block, LD.py:6995-7022).  Pitches and c_off are multiples of 8.  LD_ERR_SHAPE otherwise. */
+int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
+                      float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream);
+/* tiled_scale's accumulation (LD.py:7326-7352), fp32 NHWC: out[oh][ow][c] += ps[th][tw][c] * my[y] * mx[x] at offset (y0, x0) and
+ * div[oh][ow] += my[y] * mx[x] (my, mx: the tile's two 1-D feather ramps); ps == NULL: the final out /= div. */
+int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
+                     void* stream);
 /* The contraction kernel instantiations (GEMM / convolution / attention, the names the profile tables use) that the calling thread's
  * last ld_op_* call dispatched, in launch order, joined with ';' (e.g. "gemm3_kernel<64,160,conv>+splitk_reduce_kernel").  Reset at
  * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call. */

@@ -27,6 +27,10 @@ class VAEConfig(C.Structure):
                 ("num_res_blocks", C.c_int), ("out_ch", C.c_int), ("with_encoder", C.c_int)]
 
 
+class ESRGANConfig(C.Structure):
+    _fields_ = [("in_nc", C.c_int), ("out_nc", C.c_int), ("nf", C.c_int), ("gc", C.c_int), ("nb", C.c_int), ("scale", C.c_int)]
+
+
 class LoraTerm(C.Structure):
     _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
 
@@ -81,6 +85,19 @@ SIGNATURES = {
     "ld_vae_profile_launches": (_I, [_P, C.c_char_p, _Z]),
     "ld_vae_last_launches": (_I, [_P]),
     "ld_vae_last_flops": (C.c_double, [_P]),
+    "ld_esrgan_create": (_I, [C.POINTER(ESRGANConfig), C.POINTER(_P)]),
+    "ld_esrgan_destroy": (None, [_P]),
+    "ld_esrgan_param_count": (_I, [_P]),
+    "ld_esrgan_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "ld_esrgan_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
+    "ld_esrgan_reserve": (_I, [_P, _I, _I, _I]),
+    "ld_esrgan_workspace_bytes": (_Z, [_P]),
+    "ld_esrgan_plan_bytes": (_Z, [_P, _I, _I, _I]),
+    "ld_esrgan_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_esrgan_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_esrgan_profile_launches": (_I, [_P, C.c_char_p, _Z]),
+    "ld_esrgan_last_launches": (_I, [_P]),
+    "ld_esrgan_last_flops": (C.c_double, [_P]),
     "ld_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _Z, _P]),
     "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_groupnorm_conv_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
@@ -107,6 +124,8 @@ SIGNATURES = {
     "ld_op_linear_ln": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ld_op_esrgan_conv": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P]),
+    "ld_op_tile_blend": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
     "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),
 }

@@ -276,6 +276,79 @@ def merge_lora(sd: Dict[str, torch.Tensor], lora: Dict[str, torch.Tensor], stren
     return res
 
 
+# ------------------------------------------------------------------ ESRGAN (RRDBNet) checkpoints
+_ESRGAN_BLOCK = (re.compile(r"^RRDB_trunk\.(\d+)\.RDB(\d)\.conv(\d+)\.(weight|bias)$"), re.compile(r"^body\.(\d+)\.rdb(\d)\.conv(\d+)\.(weight|bias)$"))
+_ESRGAN_UP = re.compile(r"^(?:upconv|conv_up)(\d)\.(weight|bias)$")
+
+
+def normalize_esrgan_keys(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Any of the three RRDBNet spellings -> old-arch keys, as RRDBNet.new_to_old_arch does (LD.py:7154-7207): ESRGAN's own
+    (`model.0`, `model.1.sub.N.RDBr.convc.0`), BSRGAN / RealSR (`conv_first`, `RRDB_trunk`, `trunk_conv`, `upconvN`, `HRconv`) and
+    Real-ESRGAN (`body`, `conv_body`, `conv_upN`, `conv_hr`); a `params_ema` / `params` wrapper and a `module.` prefix are unwrapped."""
+    for wrap in ("params_ema", "params"):
+        if wrap in sd and isinstance(sd[wrap], dict):
+            sd = sd[wrap]
+            break
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    if any(k.startswith("model.") for k in sd):
+        return dict(sd)
+    out: Dict[str, torch.Tensor] = {}
+    nb = -1
+    for k, v in sd.items():
+        for pat in _ESRGAN_BLOCK:
+            m = pat.match(k)
+            if m:
+                out[f"model.1.sub.{m.group(1)}.RDB{m.group(2)}.conv{m.group(3)}.0.{m.group(4)}"] = v
+                nb = max(nb, int(m.group(1)))
+        if "conv1x1" in k:
+            out[k] = v          # kept so that detect_esrgan_config names the reason
+    nb += 1
+    max_up = 0
+    for k, v in sd.items():
+        m = _ESRGAN_UP.match(k)
+        if m:
+            out[f"model.{int(m.group(1)) * 3}.{m.group(2)}"] = v
+            max_up = max(max_up, int(m.group(1)) * 3)
+    for k, v in sd.items():
+        base, _, kind = k.rpartition(".")
+        if base == "conv_first":
+            out[f"model.0.{kind}"] = v
+        elif base in ("trunk_conv", "conv_body"):
+            out[f"model.1.sub.{nb}.{kind}"] = v
+        elif base in ("HRconv", "conv_hr"):
+            out[f"model.{max_up + 2}.{kind}"] = v
+        elif base == "conv_last":
+            out[f"model.{max_up + 4}.{kind}"] = v
+    return out
+
+
+def detect_esrgan_config(sd: Dict[str, torch.Tensor]) -> dict:
+    """RRDBNet hyper-parameters from a state dict of any spelling, read as the reference reads them (LD.py:7056-7067, 7209-7231): nb =
+    highest block index + 1, scale = 2^(number of `model.N.weight` with N > 6), in_nc / nf / out_nc from the first and last tensors.
+    ValueError, naming the reason, for what the dense-block kernel does not run."""
+    old = normalize_esrgan_keys(sd)
+    if any("conv1x1" in k for k in old):
+        raise ValueError("ESRGAN checkpoint has conv1x1 keys (the 'plus' variant): not supported")
+    blocks = [int(m.group(1)) for m in (re.match(r"^model\.1\.sub\.(\d+)\.RDB\d+\.conv\d+\.0\.(?:weight|bias)$", k) for k in old) if m]
+    if not blocks or "model.0.weight" not in old:
+        raise ValueError("not an RRDBNet (ESRGAN) state dict: no conv_first / RRDB block keys")
+    nb = max(blocks) + 1
+    tops = sorted(int(k.split(".")[1]) for k in old if re.match(r"^model\.\d+\.weight$", k))
+    scale = 2 ** sum(1 for n in tops if n > 6)
+    first, last = old["model.0.weight"], old[f"model.{tops[-1]}.weight"]
+    nf, in_nc, out_nc = int(first.shape[0]), int(first.shape[1]), int(last.shape[0])
+    gc = int(old["model.1.sub.0.RDB1.conv1.0.weight"].shape[0])
+    if in_nc != 3:
+        raise ValueError(f"ESRGAN checkpoint has in_nc = {in_nc} (a pixel-unshuffle or non-RGB variant): only in_nc = 3 is supported")
+    if out_nc != 3:
+        raise ValueError(f"ESRGAN checkpoint has out_nc = {out_nc}: only out_nc = 3 is supported")
+    if nf != 64:
+        raise ValueError(f"ESRGAN checkpoint has nf = {nf}: the dense-block kernel runs nf = 64")
+    if gc != 32:
+        raise ValueError(f"ESRGAN checkpoint has growth gc = {gc}: the dense-block kernel runs gc = 32")
+    return dict(in_nc=in_nc, out_nc=out_nc, nf=nf, gc=gc, nb=nb, scale=scale)
+
+
 def load_state_dict(path: str) -> Dict[str, torch.Tensor]:
     if path.endswith(".safetensors"):
         from safetensors.torch import load_file

@@ -494,6 +494,26 @@ int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, co
     return lora_merge_launch(a, (hipStream_t)stream);
 }
 
+int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
+                      float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream) {
+    op_begin();
+    EsrganConvArgs a;
+    a.x = (const half_t*)x; a.ldx = ldx; a.cin = cin;
+    a.n = n; a.h = h; a.w = w; a.up = up;
+    a.wt = (const half_t*)wt; a.bias = (const half_t*)bias;
+    a.y = (half_t*)y; a.ldy = ldy; a.c_off = c_off; a.cout = cout;
+    a.slope = slope;
+    a.r1 = (const half_t*)r1; a.ldr1 = ldr1; a.s1 = s1;
+    a.r2 = (const half_t*)r2; a.ldr2 = ldr2; a.s2 = s2;
+    return noted(esrgan_conv_launch(a, (hipStream_t)stream), esrgan_last_kernel_name());
+}
+
+int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
+                     void* stream) {
+    op_begin();
+    return tile_blend_launch(ps, my, mx, th, tw, out, div, oh, ow, y0, x0, c, (hipStream_t)stream);
+}
+
 int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, void* stream) {
     op_begin();
     return bislerp_launch(x, tmp, y, n, c, h, w, h_new, w_new, (hipStream_t)stream);

@@ -364,7 +364,7 @@ __device__ __forceinline__ void ln_apply(const GemmParams& p, f32x4 (&acc)[TM][T
 __device__ uint4 g_zero_row[4096];  // 64 KB of zeros: conv taps outside the image read it, stepped through like real data (one
                                     // tap's channel run at a time, so it only has to cover max(C1, C2) <= 32768 halfs)
                                     // (the library is built without relocatable device code, so every object whose kernels read the page
-                                    // gets a copy of its own — four family objects, 256 KB of device memory; only zeros are ever read from it)
+                                    // gets a copy of its own — five family objects, 320 KB of device memory; only zeros are ever read from it)
 
 // Prologue staging of a tile's per-column epilogue operands into LDS: bias_s[BN] halfs (zeros without a bias) and, for a LayerNorm-fold
 // consumer, wsum_s[BN] floats (zeros beyond N).  epi_stage_load issues the two loads as untracked asm (always a load, from a page of zeros

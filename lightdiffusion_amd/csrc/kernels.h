@@ -122,6 +122,37 @@ int hook_check_launch(const void* a, const void* b, size_t words_ab, const void*
 // bislerp (LD.py:429-518): fp32 NCHW [n][c][h][w] -> [n][c][h_new][w_new]; tmp holds n*c*h*w_new floats (width pass first)
 int bislerp_launch(const float* x, float* tmp, float* y, int n, int c, int h, int w, int h_new, int w_new, hipStream_t stream);
 
+// ---- esrgan.hip
+// The dense-block 3x3 convolution (stride 1, pad 1) of RRDBNet: y[.., c_off .. c_off + cout) = epilogue(conv3x3(x[.., 0 .. cin)))
+//   v = acc + bias;  slope != 0: v = v > 0 ? v : slope v;  r1: v = s1 v + r1;  r2: v = s2 v + r2     (fp32, one rounding at the store)
+// x: NHWC fp16, pixel pitch ldx >= cin (cin a multiple of 32 in [64, 192]); y: pitch ldy, cout in {32, 64}; y may be x itself with
+// c_off >= cin (the dense concatenation in place), any other overlap of an output with the input is LD_ERR_ARG.  (h, w): the OUTPUT size;
+// up != 0: x is [n][h / 2][w / 2] and is read through a nearest-2x upsampling.  y2: optional second copy of the output at channel 0.
+struct EsrganConvArgs {
+    const half_t* x = nullptr;
+    int ldx = 0, cin = 0;
+    int n = 0, h = 0, w = 0, up = 0;
+    const half_t* wt = nullptr;     // [cout][ky][kx][cin]
+    const half_t* bias = nullptr;   // [cout] or null
+    half_t* y = nullptr;
+    int ldy = 0, c_off = 0, cout = 0;
+    half_t* y2 = nullptr;
+    int ldy2 = 0;
+    float slope = 0.f;
+    const half_t* r1 = nullptr;
+    int ldr1 = 0;
+    float s1 = 1.f;
+    const half_t* r2 = nullptr;
+    int ldr2 = 0;
+    float s2 = 1.f;
+};
+int esrgan_conv_launch(const EsrganConvArgs& a, hipStream_t stream);
+const char* esrgan_last_kernel_name();   // instantiation the calling thread's last esrgan_conv_launch dispatched ("" = none)
+// tiled_scale's blend (LD.py:7326-7352), fp32: out[oh][ow][c] += ps[th][tw][c] * my[y] * mx[x] at (y0, x0), div[oh][ow] += my[y] * mx[x];
+// ps == null: the final out /= div
+int tile_blend_launch(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
+                      hipStream_t stream);
+
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
 // (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout

@@ -23,6 +23,7 @@ from . import weights as W
 from .clip import CLIP, CLIPTextModelHIP, LoraPatches, PromptTokenizer, _add_patches, patch_terms
 from .sampling import LATENT_SCALE, common_ksampler
 from .unet import MI355XUNet, MI355XVAE
+from .upscale import MI355XUpscaler, tiled_upscale
 
 
 class SD15LatentFormat:
@@ -217,7 +218,42 @@ class LatentUpscale:
         return (s,)
 
 
+class UpscaleModelLoader:
+    """load_model(name) -> (upscale_model,) (LD.py:7240-7272): an RRDBNet state dict, or the name of one under `model_dir`, of any of
+    the spellings checkpoint.normalize_esrgan_keys accepts."""
+
+    def __init__(self, device="cuda:0", model_dir: Optional[str] = None):
+        self.device, self.model_dir = device, model_dir
+
+    def load_model(self, model_name):
+        from . import checkpoint as CK
+        if isinstance(model_name, str):
+            path = model_name if os.path.isabs(model_name) or self.model_dir is None else os.path.join(self.model_dir, model_name)
+            sd = torch.load(path, map_location="cpu", weights_only=True) if path.endswith((".pth", ".pt")) else CK.load_state_dict(path)
+        else:
+            sd = dict(model_name)
+        cfg = CK.detect_esrgan_config(sd)
+        return (MI355XUpscaler(cfg, CK.normalize_esrgan_keys(sd), device=self.device),)
+
+
+class ImageUpscaleWithModel:
+    """upscale(upscale_model, image) -> (image,) (LD.py:7356-7395): tiled_scale with tile 512 / overlap 32 (the reference's constants),
+    clamped to [0, 1]; host fp32 [B, H, W, 3] in, host fp32 [B, H s, W s, 3] out.  Runs on the model's device."""
+
+    def __init__(self, tile: int = 512, overlap: int = 32):
+        self.tile, self.overlap = tile, overlap
+
+    def upscale(self, upscale_model: MI355XUpscaler, image):
+        s = tiled_upscale(upscale_model, image, self.tile, self.overlap)
+        return (torch.clamp(s, min=0, max=1.0).cpu(),)
+
+
 # ------------------------------------------------------------------ loaders
+def load_synthetic_upscaler(device="cuda:0", nb: int = 23, scale: int = 4, seed: int = 0) -> MI355XUpscaler:
+    """An RRDBNet with deterministic random-init weights: the offline stand-in for RealESRGAN_x4plus.pth (LD.py:84-90)."""
+    return MI355XUpscaler(W.esrgan_config(nb, scale), lambda name, shape: W.synth_tensor(name, shape, seed), device=device)
+
+
 def _attach(unet: MI355XUNet, device) -> ModelPatcher:
     patcher = ModelPatcher(SD15Model(unet), load_device=device)
     patcher.set_model_unet_function_wrapper(unet)
@@ -269,7 +305,7 @@ class CheckpointLoaderSimple:
 
 
 def txt2img(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=512, batch_size=1, seed=0, steps=20, cfg=7.0,
-            sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False):
+            sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False, upscale_model: Optional[MI355XUpscaler] = None):
     """The reference's headless `pipeline()` order (LD.py:10001-10086) with explicit arguments instead of hard-coded ones.
     `*_tokens`: a prompt string (needs a tokenizer on `clip`) or pre-tokenised [[(id, weight), ...]] chunks."""
     enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
@@ -280,7 +316,10 @@ def txt2img(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=
     if hires:   # hires-fix (LD.py:10585-10603): bislerp x2, then 10 Euler-a steps at denoise 0.45, cfg 8
         lat = LatentUpscale(model.load_device).upscale(lat, "bislerp", width * 2, height * 2)[0]
         lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45)[0]
-    return VAEDecode().decode(vae, lat)[0]
+    img = VAEDecode().decode(vae, lat)[0]
+    if upscale_model is not None:   # the image-side upscale the reference builds next to the sampler nodes (LD.py:10014-10015)
+        img = ImageUpscaleWithModel().upscale(upscale_model, img)[0]
+    return img
 
 
 def txt2img_sharded(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=512, global_batch=8, seed=0, steps=20, cfg=7.0,

@@ -243,6 +243,34 @@ def clip_param_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
     return shp
 
 
+def esrgan_config(nb: int = 23, scale: int = 4) -> dict:
+    """RRDBNet as RealESRGAN_x4plus ships it (nf 64, gc 32, 23 blocks, x4); `nb` / `scale` vary for tests."""
+    return dict(in_nc=3, out_nc=3, nf=64, gc=32, nb=nb, scale=scale)
+
+
+def esrgan_param_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
+    """Old-arch RRDBNet keys (the names the reference normalises every spelling to, LD.py:7044-7055, 7174-7192) -> shapes."""
+    nf, gc, nb = cfg["nf"], cfg["gc"], cfg["nb"]
+    n_up = int(cfg["scale"]).bit_length() - 1
+    shp: Dict[str, Tuple[int, ...]] = {}
+
+    def conv(p, o, i):
+        shp[f"{p}.weight"] = (o, i, 3, 3)
+        shp[f"{p}.bias"] = (o,)
+
+    conv("model.0", nf, cfg["in_nc"])
+    for b in range(nb):
+        for r in (1, 2, 3):
+            for c in range(5):
+                conv(f"model.1.sub.{b}.RDB{r}.conv{c + 1}.0", gc if c < 4 else nf, nf + c * gc)
+    conv(f"model.1.sub.{nb}", nf, nf)
+    for u in range(n_up):
+        conv(f"model.{3 * (u + 1)}", nf, nf)
+    conv(f"model.{3 * n_up + 2}", nf, nf)
+    conv(f"model.{3 * n_up + 4}", cfg["out_nc"], nf)
+    return shp
+
+
 # ---------------------------------------------------------------- generator
 
 def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> torch.Tensor:
