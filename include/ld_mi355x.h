@@ -293,6 +293,39 @@ const char* ld_op_last_kernel(void);
  * dst may alias base.  Also what the host's text model patches its weights with. */
 int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream);
 
+/* ---- 8-bit image operators (UltimateSDUpscale's tile plumbing, LD.py:7629-7739, kept on the device).  Images are uint8, HWC (a mask: HW),
+ * addressed by a pointer and a row pitch in BYTES, so a crop of a larger image costs nothing.  All arithmetic is integer and bit-identical
+ * to Pillow's.  Channels: 1 to 4.
+ *
+ * Separable resize (Image.resize with LANCZOS or BICUBIC) of the in_w x in_h window at src to out_w x out_h: the horizontal pass first, then
+ * the vertical, with a uint8 intermediate; each output byte is clip8((2^21 + sum pixel * tap) >> 22).  A pass runs exactly when its size
+ * changes and must then be given its taps, otherwise NULL (both NULL: a copy).  hcoef / vcoef: DEVICE int arrays [out][2 + k] = first input
+ * sample, tap count (<= k), taps in fixed point with 22 fractional bits; the caller builds them (Pillow's precompute_coeffs in double) and
+ * guarantees first + count <= input size and 255 * sum |tap| + 2^21 < 2^31.  tmp: ld_op_u8_resample_tmp_bytes(in_h, out_w, channels) bytes,
+ * read only when both passes run. */
+int ld_op_u8_resample(const void* src, int src_pitch, int in_w, int in_h, int channels, void* dst, int dst_pitch, int out_w, int out_h, const int* hcoef,
+                      int hk, const int* vcoef, int vk, void* tmp, void* stream);
+size_t ld_op_u8_resample_tmp_bytes(int in_h, int out_w, int channels);
+/* ImageFilter.GaussianBlur(radius) of the one-channel w x h image at src: three box passes along x, then three along y, uint8 after each;
+ * edges replicate at the border of THIS image, so a caller that blurs a window of a larger image grows the window by the blur's reach,
+ * 3 * (box_radius + 1) per side, or to the image's edge.  ld_op_u8_box_weights (host only) gives one pass's integer radius and weights,
+ * computed in float32 in Pillow's order.  tmp: ld_op_u8_blur_tmp_bytes(w, h) bytes.  dst may be src. */
+int ld_op_u8_box_weights(float radius, int* box_radius, unsigned* ww, unsigned* fw);
+size_t ld_op_u8_blur_tmp_bytes(int w, int h);
+int ld_op_u8_gaussian_blur(const void* src, int src_pitch, void* dst, int dst_pitch, int w, int h, float radius, void* tmp, void* stream);
+/* One job's mask inside a w x h window: 0 everywhere except the pw x ph rectangle at (px, py), window coordinates, which may hang over any
+ * edge: 255 (ImageDraw.rectangle) or pattern[ph][pw] (the pasted seam-fix gradient). */
+int ld_op_u8_mask(void* dst, int dst_pitch, int w, int h, int px, int py, int pw, int ph, const void* pattern, int pattern_pitch, void* stream);
+/* canvas[y0 .. y0 + h)[x0 .. x0 + w) = div255(tile * a + canvas * (255 - a)) per channel, div255(v) = ((v + 128) + ((v + 128) >> 8)) >> 8:
+ * process_images' paste, putalpha, masked paste, alpha_composite and convert("RGB") over an opaque image.  The region must lie inside the
+ * cw x ch canvas (LD_ERR_ARG otherwise); bytes outside it are not touched. */
+int ld_op_u8_composite(void* canvas, int canvas_pitch, int cw, int ch, const void* tile, int tile_pitch, const void* alpha, int alpha_pitch, int x0, int y0,
+                       int w, int h, int channels, void* stream);
+/* tensor_to_pil (LD.py:7445-7449): y = uint8(clip(255 * x, 0, 255)), a truncation in fp32;  pil_to_tensor (LD.py:7452-7456): y = x / 255 as a
+ * correctly rounded fp32 division.  n elements, contiguous. */
+int ld_op_u8_from_f32(const float* x, void* y, size_t n, void* stream);
+int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

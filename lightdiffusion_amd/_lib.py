@@ -128,6 +128,15 @@ SIGNATURES = {
     "ld_op_tile_blend": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
     "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),
+    "ld_op_u8_resample": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P]),
+    "ld_op_u8_resample_tmp_bytes": (_Z, [_I, _I, _I]),
+    "ld_op_u8_box_weights": (_I, [_F, C.POINTER(_I), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "ld_op_u8_blur_tmp_bytes": (_Z, [_I, _I]),
+    "ld_op_u8_gaussian_blur": (_I, [_P, _I, _P, _I, _I, _I, _F, _P, _P]),
+    "ld_op_u8_mask": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "ld_op_u8_composite": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ld_op_u8_from_f32": (_I, [_P, _P, _Z, _P]),
+    "ld_op_f32_from_u8": (_I, [_P, _P, _Z, _P]),
 }
 
 

@@ -519,4 +519,47 @@ int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int
     return bislerp_launch(x, tmp, y, n, c, h, w, h_new, w_new, (hipStream_t)stream);
 }
 
+int ld_op_u8_resample(const void* src, int src_pitch, int in_w, int in_h, int channels, void* dst, int dst_pitch, int out_w, int out_h, const int* hcoef,
+                      int hk, const int* vcoef, int vk, void* tmp, void* stream) {
+    op_begin();
+    return u8_resample_launch((const uint8_t*)src, src_pitch, in_w, in_h, channels, (uint8_t*)dst, dst_pitch, out_w, out_h, hcoef, hk, vcoef, vk,
+                              (uint8_t*)tmp, (hipStream_t)stream);
+}
+
+size_t ld_op_u8_resample_tmp_bytes(int in_h, int out_w, int channels) { return u8_resample_tmp_bytes(in_h, out_w, channels); }
+
+int ld_op_u8_box_weights(float radius, int* box_radius, unsigned* ww, unsigned* fw) {
+    if (box_radius == nullptr || ww == nullptr || fw == nullptr) return LD_ERR_ARG;
+    return u8_box_weights(radius, box_radius, ww, fw);
+}
+
+size_t ld_op_u8_blur_tmp_bytes(int w, int h) { return u8_blur_tmp_bytes(w, h); }
+
+int ld_op_u8_gaussian_blur(const void* src, int src_pitch, void* dst, int dst_pitch, int w, int h, float radius, void* tmp, void* stream) {
+    op_begin();
+    return u8_gaussian_blur_launch((const uint8_t*)src, src_pitch, (uint8_t*)dst, dst_pitch, w, h, radius, (uint8_t*)tmp, (hipStream_t)stream);
+}
+
+int ld_op_u8_mask(void* dst, int dst_pitch, int w, int h, int px, int py, int pw, int ph, const void* pattern, int pattern_pitch, void* stream) {
+    op_begin();
+    return u8_mask_launch((uint8_t*)dst, dst_pitch, w, h, px, py, pw, ph, (const uint8_t*)pattern, pattern_pitch, (hipStream_t)stream);
+}
+
+int ld_op_u8_composite(void* canvas, int canvas_pitch, int cw, int ch, const void* tile, int tile_pitch, const void* alpha, int alpha_pitch, int x0, int y0,
+                       int w, int h, int channels, void* stream) {
+    op_begin();
+    return u8_composite_launch((uint8_t*)canvas, canvas_pitch, cw, ch, (const uint8_t*)tile, tile_pitch, (const uint8_t*)alpha, alpha_pitch, x0, y0, w, h,
+                               channels, (hipStream_t)stream);
+}
+
+int ld_op_u8_from_f32(const float* x, void* y, size_t n, void* stream) {
+    op_begin();
+    return u8_from_f32_launch(x, (uint8_t*)y, n, (hipStream_t)stream);
+}
+
+int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream) {
+    op_begin();
+    return f32_from_u8_launch((const uint8_t*)x, y, n, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -1,6 +1,7 @@
 // Launcher declarations for the gfx950 kernels (internal to the shared library; the public C ABI is
 // include/ld_mi355x.h).  Every launcher validates shapes on the host and returns an LD_* status.
 #pragma once
+#include <cstdint>
 #include <cstdlib>
 #include "common.h"
 #include "gemm.h"
@@ -152,6 +153,25 @@ const char* esrgan_last_kernel_name();   // instantiation the calling thread's l
 // ps == null: the final out /= div
 int tile_blend_launch(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
                       hipStream_t stream);
+
+// ---- image.hip: uint8 images, HWC (masks HW) with a row pitch in bytes, bit-identical to Pillow (see the file's header)
+// separable resize of the in_w x in_h window at src to out_w x out_h: horizontal pass, then vertical, uint8 between them; a pass runs exactly when
+// its size changes and then takes its taps (hcoef / vcoef: device [out][2 + k] ints = first input sample, tap count, k fixed-point taps with 22
+// fractional bits, every (first + count) within the input: the host builds them); tmp: u8_resample_tmp_bytes(in_h, out_w, C), read when both run
+int u8_resample_launch(const uint8_t* src, int spitch, int in_w, int in_h, int C, uint8_t* dst, int dpitch, int out_w, int out_h, const int* hcoef, int hk,
+                       const int* vcoef, int vk, uint8_t* tmp, hipStream_t stream);
+size_t u8_resample_tmp_bytes(int in_h, int out_w, int C);
+// GaussianBlur(radius) of the one-channel w x h image at src (edges replicate at ITS border); tmp: u8_blur_tmp_bytes(w, h); src may be dst
+int u8_box_weights(float radius, int* R, unsigned* ww, unsigned* fw);      // host only: one box pass's integer radius and weights
+size_t u8_blur_tmp_bytes(int w, int h);
+int u8_gaussian_blur_launch(const uint8_t* src, int spitch, uint8_t* dst, int dpitch, int w, int h, float radius, uint8_t* tmp, hipStream_t stream);
+// dst[w x h] = 0 except the pw x ph rectangle at (px, py) (may hang over any edge): 255, or pat[ph][pw] when given
+int u8_mask_launch(uint8_t* dst, int dpitch, int w, int h, int px, int py, int pw, int ph, const uint8_t* pat, int ppitch, hipStream_t stream);
+// canvas[y0 .. y0 + h)[x0 .. x0 + w) = div255(tile a + canvas (255 - a)) per channel; the region must lie inside the cw x ch canvas
+int u8_composite_launch(uint8_t* canvas, int cpitch, int cw, int ch, const uint8_t* tile, int tpitch, const uint8_t* alpha, int apitch, int x0, int y0, int w,
+                        int h, int C, hipStream_t stream);
+int u8_from_f32_launch(const float* x, uint8_t* y, size_t n, hipStream_t stream);    // uint8(clip(255 x, 0, 255)): truncation
+int f32_from_u8_launch(const uint8_t* x, float* y, size_t n, hipStream_t stream);    // x / 255, correctly rounded
 
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.

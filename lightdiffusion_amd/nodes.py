@@ -248,6 +248,21 @@ class ImageUpscaleWithModel:
         return (torch.clamp(s, min=0, max=1.0).cpu(),)
 
 
+class UltimateSDUpscale:
+    """upscale(...) -> (images,) (LD.py:8236-8324) with the reference's argument list: host fp32 [B, H, W, 3] in, host fp32
+    [B, H', W', 3] out, H' = ceil(H upscale_by / 8) 8.  The upscale model, the tile-by-tile redraw and the Half Tile seam fix run on the
+    device on a resident uint8 canvas (usdu.py; the 8-bit image kernels are bit-identical to the reference's Pillow plumbing).
+    `stages`: replacement stage callables for the orchestration tests (usdu.upscale); the product path never passes it."""
+
+    def upscale(self, image, model, positive, negative, vae, upscale_by, seed, steps, cfg, sampler_name, scheduler, denoise, upscale_model,
+                mode_type, tile_width, tile_height, mask_blur, tile_padding, seam_fix_mode, seam_fix_denoise, seam_fix_mask_blur, seam_fix_width,
+                seam_fix_padding, force_uniform_tiles, stages=None):
+        from . import usdu
+        return usdu.upscale(image, model, positive, negative, vae, upscale_by, seed, steps, cfg, sampler_name, scheduler, denoise, upscale_model,
+                            mode_type, tile_width, tile_height, mask_blur, tile_padding, seam_fix_mode, seam_fix_denoise, seam_fix_mask_blur,
+                            seam_fix_width, seam_fix_padding, force_uniform_tiles, stages=stages)
+
+
 # ------------------------------------------------------------------ loaders
 def load_synthetic_upscaler(device="cuda:0", nb: int = 23, scale: int = 4, seed: int = 0) -> MI355XUpscaler:
     """An RRDBNet with deterministic random-init weights: the offline stand-in for RealESRGAN_x4plus.pth (LD.py:84-90)."""
@@ -373,3 +388,18 @@ def txt2img_sharded(model, clip, vae, prompt_tokens, negative_tokens, width=512,
         g = D.gather_images((images * 255.0).round().to(torch.uint8).to(model.load_device), dst=0)
         return None if g is None else g.cpu().float() / 255.0
     return D.gather_images(images, dst=0)
+
+
+def img2img(model, clip, vae, upscale_model, image, prompt_tokens, negative_tokens, upscale_by=2, seed=0, steps=8, cfg=6, sampler_name="dpmpp_2m_sde",
+            scheduler="karras", denoise=0.3, mode_type="Linear", tile_width=512, tile_height=512, mask_blur=16, tile_padding=32,
+            seam_fix_mode="Half Tile", seam_fix_denoise=0.2, seam_fix_mask_blur=16, seam_fix_width=64, seam_fix_padding=32,
+            force_uniform_tiles="enable"):
+    """The reference's img2img (`_img2img`, LD.py:10325-10417) in its call order, its constants as defaults: both prompts through the text
+    model, then UltimateSDUpscale on the image [B, H, W, 3] (host fp32 in [0, 1]) -> host fp32 [B, H', W', 3].  `*_tokens` as in txt2img.
+    (The reference sets CLIP's last layer to -2 and loads a LoRA first: CLIPSetLastLayer / LoraLoader on `clip` / `model` before the call.)"""
+    enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
+    (pc, pp), (nc, npool) = enc(prompt_tokens), enc(negative_tokens)
+    pos, neg = [[pc, {"pooled_output": pp}]], [[nc, {"pooled_output": npool}]]
+    return UltimateSDUpscale().upscale(image, model, pos, neg, vae, upscale_by, seed, steps, cfg, sampler_name, scheduler, denoise, upscale_model,
+                                       mode_type, tile_width, tile_height, mask_blur, tile_padding, seam_fix_mode, seam_fix_denoise, seam_fix_mask_blur,
+                                       seam_fix_width, seam_fix_padding, force_uniform_tiles)[0]

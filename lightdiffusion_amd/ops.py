@@ -327,6 +327,174 @@ def bislerp(samples: torch.Tensor, width: int, height: int) -> torch.Tensor:
     return y.to(samples.dtype)
 
 
+# ------------------------------------------------------------------ 8-bit image ops (image.hip): UltimateSDUpscale's tile plumbing
+# uint8 images [H, W, C] (masks [H, W]) on the device; a view whose pixels are contiguous within a row (a crop) is taken as pointer + pitch.
+# Integer arithmetic, bit-identical to Pillow.  These five — u8_from_f32, f32_from_u8, u8_resample, u8_region_mask, u8_composite_ — are the
+# seam usdu.py works through.
+_RESAMPLE_FILTERS = {"lanczos": 3.0, "bicubic": 2.0}
+
+
+def _filter_value(filt: str, x: float) -> float:
+    if filt == "lanczos":          # sinc(x) sinc(x / 3) on [-3, 3)
+        if not -3.0 <= x < 3.0:
+            return 0.0
+        sinc = lambda v: 1.0 if v == 0.0 else math.sin(math.pi * v) / (math.pi * v)
+        return sinc(x) * sinc(x / 3.0)
+    a, x = -0.5, abs(x)            # bicubic, a = -0.5
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+_COEF_ROWS = {}
+_COEF_DEV = {}
+
+
+def resample_coeffs(in_size: int, out_size: int, filt: str = "lanczos"):
+    """One axis of Pillow's precompute_coeffs + normalize_coeffs_8bpc, in double on the host: (rows, k) with rows[out] = [first input
+    sample, tap count, k taps in fixed point with 22 fractional bits].  Cached per (in, out, filter)."""
+    key = (in_size, out_size, filt)
+    if key not in _COEF_ROWS:
+        support = _RESAMPLE_FILTERS[filt]
+        scale = in_size / out_size
+        fs = max(scale, 1.0)
+        sup = support * fs
+        k = int(math.ceil(sup)) * 2 + 1
+        rows = []
+        for xx in range(out_size):
+            center = (xx + 0.5) * scale
+            lo = max(int(center - sup + 0.5), 0)
+            hi = min(int(center + sup + 0.5), in_size)
+            w = [_filter_value(filt, (j + lo - center + 0.5) / fs) for j in range(hi - lo)]
+            ww = sum(w)
+            if ww != 0.0:
+                w = [v / ww for v in w]
+            kk = [int(0.5 + v * (1 << 22)) if v >= 0 else int(-0.5 + v * (1 << 22)) for v in w]
+            # the kernels accumulate in int32: 2^21 + 255 sum |tap| must stay below 2^31 (sum |k| < 2; Lanczos is about 1.4)
+            assert (1 << 21) + 255 * sum(abs(v) for v in kk) < (1 << 31), "resample taps overflow the int32 accumulator"
+            rows.append([lo, hi - lo] + kk + [0] * (k - len(kk)))
+        _COEF_ROWS[key] = (rows, k)
+    return _COEF_ROWS[key]
+
+
+def _coeffs_on(device, in_size: int, out_size: int, filt: str):
+    d = torch.device(device)
+    key = (in_size, out_size, filt, d.index if d.index is not None else torch.cuda.current_device())
+    if key not in _COEF_DEV:                      # uploaded once
+        rows, k = resample_coeffs(in_size, out_size, filt)
+        _COEF_DEV[key] = (torch.tensor(rows, dtype=torch.int32).to(d), k)
+    return _COEF_DEV[key]
+
+
+def _u8_image(t: torch.Tensor):
+    """(pointer, row pitch in bytes, h, w, c) of a uint8 image view [H, W] or [H, W, C] whose rows are dense."""
+    assert t.is_cuda and t.dtype == torch.uint8 and t.dim() in (2, 3), "a uint8 device image [H, W] or [H, W, C]"
+    c = 1 if t.dim() == 2 else t.shape[2]
+    dense = t.stride(1) == 1 if t.dim() == 2 else (t.stride(2) == 1 and t.stride(1) == c)
+    assert dense and t.stride(0) >= t.shape[1] * c, "pixels must be contiguous within a row"
+    return t.data_ptr(), t.stride(0), t.shape[0], t.shape[1], c
+
+
+def u8_from_f32(x: torch.Tensor) -> torch.Tensor:
+    """tensor_to_pil (LD.py:7445-7449) without the PIL object: uint8(clip(255 x, 0, 255)), a truncation in fp32."""
+    x = x.contiguous()
+    assert x.is_cuda and x.dtype == torch.float32
+    y = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    check(lib().ld_op_u8_from_f32(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "ld_op_u8_from_f32")
+    return y
+
+
+def f32_from_u8(x: torch.Tensor) -> torch.Tensor:
+    """pil_to_tensor (LD.py:7452-7456): x / 255 as a correctly rounded fp32 division."""
+    x = x.contiguous()
+    assert x.is_cuda and x.dtype == torch.uint8
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(lib().ld_op_f32_from_u8(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "ld_op_f32_from_u8")
+    return y
+
+
+def u8_resample(src: torch.Tensor, size, filt: str = "lanczos") -> torch.Tensor:
+    """Image.resize(size = (w, h), LANCZOS / BICUBIC) of a uint8 image or of a crop of one (a view): horizontal pass, then vertical, each
+    skipped when its size does not change (both: a copy)."""
+    ptr, pitch, h, w, c = _u8_image(src)
+    ow, oh = int(size[0]), int(size[1])
+    dst = torch.empty((oh, ow) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
+    hco, hk = _coeffs_on(src.device, w, ow, filt) if ow != w else (None, 0)
+    vco, vk = _coeffs_on(src.device, h, oh, filt) if oh != h else (None, 0)
+    tmp = torch.empty(lib().ld_op_u8_resample_tmp_bytes(h, ow, c), dtype=torch.uint8, device=src.device) if hco is not None and vco is not None else None
+    check(lib().ld_op_u8_resample(ptr, pitch, w, h, c, dst.data_ptr(), ow * c, ow, oh, _p(hco), hk, _p(vco), vk, _p(tmp), _stream()), "ld_op_u8_resample")
+    return dst
+
+
+def u8_box_weights(radius: float):
+    """(R, ww, fw) of one box pass of GaussianBlur(radius): the integer radius and the two fixed-point weights."""
+    import ctypes
+    r, ww, fw = ctypes.c_int(0), ctypes.c_uint(0), ctypes.c_uint(0)
+    check(lib().ld_op_u8_box_weights(float(radius), ctypes.byref(r), ctypes.byref(ww), ctypes.byref(fw)), "ld_op_u8_box_weights")
+    return r.value, ww.value, fw.value
+
+
+def u8_blur_reach(radius: float) -> int:
+    """How far GaussianBlur(radius) reads along one axis: three passes of R + 1 samples."""
+    return 3 * (u8_box_weights(radius)[0] + 1)
+
+
+def _blur_window(hw, region, radius: float):
+    """The region (x1, y1, x2, y2) grown by the blur's reach and clipped to the image: a blur of that window, replicating at ITS border,
+    equals the blur of the whole image on the region (a window side is either the image's or out of the region's reach)."""
+    reach = u8_blur_reach(radius)
+    x1, y1, x2, y2 = region
+    return max(x1 - reach, 0), max(y1 - reach, 0), min(x2 + reach, hw[1]), min(y2 + reach, hw[0])
+
+
+def u8_gaussian_blur(mask: torch.Tensor, radius: float, region=None) -> torch.Tensor:
+    """ImageFilter.GaussianBlur(radius) of a one-channel uint8 image [H, W].  region (x1, y1, x2, y2): only that part of the result is
+    wanted — the window around it is blurred and the region returned (a view), equal to the same part of the full-image blur."""
+    wx1, wy1, wx2, wy2 = (0, 0, mask.shape[1], mask.shape[0]) if region is None else _blur_window(mask.shape, region, radius)
+    win = mask[wy1:wy2, wx1:wx2]
+    ptr, pitch, h, w, _ = _u8_image(win)
+    dst = torch.empty(h, w, dtype=torch.uint8, device=mask.device)
+    tmp = torch.empty(lib().ld_op_u8_blur_tmp_bytes(w, h), dtype=torch.uint8, device=mask.device)
+    check(lib().ld_op_u8_gaussian_blur(ptr, pitch, dst.data_ptr(), w, w, h, float(radius), tmp.data_ptr(), _stream()), "ld_op_u8_gaussian_blur")
+    if region is None:
+        return dst
+    return dst[region[1] - wy1:region[3] - wy1, region[0] - wx1:region[2] - wx1]
+
+
+def u8_mask(h: int, w: int, rect, pattern: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """A [h, w] mask: 0 except the rectangle rect = (x, y, width, height), which may hang over any edge: 255, or `pattern` [height, width]."""
+    device = pattern.device if pattern is not None else device
+    dst = torch.empty(h, w, dtype=torch.uint8, device=device)
+    pp, ppitch = (None, 0) if pattern is None else (_u8_image(pattern)[0], pattern.stride(0))
+    with torch.cuda.device(dst.device):
+        check(lib().ld_op_u8_mask(dst.data_ptr(), w, w, h, int(rect[0]), int(rect[1]), int(rect[2]), int(rect[3]), pp, ppitch, _stream()), "ld_op_u8_mask")
+    return dst
+
+
+def u8_region_mask(hw, rect, pattern: Optional[torch.Tensor], radius: float, region, device) -> torch.Tensor:
+    """One job's alpha: the mask of a canvas of size hw = (H, W) that is 0 except `rect` (see u8_mask), blurred with GaussianBlur(radius)
+    when radius > 0, on the crop region (x1, y1, x2, y2) only.  Nothing of canvas size is built: the mask is written into the window the
+    blur needs (see u8_gaussian_blur) and blurred there."""
+    wx1, wy1, wx2, wy2 = _blur_window(hw, region, radius) if radius > 0 else region
+    win = u8_mask(wy2 - wy1, wx2 - wx1, (rect[0] - wx1, rect[1] - wy1, rect[2], rect[3]), pattern, device)
+    if not radius > 0:
+        return win
+    return u8_gaussian_blur(win, radius, (region[0] - wx1, region[1] - wy1, region[2] - wx1, region[3] - wy1))
+
+
+def u8_composite_(canvas: torch.Tensor, tile: torch.Tensor, alpha: torch.Tensor, x0: int, y0: int) -> torch.Tensor:
+    """canvas[y0:y0+h, x0:x0+w] = div255(tile a + canvas (255 - a)) in place — process_images' paste / putalpha / alpha_composite /
+    convert("RGB") chain (LD.py:7718-7736) over an opaque canvas.  The rest of the canvas is untouched."""
+    cp, cpitch, ch, cw, c = _u8_image(canvas)
+    tp, tpitch, h, w, tc = _u8_image(tile)
+    ap, apitch, ah, aw, _ = _u8_image(alpha)
+    assert tc == c and (ah, aw) == (h, w), "tile and alpha must have the region's size"
+    check(lib().ld_op_u8_composite(cp, cpitch, cw, ch, tp, tpitch, ap, apitch, int(x0), int(y0), w, h, c, _stream()), "ld_op_u8_composite")
+    return canvas
+
+
 # ------------------------------------------------------------------ the `operations=` namespace (secondary seam)
 # The reference builds every network from an injectable namespace (`operations=ops`: UNetModel1 LD.py:5338, ResBlock1
 # 5207, SpatialTransformer 4179, CrossAttention 4005, FeedForward 3908; BaseModel picks `manual_cast` or
