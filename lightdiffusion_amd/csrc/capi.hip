@@ -2,49 +2,67 @@
 // kernel launchers; used by the parity tests and by hosts that want to compose their own graphs.
 #include <string>
 
-#include "kernels.h"
+#include "runtime.h"
 #include "../../include/ld_mi355x.h"
 
 namespace {
-// scratch for ld_op_linear's GEGLU path: the op takes weights in checkpoint row order, the kernel wants them
-// tile-interleaved, so the op repacks into caller-provided workspace
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // ld_op_last_kernel: the contraction instantiations the calling thread's last ld_op_* call dispatched, in launch order, joined with ';'
 thread_local std::string t_op_kernels;
 inline void op_begin() { t_op_kernels.clear(); }
-inline int noted(int st, const char* name) {   // (the launchers reset their name on entry: empty = nothing was dispatched)
-    if (name != nullptr && *name != '\0') {
-        if (!t_op_kernels.empty()) t_op_kernels += ';';
-        t_op_kernels += name;
-    }
+inline int noted(int st, const char* name) {
+    note_kernel(&t_op_kernels, name);
     return st;
 }
-inline int gemm_op(const GemmParams& p, hipStream_t s) { return noted(gemm_launch(p, s), gemm_last_kernel_name()); }
-inline int gemm_op(const GemmParams& p, const GemmPlan& plan, hipStream_t s) { return noted(gemm_run(p, plan, s), gemm_last_kernel_name()); }
 
-// The row-resident kernel (conv8.hip) from a caller's scratch: the head of the region holds the counters of its in-launch reduction and,
-// where the shape can have one, a copy of the weights in its layout; the split partials take what is left.
 constexpr size_t kSyncBytes = LD_SYNC_INTS * sizeof(int);
+constexpr size_t kCompositeSplitBytes = (size_t)96 << 20;   // split-K partials of the GroupNorm / skip composites: what the executors reserve
+// the row-resident kernel's (conv8.hip) share of a caller's scratch: the counters of its in-launch reduction and, where the shape can have one, a
+// copy of the weights in its layout
 inline size_t conv8_scratch_head(int cout, int cin) { return kSyncBytes + (conv8_weight_eligible(cout, cin) ? align256(conv8_weight_bytes(cout, cin)) : 0); }
-inline void conv8_scratch(GemmParams& p, void* ws, size_t partial_bytes) {
-    const int cin = p.C1 + p.C2;
-    p.sync = (int*)ws;
-    p.W8 = conv8_weight_eligible(p.N, cin) ? (const half_t*)((char*)ws + kSyncBytes) : nullptr;
-    p.partial = (float*)((char*)ws + conv8_scratch_head(p.N, cin));
-    p.partial_bytes = partial_bytes;
-}
-// launch p (laid out by conv8_scratch) by its plan; in front of the row-resident kernel, zero the counters (a caller's scratch: not known
-// to be zero) and repack the weights (per call here; the UNet executor keeps that copy resident)
-inline int conv8_scratch_op(const GemmParams& p, const GemmPlan& plan, const void* wt, hipStream_t stream) {
-    if (plan.route == GR_CONV8) {
-        if (hipMemsetAsync(p.sync, 0, kSyncBytes, stream) != hipSuccess) return LD_ERR_HIP;
-        const int st = conv8_repack_launch((const half_t*)wt, p.N, p.C1 + p.C2, const_cast<half_t*>(p.W8), stream);
-        if (st != LD_OK) return st;
+
+// One ld_op_* call: an Exec (runtime.h) over the caller's scratch.  The arena's base is the `ws` pointer, the split-K partials, the counters
+// and the row-resident kernel's weight copy are carved from it, and the name sink is ld_op_last_kernel's string — so the operators launch
+// through Exec::gemm / Exec::attention / Exec::gn_silu_conv, the functions the UNet and VAE executors run.  (The scratch handed to a launch
+// decides its split over K, so the sizes carved here are part of an operator's route: tests/test_cabi_cpu.py pins what *_ws_bytes returns.)
+struct Op {
+    Arena arena;
+    Exec ex;
+    Op(void* ws, size_t ws_bytes, void* stream) {
+        arena.base = (char*)ws;
+        arena.cap = ws != nullptr ? ws_bytes : 0;
+        ex.arena = &arena;
+        ex.stream = (hipStream_t)stream;
+        ex.names = &t_op_kernels;
     }
-    return gemm_op(p, plan, stream);
-}
-inline int attn_op(const AttnParams& a, hipStream_t s) { return noted(attention_launch(a, s), attention_last_kernel_name()); }
+    Op(const Op&) = delete;
+    bool fits() const { return align256(arena.peak) <= arena.cap; }   // everything carved so far lies inside the caller's buffer
+    // split-K partials: `bytes` of the scratch, or all that is left of it
+    void splitk(size_t bytes) {
+        ex.splitk_ws = (float*)arena.alloc(bytes);
+        ex.splitk_bytes = bytes;
+    }
+    void splitk_rest() {
+        const size_t at = align256(arena.off);
+        if (arena.base != nullptr && at <= arena.cap) splitk(arena.cap - at);
+    }
+    // The row-resident kernel (conv8.hip) from a caller's scratch: counters | weight copy (p.W8, where the shape can have one) | split partials.
+    // In front of that kernel, and of no other, a caller's scratch needs per call: the counters zeroed (not known to be zero) and the weights
+    // `wt` repacked (the UNet executor keeps that copy resident)
+    void conv8_scratch(GemmParams& p, const void* wt, size_t partial_bytes) {
+        const int cin = p.C1 + p.C2;
+        ex.sync_ws = (int*)arena.alloc(kSyncBytes);
+        p.W8 = conv8_weight_eligible(p.N, cin) ? (const half_t*)arena.alloc(conv8_weight_bytes(p.N, cin)) : nullptr;
+        splitk(partial_bytes);
+        ex.before_gemm = [](const GemmParams& q, const GemmPlan& plan, const void* wt, hipStream_t s) {
+            if (plan.route != GR_CONV8) return (int)LD_OK;
+            if (hipMemsetAsync(q.sync, 0, kSyncBytes, s) != hipSuccess) return (int)LD_ERR_HIP;
+            return conv8_repack_launch((const half_t*)wt, q.N, q.C1 + q.C2, const_cast<half_t*>(q.W8), s);
+        };
+        ex.before_gemm_arg = wt;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -65,81 +83,57 @@ const char* ld_status_string(int s) {
 }
 
 int ld_op_linear(const void* x, const void* w, const void* bias, const void* residual, void* y, int M, int N, int K, float alpha,
-                 int act, void* ws, size_t ws_bytes, void* stream_) {
+                 int act, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    hipStream_t stream = (hipStream_t)stream_;
-    GemmParams p;
-    p.A = (const half_t*)x; p.lda = K;
-    p.W = (const half_t*)w; p.ldw = K;
-    p.M = M; p.N = N; p.K = K;
+    Op op(ws, ws_bytes, stream);
+    GemmParams p = linear_params((const half_t*)x, K, (const half_t*)w, (const half_t*)bias, M, N, K, (half_t*)y, act);
     p.alpha = alpha;
-    p.bias_n = (const half_t*)bias;
     p.R = (const half_t*)residual;
-    p.act = act;
-    p.C = (half_t*)y;
-    p.ldc = p.ldr = (act == 2 ? N / 2 : N);
-    char* wsp = (char*)ws;
-    if (act == 2) {   // repack [value | gate] rows into the tile-interleaved order the fused epilogue expects
+    if (act == 2) {   // the op takes weights in checkpoint row order: repack [value | gate] rows into the tile-interleaved order the fused epilogue expects
         if (bias == nullptr || (N & 15)) return LD_ERR_ARG;
         const int bn = gemm_pick_bn(N);
         if (N % bn) return LD_ERR_SHAPE;
-        const size_t wb = align256((size_t)N * K * sizeof(half_t)), bb = align256((size_t)N * sizeof(half_t));
-        if (ws == nullptr || ws_bytes < wb + bb) return LD_ERR_ARG;
-        half_t* w2 = (half_t*)wsp;
-        half_t* b2 = (half_t*)(wsp + wb);
-        int st = repack_rows_launch(w, 0, N, K, w2, bn, stream);
+        half_t* w2 = op.arena.halfs((size_t)N * K);
+        half_t* b2 = op.arena.halfs((size_t)N);
+        if (ws == nullptr || !op.fits()) return LD_ERR_ARG;
+        int st = repack_rows_launch(w, 0, N, K, w2, bn, op.ex.stream);
         if (st != LD_OK) return st;
-        st = repack_rows_launch(bias, 0, N, 1, b2, bn, stream);
+        st = repack_rows_launch(bias, 0, N, 1, b2, bn, op.ex.stream);
         if (st != LD_OK) return st;
         p.W = w2;
         p.bias_n = b2;
         p.bn = bn;
-        wsp += wb + bb;
-        ws_bytes -= wb + bb;
     }
-    p.partial = (float*)wsp;
-    p.partial_bytes = ws ? ws_bytes : 0;
-    if (ws == nullptr) p.partial = nullptr;
-    return gemm_op(p, stream);
+    op.splitk_rest();
+    op.ex.gemm(p);
+    return op.ex.status;
 }
 
 static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
                    const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
                    size_t ws_bytes, void* stream, float* gn_part, int* gn_chunks, const void* wup = nullptr) {
     if (stride < 1 || (ksize != 1 && ksize != 3)) return LD_ERR_ARG;
-    GemmParams p;
-    if (gn_part != nullptr) {   // GroupNorm partial statistics of the output, where the kernel that runs this shape writes them (as the executors ask: unet.hip want_stats)
-        const int HW = (ksize == 3 ? (hv - 1) / stride + 1 : hv) * (ksize == 3 ? (wv - 1) / stride + 1 : wv);
-        p.gn_part = gn_part;
-        p.gn_P = gn_num_chunks(n, HW);
-        p.gn_HW = HW;
-        p.gn_ppb = (HW + p.gn_P - 1) / p.gn_P;
-        p.gn_part_done = gn_chunks;
-    }
-    p.conv = 1;
-    p.ksize = ksize;
-    p.A = (const half_t*)x1; p.A2 = (const half_t*)x2; p.C1 = c1; p.C2 = c2;
-    p.Hs = h; p.Ws = w; p.Hv = hv; p.Wv = wv; p.stride = stride;
-    p.Ho = ksize == 3 ? (hv - 1) / stride + 1 : hv;
-    p.Wo = ksize == 3 ? (wv - 1) / stride + 1 : wv;
-    p.K = ksize * ksize * (c1 + c2);
-    p.W = (const half_t*)wt; p.ldw = p.K;
+    GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, hv, wv, stride, ksize, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
     p.Wup = (const half_t*)wup;
-    p.M = n * p.Ho * p.Wo; p.N = cout;
-    p.bias_n = (const half_t*)bias;
-    p.rowvec = (const half_t*)rowvec; p.rows_per_vec = p.Ho * p.Wo; p.ldrv = cout;
-    p.R = (const half_t*)residual; p.ldr = cout;
-    p.C = (half_t*)y; p.ldc = cout;
-    p.partial = (float*)ws;
-    p.partial_bytes = ws ? ws_bytes : 0;
+    p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
+    p.R = (const half_t*)residual;
+    if (gn_part != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, gn_part, gn_chunks);   // (as the executors ask)
     const size_t head = conv8_scratch_head(cout, c1 + c2);
     if (ws != nullptr && ksize == 3 && conv8_weight_eligible(cout, c1 + c2) && ws_bytes > head + ((size_t)8 << 20)) {
-        // a roomy scratch buffer: the row-resident kernel where it takes the shape; the general kernels keep the whole buffer for their split
-        GemmParams c8 = p;
-        conv8_scratch(c8, ws, ws_bytes - head);
-        if (const GemmPlan plan = gemm_plan(c8); plan.route == GR_CONV8) return conv8_scratch_op(c8, plan, wt, (hipStream_t)stream);
+        // a roomy scratch buffer: the row-resident kernel where it takes the shape, by a carving of its own; the general kernels keep the
+        // whole buffer for their split
+        Op c8(ws, ws_bytes, stream);
+        GemmParams q = p;
+        c8.conv8_scratch(q, wt, ws_bytes - head);
+        if (const GemmPlan plan = c8.ex.plan(q); plan.route == GR_CONV8) {
+            c8.ex.gemm(q, &plan);
+            return c8.ex.status;
+        }
     }
-    return gemm_op(p, (hipStream_t)stream);
+    Op op(ws, ws_bytes, stream);
+    op.splitk_rest();
+    op.ex.gemm(p);
+    return op.ex.status;
 }
 
 int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
@@ -157,8 +151,8 @@ int ld_op_upconv2x_fold(const void* wt, int cout, int cin, void* wfold, void* st
 int ld_op_upconv2x(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* wfold, const void* bias, void* y, int cout,
                    void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    // Upsample1 as the UNet executor runs it: the folded weights are an offer that the planner takes for an exact 2x resize of more than two
-    // images; every other case is ld_op_conv's route
+    // Upsample1 as the UNet executor runs it (unet.hip L_UP: the same builder, the same Exec::gemm): the folded weights are an offer that the
+    // planner takes for an exact 2x resize of more than two images; every other case is ld_op_conv's route
     if (wfold == nullptr) return LD_ERR_ARG;
     return op_conv(x, c, nullptr, 0, n, h, w, hv, wv, 1, 3, wt, bias, nullptr, nullptr, y, cout, ws, ws_bytes, stream, nullptr, nullptr, wfold);
 }
@@ -180,112 +174,68 @@ size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int co
     op_begin();
     const size_t C = (size_t)c1 + c2, HW = (size_t)h * w;
     return align256(groupnorm_workspace_bytes(n, (int)HW)) + 2 * align256((size_t)n * C * sizeof(float)) + align256((size_t)n * HW * C * sizeof(half_t)) +
-           conv8_scratch_head(cout, c1 + c2) + ((size_t)96 << 20);
+           conv8_scratch_head(cout, c1 + c2) + kCompositeSplitBytes;
 }
 
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
                          const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws, size_t ws_bytes,
-                         void* stream_) {
+                         void* stream) {
     op_begin();
-    // GroupNorm(32) + SiLU + 3x3 convolution (stride 1, pad 1): the reference's ResBlock1.in_layers / out_layers (LD.py:5224-5262).
-    // On the halo-tile kernel with one N tile the normalisation is fused into the convolution's A operand; otherwise two-pass GroupNorm, then the conv.
+    // GroupNorm(32) + SiLU + 3x3 convolution (stride 1, pad 1): the reference's ResBlock1.in_layers / out_layers (LD.py:5224-5262), by
+    // Exec::gn_silu_conv — fused into the halo tile's loader where the plan says so, else the two-pass GroupNorm (which the row-resident kernel
+    // takes too), then the convolution.  The scratch: normalised tensor | counters | weight copy | split partials | statistics, scale, shift.
     if (x1 == nullptr || gamma == nullptr || beta == nullptr || wt == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (ws_bytes < ld_op_groupnorm_conv_ws_bytes(c1, c2, n, h, w, cout)) return LD_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int C = c1 + c2, HW = h * w;
-    char* q = (char*)ws;
-    float* part = (float*)q; q += align256(groupnorm_workspace_bytes(n, HW));
-    float* scale = (float*)q; q += align256((size_t)n * C * sizeof(float));
-    float* shift = (float*)q; q += align256((size_t)n * C * sizeof(float));
-    half_t* g = (half_t*)q; q += align256((size_t)n * HW * C * sizeof(half_t));
-    GemmParams p;
-    p.conv = 1; p.ksize = 3;
-    p.A = (const half_t*)x1; p.A2 = (const half_t*)x2; p.C1 = c1; p.C2 = c2;
-    p.Hs = p.Hv = p.Ho = h; p.Ws = p.Wv = p.Wo = w; p.stride = 1;
-    p.K = 9 * C; p.W = (const half_t*)wt; p.ldw = p.K;
-    p.M = n * HW; p.N = cout;
-    p.bias_n = (const half_t*)bias;
-    p.rowvec = (const half_t*)rowvec; p.rows_per_vec = HW; p.ldrv = cout;
-    p.R = (const half_t*)residual; p.ldr = cout;
-    p.C = (half_t*)y; p.ldc = cout;
-    conv8_scratch(p, q, (size_t)96 << 20);
-    const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
-    if (fused.can_fuse_groupnorm) {
-        int st = groupnorm_scale_shift_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, part,
-                                              scale, shift, stream);
-        if (st != LD_OK) return st;
-        p.gn_scale = scale; p.gn_shift = shift; p.gn_silu = 1;
-        return gemm_op(p, fused, stream);
-    }
-    int st = groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, 1, g, part, stream);
-    if (st != LD_OK) return st;
-    p.A = g; p.A2 = nullptr; p.C1 = C; p.C2 = 0;
-    return conv8_scratch_op(p, gemm_plan(p), (const half_t*)wt, stream);   // (the row-resident kernel takes the normalised tensor)
+    Op op(ws, ws_bytes, stream);
+    half_t* g = op.arena.halfs((size_t)n * h * w * (c1 + c2));
+    GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, h, w, 1, 3, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
+    p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
+    p.R = (const half_t*)residual;
+    op.conv8_scratch(p, wt, kCompositeSplitBytes);
+    op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g);
+    return op.ex.status;
 }
 
 size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout) {
     op_begin();
-    return align256((size_t)cout * (9 * (size_t)c + sc1 + sc2) * sizeof(half_t)) + align256((size_t)cout * sizeof(half_t)) + ((size_t)96 << 20);
+    return align256((size_t)cout * (9 * (size_t)c + sc1 + sc2) * sizeof(half_t)) + align256((size_t)cout * sizeof(half_t)) + kCompositeSplitBytes;
 }
 
-// ResBlock1's out_layers as the executor runs them (unet.hip Run::resblock): [GroupNorm + SiLU of x] + 3x3 convolution + the 1x1 skip_connection over
-// s1 / s2 as a second K segment, one contraction on the folded weights.  gamma / beta null: x is taken as it is.  part / chunks (optional): the
-// GroupNorm partial statistics of the OUTPUT where the launch writes them (as ld_op_conv_gn_partials).
+// ResBlock1's out_layers as the executor runs them (unet.hip Run::resblock; the same builders, add_skip_segment and Exec::gn_silu_conv):
+// [GroupNorm + SiLU of x] + 3x3 convolution + the 1x1 skip_connection over s1 / s2 as a second K segment, one contraction on the folded weights.
+// gamma / beta null: x is taken as it is.  part / chunks (optional): the GroupNorm partial statistics of the OUTPUT where the launch writes
+// them (as ld_op_conv_gn_partials).  The scratch: folded weights | folded bias | [normalised tensor] | split partials | [statistics, scale, shift].
 static int op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
                         const void* wskip, const void* bskip, const void* rowvec, const void* gamma, const void* beta, float eps, void* y, int cout,
-                        float* part, int* chunks, char* q, hipStream_t stream) {
+                        float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+    Op op(ws, ws_bytes, stream);
     const int K9 = 9 * c, SC = sc1 + sc2, HW = h * w;
-    half_t* wf = (half_t*)q; q += align256((size_t)cout * (K9 + SC) * sizeof(half_t));
-    half_t* bf = (half_t*)q; q += align256((size_t)cout * sizeof(half_t));
-    int st = skip_fold_launch((const half_t*)wt, (const half_t*)wskip, (const half_t*)bias, (const half_t*)bskip, cout, K9, SC, wf, bf, stream);
+    half_t* wf = op.arena.halfs((size_t)cout * (K9 + SC));
+    half_t* bf = op.arena.halfs((size_t)cout);
+    const int st = skip_fold_launch((const half_t*)wt, (const half_t*)wskip, (const half_t*)bias, (const half_t*)bskip, cout, K9, SC, wf, bf, op.ex.stream);
     if (st != LD_OK) return st;
-    GemmParams p;
-    p.conv = 1; p.ksize = 3;
-    p.A = (const half_t*)x; p.C1 = c;
-    p.Hs = p.Hv = p.Ho = h; p.Ws = p.Wv = p.Wo = w; p.stride = 1;
-    p.S1 = (const half_t*)s1; p.SC1 = sc1; p.S2 = (const half_t*)s2; p.SC2 = sc2;
-    p.K = K9 + SC; p.W = wf; p.ldw = p.K;
-    p.M = n * HW; p.N = cout;
-    p.bias_n = bf;
-    p.rowvec = (const half_t*)rowvec; p.rows_per_vec = HW; p.ldrv = cout;
-    p.C = (half_t*)y; p.ldc = cout;
-    if (part != nullptr) {
-        p.gn_part = part;
-        p.gn_P = gn_num_chunks(n, HW);
-        p.gn_HW = HW;
-        p.gn_ppb = (HW + p.gn_P - 1) / p.gn_P;
-        p.gn_part_done = chunks;
-    }
+    GemmParams p = conv_params((const half_t*)x, c, nullptr, 0, n, h, w, h, w, 1, 3, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
+    add_skip_segment(p, (const half_t*)s1, sc1, (const half_t*)s2, sc2, wf, bf);
+    p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
+    if (part != nullptr) want_gn_partials(p, n, HW, part, chunks);
     if (gamma == nullptr) {
-        p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
-        return gemm_op(p, stream);
+        op.splitk(kCompositeSplitBytes);
+        op.ex.gemm(p);
+    } else {
+        half_t* g = op.arena.halfs((size_t)n * HW * c);
+        op.splitk(kCompositeSplitBytes);
+        op.ex.gn_silu_conv(p, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, g);
     }
-    float* stat = (float*)q; q += align256(groupnorm_workspace_bytes(n, HW));
-    float* scale = (float*)q; q += align256((size_t)n * c * sizeof(float));
-    float* shift = (float*)q; q += align256((size_t)n * c * sizeof(float));
-    half_t* g = (half_t*)q; q += align256((size_t)n * HW * c * sizeof(half_t));
-    p.partial = (float*)q; p.partial_bytes = (size_t)96 << 20;
-    const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
-    if (fused.can_fuse_groupnorm) {
-        st = groupnorm_scale_shift_launch((const half_t*)x, c, nullptr, 0, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, stat, scale, shift, stream);
-        if (st != LD_OK) return st;
-        p.gn_scale = scale; p.gn_shift = shift; p.gn_silu = 1;
-        return gemm_op(p, fused, stream);
-    }
-    st = groupnorm_launch((const half_t*)x, c, nullptr, 0, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, 1, g, stat, stream);
-    if (st != LD_OK) return st;
-    p.A = g;
-    return gemm_op(p, stream);
+    return op.ex.status;
 }
 
 int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
-                    const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream_) {
+                    const void* wskip, const void* bskip, const void* rowvec, void* y, int cout, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
     if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
     if (ws_bytes < ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout)) return LD_ERR_ARG;
-    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, nullptr, nullptr, 0.f, y, cout, nullptr, nullptr, (char*)ws,
-                        (hipStream_t)stream_);
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, nullptr, nullptr, 0.f, y, cout, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int n, int h, int w) {
@@ -297,14 +247,14 @@ size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int
 
 int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const void* gamma, const void* beta, float eps, const void* wt, const void* bias,
                               const void* s1, int sc1, const void* s2, int sc2, const void* wskip, const void* bskip, const void* rowvec, void* y, int cout,
-                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream_) {
+                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
     if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
     if ((gamma == nullptr) != (beta == nullptr) || (part == nullptr) != (chunks == nullptr)) return LD_ERR_ARG;
     if (ws_bytes < ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w)) return LD_ERR_ARG;
     if (chunks != nullptr) *chunks = 0;
-    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, gamma, beta, eps, y, cout, part, chunks, (char*)ws, (hipStream_t)stream_);
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, gamma, beta, eps, y, cout, part, chunks, ws, ws_bytes, stream);
 }
 
 int ld_op_repack_conv(const void* src, int dtype, int cout, int cin, void* dst, void* stream) {
@@ -338,7 +288,9 @@ int ld_op_attention(const void* q, int ldq, const void* k, int ldk, const void* 
     a.Vt = (const half_t*)vt; a.ldvt = ldvt; a.sV = (long long)heads * d * ldvt;
     a.O = (half_t*)o; a.ldo = ldo; a.sO = (long long)lq * ldo;
     a.B = b; a.H = heads; a.Lq = lq; a.Lk = lk; a.d = d; a.scale = scale; a.causal = causal;
-    return attn_op(a, (hipStream_t)stream);
+    Op op(nullptr, 0, stream);
+    op.ex.attention(a);
+    return op.ex.status;
 }
 
 int ld_op_attention_rowv(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo, int b, int heads,
@@ -356,7 +308,9 @@ int ld_op_attention_rowv(const void* q, int ldq, const void* k, int ldk, const v
     a.V = (const half_t*)v; a.ldv = ldv; a.sV = (long long)lk * ldv;
     a.O = (half_t*)o; a.ldo = ldo; a.sO = (long long)lq * ldo;
     a.B = b; a.H = heads; a.Lq = lq; a.Lk = lk; a.d = d; a.scale = scale; a.causal = causal;
-    return attn_op(a, (hipStream_t)stream);
+    Op op(nullptr, 0, stream);
+    op.ex.attention(a);
+    return op.ex.status;
 }
 
 int ld_op_softmax_rows(void* s, int rows, int cols, void* stream) {
@@ -385,95 +339,57 @@ int ld_op_axpby(float* x, float a, const float* y, float b, const float* z, floa
     return axpby_launch(x, a, y, b, z, c, n, (hipStream_t)stream);
 }
 
-int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
-                    const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream_) {
-    op_begin();
-    // the UNet's LayerNorm fold (unet.hip, gemm.h) as a stand-alone operator pair, for parity tests:
-    //   t = x · w_prod^T + b_prod         (producer: also emits per-row (sum, sum of squares) partials of the fp16 t)
-    //   y = LayerNorm(t; gamma, beta, eps) · w^T + bias   computed as rstd * (t · W'^T - mu * wsum) + b' on the accumulators
-    if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || t_out == nullptr || y == nullptr ||
-        ws == nullptr)
+// the UNet's LayerNorm fold (unet.hip Run::transformer, gemm.h) as a stand-alone operator pair on the executor's builders (ln_producer / ln_consumer):
+//   t = x · w_prod^T + b_prod         (producer: also emits per-row (sum, sum of squares) partials of the fp16 t)
+//   y = LayerNorm(t; gamma, beta, eps) · w^T + bias   computed as rstd * (t · W'^T - mu * wsum) + b' on the accumulators
+// geglu: the transformer block's MLP input — y[M][N/2] = a * gelu(g), [a | g] = LayerNorm(t) · w^T + bias (GEGLU, LD.py:4513-4515); w rows are
+// repacked into the tile-interleaved [value | gate] order first, then folded (the fold is row-wise).
+static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w, const void* bias,
+                        void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream, bool geglu) {
+    if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || (geglu && bias == nullptr) || t_out == nullptr ||
+        y == nullptr || ws == nullptr)
         return LD_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t wb = align256((size_t)N * C * sizeof(half_t)), bb = align256((size_t)N * sizeof(half_t)), sb = align256((size_t)N * sizeof(float));
-    const size_t stb = align256((size_t)((C + 63) / 64) * M * 2 * sizeof(float));
-    if (ws_bytes < wb + bb + sb + stb) return LD_ERR_ARG;
-    char* wsp = (char*)ws;
-    half_t* w2 = (half_t*)wsp;
-    half_t* b2 = (half_t*)(wsp + wb);
-    float* wsum = (float*)(wsp + wb + bb);
-    float* stat = (float*)(wsp + wb + bb + sb);
-    int st = ln_fold_launch((const half_t*)w, N, C, (const half_t*)gamma, (const half_t*)beta, (const half_t*)bias, w2, b2, wsum, stream);
+    const int bn = geglu ? gemm_pick_bn(N) : 0;
+    if (geglu && ((N & 15) || (N % bn))) return LD_ERR_SHAPE;
+    Op op(ws, ws_bytes, stream);
+    const half_t* wr = (const half_t*)w;      // rows as the fold reads them: repacked for GEGLU
+    const half_t* br = (const half_t*)bias;
+    if (geglu) {
+        wr = op.arena.halfs((size_t)N * C);
+        br = op.arena.halfs((size_t)N);
+    }
+    half_t* w2 = op.arena.halfs((size_t)N * C);   // folded
+    half_t* b2 = op.arena.halfs((size_t)N);
+    float* wsum = (float*)op.arena.alloc((size_t)N * sizeof(float));
+    float* stat = (float*)op.arena.alloc((size_t)((C + 63) / 64) * M * 2 * sizeof(float));
+    if (!op.fits()) return LD_ERR_ARG;
+    int st = LD_OK;
+    if (geglu) {
+        st = repack_rows_launch(w, 0, N, C, const_cast<half_t*>(wr), bn, op.ex.stream);
+        if (st == LD_OK) st = repack_rows_launch(bias, 0, N, 1, const_cast<half_t*>(br), bn, op.ex.stream);
+    }
+    if (st == LD_OK) st = ln_fold_launch(wr, N, C, (const half_t*)gamma, (const half_t*)beta, br, w2, b2, wsum, op.ex.stream);
     if (st != LD_OK) return st;
     int parts = 0;
-    GemmParams a;
-    a.A = (const half_t*)x; a.lda = C;
-    a.W = (const half_t*)w_prod; a.ldw = C;
-    a.M = M; a.N = C; a.K = C;
-    a.bias_n = (const half_t*)b_prod;
-    a.C = (half_t*)t_out; a.ldc = C;
-    a.stat_out = stat; a.stat_parts_out = &parts;
-    st = gemm_op(a, stream);
-    if (st != LD_OK) return st;
-    GemmParams b;
-    b.A = (const half_t*)t_out; b.lda = C;
-    b.W = w2; b.ldw = C;
-    b.M = M; b.N = N; b.K = C;
-    b.bias_n = b2;
-    b.C = (half_t*)y; b.ldc = N;
-    b.ln_stat = stat; b.ln_parts = parts; b.ln_rows = M;
-    b.ln_inv_c = 1.0f / (float)C; b.ln_eps = eps;
-    b.ln_wsum = wsum;
-    return gemm_op(b, stream);
+    GemmParams a = linear_params((const half_t*)x, C, (const half_t*)w_prod, (const half_t*)b_prod, M, C, C, (half_t*)t_out);
+    ln_producer(a, stat, &parts);
+    op.ex.gemm(a);
+    GemmParams b = linear_params((const half_t*)t_out, C, w2, b2, M, N, C, (half_t*)y, geglu ? 2 : 0, bn);
+    ln_consumer(b, stat, parts, M, C, eps, wsum);
+    op.ex.gemm(b);   // (not launched when the producer failed)
+    return op.ex.status;
+}
+
+int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
+                    const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream) {
+    op_begin();
+    return op_linear_ln(x, w_prod, b_prod, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, false);
 }
 
 int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
-                          const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream_) {
+                          const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    // the transformer block's MLP input as the executor runs it (unet.hip): t = x · w_prod^T + b_prod with row statistics, then
-    //   y[M][N/2] = a * gelu(g),  [a | g] = LayerNorm(t) · w^T + bias     (GEGLU, LD.py:4513-4515, on the LayerNorm-folded weights)
-    // w rows are repacked into the tile-interleaved [value | gate] order first, then folded (the fold is row-wise).
-    if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || bias == nullptr || t_out == nullptr ||
-        y == nullptr || ws == nullptr)
-        return LD_ERR_ARG;
-    hipStream_t stream = (hipStream_t)stream_;
-    const int bn = gemm_pick_bn(N);
-    if ((N & 15) || (N % bn)) return LD_ERR_SHAPE;
-    const size_t wb = align256((size_t)N * C * sizeof(half_t)), bb = align256((size_t)N * sizeof(half_t)), sb = align256((size_t)N * sizeof(float));
-    const size_t stb = align256((size_t)((C + 63) / 64) * M * 2 * sizeof(float));
-    if (ws_bytes < 2 * wb + 2 * bb + sb + stb) return LD_ERR_ARG;
-    char* wsp = (char*)ws;
-    half_t* wr = (half_t*)wsp;                         // repacked rows
-    half_t* br = (half_t*)(wsp + wb);
-    half_t* w2 = (half_t*)(wsp + wb + bb);             // folded
-    half_t* b2 = (half_t*)(wsp + 2 * wb + bb);
-    float* wsum = (float*)(wsp + 2 * wb + 2 * bb);
-    float* stat = (float*)(wsp + 2 * wb + 2 * bb + sb);
-    int st = repack_rows_launch(w, 0, N, C, wr, bn, stream);
-    if (st == LD_OK) st = repack_rows_launch(bias, 0, N, 1, br, bn, stream);
-    if (st == LD_OK) st = ln_fold_launch(wr, N, C, (const half_t*)gamma, (const half_t*)beta, br, w2, b2, wsum, stream);
-    if (st != LD_OK) return st;
-    int parts = 0;
-    GemmParams a;
-    a.A = (const half_t*)x; a.lda = C;
-    a.W = (const half_t*)w_prod; a.ldw = C;
-    a.M = M; a.N = C; a.K = C;
-    a.bias_n = (const half_t*)b_prod;
-    a.C = (half_t*)t_out; a.ldc = C;
-    a.stat_out = stat; a.stat_parts_out = &parts;
-    st = gemm_op(a, stream);
-    if (st != LD_OK) return st;
-    GemmParams b;
-    b.A = (const half_t*)t_out; b.lda = C;
-    b.W = w2; b.ldw = C;
-    b.M = M; b.N = N; b.K = C;
-    b.bias_n = b2;
-    b.act = 2; b.bn = bn;
-    b.C = (half_t*)y; b.ldc = N / 2; b.ldr = N / 2;
-    b.ln_stat = stat; b.ln_parts = parts; b.ln_rows = M;
-    b.ln_inv_c = 1.0f / (float)C; b.ln_eps = eps;
-    b.ln_wsum = wsum;
-    return gemm_op(b, stream);
+    return op_linear_ln(x, w_prod, b_prod, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, true);
 }
 
 int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream) {

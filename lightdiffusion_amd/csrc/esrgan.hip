@@ -368,33 +368,20 @@ int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h,
     half_t* rrdb_in = ar.halfs(npix * nf);
     half_t* trunk_in = ar.halfs(npix * nf);
 
-    auto small = [&](const char* what, const char* kernel, long long M, int N, int K, auto&& launch) {
-        const double fl = 2.0 * M * N * K;
-        ex.flops += fl;
-        ex.launches += 1;
-        if (dry || ex.status != LD_OK) return;
-        ex.t_begin(KC_MISC, fl, 1, what, M, N, K, 1);
-        launch();
-        ex.note(hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP);
-        ex.t_end(kernel);
-    };
     auto conv = [&](EsrganConvArgs a, int wslot, int bslot) {
         a.wt = pt.ptr(wslot);
         a.bias = pt.ptr(bslot);
         a.n = b;
-        const double fl = 2.0 * a.n * a.h * (double)a.w * a.cout * 9.0 * a.cin;
-        ex.flops += fl;
-        ex.launches += 1;
-        if (dry || ex.status != LD_OK) return;
-        ex.t_begin(KC_CONV3, fl, 1, a.up ? "upconv3" : "dense3", (long long)a.n * a.h * a.w, a.cout, 9 * a.cin, 1);
-        ex.note(esrgan_conv_launch(a, stream));
-        ex.t_end(esrgan_last_kernel_name());
+        ex.launch(KC_CONV3, 2.0 * a.n * a.h * (double)a.w * a.cout * 9.0 * a.cin, a.up ? "upconv3" : "dense3", (long long)a.n * a.h * a.w, a.cout, 9 * a.cin, 1,
+                  esrgan_last_kernel_name, [&] { return esrgan_conv_launch(a, stream); });
     };
+    const auto launched = [] { return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP; };
 
     // conv_first: the trunk's input, and the first RRDB's (dense buffer 0 and the outer-residual copy)
-    small("conv_first", "esrgan_first_kernel", (long long)npix, nf, 27, [&] {
+    ex.launch(KC_MISC, 2.0 * npix * nf * 27, "conv_first", (long long)npix, nf, 27, 1, "esrgan_first_kernel", [&] {
         hipLaunchKernelGGL(esrgan_first_kernel, dim3((unsigned)((npix * 8 + 255) / 256)), dim3(256), 0, stream, x, pt.ptr(e->first_w), pt.ptr(e->first_b), dense[0],
                            ldd, trunk_in, nf, b, h, w);
+        return launched();
     });
     if (!dry && ex.status == LD_OK)
         ex.note(hipMemcpyAsync(rrdb_in, trunk_in, npix * nf * sizeof(half_t), hipMemcpyDeviceToDevice, stream) == hipSuccess ? LD_OK : LD_ERR_HIP);
@@ -443,8 +430,9 @@ int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h,
         conv(a, e->hr_w, e->hr_b);
     }
     const long long opix = (long long)b * H * W;
-    small("conv_last", "esrgan_last_kernel", opix, c.out_nc, 9 * nf, [&] {
+    ex.launch(KC_MISC, 2.0 * opix * c.out_nc * (9 * nf), "conv_last", opix, c.out_nc, 9 * nf, 1, "esrgan_last_kernel", [&] {
         hipLaunchKernelGGL(esrgan_last_kernel, dim3((unsigned)((opix + 255) / 256)), dim3(256), 0, stream, hr, nf, pt.ptr(e->last_w), pt.ptr(e->last_b), out, b, H, W);
+        return launched();
     });
     if (dry_peak != nullptr) *dry_peak = ar.peak;
     if (!dry) {
@@ -483,18 +471,11 @@ void ld_esrgan_destroy(ld_esrgan* e) {
 int ld_esrgan_param_count(const ld_esrgan* e) { return e ? (int)e->pt.slots.size() : 0; }
 
 int ld_esrgan_param_info(const ld_esrgan* e, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (e == nullptr || i < 0 || i >= (int)e->pt.slots.size()) return LD_ERR_ARG;
-    const ParamSlot& s = e->pt.slots[i];
-    if (name) *name = s.name.c_str();
-    if (ndim) *ndim = s.ndim;
-    if (shape)
-        for (int k = 0; k < 4; ++k) shape[k] = s.shape[k];
-    return LD_OK;
+    return abi_param_info(e ? &e->pt : nullptr, i, name, ndim, shape);
 }
 
 int ld_esrgan_load_param(ld_esrgan* e, const char* name, const void* src, int dtype, void* stream) {
-    if (e == nullptr || name == nullptr) return LD_ERR_ARG;
-    return e->pt.load(name, src, dtype, (hipStream_t)stream);
+    return abi_load_param(e ? &e->pt : nullptr, name, src, dtype, stream);
 }
 
 size_t ld_esrgan_plan_bytes(ld_esrgan* e, int b, int h, int w) {
@@ -542,15 +523,11 @@ int ld_esrgan_profile(ld_esrgan* e, const float* x, float* out, int b, int h, in
     e->want_timing = true;
     const int st = ld_esrgan_forward(e, x, out, b, h, w, stream);
     e->want_timing = false;
-    if (st != LD_OK) return st;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
-    e->timing.collect();
-    return LD_OK;
+    return st != LD_OK ? st : abi_profile_collect(e->timing, stream);
 }
 
 int ld_esrgan_profile_launches(const ld_esrgan* e, char* buf, size_t buf_bytes) {
-    if (e == nullptr) return LD_ERR_ARG;
-    return e->timing.format_launches(buf, buf_bytes);
+    return abi_profile_launches(e ? &e->timing : nullptr, buf, buf_bytes);
 }
 
 int ld_esrgan_last_launches(const ld_esrgan* e) { return e ? e->last_launches : 0; }

@@ -9,7 +9,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "kernels.h"
+#include "gemm_params.h"
 
 enum ParamKind { PK_VEC = 0, PK_MAT = 1, PK_CONV3 = 2, PK_GEGLU_W = 3, PK_GEGLU_B = 4 };
 
@@ -176,17 +176,29 @@ struct Timing {
     }
 };
 
+// the name sink of an Exec (Exec::names): kernel names in launch order, joined with ';' (the launchers reset their name on entry: empty = nothing was dispatched)
+inline void note_kernel(std::string* sink, const char* name) {
+    if (sink == nullptr || name == nullptr || *name == '\0') return;
+    if (!sink->empty()) *sink += ';';
+    *sink += name;
+}
+
 struct Exec {
     Timing* timing = nullptr;
     hipStream_t stream = nullptr;
     bool dry = false;
-    Arena* arena = nullptr;
+    Arena* arena = nullptr;          // activations and per-launch temporaries: the executor's reserved workspace, a private one without a base (dry), or a caller's scratch (capi.hip)
     int status = LD_OK;
     int launches = 0;
     double flops = 0.0;
     float* splitk_ws = nullptr;
     size_t splitk_bytes = 0;
     int* sync_ws = nullptr;          // LD_SYNC_INTS zeroed ints for the in-launch reductions (gemm.h GemmParams::sync); null: those kernels are not used
+    std::string* names = nullptr;    // optional: receives the contraction and attention kernels this Exec dispatched (ld_op_last_kernel)
+    // optional: runs in front of a contraction's kernel, once its plan is known, with before_gemm_arg; a status other than LD_OK takes the
+    // launch's place (capi.hip: what the row-resident kernel needs from a caller's scratch)
+    int (*before_gemm)(const GemmParams&, const GemmPlan&, const void* arg, hipStream_t) = nullptr;
+    const void* before_gemm_arg = nullptr;
 
     void note(int st) {
         if (st != LD_OK && status == LD_OK) status = st;
@@ -216,28 +228,53 @@ struct Exec {
         timing->kname.push_back(kernel_name);
     }
 
+    // Every launch of an executor: counts it (nl kernels behind one timing record) and its algorithmic FLOPs, opens the timing record
+    // (class, what, four dimensions), runs fn — which launches and returns an LD_* status — unless this is a dry run or an earlier launch
+    // failed, notes the status and closes the record under the kernel's name.
+    template <class F>
+    void launch(int cls, double fl, const char* what, long long a, long long b, long long d, long long e, const char* kernel_name, F&& fn, int nl = 1) {
+        if (open(cls, fl, nl, what, a, b, d, e)) note(fn());
+        t_end(kernel_name);
+    }
+    // ... under the name one of the launchers' last-kernel functions (gemm_last_kernel_name ...) gives after fn ran
+    template <class F>
+    void launch(int cls, double fl, const char* what, long long a, long long b, long long d, long long e, const char* (*last_kernel)(), F&& fn) {
+        const bool run = open(cls, fl, 1, what, a, b, d, e);
+        if (run) note(fn());
+        t_end(run ? last_kernel() : "");
+    }
+    bool open(int cls, double fl, int nl, const char* what, long long a, long long b, long long d, long long e) {
+        flops += fl;
+        launches += nl;
+        t_begin(cls, fl, nl, what, a, b, d, e);
+        return !dry && status == LD_OK;
+    }
+
     // the scratch every contraction of this executor launches with: set before planning, so that the plan is the launch's
     void with_scratch(GemmParams& p) const {
         if (p.batch != 1) return;
         p.partial = splitk_ws; p.partial_bytes = splitk_bytes; p.sync = sync_ws;
     }
-    // `plan`: gemm_plan of p with this executor's scratch, where the caller already asked for it
-    void gemm(GemmParams p, const GemmPlan* plan = nullptr) {
-        const double fl = 2.0 * p.M * (double)p.N * p.K * p.batch;
-        flops += fl;
+    // the plan gemm() launches p by
+    GemmPlan plan(GemmParams p) const {
         with_scratch(p);
-        launches += 1;
-        if (dry || status != LD_OK) return;
-        t_begin(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, fl, 1, p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"),
-                p.M, p.N, p.K, p.batch);
-        note(plan != nullptr ? gemm_run(p, *plan, stream) : gemm_launch(p, stream));
-        t_end(gemm_last_kernel_name());
+        return gemm_plan(p);
+    }
+    // `planned`: gemm_plan of p with this executor's scratch, where the caller already asked for it
+    void gemm(GemmParams p, const GemmPlan* planned = nullptr) {
+        with_scratch(p);
+        launch(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, 2.0 * p.M * (double)p.N * p.K * p.batch,
+               p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"), p.M, p.N, p.K, p.batch, gemm_last_kernel_name, [&] {
+                   const GemmPlan pl = planned != nullptr ? *planned : gemm_plan(p);
+                   if (before_gemm != nullptr)
+                       if (const int st = before_gemm(p, pl, before_gemm_arg, stream); st != LD_OK) return st;
+                   const int st = gemm_run(p, pl, stream);
+                   note_kernel(names, gemm_last_kernel_name());
+                   return st;
+               });
     }
     // would gemm() run this 3x3 convolution on a kernel that takes a second K segment (gemm.h S1 / S2)?
-    bool conv_takes_skip_segment(GemmParams p) const {
-        with_scratch(p);
-        return gemm_plan(p).takes_skip_segment;
-    }
+    bool conv_takes_skip_segment(const GemmParams& p) const { return plan(p).takes_skip_segment; }
     // `ready` / `ready_P`: partial statistics the producer already wrote (gemm.h gn_part; ready_P pixel chunks per image): the statistics
     // launch is skipped
     void groupnorm(const half_t* x1, int C1, const half_t* x2, int C2, int n, int HW, const half_t* g, const half_t* b, float eps,
@@ -245,11 +282,8 @@ struct Exec {
         const size_t m = arena->mark();
         if (ready_P <= 0) ready = nullptr;
         float* ws = ready != nullptr ? ready : reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n, HW)));
-        const int nl = ready != nullptr ? 1 : 2;
-        launches += nl;
-        t_begin(KC_GNORM, 0.0, nl, "groupnorm", n, HW, C1 + C2, silu);
-        if (!dry && status == LD_OK) note(groupnorm_launch(x1, C1, x2, C2, n, HW, g, b, eps, silu, y, ws, stream, ready != nullptr ? ready_P : 0));
-        t_end(ready != nullptr ? "gn_apply_kernel" : "gn_stats_kernel+gn_apply_kernel");
+        launch(KC_GNORM, 0.0, "groupnorm", n, HW, C1 + C2, silu, ready != nullptr ? "gn_apply_kernel" : "gn_stats_kernel+gn_apply_kernel",
+               [&] { return groupnorm_launch(x1, C1, x2, C2, n, HW, g, b, eps, silu, y, ws, stream, ready != nullptr ? ready_P : 0); }, ready != nullptr ? 1 : 2);
         arena->release(m);
     }
     // GroupNorm(32) + SiLU feeding a 3x3 convolution.  When the convolution runs on the halo-tile kernel the normalisation is fused
@@ -267,12 +301,9 @@ struct Exec {
             float* ws = ready != nullptr ? ready : reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n_img, HW)));
             float* scale = reinterpret_cast<float*>(arena->alloc((size_t)n_img * C * sizeof(float)));
             float* shift = reinterpret_cast<float*>(arena->alloc((size_t)n_img * C * sizeof(float)));
-            const int nl = ready != nullptr ? 1 : 2;
-            launches += nl;
-            t_begin(KC_GNORM, 0.0, nl, "gn_stats", n_img, HW, C, 1);
-            if (!dry && status == LD_OK)
-                note(groupnorm_scale_shift_launch(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, ws, scale, shift, stream, ready != nullptr ? ready_P : 0));
-            t_end(ready != nullptr ? "gn_finalize_kernel" : "gn_stats_kernel+gn_finalize_kernel");
+            launch(KC_GNORM, 0.0, "gn_stats", n_img, HW, C, 1, ready != nullptr ? "gn_finalize_kernel" : "gn_stats_kernel+gn_finalize_kernel", [&] {
+                return groupnorm_scale_shift_launch(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, ws, scale, shift, stream, ready != nullptr ? ready_P : 0);
+            }, ready != nullptr ? 1 : 2);
             p.gn_scale = scale;
             p.gn_shift = shift;
             p.gn_silu = 1;
@@ -288,11 +319,35 @@ struct Exec {
         gemm(p);
     }
     void attention(const AttnParams& p) {
-        const double fl = 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.d;
-        flops += fl;
-        launches += 1;
-        t_begin(KC_ATTN, fl, 1, "attention", (long long)p.B * p.H, p.Lq, p.Lk, p.d);
-        if (!dry && status == LD_OK) note(attention_launch(p, stream));
-        t_end(attention_last_kernel_name());
+        launch(KC_ATTN, 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.d, "attention", (long long)p.B * p.H, p.Lq, p.Lk, p.d, attention_last_kernel_name, [&] {
+            const int st = attention_launch(p, stream);
+            note_kernel(names, attention_last_kernel_name());
+            return st;
+        });
     }
 };
+
+// ---- the tails of the C ABI that the three executors (ld_unet_*, ld_vae_*, ld_esrgan_*) share; `pt` / `t`: the handle's table / timing, null for a null handle
+inline int abi_param_info(const ParamTable* pt, int i, const char** name, int* ndim, int64_t shape[4]) {
+    if (pt == nullptr || i < 0 || i >= (int)pt->slots.size()) return LD_ERR_ARG;
+    const ParamSlot& s = pt->slots[i];
+    if (name) *name = s.name.c_str();
+    if (ndim) *ndim = s.ndim;
+    if (shape)
+        for (int k = 0; k < 4; ++k) shape[k] = s.shape[k];
+    return LD_OK;
+}
+inline int abi_load_param(ParamTable* pt, const char* name, const void* src, int dtype, void* stream) {
+    if (pt == nullptr || name == nullptr) return LD_ERR_ARG;
+    return pt->load(name, src, dtype, (hipStream_t)stream);
+}
+inline int abi_profile_launches(const Timing* t, char* buf, size_t buf_bytes) {
+    if (t == nullptr) return LD_ERR_ARG;
+    return t->format_launches(buf, buf_bytes);
+}
+// behind a profiled run that returned LD_OK: wait for its launches, then read their events
+inline int abi_profile_collect(Timing& t, void* stream) {
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
+    t.collect();
+    return LD_OK;
+}

@@ -297,57 +297,32 @@ struct Run {
     int na() const { return n_alloc > 0 ? n_alloc : n; }
     // first half of a [2 * half_bytes] tensor -> its second half (a memcpy node of the step's hipGraph; layouts other than SD1.5's, whose hand-over is one dup_halves launch)
     void dup(void* base, size_t half_bytes) {
-        ex.launches += 1;
-        ex.t_begin(KC_MISC, 0.0, 1, "dup", (long long)half_bytes, 0, 0, 1);
-        if (!ex.dry && ex.status == LD_OK &&
-            hipMemcpyAsync(static_cast<char*>(base) + half_bytes, base, half_bytes, hipMemcpyDeviceToDevice, ex.stream) != hipSuccess)
-            ex.note(LD_ERR_HIP);
-        ex.t_end("hipMemcpyAsync(pair)");
+        ex.launch(KC_MISC, 0.0, "dup", (long long)half_bytes, 0, 0, 1, "hipMemcpyAsync(pair)", [&] {
+            return hipMemcpyAsync(static_cast<char*>(base) + half_bytes, base, half_bytes, hipMemcpyDeviceToDevice, ex.stream) == hipSuccess ? LD_OK : LD_ERR_HIP;
+        });
     }
 
-    // GroupNorm partial statistics of a contraction's output (gemm.h gn_part): where the launch can emit them (its split-K second pass, or
-    // the row-resident kernel) *done receives the chunk count and the GroupNorm that follows skips its statistics launch
-    void want_stats(GemmParams& p, float* buf, int HW, int* done) {
-        p.gn_part = buf;
-        p.gn_P = gn_num_chunks(n, HW);
-        p.gn_HW = HW;
-        p.gn_ppb = (HW + p.gn_P - 1) / p.gn_P;
-        p.gn_part_done = done;
-    }
-
-    half_t* conv3(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int wslot, int bslot,
-                  int cout, const half_t* rowvec, int ldrv, const half_t* R, half_t* out, int* Ho_, int* Wo_, int ksize = 3, float* stats = nullptr,
-                  int* stats_done = nullptr, const half_t* wup = nullptr) {
-        const int Ho = ksize == 3 ? (Hv - 1) / stride + 1 : Hv, Wo = ksize == 3 ? (Wv - 1) / stride + 1 : Wv;
-        GemmParams p;
-        p.conv = 1;
-        p.ksize = ksize;
-        p.A = x1; p.A2 = x2; p.C1 = C1; p.C2 = C2;
-        p.Hs = Hs; p.Ws = Ws; p.Hv = Hv; p.Wv = Wv; p.Ho = Ho; p.Wo = Wo; p.stride = stride;
-        p.W = P(wslot); p.ldw = ksize * ksize * (C1 + C2);
+    // a convolution of this run's n images on resident weights, with the row-resident kernel's copy of them where there is one
+    GemmParams conv_of(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int ksize, int wslot, int bslot,
+                       int cout, half_t* out) const {
+        GemmParams p = conv_params(x1, C1, x2, C2, n, Hs, Ws, Hv, Wv, stride, ksize, P(wslot), P(bslot), cout, out);
         p.W8 = ksize == 3 ? u->w8(wslot) : nullptr;
+        return p;
+    }
+
+    // stats / stats_done: GroupNorm partial statistics of the output, where the launch writes them (want_gn_partials)
+    half_t* conv3(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int wslot, int bslot,
+                  int cout, half_t* out, int ksize = 3, float* stats = nullptr, int* stats_done = nullptr, const half_t* wup = nullptr) {
+        GemmParams p = conv_of(x1, C1, x2, C2, Hs, Ws, Hv, Wv, stride, ksize, wslot, bslot, cout, out);
         p.Wup = wup;
-        p.M = n * Ho * Wo; p.N = cout; p.K = ksize * ksize * (C1 + C2);
-        p.bias_n = P(bslot);
-        p.rowvec = rowvec; p.rows_per_vec = Ho * Wo; p.ldrv = ldrv;
-        p.R = R; p.ldr = cout;
-        p.C = out; p.ldc = cout;
-        if (stats != nullptr) want_stats(p, stats, Ho * Wo, stats_done);
+        if (stats != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, stats, stats_done);
         ex.gemm(p);
-        if (Ho_) *Ho_ = Ho;
-        if (Wo_) *Wo_ = Wo;
         return out;
     }
 
     void linear(const half_t* x, int lda, int wslot, int bslot, const half_t* R, half_t* y, int M, int N, int K, int act = 0, int bn = 0) {
-        GemmParams p;
-        p.A = x; p.lda = lda;
-        p.W = P(wslot); p.ldw = K;
-        p.M = M; p.N = N; p.K = K;
-        p.bias_n = bslot >= 0 ? P(bslot) : nullptr;
-        p.R = R; p.ldr = (act == 2 ? N / 2 : N);
-        p.act = act; p.bn = bn;
-        p.C = y; p.ldc = (act == 2 ? N / 2 : N);
+        GemmParams p = linear_params(x, lda, P(wslot), bslot >= 0 ? P(bslot) : nullptr, M, N, K, y, act, bn);
+        p.R = R;
         ex.gemm(p);
     }
 
@@ -364,20 +339,8 @@ struct Run {
         // in_layers: GroupNorm + SiLU + conv3x3 (+ the time-embedding row vector); out_layers: GroupNorm + SiLU + conv3x3 (+ skip).
         // Each GroupNorm is fused into its convolution's A operand where that convolution runs on the halo-tile kernel
         // (Exec::gn_silu_conv); g1 / g2 are only written on the two-pass route.
-        auto conv_params = [&](const half_t* a1, int c1, const half_t* a2, int c2, int wslot, int bslot, const half_t* rowvec, int ldrv, const half_t* R,
-                               half_t* dst) {
-            GemmParams p;
-            p.conv = 1; p.ksize = 3;
-            p.A = a1; p.A2 = a2; p.C1 = c1; p.C2 = c2;
-            p.Hs = H; p.Ws = W; p.Hv = H; p.Wv = W; p.Ho = H; p.Wo = W; p.stride = 1;
-            p.W = P(wslot); p.ldw = 9 * (c1 + c2);
-            p.W8 = u->w8(wslot);
-            p.M = n * H * W; p.N = r.cout; p.K = 9 * (c1 + c2);
-            p.bias_n = P(bslot);
-            p.rowvec = rowvec; p.rows_per_vec = H * W; p.ldrv = ldrv;
-            p.R = R; p.ldr = r.cout;
-            p.C = dst; p.ldc = r.cout;
-            return p;
+        auto conv = [&](const half_t* a1, int c1, const half_t* a2, int c2, int wslot, int bslot, half_t* dst) {
+            return conv_of(a1, c1, a2, c2, H, W, H, W, 1, 3, wslot, bslot, r.cout, dst);
         };
         half_t* g1 = ar.halfs(M * r.cin);
         half_t* h1 = ar.halfs(M * r.cout);
@@ -389,10 +352,10 @@ struct Run {
         bool fold_skip = false;
         if (r.sk_w >= 0) {
             // (asked of out_layers' convolution as it stands before the skip joins it, as a residual or as a K segment)
-            fold_skip = u->fold_base != nullptr && ex.conv_takes_skip_segment(conv_params(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, nullptr, 0, nullptr, out));
+            fold_skip = u->fold_base != nullptr && ex.conv_takes_skip_segment(conv(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, out));
             half_t* sk = (!fold_skip || ex.dry) ? ar.halfs(M * r.cout) : nullptr;   // (a planning run sizes for either route: ld_unet_reserve plans before the split-K scratch exists)
             if (!fold_skip) {
-                conv3(x1, C1, x2, C2, H, W, H, W, 1, r.sk_w, r.sk_b, r.cout, nullptr, 0, nullptr, sk, nullptr, nullptr, 1);
+                conv3(x1, C1, x2, C2, H, W, H, W, 1, r.sk_w, r.sk_b, r.cout, sk, 1);
                 skip = sk;
             }
         }
@@ -400,23 +363,20 @@ struct Run {
         float* gnp = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(na(), H * W)));
         int gnp_done = 0;
         {
-            GemmParams c1 = conv_params(x1, C1, x2, C2, r.c1_w, r.c1_b, emb_all + r.emb_off, u->emb_total, nullptr, h1);
-            want_stats(c1, gnp, H * W, &gnp_done);
+            GemmParams c1 = conv(x1, C1, x2, C2, r.c1_w, r.c1_b, h1);
+            c1.rowvec = emb_all + r.emb_off; c1.ldrv = u->emb_total;
+            want_gn_partials(c1, n, H * W, gnp, &gnp_done);
             ex.gn_silu_conv(c1, n, H * W, P(r.gn1_g), P(r.gn1_b), 1e-5f, g1, in_stats, in_P);
         }
         half_t* g2 = g1;   // g1 is dead once conv1 has consumed it (stream order); reuse when it is large enough
         if (r.cout > r.cin) g2 = ar.halfs(M * r.cout);
         {
-            GemmParams c2 = conv_params(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, nullptr, 0, skip, out);
-            if (fold_skip) {
-                c2.S1 = x1; c2.SC1 = C1; c2.S2 = x2; c2.SC2 = C2;
-                c2.W = reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_w);
-                c2.K = 9 * r.cout + r.cin; c2.ldw = c2.K;
-                c2.bias_n = reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_b);
-                c2.R = nullptr;
-                c2.W8 = nullptr;
-            }
-            want_stats(c2, gno, H * W, &gno_done);
+            GemmParams c2 = conv(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, out);
+            if (fold_skip)
+                add_skip_segment(c2, x1, C1, x2, C2, reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_w), reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_b));
+            else
+                c2.R = skip;
+            want_gn_partials(c2, n, H * W, gno, &gno_done);
             ex.gn_silu_conv(c2, n, H * W, P(r.gn2_g), P(r.gn2_b), 1e-5f, g2, gnp_done ? gnp : nullptr, gnp_done);
         }
         ar.release(mk);
@@ -445,36 +405,23 @@ struct Run {
         float* stat = reinterpret_cast<float*>(ar.alloc((size_t)((C + 63) / 64) * Ma * 2 * sizeof(float)));
         int parts = 0;
         char* fb = u->fold_base;
-        auto producer = [&](const half_t* x_, int lda, int wslot, int bslot, const half_t* R, int K) {   // t = x_ W^T + b (+ R), with row stats
-            GemmParams p;
-            p.A = x_; p.lda = lda;
-            p.W = P(wslot); p.ldw = K;
-            p.M = M; p.N = C; p.K = K;
-            p.bias_n = P(bslot);
-            p.R = R; p.ldr = C;
-            p.C = t; p.ldc = C;
-            p.stat_out = stat;
-            p.stat_parts_out = &parts;
+        auto producer = [&](const half_t* x_, int wslot, int bslot, const half_t* R) {   // t = x_ W^T + b (+ R), with row stats
+            GemmParams p = linear_params(x_, C, P(wslot), P(bslot), M, C, C, t);
+            p.R = R;
+            ln_producer(p, stat, &parts);
             ex.gemm(p);
         };
-        auto ln_args = [&](GemmParams& p, size_t wsum_off) {
-            p.ln_stat = stat; p.ln_parts = parts; p.ln_rows = M;
-            p.ln_inv_c = 1.0f / (float)C; p.ln_eps = 1e-5f;
-            p.ln_wsum = reinterpret_cast<const float*>(fb + wsum_off);
+        // out = LN(t) W^T + b on the folded weights / bias / row sums at these offsets of the fold buffer
+        auto consumer = [&](size_t w_off, size_t b_off, size_t wsum_off, int N, half_t* dst, int act = 0, int bn = 0) {
+            GemmParams p = linear_params(t, C, reinterpret_cast<const half_t*>(fb + w_off), reinterpret_cast<const half_t*>(fb + b_off), M, N, C, dst, act, bn);
+            ln_consumer(p, stat, parts, M, C, 1e-5f, reinterpret_cast<const float*>(fb + wsum_off));
+            ex.gemm(p);
         };
-        producer(g, C, s.pin_w, s.pin_b, nullptr, C);
+        producer(g, s.pin_w, s.pin_b, nullptr);
         // ---- self attention: x += to_out(attn(LN1(x)))
-        {   // [q | k | v] = LN1(t) [Wq ; Wk ; Wv]^T — one launch; the attention kernel reads V row-major (transposing LDS reads), so there
-            // is no V^T projection
-            GemmParams p;
-            p.A = t; p.lda = C;
-            p.W = reinterpret_cast<const half_t*>(fb + s.f_qk_w); p.ldw = C;
-            p.M = M; p.N = 3 * C; p.K = C;
-            p.C = qkv; p.ldc = 3 * C;
-            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_qk_b);
-            ln_args(p, s.f_qk_s);
-            ex.gemm(p);
-        }
+        // [q | k | v] = LN1(t) [Wq ; Wk ; Wv]^T — one launch; the attention kernel reads V row-major (transposing LDS reads), so there
+        // is no V^T projection
+        consumer(s.f_qk_w, s.f_qk_b, s.f_qk_s, 3 * C, qkv);
         {
             AttnParams a;
             a.Q = qkv; a.ldq = 3 * C; a.sQ = (long long)L * 3 * C;
@@ -491,29 +438,17 @@ struct Run {
         // everything else runs on all n_alloc samples (the statistics of the first half are not needed again: the out-projection of attn2
         // rewrites them for all rows).
         const bool split_here = pair_pending;
-        producer(ao, C, s.o1_w, s.o1_b, t, C);
+        producer(ao, s.o1_w, s.o1_b, t);
         // ---- cross attention against the hoisted context K / V^T
         half_t* q2 = qkv;   // reuse
-        {
-            GemmParams p;
-            p.A = t; p.lda = C;
-            p.W = reinterpret_cast<const half_t*>(fb + s.f_q2_w); p.ldw = C;
-            p.M = M; p.N = C; p.K = C;
-            p.C = q2; p.ldc = C;
-            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_q2_b);
-            ln_args(p, s.f_q2_s);
-            ex.gemm(p);
-        }
+        consumer(s.f_q2_w, s.f_q2_b, s.f_q2_s, C, q2);
         if (split_here) {
             const size_t hb = (size_t)M * C * sizeof(half_t);
             DupArgs da;
             da.count = 3;
             da.base[0] = reinterpret_cast<char*>(t); da.base[1] = reinterpret_cast<char*>(q2); da.base[2] = reinterpret_cast<char*>(const_cast<half_t*>(x));
             da.bytes[0] = da.bytes[1] = da.bytes[2] = hb;
-            ex.launches += 1;
-            ex.t_begin(KC_MISC, 0.0, 1, "dup3", (long long)hb, 0, 0, 1);
-            if (!ex.dry && ex.status == LD_OK) ex.note(dup_halves_launch(da, ex.stream));
-            ex.t_end("dup_halves_kernel");
+            ex.launch(KC_MISC, 0.0, "dup3", (long long)hb, 0, 0, 1, "dup_halves_kernel", [&] { return dup_halves_launch(da, ex.stream); });
             pair_pending = false;
             n = n_alloc;
             M = n * L;
@@ -529,32 +464,16 @@ struct Run {
             a.scale = 1.0f / sqrtf((float)d);
             ex.attention(a);
         }
-        producer(ao, C, s.o2_w, s.o2_b, t, C);
+        producer(ao, s.o2_w, s.o2_b, t);
         // ---- GEGLU feed-forward: x = ff2(a * gelu(gate)) + x
         ff = ar.halfs(Ma * 4 * C);
-        {
-            GemmParams p;
-            p.A = t; p.lda = C;
-            p.W = reinterpret_cast<const half_t*>(fb + s.f_ff1_w); p.ldw = C;
-            p.M = M; p.N = 8 * C; p.K = C;
-            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_ff1_b);
-            p.act = 2; p.bn = s.bn;
-            p.C = ff; p.ldc = 4 * C; p.ldr = 4 * C;
-            ln_args(p, s.f_ff1_s);
-            ex.gemm(p);
-        }
+        consumer(s.f_ff1_w, s.f_ff1_b, s.f_ff1_s, 8 * C, ff, 2, s.bn);
         {
             // out = x + proj_out(t + ff2(ff)) as one contraction over [ff | t] (K = 5C) against the folded [Wpo W2 | Wpo] (misc.hip)
-            GemmParams p;
-            p.conv = 1; p.ksize = 1;
-            p.A = ff; p.A2 = t; p.C1 = 4 * C; p.C2 = C;
-            p.Hs = p.Hv = p.Ho = H; p.Ws = p.Wv = p.Wo = W; p.stride = 1;
-            p.W = reinterpret_cast<const half_t*>(fb + s.f_mo_w); p.ldw = 5 * C;
-            p.M = M; p.N = C; p.K = 5 * C;
-            p.bias_n = reinterpret_cast<const half_t*>(fb + s.f_mo_b);
-            p.R = x; p.ldr = C;
-            p.C = out; p.ldc = C;
-            want_stats(p, gno, L, &gno_done);
+            GemmParams p = conv_params(ff, 4 * C, t, C, n, H, W, H, W, 1, 1, reinterpret_cast<const half_t*>(fb + s.f_mo_w),
+                                       reinterpret_cast<const half_t*>(fb + s.f_mo_b), C, out);
+            p.R = x;
+            want_gn_partials(p, n, L, gno, &gno_done);
             ex.gemm(p);
         }
         ar.release(mk);
@@ -649,10 +568,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
 
     // timestep embedding -> time_embed MLP -> all ResBlock emb_layers at once (every consumer applies SiLU first)
     half_t* temb = ar.halfs((size_t)n * mc);
-    ex.launches += 1;
-    ex.t_begin(KC_MISC, 0.0, 1);
-    if (!dry) ex.note(timestep_embed_launch(sigma, u->log_sigmas, 1000, n, mc, temb, nullptr, stream, in_mod));
-    ex.t_end("timestep_embed_kernel");
+    ex.launch(KC_MISC, 0.0, "", 0, 0, 0, 0, "timestep_embed_kernel", [&] { return timestep_embed_launch(sigma, u->log_sigmas, 1000, n, mc, temb, nullptr, stream, in_mod); });
     half_t* e1 = ar.halfs((size_t)n * ted);
     R.linear(temb, mc, u->te0_w, u->te0_b, nullptr, e1, n, ted, mc, 1);
     half_t* semb = ar.halfs((size_t)n * ted);
@@ -682,7 +598,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                     half_t* o = ar.halfs((size_t)n * Ho * Wo * cw.cout);
                     float* gno = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(n, Ho * Wo)));
                     int gno_done = 0;
-                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 2, cw.w, cw.b, cw.cout, nullptr, 0, nullptr, o, nullptr, nullptr, 3, gno, &gno_done);
+                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 2, cw.w, cw.b, cw.cout, o, 3, gno, &gno_done);
                     f = {o, cw.cout, Ho, Wo, gno_done ? gno : nullptr, gno_done};
                     break;
                 }
@@ -693,7 +609,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                     // (the folded weights are an offer: gemm_plan takes them for an exact 2x resize above the row-resident kernel's batch.  The launch is
                     // counted as the 3x3 convolution it implements — last_flops is algorithmic work — and executes 4/9 of it)
                     const half_t* wup = (u->fold_base != nullptr && cw.f_up >= 0) ? reinterpret_cast<const half_t*>(u->fold_base + cw.f_up) : nullptr;
-                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, nullptr, 0, nullptr, o, nullptr, nullptr, 3, nullptr, nullptr, wup);
+                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, o, 3, nullptr, nullptr, wup);
                     f = {o, cw.cout, Hv, Wv};
                     break;
                 }
@@ -713,11 +629,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         a.x = x; a.scale_sigma = sigma; a.w = u->pt.ptr(cw.w); a.b = u->pt.ptr(cw.b); a.y = o;
         a.N = R.n; a.Cin = c.in_channels; a.H = h; a.W = w; a.Cout = mc;
         if (R.pair_pending) a.dup_off = (long long)R.n * h * w * mc;   // a skip connection: read by the last output block on all n samples
-        ex.launches += 1;
-        ex.flops += 2.0 * R.n * h * w * mc * 9.0 * c.in_channels;
-        ex.t_begin(KC_MISC, 2.0 * R.n * h * w * mc * 9.0 * c.in_channels, 1);
-        if (!dry) ex.note(small_conv_in_launch(a, stream));
-        ex.t_end("small_conv_in_kernel");
+        ex.launch(KC_MISC, 2.0 * R.n * h * w * mc * 9.0 * c.in_channels, "", 0, 0, 0, 0, "small_conv_in_kernel", [&] { return small_conv_in_launch(a, stream); });
         f = {o, mc, h, w};
         hs.push_back(f);
     }
@@ -752,11 +664,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         a.N = n; a.H = f.H; a.W = f.W; a.Cin = f.C; a.Cout = c.out_channels;
         a.mode = eps_only ? 2 : 0;
         a.x_in = x; a.sigma = sigma; a.out = out; a.in_mod = in_mod;
-        ex.launches += 1;
-        ex.flops += 2.0 * n * f.H * f.W * f.C * 9.0 * c.out_channels;
-        ex.t_begin(KC_MISC, 2.0 * n * f.H * f.W * f.C * 9.0 * c.out_channels, 1);
-        if (!dry) ex.note(small_conv_out_launch(a, stream));
-        ex.t_end("small_conv_out_kernel");
+        ex.launch(KC_MISC, 2.0 * n * f.H * f.W * f.C * 9.0 * c.out_channels, "", 0, 0, 0, 0, "small_conv_out_kernel", [&] { return small_conv_out_launch(a, stream); });
     }
     u->last_launches = ex.launches;
     u->last_flops = ex.flops;
@@ -846,13 +754,7 @@ void ld_unet_destroy(ld_unet* u) {
 int ld_unet_param_count(const ld_unet* u) { return u ? (int)u->pt.slots.size() : 0; }
 
 int ld_unet_param_info(const ld_unet* u, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (u == nullptr || i < 0 || i >= (int)u->pt.slots.size()) return LD_ERR_ARG;
-    const ParamSlot& s = u->pt.slots[i];
-    if (name) *name = s.name.c_str();
-    if (ndim) *ndim = s.ndim;
-    if (shape)
-        for (int k = 0; k < 4; ++k) shape[k] = s.shape[k];
-    return LD_OK;
+    return abi_param_info(u ? &u->pt : nullptr, i, name, ndim, shape);
 }
 
 int ld_unet_load_param(ld_unet* u, const char* name, const void* src, int dtype, void* stream) {
@@ -863,7 +765,7 @@ int ld_unet_load_param(ld_unet* u, const char* name, const void* src, int dtype,
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
         u->drop_backup(it->second);
     }
-    return u->pt.load(name, src, dtype, (hipStream_t)stream);
+    return abi_load_param(&u->pt, name, src, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- LoRA patches (load-class calls)
@@ -1014,18 +916,11 @@ int ld_unet_set_context(ld_unet* u, const void* ctx, int dtype, int n, int token
     if (st != LD_OK) return st;
     for (size_t i = 0; i < u->st.size(); ++i) {
         const StW& s = u->st[i];
-        GemmParams k;   // K = ctx · Wk^T : [n*Tp][C]
-        k.A = u->ctx16; k.lda = D;
-        k.W = u->pt.ptr(s.k2_w); k.ldw = D;
-        k.M = n * Tp; k.N = s.c; k.K = D;
-        k.C = u->ctx_k[i]; k.ldc = s.c;
-        st = gemm_launch(k, stream);
+        // K = ctx · Wk^T : [n*Tp][C]
+        st = gemm_launch(linear_params(u->ctx16, D, u->pt.ptr(s.k2_w), nullptr, n * Tp, s.c, D, u->ctx_k[i]), stream);
         if (st != LD_OK) return st;
-        GemmParams v;   // V^T[b] = Wv · ctx_b^T : [C][Tp]
-        v.A = u->pt.ptr(s.v2_w); v.lda = D; v.sA = 0;
-        v.W = u->ctx16; v.ldw = D; v.sW = (long long)Tp * D;
-        v.M = s.c; v.N = Tp; v.K = D; v.batch = n;
-        v.C = u->ctx_vt[i]; v.ldc = Tp; v.sC = (long long)s.c * Tp;
+        GemmParams v = linear_params(u->pt.ptr(s.v2_w), D, u->ctx16, nullptr, s.c, Tp, D, u->ctx_vt[i]);   // V^T[b] = Wv · ctx_b^T : [C][Tp]
+        v.batch = n; v.sW = (long long)Tp * D; v.sC = (long long)s.c * Tp;
         st = gemm_launch(v, stream);
         if (st != LD_OK) return st;
     }
@@ -1082,9 +977,8 @@ static int profile_any(ld_unet* u, const float* x, const float* sigma, float* ou
     u->want_timing = true;
     int st = forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair);
     u->want_timing = false;
+    if (st == LD_OK) st = abi_profile_collect(u->timing, stream);
     if (st != LD_OK) return st;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
-    u->timing.collect();
     for (int i = 0; i < KC_COUNT; ++i) {
         ms[i] = u->timing.ms[i];
         flops[i] = u->timing.flops[i];
@@ -1106,8 +1000,7 @@ int ld_unet_profile_kernels(const ld_unet* u, char* buf, size_t buf_bytes) {
 }
 
 int ld_unet_profile_launches(const ld_unet* u, char* buf, size_t buf_bytes) {
-    if (u == nullptr) return LD_ERR_ARG;
-    return u->timing.format_launches(buf, buf_bytes);
+    return abi_profile_launches(u ? &u->timing : nullptr, buf, buf_bytes);
 }
 
 int ld_unet_last_launches(const ld_unet* u) { return u ? u->last_launches : 0; }

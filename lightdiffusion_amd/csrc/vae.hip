@@ -174,25 +174,8 @@ struct VRun {
         ex.groupnorm(x, C, nullptr, 0, n, HW, P(gslot), P(bslot), 1e-6f, silu, y, ready ? st_buf : nullptr, ready ? st_P : 0);
     }
 
-    void conv(const half_t* x, int cin, int Hs, int Ws, int Hv, int Wv, int ksize, int wslot, int bslot, int cout, const half_t* R, half_t* out,
-              int stride = 1, int pad = -1, int Ho = 0, int Wo = 0, float* stats = nullptr) {
-        GemmParams p;
-        p.conv = 1;
-        p.ksize = ksize;
-        p.pad = pad;
-        p.A = x; p.C1 = cin;
-        p.Hs = Hs; p.Ws = Ws; p.Hv = Hv; p.Wv = Wv; p.Ho = Ho ? Ho : Hv; p.Wo = Wo ? Wo : Wv; p.stride = stride;
-        p.W = P(wslot); p.ldw = ksize * ksize * cin;
-        p.M = n * p.Ho * p.Wo; p.N = cout; p.K = ksize * ksize * cin;
-        p.bias_n = P(bslot);
-        p.R = R; p.ldr = cout;
-        p.C = out; p.ldc = cout;
-        int done = 0;
-        if (stats != nullptr) {
-            p.gn_part = stats;
-            p.gn_part_done = &done;
-        }
-        ex.gemm(p);
+    // after a convolution wrote `out`: the statistics it left (done chunks per image), or none
+    void wrote(half_t* out, float* stats, int done) {
         if (stats != nullptr) {
             st_of = out;
             st_buf = stats;
@@ -202,36 +185,29 @@ struct VRun {
         }
     }
 
+    // (a stride above 1 comes with its Ho, Wo: the encoder's downsampling)
+    void conv(const half_t* x, int cin, int Hs, int Ws, int Hv, int Wv, int ksize, int wslot, int bslot, int cout, const half_t* R, half_t* out,
+              int stride = 1, int pad = -1, int Ho = 0, int Wo = 0, float* stats = nullptr) {
+        GemmParams p = conv_params(x, cin, nullptr, 0, n, Hs, Ws, Hv, Wv, stride, ksize, P(wslot), P(bslot), cout, out, pad, Ho, Wo);
+        p.R = R;
+        int done = 0;
+        if (stats != nullptr) want_gn_tile_partials(p, stats, &done);
+        ex.gemm(p);
+        wrote(out, stats, done);
+    }
+
     // GroupNorm (eps 1e-6) + swish + 3x3 convolution (norm1 -> conv1, norm2 -> conv2 of a ResnetBlock): where the convolution's output is one
     // halo tile wide (N = 256 at 256-pixel rows, N = 128 at 512-pixel rows) the normalisation is applied inside its halo loader and only the
     // statistics are finalised here (Exec::gn_silu_conv); otherwise the two-pass GroupNorm into `g`, then the convolution, as before.
     void gn_conv(const half_t* x, int cin, int H, int W, int gslot, int bslot, half_t* g, int wslot, int cbslot, int cout, const half_t* R, half_t* out,
                  float* stats) {
-        GemmParams p;
-        p.conv = 1;
-        p.ksize = 3;
-        p.pad = -1;
-        p.A = x; p.C1 = cin;
-        p.Hs = p.Hv = p.Ho = H; p.Ws = p.Wv = p.Wo = W; p.stride = 1;
-        p.W = P(wslot); p.ldw = 9 * cin;
-        p.M = n * H * W; p.N = cout; p.K = 9 * cin;
-        p.bias_n = P(cbslot);
-        p.R = R; p.ldr = cout;
-        p.C = out; p.ldc = cout;
+        GemmParams p = conv_params(x, cin, nullptr, 0, n, H, W, H, W, 1, 3, P(wslot), P(cbslot), cout, out);
+        p.R = R;
         int done = 0;
-        if (stats != nullptr) {
-            p.gn_part = stats;
-            p.gn_part_done = &done;
-        }
+        if (stats != nullptr) want_gn_tile_partials(p, stats, &done);
         const bool ready = x == st_of && st_P > 0;
         ex.gn_silu_conv(p, n, H * W, P(gslot), P(bslot), 1e-6f, g, ready ? st_buf : nullptr, ready ? st_P : 0);
-        if (stats != nullptr) {
-            st_of = out;
-            st_buf = stats;
-            st_P = done;
-        } else if (out == st_of) {
-            st_of = nullptr;
-        }
+        wrote(out, stats, done);
     }
 
     // ResnetBlock.forward, LD.py:3560-3576 (GroupNorm eps 1e-6, swish)
@@ -272,13 +248,7 @@ struct VRun {
             // round 6: [q | k | v] as ONE projection, then flash attention over the single head (flash_attn512_kernel: V row-major, the
             // score matrix never exists — it was 2.1 GB of fp16 at 1024^2, b = 4 — and the V^T GEMM, the softmax pass and a GEMM are gone)
             half_t* qkv = ar.halfs(M * 3 * C);
-            {
-                GemmParams p;
-                p.A = g; p.lda = C; p.W = P(aw.q_w); p.ldw = C;
-                p.M = (int)M; p.N = 3 * C; p.K = C; p.bias_n = P(aw.q_b);
-                p.C = qkv; p.ldc = 3 * C;
-                ex.gemm(p);
-            }
+            ex.gemm(linear_params(g, C, P(aw.q_w), P(aw.q_b), (int)M, 3 * C, C, qkv));
             AttnParams a;
             a.Q = qkv; a.K = qkv + C; a.V = qkv + 2 * C;
             a.ldq = a.ldk = a.ldv = 3 * C;
@@ -290,55 +260,34 @@ struct VRun {
         } else {
             // any other width: three GEMMs around a row softmax over the materialised L x L scores
             half_t* qk = ar.halfs(M * 2 * C);
-            {
-                GemmParams p;
-                p.A = g; p.lda = C; p.W = P(aw.q_w); p.ldw = C;
-                p.M = (int)M; p.N = 2 * C; p.K = C; p.bias_n = P(aw.q_b);
-                p.C = qk; p.ldc = 2 * C;
-                ex.gemm(p);
-            }
+            ex.gemm(linear_params(g, C, P(aw.q_w), P(aw.q_b), (int)M, 2 * C, C, qk));
             // key axis padded to a multiple of 8 (16-byte rows): pad keys get zero scores, zero probabilities and a finite V^T
             // column (bias only), so any latent size works (63x63, 65x65 ...), as in the reference
             const int Lp = (L + 7) & ~7;
             half_t* vt = ar.halfs((size_t)n * C * Lp);
             {   // V^T[b] = Wv · g_b^T + bv (bias along rows)
-                GemmParams p;
-                p.A = P(aw.v_w); p.lda = C; p.sA = 0;
-                p.W = g; p.ldw = C; p.sW = (long long)L * C;
-                p.M = C; p.N = Lp; p.n_valid = L; p.K = C; p.batch = n;
-                p.bias_m = P(aw.v_b);
-                p.C = vt; p.ldc = Lp; p.sC = (long long)C * Lp;
+                GemmParams p = linear_params(P(aw.v_w), C, g, nullptr, C, Lp, C, vt);
+                p.n_valid = L; p.bias_m = P(aw.v_b);
+                p.batch = n; p.sW = (long long)L * C; p.sC = (long long)C * Lp;
                 ex.gemm(p);
             }
             half_t* s = ar.halfs((size_t)n * L * Lp);
             {   // S_b = Q_b K_b^T / sqrt(C)
-                GemmParams p;
-                p.A = qk; p.lda = 2 * C; p.sA = (long long)L * 2 * C;
-                p.W = qk + C; p.ldw = 2 * C; p.sW = (long long)L * 2 * C;
-                p.M = L; p.N = Lp; p.n_valid = L; p.K = C; p.batch = n;
-                p.alpha = 1.0f / sqrtf((float)C);
-                p.C = s; p.ldc = Lp; p.sC = (long long)L * Lp;
+                GemmParams p = linear_params(qk, 2 * C, qk + C, nullptr, L, Lp, C, s, 0, 0, /*ldw=*/2 * C);
+                p.n_valid = L; p.alpha = 1.0f / sqrtf((float)C);
+                p.batch = n; p.sA = p.sW = (long long)L * 2 * C; p.sC = (long long)L * Lp;
                 ex.gemm(p);
             }
-            ex.launches += 1;
-            ex.t_begin(KC_MISC, 0.0, 1, "softmax", (long long)n * L, Lp, 0, 1);
-            if (!ex.dry && ex.status == LD_OK) ex.note(softmax_rows_launch(s, n * L, Lp, Lp, ex.stream, L));
-            ex.t_end("softmax_rows_kernel");
+            ex.launch(KC_MISC, 0.0, "softmax", (long long)n * L, Lp, 0, 1, "softmax_rows_kernel", [&] { return softmax_rows_launch(s, n * L, Lp, Lp, ex.stream, L); });
             {   // O_b = P_b V_b  (W operand = V^T [C][Lp]; the pad keys carry zero probability)
-                GemmParams p;
-                p.A = s; p.lda = Lp; p.sA = (long long)L * Lp;
-                p.W = vt; p.ldw = Lp; p.sW = (long long)C * Lp;
-                p.M = L; p.N = C; p.K = Lp; p.batch = n;
-                p.C = o; p.ldc = C; p.sC = (long long)L * C;
+                GemmParams p = linear_params(s, Lp, vt, nullptr, L, C, Lp, o);
+                p.batch = n; p.sA = (long long)L * Lp; p.sW = (long long)C * Lp; p.sC = (long long)L * C;
                 ex.gemm(p);
             }
         }
         {
-            GemmParams p;
-            p.A = o; p.lda = C; p.W = P(aw.o_w); p.ldw = C;
-            p.M = (int)M; p.N = C; p.K = C; p.bias_n = P(aw.o_b);
-            p.R = x; p.ldr = C;
-            p.C = out; p.ldc = C;
+            GemmParams p = linear_params(o, C, P(aw.o_w), P(aw.o_b), (int)M, C, C, out);
+            p.R = x;
             ex.gemm(p);
         }
         ar.release(mk);
@@ -372,11 +321,8 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
         a.x = z; a.pre_w = v->pt.ptr(v->pq_w); a.pre_b = v->pt.ptr(v->pq_b);
         a.w = v->pt.ptr(v->cin_w); a.b = v->pt.ptr(v->cin_b); a.y = f;
         a.N = b; a.Cin = c.z_channels; a.H = H; a.W = W; a.Cout = C;
-        ex.launches += 1;
-        ex.flops += 2.0 * b * H * W * C * 9.0 * c.z_channels;
-        ex.t_begin(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.z_channels, 1, "conv_in", (long long)b * H * W, C, 9 * c.z_channels, 1);
-        if (!dry) ex.note(small_conv_in_launch(a, stream));
-        ex.t_end("small_conv_in_kernel");
+        ex.launch(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.z_channels, "conv_in", (long long)b * H * W, C, 9 * c.z_channels, 1, "small_conv_in_kernel",
+                  [&] { return small_conv_in_launch(a, stream); });
     }
     f = R.resblock(v->mid1, f, H, W);
     f = R.attn(v->mid_attn, f, H, W);
@@ -401,17 +347,11 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
         // conv_out (C -> 3): on the halo-tile MFMA kernel when the image is cut into its 4-row x 128-pixel tiles (weights zero-padded to
         // 32 rows, 8 stored columns, then one elementwise pass for clamp((v + 1) / 2) -> fp32 NHWC): 1427 -> ~200 us at 512x512 x 8;
         // other sizes keep the vector-ALU kernel
-        GemmParams q;
-        q.conv = 1; q.ksize = 3; q.pad = -1; q.stride = 1;
-        q.A = g; q.C1 = C;
-        q.Hs = H; q.Ws = W; q.Hv = H; q.Wv = W; q.Ho = H; q.Wo = W;
-        q.W = v->co_pad; q.ldw = 9 * C;
-        q.M = b * H * W; q.N = 32; q.n_valid = 8; q.K = 9 * C;
-        q.bias_n = v->co_pad != nullptr ? v->co_pad + (size_t)32 * 9 * C : nullptr;
-        ex.with_scratch(q);
         const size_t mk8 = ar.mark();
         half_t* t8 = ar.halfs((size_t)b * H * W * 8);   // (the 8 stored columns: 1/16 of g; given back when the convolution does not take the halo tile)
-        q.C = t8; q.ldc = 8;
+        GemmParams q = conv_params(g, C, nullptr, 0, b, H, W, H, W, 1, 3, v->co_pad, v->co_pad != nullptr ? v->co_pad + (size_t)32 * 9 * C : nullptr, 32, t8);
+        q.n_valid = 8; q.ldc = 8;   // (32 padded weight rows; 8 columns are stored)
+        ex.with_scratch(q);
         const GemmPlan qp = v->co_pad != nullptr && c.out_ch <= 8 ? gemm_plan(q) : GemmPlan();
         if (qp.halo_tile) {
             if (!dry) {   // the three real rows of the weight matrix and the biases into the padded copies (stream-ordered, 7 KB)
@@ -420,25 +360,17 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
                     hipMemcpyAsync(v->co_pad + (size_t)32 * 9 * C, v->pt.ptr(v->co_b), c.out_ch * sizeof(half_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
                     ex.note(LD_ERR_HIP);
             }
-            const double fl = 2.0 * b * H * W * C * 9.0 * c.out_ch;
-            ex.launches += 2;
-            ex.flops += fl;
-            ex.t_begin(KC_CONV3, fl, 1, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1);
-            if (!dry && ex.status == LD_OK) ex.note(gemm_run(q, qp, stream));
-            ex.t_end(gemm_last_kernel_name());
-            ex.t_begin(KC_MISC, 0.0, 1, "out_finish", (long long)b * H * W, c.out_ch, 0, 1);
-            if (!dry && ex.status == LD_OK) ex.note(vae_out_finish_launch(t8, out, (long long)b * H * W, c.out_ch, stream));
-            ex.t_end("vae_out_finish_kernel");
+            ex.launch(KC_CONV3, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1, gemm_last_kernel_name,
+                      [&] { return gemm_run(q, qp, stream); });
+            ex.launch(KC_MISC, 0.0, "out_finish", (long long)b * H * W, c.out_ch, 0, 1, "vae_out_finish_kernel",
+                      [&] { return vae_out_finish_launch(t8, out, (long long)b * H * W, c.out_ch, stream); });
         } else {
             ar.release(mk8);
             SmallConvOutArgs a;
             a.x = g; a.w = v->pt.ptr(v->co_w); a.b = v->pt.ptr(v->co_b);
             a.N = b; a.H = H; a.W = W; a.Cin = C; a.Cout = c.out_ch; a.mode = 1; a.out = out;
-            ex.launches += 1;
-            ex.flops += 2.0 * b * H * W * C * 9.0 * c.out_ch;
-            ex.t_begin(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.out_ch, 1, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1);
-            if (!dry) ex.note(small_conv_out_launch(a, stream));
-            ex.t_end("small_conv_out_kernel");
+            ex.launch(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1, "small_conv_out_kernel",
+                      [&] { return small_conv_out_launch(a, stream); });
         }
     }
     v->last_launches = ex.launches;
@@ -474,9 +406,8 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
         SmallConvInArgs a;
         a.x = px; a.w = v->pt.ptr(v->e_cin_w); a.b = v->pt.ptr(v->e_cin_b); a.y = f;
         a.N = b; a.Cin = c.out_ch; a.H = H; a.W = W; a.Cout = C;
-        ex.launches += 1;
-        ex.flops += 2.0 * b * H * W * C * 9.0 * c.out_ch;
-        if (!dry) ex.note(small_conv_in_launch(a, stream));
+        ex.launch(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_in", (long long)b * H * W, C, 9 * c.out_ch, 1, "small_conv_in_kernel",
+                  [&] { return small_conv_in_launch(a, stream); });
     }
     for (int lvl = 0; lvl < c.num_levels; ++lvl) {
         for (const VResW& r : v->down[lvl]) {
@@ -503,8 +434,8 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
         const int Z2 = 2 * c.z_channels;
         half_t* m = ar.halfs((size_t)b * H * W * Z2);
         R.conv(g, C, H, W, H, W, 3, v->e_co_w, v->e_co_b, Z2, nullptr, m);
-        ex.launches += 1;
-        if (!dry && ex.status == LD_OK) ex.note(small_pointwise_launch(m, v->pt.ptr(v->e_q_w), v->pt.ptr(v->e_q_b), moments, b, H * W, Z2, stream));
+        ex.launch(KC_MISC, 0.0, "quant_conv", (long long)b * H * W, Z2, Z2, 1, "small_pointwise_kernel",
+                  [&] { return small_pointwise_launch(m, v->pt.ptr(v->e_q_w), v->pt.ptr(v->e_q_b), moments, b, H * W, Z2, stream); });
     }
     if (H != h || W != w) ex.note(LD_ERR_SHAPE);
     v->last_launches = ex.launches;
@@ -549,21 +480,30 @@ void ld_vae_destroy(ld_vae* v) {
 int ld_vae_param_count(const ld_vae* v) { return v ? (int)v->pt.slots.size() : 0; }
 
 int ld_vae_param_info(const ld_vae* v, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (v == nullptr || i < 0 || i >= (int)v->pt.slots.size()) return LD_ERR_ARG;
-    const ParamSlot& s = v->pt.slots[i];
-    if (name) *name = s.name.c_str();
-    if (ndim) *ndim = s.ndim;
-    if (shape)
-        for (int k = 0; k < 4; ++k) shape[k] = s.shape[k];
-    return LD_OK;
+    return abi_param_info(v ? &v->pt : nullptr, i, name, ndim, shape);
 }
 
 int ld_vae_load_param(ld_vae* v, const char* name, const void* src, int dtype, void* stream) {
-    if (v == nullptr || name == nullptr) return LD_ERR_ARG;
-    return v->pt.load(name, src, dtype, (hipStream_t)stream);
+    return abi_load_param(v ? &v->pt : nullptr, name, src, dtype, stream);
 }
 
 size_t ld_vae_workspace_bytes(const ld_vae* v) { return v ? v->ws_bytes : 0; }
+
+// host-only dry run of the executor: the workspace a (b, h, w) decode (and encode, when the encoder is loaded) needs, without allocating
+static int vae_plan(ld_vae* v, int b, int h, int w, size_t* bytes) {
+    size_t peak = 0;
+    int st = run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, &peak);
+    if (st != LD_OK) return st;
+    if (v->cfg.with_encoder) {
+        size_t pe = 0;
+        st = run_encode(v, true, nullptr, nullptr, b, h, w, nullptr, &pe);
+        if (st != LD_OK) return st;
+        if (pe > peak) peak = pe;
+    }
+    v->plan_b = v->plan_h = v->plan_w = 0;          // (the dry run re-planned the arena marks: the next real call plans its own shape)
+    *bytes = (peak + 4095) / 4096 * 4096 + ((size_t)96 << 20) + 4096;
+    return LD_OK;
+}
 
 int ld_vae_reserve(ld_vae* v, int max_b, int max_h, int max_w) {
     if (v == nullptr || max_b < 1 || max_h < 1 || max_w < 1) return LD_ERR_ARG;
@@ -573,18 +513,12 @@ int ld_vae_reserve(ld_vae* v, int max_b, int max_h, int max_w) {
     }
     v->arena = Arena();
     v->plan_b = v->plan_h = v->plan_w = 0;
-    size_t peak = 0;
-    int st = run_decode(v, true, nullptr, nullptr, max_b, max_h, max_w, nullptr, &peak);
+    size_t bytes = 0;
+    const int st = vae_plan(v, max_b, max_h, max_w, &bytes);
     if (st != LD_OK) return st;
-    if (v->cfg.with_encoder) {
-        size_t pe = 0;
-        st = run_encode(v, true, nullptr, nullptr, max_b, max_h, max_w, nullptr, &pe);
-        if (st != LD_OK) return st;
-        if (pe > peak) peak = pe;
-    }
-    const size_t act = (peak + 4095) / 4096 * 4096;
+    v->ws_bytes = bytes;
     v->splitk_bytes = (size_t)96 << 20;
-    v->ws_bytes = act + v->splitk_bytes + 4096;
+    const size_t act = v->ws_bytes - v->splitk_bytes - 4096;
     if (hipMalloc((void**)&v->ws_base, v->ws_bytes) != hipSuccess) {
         v->ws_base = nullptr;
         return LD_ERR_HIP;
@@ -596,17 +530,9 @@ int ld_vae_reserve(ld_vae* v, int max_b, int max_h, int max_w) {
 }
 
 size_t ld_vae_plan_bytes(ld_vae* v, int b, int h, int w) {
-    // host-only dry run of the executor: the workspace a (b, h, w) decode (and encode, when the encoder is loaded) needs, without allocating
-    if (v == nullptr || b < 1 || h < 1 || w < 1) return 0;
-    size_t peak = 0;
-    if (run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, &peak) != LD_OK) return 0;
-    if (v->cfg.with_encoder) {
-        size_t pe = 0;
-        if (run_encode(v, true, nullptr, nullptr, b, h, w, nullptr, &pe) != LD_OK) return 0;
-        if (pe > peak) peak = pe;
-    }
-    v->plan_b = v->plan_h = v->plan_w = 0;          // (the dry run re-planned the arena marks: the next real call plans its own shape)
-    return (peak + 4095) / 4096 * 4096 + ((size_t)96 << 20) + 4096;
+    size_t bytes = 0;
+    if (v == nullptr || b < 1 || h < 1 || w < 1 || vae_plan(v, b, h, w, &bytes) != LD_OK) return 0;
+    return bytes;
 }
 
 int ld_vae_decode(ld_vae* v, const float* z, float* out, int b, int h, int w, void* stream) {
@@ -643,15 +569,11 @@ int ld_vae_profile(ld_vae* v, const float* z, float* out, int b, int h, int w, v
     v->want_timing = true;
     const int st = ld_vae_decode(v, z, out, b, h, w, stream);
     v->want_timing = false;
-    if (st != LD_OK) return st;
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
-    v->timing.collect();
-    return LD_OK;
+    return st != LD_OK ? st : abi_profile_collect(v->timing, stream);
 }
 
 int ld_vae_profile_launches(const ld_vae* v, char* buf, size_t buf_bytes) {
-    if (v == nullptr) return LD_ERR_ARG;
-    return v->timing.format_launches(buf, buf_bytes);
+    return abi_profile_launches(v ? &v->timing : nullptr, buf, buf_bytes);
 }
 
 int ld_vae_last_launches(const ld_vae* v) { return v ? v->last_launches : 0; }

@@ -51,3 +51,33 @@ def test_isa_check_of_untracked_loads(tmp_path):
         pytest.skip("no hipcc")
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "isa_check.py"), "conv8.hip"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+# (n, h, w, c1, c2, cout) of three GN_CONV_ROUTES rows (tests/test_routes_gpu.py; cout = 320 can have the row-resident kernel's weight copy in
+# its scratch, 256 cannot) -> ld_op_groupnorm_conv_ws_bytes, ld_op_groupnorm_ws_bytes, ld_op_conv_gn_partials_floats
+GN_CONV_WS = [
+    ((12, 64, 64, 320, 0, 320), 134989824, 786432, 196608),
+    ((12, 64, 64, 128, 192, 320), 134989824, 786432, 196608),
+    ((3, 128, 128, 256, 0, 256), 126035968, 196608, 49152),
+]
+# (n, h, w, c, sc1, sc2, cout) of the SKIP_ROUTES row and two rows of tests/test_conv6_skip_gpu.py -> ld_op_conv_skip_ws_bytes,
+# ld_op_groupnorm_conv_skip_ws_bytes
+SKIP_WS = [
+    ((12, 64, 64, 320, 320, 320, 320), 102916864, 135191296),
+    ((6, 64, 64, 1024, 320, 0, 320), 106767104, 157541120),
+    ((12, 16, 16, 1280, 1280, 1280, 1280), 136710656, 144747008),
+]
+
+
+def test_op_workspace_sizes_are_pinned():
+    """The scratch an operator hands to a launch decides its split over K (ops._ws), so the sizes the composites ask for are part of their
+    routes: literal values (pure host functions, no GPU), so that a change to how the scratch is carved cannot move a route unnoticed."""
+    from lightdiffusion_amd._lib import lib
+    l = lib()
+    for (n, h, w, c1, c2, cout), conv_ws, gn_ws, part_floats in GN_CONV_WS:
+        assert l.ld_op_groupnorm_conv_ws_bytes(c1, c2, n, h, w, cout) == conv_ws, (n, h, w, c1, c2, cout)
+        assert l.ld_op_groupnorm_ws_bytes(n, h * w) == gn_ws, (n, h * w)
+        assert l.ld_op_conv_gn_partials_floats(n, h * w) == part_floats, (n, h * w)
+    for (n, h, w, c, sc1, sc2, cout), skip_ws, gn_skip_ws in SKIP_WS:
+        assert l.ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout) == skip_ws, (c, sc1, sc2, cout)
+        assert l.ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w) == gn_skip_ws, (n, h, w, c, sc1, sc2, cout)
