@@ -258,6 +258,49 @@ int ld_op_axpby(float* x, float a, const float* y, float b, const float* z, floa
 int ld_op_hook_check(const void* a, const void* b, size_t words_ab, const void* x, size_t half_words_x, const void* sigma, int half_sigma,
                      int* flags, int epoch, void* stream);
 
+/* ---- The norm, boundary-convolution and fold kernels on their own, for element-wise parity tests (tests/errbound.py): each is the
+ * kernel's launcher behind an argument check, no device code of its own. */
+/* softmax_rows with a row pitch ld >= cols (elements, a multiple of 8) and `valid` <= cols real columns (0 = cols): columns >= valid are
+ * written as zeros, elements cols .. ld-1 of a row are not touched */
+int ld_op_softmax_rows_ld(void* s, int rows, int cols, long long ld, int valid, void* stream);
+/* GroupNorm(32) in its consumer-facing forms.  ld_op_groupnorm_chunks: pixel chunks per image of the statistics pass.
+ * ld_op_groupnorm_stats: part [n][chunks][32][2] floats (sum, sum of squares).  ld_op_groupnorm_from_partials: the apply pass alone over
+ * part [n][pstat][32][2] a producer wrote (pstat >= 1, any chunking of the image's pixels).  ld_op_groupnorm_scale_shift: scale / shift
+ * [n][c1 + c2] fp32 with  y = x * scale + shift  — the values the apply pass multiplies by, bit for bit; stats_ready = 0 runs the statistics
+ * pass into ws (>= ld_op_groupnorm_ws_bytes), > 0 reads ws as [n][stats_ready][32][2]. */
+int ld_op_groupnorm_chunks(int n, int hw);
+int ld_op_groupnorm_stats(const void* x1, int c1, const void* x2, int c2, int n, int hw, float* part, void* stream);
+int ld_op_groupnorm_from_partials(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
+                                  int silu, void* y, float* part, int pstat, void* stream);
+int ld_op_groupnorm_scale_shift(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
+                                float* ws, int stats_ready, float* scale, float* shift, void* stream);
+/* 3x3 pad-1 convolution from cin <= 4 channels: x fp32 NCHW [n][cin][h][w] -> y fp16 NHWC [n][h][w][cout], cout a multiple of 8, wt [cout][9 cin]
+ * (tap-major).  scale_sigma [n] (optional): x is scaled by 1 / sqrt(sigma^2 + 1) and rounded to fp16 first; pre_w [cin][cin], pre_b (optional):
+ * a 1x1 convolution in front, rounded to fp16; dup_off != 0: every output is stored a second time at y + dup_off (elements). */
+int ld_op_small_conv_in(const float* x, const float* scale_sigma, const void* pre_w, const void* pre_b, const void* wt, const void* bias, void* y,
+                        int n, int cin, int h, int w, int cout, long long dup_off, void* stream);
+/* 3x3 pad-1 convolution to cout <= 4 channels from x fp16 NHWC [n][h][w][cin], cin a multiple of 8 up to 512, wt [cout][9 cin], out fp32.
+ * mode 0: out NCHW = x_in - fp16(v) * sigma (x_in [n][cout][h][w], sigma [n]; in_mod > 0: both hold in_mod samples, sample i reads i % in_mod);
+ * mode 1: out NHWC = clamp((v + 1) / 2, 0, 1);  mode 2: out NCHW = v. */
+int ld_op_small_conv_out(const void* x, const void* wt, const void* bias, int n, int h, int w, int cin, int cout, int mode, const float* x_in,
+                         const float* sigma, int in_mod, float* out, void* stream);
+/* out fp32 NCHW [n][c][hw] = fp16(bias + w x) of x fp16 [n][hw][8], w [c][c]; c == 8 */
+int ld_op_small_pointwise(const void* x, const void* wt, const void* bias, float* out, int n, int hw, int c, void* stream);
+/* out fp32 [npix][cout] = clamp((t8 + 1) / 2, 0, 1) of the first cout <= 8 columns of t8 fp16 [npix][8] */
+int ld_op_vae_out_finish(const void* t8, float* out, long long npix, int cout, void* stream);
+/* ld_op_timestep_embed with sigma_mod > 0: sigma holds sigma_mod samples and sample i reads sigma[i % sigma_mod] */
+int ld_op_timestep_embed_mod(const float* sigma, const float* log_sigmas, int n_sigmas, int n, int dim, void* out_f16, float* t_out, int sigma_mod,
+                             void* stream);
+/* count <= 3 ranges: bytes [base_i, base_i + bytes_i) are copied to [base_i + bytes_i, base_i + 2 bytes_i); bases and lengths multiples of 16 */
+int ld_op_dup_halves(void* base0, size_t bytes0, void* base1, size_t bytes1, void* base2, size_t bytes2, int count, void* stream);
+/* src [n][t][d] (dtype LD_F16 / LD_F32) -> dst fp16 [n][tp][d], rows t .. tp-1 zero */
+int ld_op_ctx_pad(const void* src, int dtype, int n, int t, int tp, int d, void* dst, void* stream);
+/* w_out [c][5c] = [wpo w2 | wpo], b_out = wpo b2 + bpo  (wpo [c][c], w2 [c][4c]): fp32 sums, one rounding to fp16 */
+int ld_op_mlp_out_fold(const void* wpo, const void* w2, const void* b2, const void* bpo, int c, void* w_out, void* b_out, void* stream);
+/* w_out [n][k] = fp16(w * gamma), b_out [n] = fp16(bias + w beta) (bias optional), wsum [n] = fp32 row sums of the ROUNDED w_out */
+int ld_op_ln_fold(const void* w, int n, int k, const void* gamma, const void* beta, const void* bias, void* w_out, void* b_out, float* wsum,
+                  void* stream);
+
 /* The LayerNorm fold of the UNet's transformer blocks (BasicTransformerBlock, LD.py:4117-4162: every attention / GEGLU
  * projection reads LayerNorm(x)) as an operator pair, for parity tests: t[M][C] = x · w_prod^T + b_prod (the GEMM that writes the
  * residual stream, emitting per-row statistics) and y[M][N] = LayerNorm(t; gamma, beta, eps) · w^T + bias, finished on the fp32
@@ -287,7 +330,8 @@ int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, 
                      void* stream);
 /* The contraction kernel instantiations (GEMM / convolution / attention, the names the profile tables use) that the calling thread's
  * last ld_op_* call dispatched, in launch order, joined with ';' (e.g. "gemm3_kernel<64,160,conv>+splitk_reduce_kernel").  Reset at
- * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call. */
+ * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call.
+ * The two small convolutions name their instantiation too ("small_conv_in_kernel<3>", "small_conv_out_kernel<9,1>"). */
 const char* ld_op_last_kernel(void);
 /* The merge kernel of ld_unet_patch_param on a plain row-major matrix: dst[rows][cols] = round_fp16(float(base) + sum_j scale_j up_j down_j);
  * dst may alias base.  Also what the host's text model patches its weights with. */

@@ -121,6 +121,20 @@ SIGNATURES = {
     "ld_op_cfg_combine": (_I, [_P, _P, _F, _Z, _P]),
     "ld_op_axpby": (_I, [_P, _F, _P, _F, _P, _F, _Z, _P]),
     "ld_op_hook_check": (_I, [_P, _P, _Z, _P, _Z, _P, _I, _P, _I, _P]),
+    "ld_op_softmax_rows_ld": (_I, [_P, _I, _I, C.c_longlong, _I, _P]),
+    "ld_op_groupnorm_chunks": (_I, [_I, _I]),
+    "ld_op_groupnorm_stats": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    "ld_op_groupnorm_from_partials": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _I, _P]),
+    "ld_op_groupnorm_scale_shift": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _P, _P, _P]),
+    "ld_op_small_conv_in": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_longlong, _P]),
+    "ld_op_small_conv_out": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "ld_op_small_pointwise": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ld_op_vae_out_finish": (_I, [_P, _P, C.c_longlong, _I, _P]),
+    "ld_op_timestep_embed_mod": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
+    "ld_op_dup_halves": (_I, [_P, _Z, _P, _Z, _P, _Z, _I, _P]),
+    "ld_op_ctx_pad": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "ld_op_mlp_out_fold": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
+    "ld_op_ln_fold": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ld_op_linear_ln": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

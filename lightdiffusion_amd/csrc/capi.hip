@@ -339,6 +339,108 @@ int ld_op_axpby(float* x, float a, const float* y, float b, const float* z, floa
     return axpby_launch(x, a, y, b, z, c, n, (hipStream_t)stream);
 }
 
+// ---- the norm, boundary-convolution and fold kernels on their own (tests/test_norm_gpu.py, tests/test_small_kernels_gpu.py)
+int ld_op_softmax_rows_ld(void* s, int rows, int cols, long long ld, int valid, void* stream) {
+    op_begin();
+    if (valid < 0 || ld < cols) return LD_ERR_SHAPE;
+    return softmax_rows_launch((half_t*)s, rows, cols, ld, (hipStream_t)stream, valid);
+}
+
+int ld_op_groupnorm_chunks(int n, int hw) {
+    op_begin();
+    return gn_num_chunks(n, hw);
+}
+
+int ld_op_groupnorm_stats(const void* x1, int c1, const void* x2, int c2, int n, int hw, float* part, void* stream) {
+    op_begin();
+    return groupnorm_stats_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, part, (hipStream_t)stream);
+}
+
+int ld_op_groupnorm_from_partials(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
+                                  int silu, void* y, float* part, int pstat, void* stream) {
+    op_begin();
+    if (pstat < 1) return LD_ERR_ARG;
+    return groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps, silu, (half_t*)y, part,
+                            (hipStream_t)stream, pstat);
+}
+
+int ld_op_groupnorm_scale_shift(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
+                                float* ws, int stats_ready, float* scale, float* shift, void* stream) {
+    op_begin();
+    if (stats_ready < 0) return LD_ERR_ARG;
+    return groupnorm_scale_shift_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps, ws, scale,
+                                        shift, (hipStream_t)stream, stats_ready);
+}
+
+int ld_op_small_conv_in(const float* x, const float* scale_sigma, const void* pre_w, const void* pre_b, const void* wt, const void* bias, void* y,
+                        int n, int cin, int h, int w, int cout, long long dup_off, void* stream) {
+    op_begin();
+    if ((pre_w == nullptr) != (pre_b == nullptr) || n <= 0 || h <= 0 || w <= 0 || (dup_off & 7)) return LD_ERR_ARG;
+    SmallConvInArgs a;
+    a.x = x; a.scale_sigma = scale_sigma; a.pre_w = (const half_t*)pre_w; a.pre_b = (const half_t*)pre_b;
+    a.w = (const half_t*)wt; a.b = (const half_t*)bias; a.y = (half_t*)y;
+    a.N = n; a.Cin = cin; a.H = h; a.W = w; a.Cout = cout; a.dup_off = dup_off;
+    const int st = small_conv_in_launch(a, (hipStream_t)stream);
+    return noted(st, small_conv_last_kernel_name());
+}
+
+int ld_op_small_conv_out(const void* x, const void* wt, const void* bias, int n, int h, int w, int cin, int cout, int mode, const float* x_in,
+                         const float* sigma, int in_mod, float* out, void* stream) {
+    op_begin();
+    if (n <= 0 || h <= 0 || w <= 0 || mode < 0 || mode > 2 || in_mod < 0) return LD_ERR_ARG;
+    SmallConvOutArgs a;
+    a.x = (const half_t*)x; a.w = (const half_t*)wt; a.b = (const half_t*)bias;
+    a.N = n; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout; a.mode = mode;
+    a.x_in = x_in; a.sigma = sigma; a.in_mod = in_mod; a.out = out;
+    const int st = small_conv_out_launch(a, (hipStream_t)stream);
+    return noted(st, small_conv_last_kernel_name());
+}
+
+int ld_op_small_pointwise(const void* x, const void* wt, const void* bias, float* out, int n, int hw, int c, void* stream) {
+    op_begin();
+    return small_pointwise_launch((const half_t*)x, (const half_t*)wt, (const half_t*)bias, out, n, hw, c, (hipStream_t)stream);
+}
+
+int ld_op_vae_out_finish(const void* t8, float* out, long long npix, int cout, void* stream) {
+    op_begin();
+    return vae_out_finish_launch((const half_t*)t8, out, npix, cout, (hipStream_t)stream);
+}
+
+int ld_op_timestep_embed_mod(const float* sigma, const float* log_sigmas, int n_sigmas, int n, int dim, void* out, float* t_out, int sigma_mod,
+                             void* stream) {
+    op_begin();
+    return timestep_embed_launch(sigma, log_sigmas, n_sigmas, n, dim, (half_t*)out, t_out, (hipStream_t)stream, sigma_mod);
+}
+
+int ld_op_dup_halves(void* base0, size_t bytes0, void* base1, size_t bytes1, void* base2, size_t bytes2, int count, void* stream) {
+    op_begin();
+    DupArgs a;
+    a.base[0] = (char*)base0; a.bytes[0] = bytes0;
+    a.base[1] = (char*)base1; a.bytes[1] = bytes1;
+    a.base[2] = (char*)base2; a.bytes[2] = bytes2;
+    a.count = count;
+    return dup_halves_launch(a, (hipStream_t)stream);
+}
+
+int ld_op_ctx_pad(const void* src, int dtype, int n, int t, int tp, int d, void* dst, void* stream) {
+    op_begin();
+    if ((dtype != LD_F16 && dtype != LD_F32) || n <= 0 || t <= 0 || d <= 0) return LD_ERR_ARG;
+    return ctx_pad_launch(src, dtype == LD_F32, n, t, tp, d, (half_t*)dst, (hipStream_t)stream);
+}
+
+int ld_op_mlp_out_fold(const void* wpo, const void* w2, const void* b2, const void* bpo, int c, void* w_out, void* b_out, void* stream) {
+    op_begin();
+    return mlp_out_fold_launch((const half_t*)wpo, (const half_t*)w2, (const half_t*)b2, (const half_t*)bpo, c, (half_t*)w_out, (half_t*)b_out,
+                               (hipStream_t)stream);
+}
+
+int ld_op_ln_fold(const void* w, int n, int k, const void* gamma, const void* beta, const void* bias, void* w_out, void* b_out, float* wsum,
+                  void* stream) {
+    op_begin();
+    return ln_fold_launch((const half_t*)w, n, k, (const half_t*)gamma, (const half_t*)beta, (const half_t*)bias, (half_t*)w_out, (half_t*)b_out, wsum,
+                          (hipStream_t)stream);
+}
+
 // the UNet's LayerNorm fold (unet.hip Run::transformer, gemm.h) as a stand-alone operator pair on the executor's builders (ln_producer / ln_consumer):
 //   t = x · w_prod^T + b_prod         (producer: also emits per-row (sum, sum of squares) partials of the fp16 t)
 //   y = LayerNorm(t; gamma, beta, eps) · w^T + bias   computed as rstd * (t · W'^T - mu * wsum) + b' on the accumulators

@@ -88,6 +88,7 @@ struct SmallConvOutArgs {       // 3x3 pad-1 conv to <= 4 output channels from a
     int in_mod = 0;                // > 0: x_in / sigma hold in_mod samples and sample n reads n % in_mod (CFG pair: both halves see the same latents)
 };
 int small_conv_out_launch(const SmallConvOutArgs& a, hipStream_t stream);
+const char* small_conv_last_kernel_name();   // instantiation the calling thread's last small_conv_in_launch / small_conv_out_launch dispatched ("" = none)
 
 // VAE output tail behind the MFMA output convolution: t8 [npix][8] fp16 (first `cout` columns valid) -> out [npix][cout] fp32 =
 // clamp((v + 1) / 2, 0, 1)  (VAE.process_output, LD.py:6296-6298)

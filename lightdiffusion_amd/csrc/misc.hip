@@ -352,9 +352,14 @@ inline int grid_for(long long total, int threads, int cap = 4096) {
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
+thread_local const char* t_last_small_conv = "";
+
 }  // namespace
 
+const char* small_conv_last_kernel_name() { return t_last_small_conv; }
+
 int small_conv_in_launch(const SmallConvInArgs& a, hipStream_t stream) {
+    t_last_small_conv = "";
     if (a.x == nullptr || a.w == nullptr || a.b == nullptr || a.y == nullptr) return LD_ERR_ARG;
     if (a.Cin < 1 || a.Cin > 4 || (a.Cout & 7) || a.Cout <= 0) return LD_ERR_SHAPE;
     const size_t lds = (size_t)a.Cout * 9 * a.Cin * sizeof(half_t);
@@ -362,15 +367,16 @@ int small_conv_in_launch(const SmallConvInArgs& a, hipStream_t stream) {
     const long long total = (long long)a.N * a.H * a.W * (a.Cout >> 3);
     const dim3 grid(grid_for(total, 256, 1024));
     switch (a.Cin) {
-        case 1: hipLaunchKernelGGL(small_conv_in_kernel<1>, grid, dim3(256), lds, stream, a); break;
-        case 2: hipLaunchKernelGGL(small_conv_in_kernel<2>, grid, dim3(256), lds, stream, a); break;
-        case 3: hipLaunchKernelGGL(small_conv_in_kernel<3>, grid, dim3(256), lds, stream, a); break;
-        default: hipLaunchKernelGGL(small_conv_in_kernel<4>, grid, dim3(256), lds, stream, a); break;
+        case 1: hipLaunchKernelGGL(small_conv_in_kernel<1>, grid, dim3(256), lds, stream, a); t_last_small_conv = "small_conv_in_kernel<1>"; break;
+        case 2: hipLaunchKernelGGL(small_conv_in_kernel<2>, grid, dim3(256), lds, stream, a); t_last_small_conv = "small_conv_in_kernel<2>"; break;
+        case 3: hipLaunchKernelGGL(small_conv_in_kernel<3>, grid, dim3(256), lds, stream, a); t_last_small_conv = "small_conv_in_kernel<3>"; break;
+        default: hipLaunchKernelGGL(small_conv_in_kernel<4>, grid, dim3(256), lds, stream, a); t_last_small_conv = "small_conv_in_kernel<4>"; break;
     }
     return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
 }
 
 int small_conv_out_launch(const SmallConvOutArgs& a, hipStream_t stream) {
+    t_last_small_conv = "";
     if (a.x == nullptr || a.w == nullptr || a.b == nullptr || a.out == nullptr) return LD_ERR_ARG;
     if (a.Cout < 1 || a.Cout > 4 || (a.Cin & 7)) return LD_ERR_SHAPE;
     if (a.mode == 0 && (a.x_in == nullptr || a.sigma == nullptr)) return LD_ERR_ARG;
@@ -382,9 +388,9 @@ int small_conv_out_launch(const SmallConvOutArgs& a, hipStream_t stream) {
     if (waves > 8192) waves = 8192;
     if (waves < 4) waves = 4;
     const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    if (nch <= 3) hipLaunchKernelGGL((small_conv_out_kernel<3, 4>), grid, block, 0, stream, a);
-    else if (nch <= 6) hipLaunchKernelGGL((small_conv_out_kernel<6, 2>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((small_conv_out_kernel<9, 1>), grid, block, 0, stream, a);
+    if (nch <= 3) { hipLaunchKernelGGL((small_conv_out_kernel<3, 4>), grid, block, 0, stream, a); t_last_small_conv = "small_conv_out_kernel<3,4>"; }
+    else if (nch <= 6) { hipLaunchKernelGGL((small_conv_out_kernel<6, 2>), grid, block, 0, stream, a); t_last_small_conv = "small_conv_out_kernel<6,2>"; }
+    else { hipLaunchKernelGGL((small_conv_out_kernel<9, 1>), grid, block, 0, stream, a); t_last_small_conv = "small_conv_out_kernel<9,1>"; }
     return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
 }
 

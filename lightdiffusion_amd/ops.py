@@ -302,6 +302,121 @@ def timestep_embed(sigma: torch.Tensor, log_sigmas: torch.Tensor, dim: int):
     return out, t
 
 
+# ------------------------------------------------------------------ the norm, boundary-convolution and fold kernels on their own
+# (the seam of tests/test_norm_gpu.py and tests/test_small_kernels_gpu.py; the executors call the launchers directly)
+def softmax_rows_ld_(s: torch.Tensor, cols: int, valid: int = 0) -> torch.Tensor:
+    """In-place row softmax over the first `cols` columns of s [rows][ld]; columns valid .. cols-1 become zeros, cols .. ld-1 stay."""
+    ld = s.shape[-1]
+    check(lib().ld_op_softmax_rows_ld(_p(s), s.numel() // ld, cols, ld, valid, _stream()), "ld_op_softmax_rows_ld")
+    return s
+
+
+def _gn_dims(x, x2):
+    n, c1 = x.shape[0], x.shape[-1]
+    return n, c1, 0 if x2 is None else x2.shape[-1], x.numel() // (n * c1)
+
+
+def group_norm_stats(x: torch.Tensor, x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The statistics pass alone: partial (sum, sum of squares) [n][chunks][32][2] fp32."""
+    n, c1, c2, hw = _gn_dims(x, x2)
+    part = torch.empty(n, lib().ld_op_groupnorm_chunks(n, hw), 32, 2, dtype=torch.float32, device=x.device)
+    check(lib().ld_op_groupnorm_stats(_p(x), c1, _p(x2), c2, n, hw, _p(part), _stream()), "ld_op_groupnorm_stats")
+    return part
+
+
+def group_norm_from_partials(x: torch.Tensor, part: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, silu: bool = False,
+                             x2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The apply pass alone over a producer's partials [n][pstat][32][2]."""
+    n, c1, c2, hw = _gn_dims(x, x2)
+    y = torch.empty(*x.shape[:-1], c1 + c2, dtype=torch.float16, device=x.device)
+    check(lib().ld_op_groupnorm_from_partials(_p(x), c1, _p(x2), c2, n, hw, _p(gamma), _p(beta), eps, int(silu), _p(y), _p(part), part.shape[1],
+                                              _stream()), "ld_op_groupnorm_from_partials")
+    return y
+
+
+def group_norm_scale_shift(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, x2: Optional[torch.Tensor] = None,
+                           part: Optional[torch.Tensor] = None):
+    """(scale, shift) [n][C] fp32 of y = x * scale + shift; part: a producer's partials [n][pstat][32][2] (None: the statistics pass runs)."""
+    n, c1, c2, hw = _gn_dims(x, x2)
+    scale = torch.empty(n, c1 + c2, dtype=torch.float32, device=x.device)
+    shift = torch.empty_like(scale)
+    ws = part if part is not None else _ws(lib().ld_op_groupnorm_ws_bytes(n, hw), x.device)
+    check(lib().ld_op_groupnorm_scale_shift(_p(x), c1, _p(x2), c2, n, hw, _p(gamma), _p(beta), eps, _p(ws), 0 if part is None else part.shape[1],
+                                            _p(scale), _p(shift), _stream()), "ld_op_groupnorm_scale_shift")
+    return scale, shift
+
+
+def small_conv_in(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, scale_sigma: Optional[torch.Tensor] = None,
+                  pre_w: Optional[torch.Tensor] = None, pre_b: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+                  dup_off: int = 0) -> torch.Tensor:
+    """3x3 conv from x fp32 NCHW (<= 4 channels) to NHWC fp16; weight [Cout][9 Cin] tap-major.  y: a caller's buffer (with dup_off)."""
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if y is None:
+        y = torch.empty(n, h, w, cout, dtype=torch.float16, device=x.device)
+    check(lib().ld_op_small_conv_in(_p(x), _p(scale_sigma), _p(pre_w), _p(pre_b), _p(weight), _p(bias), _p(y), n, cin, h, w, cout, dup_off,
+                                    _stream()), "ld_op_small_conv_in")
+    return y
+
+
+def small_conv_out(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, mode: int, x_in: Optional[torch.Tensor] = None,
+                   sigma: Optional[torch.Tensor] = None, in_mod: int = 0) -> torch.Tensor:
+    """3x3 conv from x fp16 NHWC to <= 4 channels, fp32; weight [Cout][9 Cin].  mode 0: x_in - fp16(v) sigma (NCHW), 1: clamp((v + 1) / 2)
+    (NHWC), 2: v (NCHW)."""
+    n, h, w, cin = x.shape
+    cout = weight.shape[0]
+    out = torch.empty((n, h, w, cout) if mode == 1 else (n, cout, h, w), dtype=torch.float32, device=x.device)
+    check(lib().ld_op_small_conv_out(_p(x), _p(weight), _p(bias), n, h, w, cin, cout, mode, _p(x_in), _p(sigma), in_mod, _p(out), _stream()),
+          "ld_op_small_conv_out")
+    return out
+
+
+def small_pointwise(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    n, hw, c = x.shape
+    out = torch.empty(n, c, hw, dtype=torch.float32, device=x.device)
+    check(lib().ld_op_small_pointwise(_p(x), _p(weight), _p(bias), _p(out), n, hw, c, _stream()), "ld_op_small_pointwise")
+    return out
+
+
+def vae_out_finish(t8: torch.Tensor, cout: int) -> torch.Tensor:
+    npix = t8.numel() // 8
+    out = torch.empty(npix, cout, dtype=torch.float32, device=t8.device)
+    check(lib().ld_op_vae_out_finish(_p(t8), _p(out), npix, cout, _stream()), "ld_op_vae_out_finish")
+    return out
+
+
+def timestep_embed_mod(sigma: torch.Tensor, log_sigmas: torch.Tensor, dim: int, n: int, sigma_mod: int):
+    out = torch.empty(n, dim, dtype=torch.float16, device=sigma.device)
+    t = torch.empty(n, dtype=torch.float32, device=sigma.device)
+    check(lib().ld_op_timestep_embed_mod(_p(sigma), _p(log_sigmas), log_sigmas.numel(), n, dim, _p(out), _p(t), sigma_mod, _stream()),
+          "ld_op_timestep_embed_mod")
+    return out, t
+
+
+def ctx_pad(src: torch.Tensor, tp: int) -> torch.Tensor:
+    n, t, d = src.shape
+    dst = torch.empty(n, tp, d, dtype=torch.float16, device=src.device)
+    check(lib().ld_op_ctx_pad(_p(src), F32 if src.dtype == torch.float32 else F16, n, t, tp, d, _p(dst), _stream()), "ld_op_ctx_pad")
+    return dst
+
+
+def mlp_out_fold(wpo: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, bpo: torch.Tensor):
+    c = wpo.shape[0]
+    w_out = torch.empty(c, 5 * c, dtype=torch.float16, device=wpo.device)
+    b_out = torch.empty(c, dtype=torch.float16, device=wpo.device)
+    check(lib().ld_op_mlp_out_fold(_p(wpo), _p(w2), _p(b2), _p(bpo), c, _p(w_out), _p(b_out), _stream()), "ld_op_mlp_out_fold")
+    return w_out, b_out
+
+
+def ln_fold(weight: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor] = None):
+    n, k = weight.shape
+    w_out = torch.empty_like(weight)
+    b_out = torch.empty(n, dtype=torch.float16, device=weight.device)
+    wsum = torch.empty(n, dtype=torch.float32, device=weight.device)
+    check(lib().ld_op_ln_fold(_p(weight), n, k, _p(gamma), _p(beta), _p(bias), _p(w_out), _p(b_out), _p(wsum), _stream()), "ld_op_ln_fold")
+    return w_out, b_out, wsum
+
+
 def cfg_combine(den2: torch.Tensor, cfg: float) -> torch.Tensor:
     """den2 = [uncond ; cond] stacked on dim 0 (fp32) -> uncond + (cond - uncond) * cfg   (cfg_function, LD.py:2594-2606)."""
     half = den2.shape[0] // 2

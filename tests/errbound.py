@@ -36,11 +36,60 @@ def c_acc(K: int) -> float:
     return 2.0 * 1.5e-7 * max(1.0, math.sqrt(K / 1024.0))
 
 
-def signed_bias(y: torch.Tensor, ref: torch.Tensor, floor_frac: float = 1e-3) -> float:
-    """s = mean((y - y_hat) sign(y_hat)) / mean(|y_hat|) over the elements with |y_hat| above floor_frac * max|y_hat|."""
+def bias_kept_fraction(ref: torch.Tensor, floor_frac: float = 1e-3) -> float:
+    """Share of the elements the bias statistic keeps (|y_hat| above floor_frac * max|y_hat|)."""
+    a = ref.double().abs()
+    return float((a > floor_frac * float(a.max())).double().mean())
+
+
+def rtn_noise(n: float) -> float:
+    """What the bias statistic of n elements may show by chance under round to nearest: four standard deviations of the mean of n independent
+    relative rounding errors, each uniform within +-U (standard deviation U / sqrt(3)).  1.1e-5 at 1e4 elements — inside BIAS_TOL's own room —
+    but 1e-4 at a 100-element output, which the fixed tolerance alone would fail one time in ten."""
+    return 4.0 * U / math.sqrt(3.0 * max(1.0, n))
+
+
+def independent_roundings(ref: torch.Tensor, keep: torch.Tensor | None = None, floor_frac: float = 1e-3) -> float:
+    """The n of rtn_noise for an output.  The bias statistic is the |y_hat|-weighted mean of the kept elements' relative rounding errors, and equal
+    values round equally, so its chance level is that of  n_eff = (sum W_v)^2 / sum W_v^2  independent errors, W_v the summed |y_hat| of each
+    DISTINCT kept value v: the element count for distinct values of one size, 1 for a softmax whose rows are all three tied maxima (p = 1/3, each
+    rounded down by 2.4e-4), about five for rows of m = 1 .. 6 tied maxima however many rows there are."""
+    a = ref.double().abs().flatten()
+    k = (a > floor_frac * float(a.max())) if keep is None else (keep.flatten().to(a.device) & (a > 0))
+    if int(k.sum()) == 0:
+        return 1.0
+    vals, inv = torch.unique(a[k], return_inverse=True)
+    w = torch.zeros_like(vals).scatter_add_(0, inv, a[k])
+    return float(w.sum() ** 2 / (w * w).sum())
+
+
+def subnormal_bias_allowance(ref: torch.Tensor, keep: torch.Tensor) -> float:
+    """What fp16's subnormal range may add to the bias statistic over `keep`: below 2^-14 the rounding error is absolute, up to 2^-25 per element,
+    and does not average out against |y_hat| (everything below 2^-25 rounds DOWN to zero) — mean(2^-25 over the kept subnormal elements) /
+    mean |y_hat|.  Zero for an output in the normal range; it voids the statistic where most kept values are subnormal (a 4096-column softmax
+    of scale-4 scores: the median probability is 8e-8), where the element bound alone holds the kernel."""
+    a = ref.double().abs().flatten()
+    k = keep.flatten().to(a.device) & (a > 0)
+    if int(k.sum()) == 0:
+        return 0.0
+    return float(((a[k] < 2.0 ** -14).double() * 2.0 ** -25).mean() / a[k].mean())
+
+
+def top_half_per_row(ref: torch.Tensor) -> torch.Tensor:
+    """Mask of the largest 50 % of every row of `ref` (the softmax's bias statistic: a row's small probabilities are fp16 subnormals)."""
+    k = max(1, ref.shape[-1] // 2)
+    thr = ref.double().topk(k, dim=-1).values[..., -1:]
+    return ref.double() >= thr
+
+
+def signed_bias(y: torch.Tensor, ref: torch.Tensor, floor_frac: float = 1e-3, keep: torch.Tensor | None = None) -> float:
+    """s = mean((y - y_hat) sign(y_hat)) / mean(|y_hat|) over the elements with |y_hat| above floor_frac * max|y_hat| (and inside `keep`)."""
     y, ref = y.double().flatten(), ref.double().flatten().to(y.device)
     a = ref.abs()
-    keep = a > floor_frac * float(a.max())
+    if keep is not None:
+        keep = keep.flatten().to(y.device) & (a > 0)
+    else:
+        keep = a > floor_frac * float(a.max())
     if int(keep.sum()) == 0:
         return 0.0
     return float(((y - ref)[keep] * ref[keep].sign()).mean() / a[keep].mean())
@@ -69,7 +118,7 @@ def locate(index: int, shape, image_rows: int | None = None, width: int | None =
 
 
 def check(y: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, what: str, *, image_rows=None, width=None, tile=None,
-          bias_extra: float = 0.0, floor_frac: float = 1e-3):
+          bias_extra: float = 0.0, floor_frac: float = 1e-3, keep: torch.Tensor | None = None):
     """Assert |y - y_hat| <= bound element-wise and |signed_bias| <= BIAS_TOL + bias_extra.  Both criteria are evaluated and reported
     together; the message names the worst element, its tile and the ratio error / bound."""
     y = y.to(ref.device).double()
@@ -87,7 +136,7 @@ def check(y: torch.Tensor, ref: torch.Tensor, bound: torch.Tensor, what: str, *,
         nbad = int((ratio > 1.0).sum())
         fails.append(f"element bound: {nbad} of {ratio.numel()} outside, worst {locate(worst, tuple(ref.shape), image_rows, width, tile)}: "
                      f"got {float(y.flatten()[worst]):.6g}, fp64 {float(ref.flatten()[worst]):.6g}, error / bound = {r:.3g}")
-    s = signed_bias(y, ref, floor_frac)
+    s = signed_bias(y, ref, floor_frac, keep)
     tol = BIAS_TOL + bias_extra
     if abs(s) > tol:
         fails.append(f"signed bias {s:.3g} outside +-{tol:.3g} (a systematic rounding or scaling error)")
@@ -239,3 +288,287 @@ def attention_ref(q, k, v, heads, causal=False, ones=None):
     bound = 2 * U * o.abs() + t_p + t_s + t_a + TINY
     back = lambda t: t.transpose(1, 2).reshape(b, lq, c)
     return back(o), back(bound)
+
+
+# ------------------------------------------------------------------ references and bounds of the norm, boundary-conv and fold kernels
+# (norm.hip, misc.hip).  Observed worst error / bound and signed bias per family on the MI355X: see each docstring's last line.
+
+def _gn_stats(x1, x2, eps):
+    """fp64 group statistics of the channel concat [n][HW][C] and their fp32 error model (see groupnorm_ref)."""
+    x = (x1 if x2 is None else torch.cat([x1, x2], dim=-1)).double()
+    n, c = x.shape[0], x.shape[-1]
+    x = x.reshape(n, -1, c)
+    cpg = c // 32
+    xg = x.reshape(n, -1, 32, cpg)
+    cnt = xg.shape[1] * cpg
+    mu = xg.mean(dim=(1, 3))                                   # [n][32]
+    msq = (xg * xg).mean(dim=(1, 3))
+    e_mu = c_acc(cnt) * xg.abs().mean(dim=(1, 3))
+    e_msq = c_acc(cnt) * msq
+    var = (msq - mu * mu).clamp_min(0.0)
+    e_cancel = 2.0 * mu.abs() * e_mu + 2.0 ** -23 * (msq + mu * mu)      # what var = msq - mu^2 adds to e_msq: grows as (mu / sigma)^2
+    e_var = e_msq + e_cancel
+    rstd = (var + eps).rsqrt()
+    # d rstd / rstd for a var off by up to e_var (and clamped at 0): e_var / (2 (var + eps)) to first order; the downward side is taken
+    # exactly, (1 - r)^-1/2 - 1 with r = min(e_var, var) / (var + eps) < 1, because a constant group has e_var >> var + eps
+    r_dn = torch.minimum(e_var, var) / (var + eps)
+    rel = torch.maximum((1.0 - r_dn).rsqrt() - 1.0, e_var / (2.0 * (var + eps))) + 2.0 ** -22
+    rel_nocancel = torch.maximum((1.0 - torch.minimum(e_msq, var) / (var + eps)).rsqrt() - 1.0, e_msq / (2.0 * (var + eps))) + 2.0 ** -22
+    per_c = lambda t: t.repeat_interleave(cpg, dim=1).unsqueeze(1)        # [n][32] -> [n][1][C]
+    return x, per_c(mu), per_c(rstd), per_c(rel), per_c(e_mu), per_c(rel_nocancel)
+
+
+def groupnorm_scale_shift_ref(x1, x2, gamma, beta, eps):
+    """fp64 (sc, sh) [n][C] of y = x sc + sh, sc = rstd gamma, sh = beta - mu sc, with their bounds (no fp16 store: both are fp32):
+        |d sc| <= |sc| (rel_rstd + 2^-23),   |d sh| <= |mu sc| (rel_rstd + 2^-22) + e_mu |sc| + 2^-23 |sh|     (rel_rstd, e_mu: groupnorm_ref).
+    Observed on the MI355X: worst error / bound 0.32 (scale), 0.33 (shift), signed bias below 1e-6."""
+    x, mu, rstd, rel, e_mu, _ = _gn_stats(x1, x2, eps)
+    ga, be = gamma.double().to(x.device), beta.double().to(x.device)
+    sc = rstd * ga
+    sh = be - mu * sc
+    b_sc = sc.abs() * (rel + 2.0 ** -23) + 1e-30
+    b_sh = (mu * sc).abs() * (rel + 2.0 ** -22) + e_mu * sc.abs() + 2.0 ** -23 * sh.abs() + 1e-30
+    return sc[:, 0], b_sc[:, 0], sh[:, 0], b_sh[:, 0]
+
+
+def groupnorm_ref(x1, x2, gamma, beta, eps, silu, parts=False):
+    """fp64 GroupNorm(32) (+SiLU) of the channel concat of NHWC x1, x2 ([n][..][C1], [n][..][C2]) from the fp16 inputs: y_hat [n][HW][C], bound.
+    Rounding points of gn_stats_kernel / gn_apply_kernel (norm.hip):
+      * fp32 sums of x and x^2 over cnt = HW C/32 values (per-thread chains, LDS and shuffle trees, a sweep over the chunk partials):
+        e_mu = c_acc(cnt) mean|x|,  e_msq = c_acc(cnt) mean x^2;
+      * var = msq - mu^2 in fp32:  e_var = e_msq + 2 |mu| e_mu + 2^-23 (msq + mu^2) — the cancellation term, growing as (mu / sigma)^2;
+      * rstd = rsqrtf(var + eps):  rel_rstd = e_var / (2 (var + eps)) + 2^-22 (the downward side exactly, see _gn_stats);
+      * y = x sc + sh with sc = rstd gamma, sh = beta - mu sc in fp32:
+            |x - mu| rstd |gamma| rel_rstd + e_mu rstd |gamma| + 2^-23 (|x sc| + |mu sc| + |sh| + |y|)
+        (|mu sc| beside |sh|: the product inside sh rounds relative to itself, and beta may cancel it in sh);
+      * SiLU x / (1 + __expf(-x)): the linear bound times L_ACT, + 2^-21 |y| for exp / add / divide, + 2^-23 |x| |y| for the rounding of
+        the exponential's argument (x log2 e) — only visible beyond |x| ~ 4;
+      * the fp16 store: U |y| + TINY.
+    parts=True: also returns the share of the bound that the cancellation term contributes, per element.
+    Observed on the MI355X (tests/test_norm_gpu.py): worst error / bound 0.997 (the fp16 store; from re-chunked partials 0.985, mu / sigma = 30 and a
+    constant group 0.986, the chunk partials of gn_stats_kernel alone 0.44), signed bias below 1e-5 from 2000 elements on, -6.7e-5 at a 64-element output."""
+    x, mu, rstd, rel, e_mu, rel0 = _gn_stats(x1, x2, eps)
+    ga, be = gamma.double().to(x.device), beta.double().to(x.device)
+    sc = rstd * ga
+    sh = be - mu * sc
+    y = (x - mu) * sc + be
+    fp32 = 2.0 ** -23 * ((x * sc).abs() + (mu * sc).abs() + sh.abs() + y.abs())
+    lin = lambda r: (x - mu).abs() * sc.abs() * r + e_mu * sc.abs() + fp32
+    b, b0 = lin(rel), lin(rel0)
+    if silu:
+        pre = y
+        y = pre * torch.sigmoid(pre)
+        act = (2.0 ** -21 + 2.0 ** -23 * pre.abs()) * y.abs()
+        b, b0 = L_ACT * b + act, L_ACT * b0 + act
+    store = U * y.abs() + TINY
+    if parts:
+        return y, b + store, (b - b0) / (b + store)
+    return y, b + store
+
+
+def layernorm_ref(x, gamma, beta, eps):
+    """fp64 LayerNorm over the last dim from the fp16 inputs: y_hat, bound.  layernorm_kernel (norm.hip) holds the row in registers and takes
+    two passes, mu then sum (x - mu)^2, so there is no cancellation term; what remains of a large mean is the fp32 sum's own error:
+      * e_mu = c_acc(C) mean|x|; every d = x - mu carries it, and since sum d = 0 the variance sees it only as e_mu^2:
+        rel_rstd = (c_acc(C) var + e_mu^2) / (2 (var + eps)) + 2^-22;
+      * y = d rstd gamma + beta in fp32 (four roundings): |d| rstd |gamma| rel_rstd + e_mu rstd |gamma| + 2^-22 (|d rstd gamma| + |y|);
+      * the fp16 store: U |y| + TINY.
+    Observed on the MI355X (tests/test_norm_gpu.py): worst error / bound 0.996, signed bias below 3.2e-5 from 320 elements on, 1.0e-4 at one row of 8."""
+    xd = x.double()
+    c = xd.shape[-1]
+    ga, be = gamma.double().to(xd.device), beta.double().to(xd.device)
+    mu = xd.mean(-1, keepdim=True)
+    d = xd - mu
+    var = (d * d).mean(-1, keepdim=True)
+    e_mu = c_acc(c) * xd.abs().mean(-1, keepdim=True)
+    rstd = (var + eps).rsqrt()
+    rel = (c_acc(c) * var + e_mu * e_mu) / (2.0 * (var + eps)) + 2.0 ** -22
+    dn = d * rstd * ga
+    y = dn + be
+    b = dn.abs() * rel + e_mu * rstd * ga.abs() + 2.0 ** -22 * (dn.abs() + y.abs())
+    return y, b + U * y.abs() + TINY
+
+
+def softmax_ref(s, valid=None):
+    """fp64 row softmax over the first `valid` columns of the fp16 scores s [rows][cols] (the rest: exactly 0): p_hat, bound
+        U p + TINY                        the fp16 store (TINY: most of a long row are fp16 subnormals)
+      + (2^-21 + 2^-23 |s - max|) p       __expf = exp2(x log2 e): the argument's rounding scales with |s - max|; exp2, the fp32 sum of the row
+                                          and the reciprocal are a few 2^-24 each.
+    Observed on the MI355X (tests/test_norm_gpu.py): worst error / bound 0.993.  Signed bias over the largest half of every row: below 2e-5 for 300
+    rows of 8 or 40 scale-4 scores; 9.4e-5 for one row of 4096 (half of the kept values are fp16 subnormals: subnormal_bias_allowance; round to
+    nearest of the fp64 reference gives the same 9.4e-5) and -1.2e-4 for scores near +-60000 (p = 1 / m for m tied maxima: independent_roundings)."""
+    sd = s.double()
+    cols = sd.shape[-1]
+    valid = cols if valid is None or valid <= 0 else valid
+    sv = sd[..., :valid]
+    mx = sv.amax(-1, keepdim=True)
+    pv = torch.softmax(sv, dim=-1)
+    p = torch.zeros_like(sd)
+    p[..., :valid] = pv
+    bound = torch.full_like(sd, TINY)
+    bound[..., :valid] = U * pv + TINY + (2.0 ** -21 + 2.0 ** -23 * (sv - mx).abs()) * pv
+    return p, bound
+
+
+def tapmajor_to_oihw(w, cin):
+    """[Cout][9 Cin] (tap-major, channel-minor: the small convolutions' layout) -> [Cout][Cin][3][3]."""
+    co = w.shape[0]
+    return w.reshape(co, 9, cin).permute(0, 2, 1).reshape(co, cin, 3, 3)
+
+
+def small_conv_in_ref(x, w, b, scale_sigma=None, pre_w=None, pre_b=None):
+    """fp64 reference of small_conv_in_kernel (misc.hip): x fp32 NCHW [n][cin][h][w], w fp16 [Cout][9 cin] tap-major, b fp16 -> y_hat
+    [n h w][Cout], bound.  The kernel's stated intermediate roundings are mirrored:
+      * v = half(x * inscale), inscale = 1 / sqrt(sigma^2 + 1) in fp32 (1 without scale_sigma: then v = half(x), reproduced exactly).  A
+        one-ulp difference of inscale between the device and this mirror can flip the fp16 rounding of an input: e_v = U |v| with scale_sigma;
+      * the 1x1 pre-conv t = half(pre_b + pre_w v) (fp32 on the device, fp64 here: the rounding of t can flip): e_t = |pre_w| e_v + U |t|;
+        it applies inside the image only — the 3x3 taps outside it read zeros, not pre_b;
+      * the input-side error reaches the output as im2col(e) |w|^T; accumulation from the bias in fp32: c_acc(9 cin) (absdot + |b|);
+      * the fp16 store: U |y| + TINY.
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): worst error / bound 0.994, signed bias below 1e-5 from 2000 elements on, 6.8e-5 at 72 elements."""
+    n, cin, h, wd = x.shape
+    if scale_sigma is not None:
+        sg = scale_sigma.float().to(x.device)
+        inscale = 1.0 / torch.sqrt(sg * sg + 1.0)
+        v = (x.float() * inscale.reshape(n, 1, 1, 1)).half()
+        e = U * v.double().abs()
+    else:
+        v = x.float().half()
+        e = torch.zeros_like(v, dtype=torch.float64)
+    vd = v.double()
+    if pre_w is not None:
+        pw, pb = pre_w.double().to(x.device), pre_b.double().to(x.device)
+        t = torch.einsum("oc,nchw->nohw", pw, vd) + pb.reshape(1, -1, 1, 1)
+        th = t.half()
+        e = torch.einsum("oc,nchw->nohw", pw.abs(), e) + U * th.double().abs()
+        vd = th.double()
+    wo = tapmajor_to_oihw(w.to(x.device), cin)
+    wm = wo.double().reshape(wo.shape[0], -1)
+    cols = im2col(vd.permute(0, 2, 3, 1), 3)
+    ecols = im2col(e.permute(0, 2, 3, 1), 3)
+    bd = b.double().to(x.device)
+    y = cols @ wm.t() + bd
+    absdot = cols.abs() @ wm.abs().t()
+    bound = ecols @ wm.abs().t() + c_acc(9 * cin) * (absdot + bd.abs()) + U * y.abs() + TINY
+    return y, bound
+
+
+def _fp16_ulp(a):
+    """Spacing of the fp16 numbers around |a| (the larger one at a power of two)."""
+    _, e = torch.frexp(a.abs().clamp_min(2.0 ** -30))
+    return torch.pow(2.0, (e - 11).double()).clamp_min(2.0 ** -24)
+
+
+def small_conv_out_ref(x, w, b, mode, x_in=None, sigma=None, in_mod=0):
+    """fp64 reference of small_conv_out_kernel (misc.hip): x fp16 NHWC, w fp16 [Cout][9 Cin] tap-major -> (y_hat, bound) in the layout the
+    kernel writes (mode 1: [n h w][Cout]; modes 0, 2: NCHW [n][Cout][h][w]).  v = conv + b: packed fp16 dot products accumulated in fp32 per lane,
+    a shuffle tree and the bias add:  e_v = c_acc(9 Cin) (absdot + |b|) + 2^-23 |v|.  No fp16 store: the outputs are fp32.
+      mode 2: v.                                                       bound e_v
+      mode 1: clamp((v + 1) / 2, 0, 1) (1-Lipschitz).                   bound e_v / 2 + 2^-23 (|v| + 1) / 2
+      mode 0: x_in - eps sigma with eps = half(v), mirrored as half(v_hat): the device's eps is the same fp16 number unless v_hat lies within e_v
+              of a rounding boundary, where it may be the neighbour: bound = sigma ulp16(v) there, + 2^-23 (|x_in| + 2 |eps sigma|) everywhere.
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): worst error / bound 0.20 (mode 2), 0.16 (mode 1), 1.000 (mode 0: where eps may be the
+    neighbouring fp16 number it sometimes is — the bound there IS that step; 0.45 elsewhere), signed bias below 3e-7."""
+    n, h, wd, cin = x.shape
+    co = w.shape[0]
+    cols = im2col(x, 3)
+    wm = tapmajor_to_oihw(w.to(x.device), cin).double().reshape(co, -1)
+    y = cols @ wm.t()
+    absdot = cols.abs() @ wm.abs().t()
+    bd = b.double().to(x.device)
+    v = y + bd
+    e_v = c_acc(9 * cin) * (absdot + bd.abs()) + 2.0 ** -23 * v.abs() + 1e-30
+    nchw = lambda t: t.reshape(n, h, wd, co).permute(0, 3, 1, 2)
+    if mode == 2:
+        return nchw(v), nchw(e_v)
+    if mode == 1:
+        return ((v + 1.0) * 0.5).clamp(0.0, 1.0), 0.5 * e_v + 2.0 ** -24 * (v.abs() + 1.0)
+    eps = v.half().double()
+    ulp = torch.maximum(_fp16_ulp(v), _fp16_ulp(eps))
+    flip = (0.5 * ulp - (v - eps).abs()) <= e_v
+    idx = torch.arange(n, device=x.device) % (in_mod if in_mod > 0 else n)
+    sg = sigma.double().to(x.device)[idx].reshape(n, 1, 1, 1)
+    xi = x_in.double().to(x.device)[idx]
+    out = xi - nchw(eps) * sg
+    bound = nchw(flip.double() * ulp) * sg.abs() + 2.0 ** -23 * (xi.abs() + 2.0 * (nchw(eps) * sg).abs()) + 1e-30
+    return out, bound
+
+
+def small_pointwise_ref(x, w, b):
+    """fp64 out [n][C][hw] = b + w x of x fp16 [n][hw][8] (small_pointwise_kernel: fp32 chain of 8, rounded to fp16, stored as fp32):
+    bound U |y| + c_acc(8) (absdot + |b|) + TINY.
+    Observed on the MI355X: worst error / bound 0.998, signed bias 1.6e-7 at 2.4e6 elements."""
+    xd, wd, bd = x.double(), w.double().to(x.device), b.double().to(x.device)
+    y = xd @ wd.t() + bd
+    bound = U * y.abs() + c_acc(8) * (xd.abs() @ wd.abs().t() + bd.abs()) + TINY
+    return y.transpose(1, 2), bound.transpose(1, 2)
+
+
+def vae_out_finish_ref(t8, cout):
+    """fp64 clamp((v + 1) / 2, 0, 1) of the first cout columns of t8 fp16 [npix][8]: one fp32 add (the halving is exact): bound 2^-24 (|v| + 1).
+    Observed on the MI355X: worst error / bound 0.50, signed bias 2e-13."""
+    v = t8.double().reshape(-1, 8)[:, :cout]
+    return ((v + 1.0) * 0.5).clamp(0.0, 1.0), 2.0 ** -24 * (v.abs() + 1.0)
+
+
+def timestep_ref(sigma, log_sigmas, dim, n=None, sigma_mod=0):
+    """The timestep lookup and sinusoidal embedding of timestep_embed_kernel (misc.hip) in fp64 from the fp32 sigma and table:
+    t [n] (the first-occurrence argmin of |log sigma - log_sigmas|, exact), margin [n] (how far the runner-up VALUE's distance lies above the best:
+    a case is well posed for an fp32 logf when this is >> 1e-6), emb_hat [n][dim] = [cos(t f) | sin(t f)], bound:
+        U                                   the fp16 store of a value in [-1, 1] (absolute)
+      + 2^-23 t f (|x| + 2)                 f = expf(x), x = -ln(1e4) i / half in fp32: x's two roundings make f off by 2^-23 |x| relative, expf and
+                                            the product t f another 2^-23 — argument rounding, largest at t = 999 near |x| = 1
+      + 2^-22                               cosf / sinf.
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): t exact in every case; worst error / bound 0.499 (the store), signed bias below 3.5e-5."""
+    sg = sigma.double().flatten()
+    n = sg.numel() if n is None else n
+    if sigma_mod > 0:
+        sg = sg[torch.arange(n, device=sg.device) % sigma_mod]
+    tab = log_sigmas.double().flatten().to(sg.device)
+    dist = (sg.log().unsqueeze(1) - tab.unsqueeze(0)).abs()              # [n][n_sig]
+    t = dist.argmin(dim=1)
+    best = dist.gather(1, t.unsqueeze(1))
+    other = dist.masked_fill(tab.unsqueeze(0) == tab[t].unsqueeze(1), float("inf"))
+    margin = (other.amin(dim=1, keepdim=True) - best).flatten()
+    half = dim // 2
+    xarg = -math.log(10000.0) * torch.arange(half, dtype=torch.float64, device=sg.device) / half
+    f = xarg.exp()
+    arg = t.double().unsqueeze(1) * f.unsqueeze(0)
+    emb = torch.cat([arg.cos(), arg.sin()], dim=1)
+    b = U + 2.0 ** -23 * arg * (xarg.abs().unsqueeze(0) + 2.0) + 2.0 ** -22
+    return t, margin, emb, torch.cat([b, b], dim=1)
+
+
+def mlp_out_fold_ref(wpo, w2, b2, bpo):
+    """fp64 W' [C][5C] = [Wpo W2 | Wpo] and b' = Wpo b2 + bpo from the fp16 weights (mlp_out_fold_kernel: fp32 chains of C, one rounding):
+    (w_hat, w_bound, b_hat, b_bound) with  U |w'| + c_acc(C) sum|Wpo||W2| + TINY;  the identity columns [4C, 5C) are copies: bound 1e-300 there
+    (any difference fails; the test also compares them bitwise).
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): worst error / bound 0.993 (W'), 0.985 (b'), signed bias 6.4e-7 (W'), 2.2e-5 (b', 64 elements)."""
+    a, m = wpo.double(), w2.double()
+    c = a.shape[0]
+    prod = a @ m
+    pb = U * prod.abs() + c_acc(c) * (a.abs() @ m.abs()) + TINY
+    bh = a @ b2.double() + bpo.double()
+    bb = U * bh.abs() + c_acc(c) * (a.abs() @ b2.double().abs() + bpo.double().abs()) + TINY
+    return torch.cat([prod, a], dim=1), torch.cat([pb, torch.full_like(a, 1e-300)], dim=1), bh, bb
+
+
+def ln_fold_ref(w, gamma, beta, bias=None):
+    """fp64 W' = W diag(gamma) and b' = bias + W beta from the fp16 inputs (ln_fold_kernel): (w_hat, w_bound, b_hat, b_bound).
+    W': an fp16 x fp16 product is exact in fp32, so its one rounding is U |w'| + TINY;  b': U |b'| + c_acc(K) (sum|W||beta| + |bias|) + TINY.
+    wsum is checked against the DEVICE's rounded W' (wsum_ref).
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): W' bitwise half(w gamma) (error / bound 0.996, bias 1.6e-6); b' 0.963, bias 3.3e-5 at 192
+    elements; wsum 0.067 of its bound."""
+    wd, ga, be = w.double(), gamma.double(), beta.double()
+    k = wd.shape[1]
+    wh = wd * ga
+    b0 = torch.zeros(wd.shape[0], dtype=torch.float64, device=w.device) if bias is None else bias.double()
+    bh = b0 + wd @ be
+    bb = U * bh.abs() + c_acc(k) * (wd.abs() @ be.abs() + b0.abs()) + TINY
+    return wh, U * wh.abs() + TINY, bh, bb
+
+
+def wsum_ref(w_out):
+    """fp64 row sums of the device's fp16 W' and the bound of their fp32 sum: c_acc(K) sum|W'| (+ 1e-30: an all-zero row is exact)."""
+    wd = w_out.double()
+    return wd.sum(-1), c_acc(wd.shape[1]) * wd.abs().sum(-1) + 1e-30

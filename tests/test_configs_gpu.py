@@ -169,7 +169,9 @@ def test_vae_decode_non_square_bands_against_oracle():
 
 
 def test_vae_latents_not_multiple_of_8():
-    """5x7 and 3x3 latents: the mid-block attention's key axis (h*w = 35 / 9) is not a multiple of 8 (padded, masked softmax)."""
+    """5x7 and 3x3 latents: the mid-block attention's key axis (h*w = 35 / 9) is not a multiple of 8.  The mid width here is 256, so this runs
+    flash_attn512_kernel's masked variant (the last key tile is partly padding); the three-GEMM fallback with its padded, masked row softmax is
+    test_vae_fallback_attention's."""
     from lightdiffusion_amd.unet import synthetic_vae
     from oracle import sd15_ref as O
     cfg = W.tiny_vae_config()
@@ -181,6 +183,28 @@ def test_vae_latents_not_multiple_of_8():
         img = v.decode(z)
         ref = O.vae_decode(sdv, cfg, z)
         assert img.shape == ref.shape and float((img - ref).abs().max()) < 2.0 / 255.0
+
+
+def test_vae_fallback_attention():
+    """A mid width that is neither 256 nor 512 takes VRun::attn's fallback: three batched GEMMs (n_valid, bias_m, batch strides) around
+    softmax_rows_kernel with ld = Lp, valid = L.  Both committed configs have a mid width of 256 or 512, so only a synthetic one reaches it:
+    ch = 64 with ch_mult [1, 1, 1, 1] (mid width 64) is the smallest the decoder builds — every level's width must be a multiple of 64 and
+    decode() is fixed at 8x, four levels.  Latents 5x7 (L = 35, Lp = 40), 8x8 (L = Lp) and 3x3 at batch 2 (L = 9, Lp = 16, a batch stride)."""
+    from lightdiffusion_amd.unet import synthetic_vae
+    from oracle import sd15_ref as O
+    cfg = dict(z_channels=4, ch=64, ch_mult=[1, 1, 1, 1], num_res_blocks=2, out_ch=3)
+    sdv = W.synth_state_dict(W.vae_decoder_param_shapes(cfg))
+    v = synthetic_vae(cfg, max_batch=2, max_hw=(8, 8))
+    g = torch.Generator().manual_seed(29)
+    for shape in ((1, 4, 5, 7), (1, 4, 8, 8), (2, 4, 3, 3)):
+        z = torch.randn(shape, generator=g)
+        img = v.decode(z)
+        ref = O.vae_decode(sdv, cfg, z)
+        assert img.shape == ref.shape and float((img - ref).abs().max()) < 2.0 / 255.0, shape
+        kinds = [r[4] for r in v.profile_decode(z)]
+        assert "softmax_rows_kernel" in kinds and not any(k.startswith("flash_attn512_kernel") for k in kinds), kinds
+    del v
+    torch.cuda.empty_cache()
 
 
 # ------------------------------------------------------------------ reference block goldens through the operator seam
