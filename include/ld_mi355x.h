@@ -16,6 +16,7 @@
  *   ld_vae_decode        VAE.decode (LD.py:6357-6381) = post_quant_conv + Decoder.forward (3470-3473, 3857-3882)
  *                        + process_output clamp + NCHW→NHWC.
  *   ld_esrgan_forward    RRDBNet.forward (LD.py:7025-7234), the model ImageUpscaleWithModel.upscale applies per tile (LD.py:7356-7395).
+ *   ld_taesd_decode      TAESD.decode (LD.py:749-754) on Decoder2 (714-721), the latent preview taesd_preview shows per sampler step (761-768).
  *   ld_op_*              single operators, for parity tests: the `operations=` classes of LD.py:2342-2429
  *                        (Linear / Conv2d / GroupNorm / LayerNorm) and optimized_attention (3966-3988).
  */
@@ -180,6 +181,33 @@ int ld_esrgan_last_launches(const ld_esrgan* e);
 /* 2 * pixels * cout * 9 cin over every convolution of the last forward, the two 3-channel ends included */
 double ld_esrgan_last_flops(const ld_esrgan* e);
 
+/* ------------------------------------------------------------------ TAESD latent preview (Decoder2 / TAESD.decode, LD.py:688-754) */
+typedef struct ld_taesd ld_taesd;
+
+/* The decoder has one shape; parameter names are the keys of taesd_decoder.safetensors (Decoder2's state dict), 67 tensors: 1.weight,
+ * 1.bias, {3,4,5,8,9,10,13,14,15,18}.conv.{0,2,4}.{weight,bias}, {7,12,17}.weight, 19.weight, 19.bias (weights OIHW).  vae_shift = 0 and
+ * vae_scale = 1 (LD.py:729-730) are not in that file and are those constants here. */
+int ld_taesd_create(ld_taesd** out);
+void ld_taesd_destroy(ld_taesd* t);
+int ld_taesd_param_count(const ld_taesd* t);
+int ld_taesd_param_info(const ld_taesd* t, int index, const char** name, int* ndim, int64_t shape[4]);
+int ld_taesd_load_param(ld_taesd* t, const char* name, const void* dev_src, int dtype, void* stream);
+int ld_taesd_reserve(ld_taesd* t, int max_b, int max_h, int max_w);   /* latent size */
+size_t ld_taesd_workspace_bytes(const ld_taesd* t);
+/* workspace bytes ld_taesd_reserve(b, h, w) would allocate (host-only dry run; 0 on an invalid shape) */
+size_t ld_taesd_plan_bytes(ld_taesd* t, int b, int h, int w);
+/* latent: [b][h][w][4] fp32 NHWC, the model-space x of the sampler loop; out_f32: [b][8h][8w][3] fp32 NHWC = (Decoder2(latent) - 0.5) * 2;
+ * out_u8 (may be NULL): [b][8h][8w][3] uint8 = uint8(clip(255 ((out_f32 + 1) * 0.5), 0, 255)), fp32 in that order, truncated.  Only
+ * enqueues on `stream`; allocates nothing once ld_taesd_reserve covers the shape (LD_ERR_SHAPE when it does not). */
+int ld_taesd_decode(ld_taesd* t, const float* latent, float* out_f32, void* out_u8, int b, int h, int w, void* stream);
+/* ld_taesd_decode with a HIP-event pair around every launch (synchronises the stream), and that run's per-launch table in the format of
+ * ld_unet_profile_launches */
+int ld_taesd_profile(ld_taesd* t, const float* latent, float* out_f32, void* out_u8, int b, int h, int w, void* stream);
+int ld_taesd_profile_launches(const ld_taesd* t, char* buf, size_t buf_bytes);
+int ld_taesd_last_launches(const ld_taesd* t);
+/* 2 * pixels * cout * 9 cin over every convolution of the last decode, the two ends included */
+double ld_taesd_last_flops(const ld_taesd* t);
+
 /* ------------------------------------------------------------------ single operators (fp16 device tensors unless noted) */
 /* y[M][N] = act(alpha * x[M][K] · w[N][K]^T + bias[N]) + residual[M][N];  act: 0 none, 1 SiLU, 3 quick-GELU, 2 GEGLU (w, bias in
  * checkpoint row order [value | gate]; y is [M][N/2]).  ws/ws_bytes: optional split-K scratch. */
@@ -324,6 +352,11 @@ int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int
  * through a nearest-2x upsampling (upconv_block, LD.py:6995-7022).  Pitches and c_off are multiples of 8.  LD_ERR_SHAPE otherwise. */
 int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
                       float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream);
+/* TAESD's 64 -> 64 convolution (stride 1, pad 1) on the same halo-tile main loop under its own epilogue (Block, LD.py:695-702):
+ *   y[n][h][w][64] = relu?(conv3x3(x; wt) + bias? + residual?)     (fp32, one rounding at the store)
+ * x, residual, y: fp16 NHWC of pitch 64; wt [64][9 * 64] as ld_op_repack_conv writes it; bias, residual may be NULL.  (h, w) is the output
+ * size; up != 0: x is [n][h/2][w/2][64] and is read through a nearest-2x upsampling (h, w even).  y overlapping x or residual: LD_ERR_ARG. */
+int ld_op_taesd_conv(const void* x, int n, int h, int w, int up, const void* wt, const void* bias, const void* residual, int relu, void* y, void* stream);
 /* tiled_scale's accumulation (LD.py:7326-7352), fp32 NHWC: out[oh][ow][c] += ps[th][tw][c] * my[y] * mx[x] at offset (y0, x0) and
  * div[oh][ow] += my[y] * mx[x] (my, mx: the tile's two 1-D feather ramps); ps == NULL: the final out /= div. */
 int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,

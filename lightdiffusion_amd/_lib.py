@@ -98,6 +98,19 @@ SIGNATURES = {
     "ld_esrgan_profile_launches": (_I, [_P, C.c_char_p, _Z]),
     "ld_esrgan_last_launches": (_I, [_P]),
     "ld_esrgan_last_flops": (C.c_double, [_P]),
+    "ld_taesd_create": (_I, [C.POINTER(_P)]),
+    "ld_taesd_destroy": (None, [_P]),
+    "ld_taesd_param_count": (_I, [_P]),
+    "ld_taesd_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "ld_taesd_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
+    "ld_taesd_reserve": (_I, [_P, _I, _I, _I]),
+    "ld_taesd_workspace_bytes": (_Z, [_P]),
+    "ld_taesd_plan_bytes": (_Z, [_P, _I, _I, _I]),
+    "ld_taesd_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ld_taesd_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ld_taesd_profile_launches": (_I, [_P, C.c_char_p, _Z]),
+    "ld_taesd_last_launches": (_I, [_P]),
+    "ld_taesd_last_flops": (C.c_double, [_P]),
     "ld_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _Z, _P]),
     "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_groupnorm_conv_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
@@ -139,6 +152,7 @@ SIGNATURES = {
     "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_esrgan_conv": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P]),
+    "ld_op_taesd_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "ld_op_tile_blend": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
     "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),

@@ -526,6 +526,13 @@ int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int 
     return noted(esrgan_conv_launch(a, (hipStream_t)stream), esrgan_last_kernel_name());
 }
 
+int ld_op_taesd_conv(const void* x, int n, int h, int w, int up, const void* wt, const void* bias, const void* residual, int relu, void* y, void* stream) {
+    op_begin();
+    return noted(taesd_conv_launch((const half_t*)x, n, h, w, up, (const half_t*)wt, (const half_t*)bias, (const half_t*)residual, relu, (half_t*)y,
+                                   (hipStream_t)stream),
+                 taesd_last_kernel_name());
+}
+
 int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
                      void* stream) {
     op_begin();

@@ -147,6 +147,7 @@ struct EsrganConvArgs {
     const half_t* r2 = nullptr;
     int ldr2 = 0;
     float s2 = 1.f;
+    int relu = 0;                   // read by TAESD's epilogue only (taesd.hip): v = relu?(acc + bias + r1)
 };
 int esrgan_conv_launch(const EsrganConvArgs& a, hipStream_t stream);
 const char* esrgan_last_kernel_name();   // instantiation the calling thread's last esrgan_conv_launch dispatched ("" = none)
@@ -154,6 +155,14 @@ const char* esrgan_last_kernel_name();   // instantiation the calling thread's l
 // ps == null: the final out /= div
 int tile_blend_launch(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
                       hipStream_t stream);
+
+// ---- taesd.hip: the TAESD decoder's convolutions (LD.py:688-721), fp16 NHWC of pitch 64 between them
+// 64 -> 64 on the halo-tile main loop of halo_conv.h: y = relu?(conv3x3(x) + bias? + residual?), fp32 to the one rounding at the store.
+// (h, w): the OUTPUT size; up != 0: x is [n][h / 2][w / 2][64] and is read through a nearest-2x upsampling.  y must not overlap x;
+// residual [n][h][w][64] may be any buffer but y.
+int taesd_conv_launch(const half_t* x, int n, int h, int w, int up, const half_t* wt, const half_t* bias, const half_t* residual, int relu, half_t* y,
+                      hipStream_t stream);
+const char* taesd_last_kernel_name();   // instantiation the calling thread's last taesd_conv_launch dispatched ("" = none)
 
 // ---- image.hip: uint8 images, HWC (masks HW) with a row pitch in bytes, bit-identical to Pillow (see the file's header)
 // separable resize of the in_w x in_h window at src to out_w x out_h: horizontal pass, then vertical, uint8 between them; a pass runs exactly when

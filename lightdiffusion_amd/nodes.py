@@ -21,6 +21,7 @@ import torch
 from . import sampling
 from . import weights as W
 from .clip import CLIP, CLIPTextModelHIP, LoraPatches, PromptTokenizer, _add_patches, patch_terms
+from .preview import LatentPreviewer, MI355XTAESD
 from .sampling import LATENT_SCALE, common_ksampler
 from .unet import MI355XUNet, MI355XVAE
 from .upscale import MI355XUpscaler, tiled_upscale
@@ -152,8 +153,13 @@ class CLIPSetLastLayer:
 
 
 class KSampler2:
-    def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0):
-        return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise)
+    def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
+               preview: Optional[LatentPreviewer] = None):
+        """`preview`: a LatentPreviewer that shows the running latent through TAESD every step, where the reference's sampler loops call
+        taesd_preview (LD.py:937, 1105, 1237); its `every` counts from this call's first step."""
+        if preview is not None:
+            preview.reset()
+        return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=preview)
 
 
 class LoraLoader:
@@ -236,6 +242,20 @@ class UpscaleModelLoader:
         return (MI355XUpscaler(cfg, CK.normalize_esrgan_keys(sd), device=self.device),)
 
 
+class TAESDLoader:
+    """load(name) -> (taesd,): the TAESD decoder of the latent preview from `taesd_decoder.safetensors` (LD.py:733-737), a path, a name
+    under `model_dir`, or a state dict with Decoder2's keys."""
+
+    def __init__(self, device="cuda:0", model_dir: Optional[str] = None):
+        self.device, self.model_dir = device, model_dir
+
+    def load(self, name="taesd_decoder.safetensors"):
+        if isinstance(name, (str, os.PathLike)):
+            name = os.fspath(name)
+            name = name if os.path.isabs(name) or self.model_dir is None else os.path.join(self.model_dir, name)
+        return (MI355XTAESD(name, device=self.device),)
+
+
 class ImageUpscaleWithModel:
     """upscale(upscale_model, image) -> (image,) (LD.py:7356-7395): tiled_scale with tile 512 / overlap 32 (the reference's constants),
     clamped to [0, 1]; host fp32 [B, H, W, 3] in, host fp32 [B, H s, W s, 3] out.  Runs on the model's device."""
@@ -267,6 +287,11 @@ class UltimateSDUpscale:
 def load_synthetic_upscaler(device="cuda:0", nb: int = 23, scale: int = 4, seed: int = 0) -> MI355XUpscaler:
     """An RRDBNet with deterministic random-init weights: the offline stand-in for RealESRGAN_x4plus.pth (LD.py:84-90)."""
     return MI355XUpscaler(W.esrgan_config(nb, scale), lambda name, shape: W.synth_tensor(name, shape, seed), device=device)
+
+
+def load_synthetic_taesd(device="cuda:0", seed: int = 0, **kw) -> MI355XTAESD:
+    """A TAESD decoder with deterministic random-init weights: the offline stand-in for taesd_decoder.safetensors (LD.py:92-98)."""
+    return MI355XTAESD(lambda name, shape: W.synth_tensor("taesd_decoder." + name, shape, seed), device=device, **kw)
 
 
 def _attach(unet: MI355XUNet, device) -> ModelPatcher:
@@ -320,14 +345,16 @@ class CheckpointLoaderSimple:
 
 
 def txt2img(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=512, batch_size=1, seed=0, steps=20, cfg=7.0,
-            sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False, upscale_model: Optional[MI355XUpscaler] = None):
+            sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False, upscale_model: Optional[MI355XUpscaler] = None,
+            preview: Optional[LatentPreviewer] = None):
     """The reference's headless `pipeline()` order (LD.py:10001-10086) with explicit arguments instead of hard-coded ones.
-    `*_tokens`: a prompt string (needs a tokenizer on `clip`) or pre-tokenised [[(id, weight), ...]] chunks."""
+    `*_tokens`: a prompt string (needs a tokenizer on `clip`) or pre-tokenised [[(id, weight), ...]] chunks.  `preview`: a LatentPreviewer
+    for the first sampler pass (the hires pass has another latent shape and runs without one)."""
     enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
     (pc, pp), (nc, npool) = enc(prompt_tokens), enc(negative_tokens)
     pos, neg = [[pc, {"pooled_output": pp}]], [[nc, {"pooled_output": npool}]]
     lat = EmptyLatentImage().generate(width, height, batch_size)[0]
-    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat)[0]
+    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, preview=preview)[0]
     if hires:   # hires-fix (LD.py:10585-10603): bislerp x2, then 10 Euler-a steps at denoise 0.45, cfg 8
         lat = LatentUpscale(model.load_device).upscale(lat, "bislerp", width * 2, height * 2)[0]
         lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45)[0]

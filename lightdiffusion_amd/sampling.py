@@ -472,11 +472,11 @@ def sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negativ
     return out.to("cpu")
 
 
-def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, **_ignored):
-    """LD.py:6657-6701."""
+def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, callback=None, **_ignored):
+    """LD.py:6657-6701.  `callback`: the sampler loop's per-step callback ({"x", "i", "sigma", "denoised"}), e.g. a preview.LatentPreviewer."""
     latent_image = latent["samples"]
     noise = prepare_noise(latent_image, seed, latent.get("batch_index"))
-    samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, seed=seed)
+    samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=callback, seed=seed)
     out = latent.copy()
     out["samples"] = samples
     return (out,)

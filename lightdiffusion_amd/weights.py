@@ -271,6 +271,27 @@ def esrgan_param_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
     return shp
 
 
+def taesd_decoder_param_shapes() -> Dict[str, Tuple[int, ...]]:
+    """Keys of taesd_decoder.safetensors = Decoder2's state dict (LD.py:714-721), in its order: 67 tensors.  The Sequential's indices:
+    1 the first convolution, {3,4,5 | 8,9,10 | 13,14,15 | 18} Blocks (`conv.{0,2,4}`), {7,12,17} the bias-free convolution behind each
+    nearest-2x upsampling, 19 the last convolution."""
+    shp: Dict[str, Tuple[int, ...]] = {"1.weight": (64, 4, 3, 3), "1.bias": (64,)}
+
+    def block(i):
+        for k in (0, 2, 4):
+            shp[f"{i}.conv.{k}.weight"] = (64, 64, 3, 3)
+            shp[f"{i}.conv.{k}.bias"] = (64,)
+
+    for s in range(3):
+        for j in range(3):
+            block(3 + 5 * s + j)
+        shp[f"{7 + 5 * s}.weight"] = (64, 64, 3, 3)
+    block(18)
+    shp["19.weight"] = (3, 64, 3, 3)
+    shp["19.bias"] = (3,)
+    return shp
+
+
 # ---------------------------------------------------------------- generator
 
 def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> torch.Tensor:
