@@ -259,12 +259,31 @@ def cpu_rows_conv(x, w_oihw, rows, stride=1, out_hw=None, x2=None):
     return torch.stack(out)
 
 
-def attention_ref(q, k, v, heads, causal=False, ones=None):
+def attention_ref(q, k, v, heads, causal=False, ones=None, p_subnormal=False):
     """fp64 softmax(q k^T / sqrt(d)) v on the device from the fp16 inputs ([b][L][heads d]) and its element bound:
         2 * 2^-11 |o_hat|                      output rounding + (without the ones column) P's rounding against an unrounded denominator
       + 2^-11 sum p |v - o_hat| / sum p          P rounded to fp16 (RTN: relative 2^-11 per weight)
       + sum p |ds| |v - o_hat| / sum p           Q * scale * log2(e) rounded once: |ds_j| <= 2^-11 scale sum_c |q_c| |k_jc|
-      + c_acc(Lk) sum p |v| / sum p + 2^-24     fp32 accumulation of O and the fp32 reciprocal."""
+      + c_acc(Lk) sum p |v| / sum p + 2^-24     fp32 accumulation of O and the fp32 reciprocal
+      + 2^-25 sum_{j in S} (|v_j| + |o_hat|)     P's subnormal range, S = {j: (s_j - max s) log2(e) < -14}: the kernels round P_j = 2^(s_j - m_ref)
+                                              to fp16 relative to a reference m_ref <= max s, so a weight computed below 2^-14 — only keys of
+                                              S can be — carries an ABSOLUTE error of up to 2^-25 (everything below 2^-25 becomes 0), not a
+                                              relative 2^-11; later moves of the reference only shrink it, and the denominator is >= 1 (the
+                                              maximum's own weight).  |v_j| + |o_hat| covers both denominators (the ones column sums the
+                                              rounded P, l_run the unrounded).  Only with p_subnormal=True (the peaked tests): on scores at
+                                              scale 1 S is empty but for one or two keys of a few d <= 16 rows (a spread of 15.6 exp2 units
+                                              at most over ATTN_ROUTES), and those rows keep the bound they had; under peaked scores S is
+                                              most keys of a row: 250 keys each 2^-20 of the peak move a |o_hat| of 2e-6 by 4e-7.
+    Observed on the MI355X over ATTN_PEAKED (tests/test_routes_gpu.py), worst error / bound and largest signed bias per pattern family, with
+    the same figures of the fp32 emulation of the recursion (tests/test_errbound_cpu.py) behind them:
+        spike    0.269,  2.0e-5   (emulation 0.255,  1.8e-5)        stairs   0.326, -2.5e-5   (emulation 0.326,  8.9e-6)
+        descend  0.318, -2.3e-5   (emulation 0.318, -2.0e-5)        onehot   0.405,  3.6e-5   (emulation 0.405, -2.8e-5)
+        offset   0.080, -2.5e-5   (emulation 0.059,  1.4e-5; with q0 = 4 sqrt(d) itself, whose scaled value rounds 2.2e-4 low in every row alike,
+                                   the bias was -2.35e-4 / -1.55e-4: attn_patterns._offset_q0 picks a q0 whose scaled value is an fp16 number)
+    all inside the plain BIAS_TOL.
+    Without the subnormal term one element of 262144 of flash_attn512_kernel<512,plain> under spike stood at error / bound 1.002, and the
+    emulation returned the same fp16 number.  (|v_j| + |o_hat| rather than |v_j - o_hat|: against the unrounded denominator l_run the error is
+    sum err_j v_j, which |v_j - o_hat| does not cover where the v_j are alike; and no [Lq][Lk][d] temporary, as above.)"""
     b, lq, c = q.shape
     lk = k.shape[1]
     d = c // heads
@@ -286,6 +305,9 @@ def attention_ref(q, k, v, heads, causal=False, ones=None):
     t_s = (p * ds) @ vd.abs() + (p * ds).sum(-1, keepdim=True) * o.abs()
     t_a = c_acc(lk) * pv
     bound = 2 * U * o.abs() + t_p + t_s + t_a + TINY
+    if p_subnormal:
+        sub = (((s - s.amax(-1, keepdim=True)) * 1.4426950408889634 < -14.0) & torch.isfinite(s)).double()
+        bound = bound + 2.0 ** -25 * (sub @ vd.abs() + sub.sum(-1, keepdim=True) * o.abs())
     back = lambda t: t.transpose(1, 2).reshape(b, lq, c)
     return back(o), back(bound)
 

@@ -104,6 +104,89 @@ def test_attention_bound_accepts_rtn_and_rejects_truncated_p(d):
     assert float(_simulated_attention(q, k, ones, heads, rtz=True).float().max()) < 1.0
 
 
+def _simulated_lazy_attention(q, k, v, heads, ones, causal, defect=None):
+    """The flash kernels' lazy-reference recursion in torch fp32 (attention.hip): Q * scale * log2(e) rounded to fp16 once; per 32-key
+    subtile the scores relative to the reference m_ref; the first subtile sets m_ref to its maximum, a later one moves it (per row) by
+    delta = its maximum where that exceeds TAU and by 0 elsewhere; a move scales O and l by alpha = 2^-delta and shifts the scores; P is
+    rounded to fp16 to nearest, the numerator sums the rounded P, the denominator the rounded P (`ones`: the spare V column of 1.0, part
+    of O) or the unrounded weights (l_run).  defect: 'o' O not rescaled, 'l' l_run not rescaled (the unrounded denominator only), 'shift'
+    scores not shifted after a move, 'wave' every row of a 32-row wave rescaled by the wave's largest delta (scores by their own)."""
+    import attn_patterns as AP
+    b, lq, c = q.shape
+    lk, d = k.shape[1], c // heads
+    c2 = float(torch.tensor(1.0 / math.sqrt(d), dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32))
+    qs = (q.float() * c2).half().float().reshape(b, lq, heads, d).transpose(1, 2)
+    kf = k.float().reshape(b, lk, heads, d).transpose(1, 2)
+    vf = v.float().reshape(b, lk, heads, d).transpose(1, 2)
+    m = torch.zeros(b, heads, lq, 1)
+    l = torch.zeros(b, heads, lq, 1)
+    o = torch.zeros(b, heads, lq, d)
+    rows = torch.arange(lq).view(lq, 1)
+    for t in range((lk + AP.SUB - 1) // AP.SUB):
+        keys = torch.arange(t * AP.SUB, min(lk, (t + 1) * AP.SUB))
+        s = qs @ kf[:, :, keys].transpose(-1, -2) - m
+        if causal:
+            s = s.masked_fill(keys.view(1, -1) > rows, float("-inf"))
+        mx = s.amax(-1, keepdim=True)
+        delta = mx if t == 0 else torch.where(mx > AP.TAU, mx, torch.zeros_like(mx))
+        dscale = delta
+        if defect == "wave" and t > 0:
+            pad = (-lq) % 32
+            dw = torch.cat([delta, torch.zeros(b, heads, pad, 1)], 2).view(b, heads, -1, 32, 1).amax(3, keepdim=True)
+            dscale = dw.expand(-1, -1, -1, 32, -1).reshape(b, heads, -1, 1)[:, :, :lq]
+        alpha = torch.exp2(-dscale)
+        m = m + delta
+        if not (defect == "shift" and t > 0):
+            s = s - delta
+        if defect != "o":
+            o = o * alpha
+        if not (defect == "l" or (defect == "o" and ones)):
+            l = l * alpha
+        p = torch.exp2(s)
+        ph = p.half().float()
+        o = o + ph @ vf[:, :, keys]
+        l = l + (ph if ones else p).sum(-1, keepdim=True)
+    return (o * (1.0 / l)).half().transpose(1, 2).reshape(b, lq, c)
+
+
+PEAKED_CPU_SHAPES = [(2, 2, 100, 192, False), (1, 2, 128, 128, True)]
+
+
+@pytest.mark.parametrize("b,heads,lq,lk,causal", PEAKED_CPU_SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("d", [8, 40, 64, 160])
+@pytest.mark.parametrize("pattern", ["spike", "stairs", "descend", "offset", "onehot"])
+def test_lazy_rescale_emulation_under_peaked_scores(pattern, d, b, heads, lq, lk, causal):
+    """The correct emulation of the lazy-reference recursion stays inside errbound.attention_ref's element bound and bias tolerance on every
+    peaked pattern of tests/attn_patterns.py, on both denominator paths; its onehot rows equal the key's v row bit for bit; spike and stairs
+    move the reference after the first subtile in at least a third of the rows."""
+    import attn_patterns as AP
+    q, k, v, facts = AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)
+    ref, bound = EB.attention_ref(q, k, v, heads, causal, p_subnormal=True)
+    for ones in (True, False):
+        y = _simulated_lazy_attention(q, k, v, heads, ones, causal)
+        r, s = EB.check(y, ref, bound, f"{pattern} d{d} ones={ones}")
+        print(f"{pattern} d{d} causal={causal} ones={ones}: error / bound {r:.3f}, signed bias {s:.2e}")
+        same = AP.onehot_rows_equal_v(y, v, heads, facts)
+        assert same is True, f"onehot rows differ from v: {facts['onehot'][~same].tolist()}"
+    late = float(facts["moves"].any(-1).double().mean())
+    if pattern in ("spike", "stairs"):
+        assert late >= 1.0 / 3.0, late
+
+
+@pytest.mark.parametrize("b,heads,lq,lk,causal", PEAKED_CPU_SHAPES, ids=lambda v: str(v))
+@pytest.mark.parametrize("d", [8, 40, 64, 160])
+@pytest.mark.parametrize("pattern", ["spike", "stairs"])
+def test_lazy_rescale_defects_are_rejected_by_the_element_bound(pattern, d, b, heads, lq, lk, causal):
+    """What a wrong rescale arm would return is outside the element bound: O not rescaled, l_run not rescaled (the unrounded denominator),
+    scores not shifted after a move, the wave's largest delta used for every lane's alpha."""
+    import attn_patterns as AP
+    q, k, v, _ = AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)
+    ref, bound = EB.attention_ref(q, k, v, heads, causal, p_subnormal=True)
+    for defect, ones in (("o", True), ("o", False), ("l", False), ("shift", True), ("shift", False), ("wave", True), ("wave", False)):
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(_simulated_lazy_attention(q, k, v, heads, ones, causal, defect), ref, bound, f"{pattern} d{d} {defect} ones={ones}")
+
+
 def test_cpu_conv_reference_matches_im2col():
     g = torch.Generator().manual_seed(5)
     x = torch.randn(2, 7, 5, 64, generator=g).half()
@@ -129,6 +212,61 @@ def test_every_contraction_kernel_template_has_a_route_row():
             "flash_attn2_kernel", "flash_attn512_kernel"} <= names
     pinned = {n.split("<")[0] for n in R.route_names()}
     assert not names - pinned, f"kernel templates without a route row: {sorted(names - pinned)}"
+
+
+def test_every_attention_route_has_a_peaked_row():
+    """An attention instantiation cannot land with flat-score coverage only: every flash_attn* route of ATTN_ROUTES is also a route of
+    ATTN_PEAKED, with all five patterns (the 8-wave rows, whose fp64 reference is a few GB, with spike and onehot at least)."""
+    import test_routes_gpu as R
+    peaked = {}
+    for row in R.ATTN_PEAKED:
+        if row[0] != "qkv":
+            peaked.setdefault(row[7], set()).update(row[8])
+    for route in sorted({row[-1] for row in R.ATTN_ROUTES}):
+        assert route.startswith("flash_attn"), route
+        want = {"spike", "onehot"} if route.endswith(",8>") else set(R.ALL_PATTERNS)
+        assert want <= peaked.get(route, set()), f"{route}: peaked patterns {sorted(peaked.get(route, set()))}, wanted {sorted(want)}"
+    assert {row[7] for row in R.ATTN_PEAKED if row[0] == "qkv"} >= {"flash_attn2_kernel<3,rowV,plain,4>", "flash_attn2_kernel<5,rowV,plain,4>",
+                                                                    "flash_attn2_kernel<10,rowV,plain,4>", "flash_attn512_kernel<512,plain>"}
+
+
+def test_peaked_inputs_hold_their_margins_for_every_route_row():
+    """attn_patterns.make asserts its conditions on the inputs (every threshold comparison outside the rounding window, every planted row at its
+    jump, onehot margins >= 40, at most one query in 8 rescaled, the offset rows' first references) while it builds: build every case of
+    ATTN_PEAKED here, and hold each case's facts to what its pattern is for."""
+    import attn_patterns as AP
+    import test_routes_gpu as R
+    for seam, b, heads, lq, lk, d, causal, route, pattern in R.ATTN_PEAKED_CASES:
+        facts = AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)[3]
+        moves, pl, jumps = facts["moves"], facts["planted"], facts["jumps"]
+        nsub, what = moves.shape[-1], (route, pattern, b, heads, lq, lk, d)
+        if pattern in ("spike", "stairs", "onehot"):
+            assert bool(moves[..., 2:].any()), what            # a move in a subtile of the second 64-key tile or later
+        if pattern == "onehot":
+            assert len(facts["onehot"]) >= 4 * b * heads, what
+        if pattern == "descend":
+            assert not bool(moves.any()) and len(pl) >= 16 * b * heads, what
+        if pattern == "spike":
+            # every position of a subtile (all 16 accumulator elements of both half-waves), every later subtile, the last valid key; at least
+            # a third of the jump-6 keys stand 6 .. TAU above the reference and leave it where it is (another row's key can share their subtile)
+            # (causal 77 x 77 has 45 later keys, two of three of them planted: 18 positions)
+            npos = len(set((pl[:, 3] % AP.SUB).tolist()))
+            assert npos == AP.SUB or (lk - AP.SUB < 2 * AP.SUB and 2 * npos >= AP.SUB), what
+            assert set(pl[:, 4].tolist()) == set(range(1, nsub)), what
+            assert causal or bool((pl[:, 3] == lk - 1).any()), what
+            six = pl[jumps == 6.0]
+            assert float((facts["gaps"][six[:, 0], six[:, 1], six[:, 2], six[:, 4]] < AP.TAU).double().mean()) >= 1.0 / 3.0, what
+            # some lanes of a wave move while others take delta = 0: at least an eighth of the (32-query wave, later subtile) pairs are mixed
+            # (at d <= 40 hardly a ROW stays flat throughout: every query sees every planted key at 1 / sqrt(d) of its score)
+            pad = (-lq) % 32
+            w = torch.cat([moves[..., 1:], torch.zeros(b, heads, pad, nsub - 1, dtype=torch.bool)], 2).view(b, heads, -1, 32, nsub - 1)
+            real = (torch.arange(lq + pad) < lq).view(1, 1, -1, 32, 1)
+            mixed = w.any(3) & ~(w | ~real).all(3)
+            assert float(mixed.double().mean()) >= 1.0 / 8.0, what
+        if pattern == "stairs":
+            # rows whose reference moves in EVERY later full subtile, and in the ragged last one as well (Lk = 161: it holds one key, so
+            # one planted row per (batch, head))
+            assert int(moves[..., 1:lk // AP.SUB].all(-1).sum()) >= 4 * b * heads and int(moves[..., 1:].all(-1).sum()) >= b * heads, what
 
 
 # ------------------------------------------------------------------ the references of the norm, boundary-conv and fold kernels (norm.hip, misc.hip)

@@ -9,6 +9,14 @@ the route it moved to has to get its own row.
 Bounds (tests/errbound.py): |y - y_hat| <= 2^-11 |y_hat| + c_acc(K) |A| |W| + L_act (2^-23 |pre| + ...) + eps_act + 2^-24, plus per extra fp16
 rounding of an operand (GroupNorm-normalised loader, LayerNorm-folded weights, attention's scaled Q and P) 2^-11 of that operand propagated;
 |mean signed error| / mean |y_hat| <= 2^-11 / 8 (+ the GELU fit's documented bias for GEGLU).
+
+ATTN_PEAKED / test_attention_route_peaked: randn inputs at scale 1 never move the attention's lazy softmax reference after the first 32-key
+subtile, so the rescale arm of flash_attn2_kernel / flash_attn512_kernel (O and l scaled, scores shifted, the MFMA's C operand rewritten) ran in
+no row of ATTN_ROUTES.  The peaked table runs every attention instantiation of ATTN_ROUTES on the inputs of tests/attn_patterns.py, whose moves an
+fp64 run of the recursion records and whose margins keep them independent of rounding: spike (one planted key per row in a later subtile, 6 / 10 /
+20 / 40 units above the reference, every position of the subtile, a flat row beside every two peaked ones), stairs (a move in every subtile),
+descend (all weight in the first subtile, the rest underflows in P), offset (every score of a row +-35 units away from zero), onehot (one key
+40 units above all others: the output row is that key's v row bit for bit).  Same route assertion, same element bound.
 """
 import math
 
@@ -108,6 +116,72 @@ def test_attention_unsupported_head_dims_rejected(ops):
         with pytest.raises(LDError):
             ops.attention(q, q, q, 1)
         assert ops.last_kernel() == ""
+
+
+# ------------------------------------------------------------------ attention under peaked scores: the lazy softmax rescale per route
+
+# (seam, b, heads, Lq, Lk, d, causal, expected route, patterns).  seam: 'vt' ops.attention (transposed V), 'rowv' ops.attention_rowv,
+# 'qkv' ops.attention_qkv (row pitch 3C, one batch stride).  The shapes are the smallest that cross a 64-key tile boundary with a move:
+# Lk = 192 is three full tiles, Lk = 161 leaves 33 keys in the last tile, one valid key alone in its second subtile.
+ALL_PATTERNS = ("spike", "stairs", "descend", "offset", "onehot")
+ATTN_PEAKED = []
+for _d, _dk in [(8, 1), (16, 1), (24, 2), (32, 2), (40, 3), (48, 3), (56, 4), (64, 4), (72, 5), (80, 5), (88, 6), (96, 6),
+                (120, 8), (128, 8), (152, 10), (160, 10)]:
+    for _rowv in (False, True):
+        _seam = "rowv" if _rowv else "vt"
+        ATTN_PEAKED.append((_seam, 2, 2, 100, 192, _d, False, _fa2(_dk, _rowv, False, 4), ALL_PATTERNS))
+        ATTN_PEAKED.append((_seam, 1, 2, 200, 161, _d, False, _fa2(_dk, _rowv, True, 4), ALL_PATTERNS))
+for _d, _dk in [(64, 4), (160, 10)]:
+    ATTN_PEAKED.append(("vt", 1, 2, 77, 77, _d, True, _fa2(_dk, False, True, 4), ALL_PATTERNS))
+    ATTN_PEAKED.append(("rowv", 1, 2, 128, 128, _d, True, _fa2(_dk, True, True, 4), ALL_PATTERNS))
+for _D in (256, 512):
+    ATTN_PEAKED.append(("rowv", 2, 1, 256, 256, _D, False, f"flash_attn512_kernel<{_D},plain>", ALL_PATTERNS))
+    ATTN_PEAKED.append(("rowv", 1, 1, 200, 161, _D, False, f"flash_attn512_kernel<{_D},masked>", ALL_PATTERNS))
+    ATTN_PEAKED.append(("rowv", 1, 1, 192, 192, _D, True, f"flash_attn512_kernel<{_D},masked>", ALL_PATTERNS))
+for _d, _dk in [(40, 3), (64, 4)]:
+    for _rowv in (False, True):
+        # 8-wave workgroups (the fp64 reference of one case is a few GB): two patterns
+        ATTN_PEAKED.append(("rowv" if _rowv else "vt", 8, 8, 2048, 192, _d, False, _fa2(_dk, _rowv, False, 8), ("spike", "onehot")))
+        ATTN_PEAKED.append(("rowv" if _rowv else "vt", 8, 8, 2048, 191, _d, False, _fa2(_dk, _rowv, True, 8), ("spike", "onehot")))
+for _d, _dk in [(40, 3), (80, 5), (160, 10)]:
+    ATTN_PEAKED.append(("qkv", 2, 8, 192, 192, _d, False, _fa2(_dk, True, False, 4), ("spike", "stairs")))       # the executors' own layout
+ATTN_PEAKED.append(("qkv", 2, 1, 256, 256, 512, False, "flash_attn512_kernel<512,plain>", ("spike", "stairs")))
+ATTN_PEAKED_CASES = [row[:8] + (pat,) for row in ATTN_PEAKED for pat in row[8]]
+
+
+@pytest.mark.parametrize("seam,b,heads,lq,lk,d,causal,route,pattern", ATTN_PEAKED_CASES, ids=lambda v: str(v))
+def test_attention_route_peaked(ops, seam, b, heads, lq, lk, d, causal, route, pattern):
+    """The same route, element bound and bias statistic as test_attention_route on inputs whose softmax reference moves after the first subtile
+    (tests/attn_patterns.py), and the onehot rows bit for bit."""
+    import attn_patterns as AP
+    q, k, v, facts = (t.to(DEV) if isinstance(t, torch.Tensor) else t for t in AP.make(pattern, b, heads, lq, lk, d, causal, seed=d))
+    if seam == "qkv":
+        o = ops.attention_qkv(torch.cat([q, k, v], -1).contiguous(), heads, causal=causal)
+    else:
+        o = _attn_call(ops, seam == "rowv", q, k, v, heads, causal)
+    assert ops.last_kernel() == route
+    ref, bound = EB.attention_ref(q, k, v, heads, causal, p_subnormal=True)
+    what = f"{route} {seam} {pattern} b{b} h{heads} Lq{lq} Lk{lk} d{d}"
+    same = AP.onehot_rows_equal_v(o, v, heads, facts)
+    try:
+        r, s = EB.check(o, ref, bound, what)
+    except AssertionError as e:
+        raise AssertionError(f"{e}\n{_peaked_context(str(e), facts, heads, d)}") from None
+    print(f"PEAKED {what}: error / bound {r:.3f}, signed bias {s:.2e}, rows with a late move "
+          f"{float(facts['moves'].any(-1).double().mean()):.2f}")
+    assert same is True, f"{what}: onehot rows differ from their key's v row (b, head, row, key): {facts['onehot'][~same.cpu()].tolist()}"
+
+
+def _peaked_context(msg, facts, heads, d):
+    """The recursion's facts of the query that errbound.check named as the worst element ('element (b, row, column)')."""
+    import re
+    m = re.search(r"element \((\d+), (\d+), (\d+)\)", msg)
+    if m is None:
+        return ""
+    bi, row, col = (int(x) for x in m.groups())
+    mv, gp = facts["moves"][bi, col // d, row], facts["gaps"][bi, col // d, row]
+    return (f"query (b {bi}, head {col // d}, row {row}): reference moves in subtiles {mv.nonzero().flatten().tolist()}, "
+            f"subtile maximum minus reference {[round(float(x), 2) for x in gp]}")
 
 
 # ------------------------------------------------------------------ linear (ld_op_linear / ld_op_linear_ln*)
