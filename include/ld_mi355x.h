@@ -403,6 +403,17 @@ int ld_op_u8_composite(void* canvas, int canvas_pitch, int cw, int ch, const voi
 int ld_op_u8_from_f32(const float* x, void* y, size_t n, void* stream);
 int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream);
 
+/* ---- CLIP text model input stage with textual-inversion vectors (CLIPEmbeddings + SDClipModel.set_up_textual_embeddings, LD.py:4394-4410, 4642-4690).
+ * out[b][l] = round_fp16(float(row(ids[b*L + l])) + float(pos[l])), fp16 [B, L, h].  `table` is the resident fp16 token table [V, h] (EOS = row V-1),
+ * `extra` the prompt's E custom vectors, fp32 [E, h] (may be NULL when E == 0), `pos` the fp16 position table (at least L rows of h).
+ *   id <  V-1          : table[id]
+ *   V-1 <= id < V-1+E  : extra[id - (V-1)]
+ *   id == V-1+E        : table[V-1]   (the remapped EOS: again the largest id)
+ * The table is read in place: nothing of V rows is built per prompt.  An id outside [0, V+E) reads no table memory and gives a row of zeros
+ * (callers range-check ids on the host; the guard only keeps a bad id from reading out of bounds).
+ * LD_ERR_SHAPE: h not a multiple of 8, a pointer not 16-byte aligned;  LD_ERR_ARG: a NULL pointer, a count < 1.  Nothing is launched then. */
+int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ CLIPTextModel_ (LD.py:4413-4463), CLIP.tokenize / encode_from_tokens / clip_laye
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+import logging
+from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -69,27 +70,60 @@ class PromptTokenizer:
     fewer than 8 tokens are never split across chunks; longer words are split and the chunk is closed with EOS."""
 
     max_word_length = 8
+    embedding_identifier = "embedding:"
 
     def __init__(self, word_tokenizer: Callable[[str], List[int]], max_length: int = 77, start_token: int = START_TOKEN,
-                 end_token: int = END_TOKEN, pad_with_end: bool = True):
+                 end_token: int = END_TOKEN, pad_with_end: bool = True, embedding_directory=None, embedding_size: int = 768,
+                 embedding_key: str = "clip_l"):
+        """`embedding_directory` (a path or a list of paths; None: no textual inversion, `embedding:x` is an ordinary word) is searched with
+        its sub-directories for the file a word `embedding:name` names; `embedding_size` is the text model's hidden size."""
         self.word_tokenizer = word_tokenizer
         self.max_length, self.start_token, self.end_token = max_length, start_token, end_token
         self.pad_token = end_token if pad_with_end else 0
+        self.embedding_directory, self.embedding_size, self.embedding_key = embedding_directory, embedding_size, embedding_key
 
     @classmethod
-    def from_pretrained(cls, tokenizer_dir: str) -> "PromptTokenizer":
+    def from_pretrained(cls, tokenizer_dir: str, embedding_directory=None, embedding_size: int = 768,
+                        embedding_key: str = "clip_l") -> "PromptTokenizer":
         """Build on HuggingFace's CLIPTokenizer files (the reference loads them from `_internal/sd1_tokenizer/`)."""
         from transformers import CLIPTokenizer
         tok = CLIPTokenizer.from_pretrained(tokenizer_dir)
         empty = tok("")["input_ids"]
-        return cls(lambda w: tok(w)["input_ids"][1:-1], start_token=empty[0], end_token=empty[1])
+        return cls(lambda w: tok(w)["input_ids"][1:-1], start_token=empty[0], end_token=empty[1], embedding_directory=embedding_directory,
+                   embedding_size=embedding_size, embedding_key=embedding_key)
 
-    def tokenize_with_weights(self, text: str) -> List[List[Tuple[int, float]]]:
-        words: List[List[Tuple[int, float]]] = []
+    def _try_get_embedding(self, name: str):
+        """(vectors or None, leftover text): `name` as it stands, else with the commas around it stripped — what follows the stripped name
+        is handed back to be tokenised as a word (SDTokenizer._try_get_embedding, LD.py:4917-4934)."""
+        from .embeddings import load_embed
+        embed = load_embed(name, self.embedding_directory, self.embedding_size, self.embedding_key)
+        if embed is None:
+            stripped = name.strip(",")
+            if len(stripped) < len(name):
+                return load_embed(stripped, self.embedding_directory, self.embedding_size, self.embedding_key), name[len(stripped):]
+        return embed, ""
+
+    def tokenize_with_weights(self, text: str) -> List[List[Tuple[Union[int, torch.Tensor], float]]]:
+        """77-slot chunks of (token, weight).  A token is an id, or — for a word `embedding:name` with an embedding directory set — one
+        fp32 vector of the named file: the file's rows form one group, chunked like a word's ids."""
+        words: List[List[Tuple[Union[int, torch.Tensor], float]]] = []
         for seg, w in parse_prompt_weights(escape_important(text), 1.0):
             for word in unescape_important(seg).replace("\n", " ").split(" "):
-                if word:
-                    words.append([(t, w) for t in self.word_tokenizer(word)])
+                if not word:
+                    continue
+                if word.startswith(self.embedding_identifier) and self.embedding_directory is not None:
+                    name = word[len(self.embedding_identifier):].strip("\n")
+                    embed, leftover = self._try_get_embedding(name)
+                    if embed is None:
+                        logging.warning("embedding:%s does not exist, ignoring", name)      # dropped: never BPE'd as if it were English
+                    elif embed.dim() == 1:
+                        words.append([(embed, w)])
+                    else:
+                        words.append([(embed[r], w) for r in range(embed.shape[0])])
+                    if leftover == "":
+                        continue
+                    word = leftover
+                words.append([(t, w) for t in self.word_tokenizer(word)])
         chunks: List[List[Tuple[int, float]]] = [[(self.start_token, 1.0)]]
         cur = chunks[0]
         room = self.max_length - 1                       # slots before the closing EOS
@@ -157,8 +191,8 @@ class CLIPTextModelHIP:
     """CLIP-L text transformer (CLIPTextModel_, LD.py:4413-4463) on the HIP kernels — the package's ONLY text model
     (the torch CPU restatement used by host-logic tests lives in oracle/sd15_ref.py: `clip_text_model`): LayerNorm, fused [q|k|v] projection, causal
     flash attention, out-projection + residual epilogue, fc1 + quick-GELU epilogue, fc2 + residual epilogue — all through
-    the C ABI (`ops`), fp16 storage / fp32 accumulation.  Only the embedding gather (77 rows) and the final row pick for the
-    pooled output stay torch indexing.  The reference computes this model in fp32; the conditioning it feeds is cast to
+    the C ABI (`ops`), fp16 storage / fp32 accumulation; the input stage (token gather + position add, with the prompt's textual-inversion
+    vectors read from a side table) is `ops.clip_embed`.  Only the final row pick for the pooled output stays torch indexing.  The reference computes this model in fp32; the conditioning it feeds is cast to
     fp16 by `apply_model` (LD.py:5846), so the tolerance here is the per-op fp16 one."""
 
     def __init__(self, cfg: dict, weights: Dict[str, torch.Tensor], device="cuda:0"):
@@ -220,13 +254,19 @@ class CLIPTextModelHIP:
         self.applied_patches_uuid = uuid if uuid is not None else object()   # (a direct call: matches no patcher, so the next lazy swap restores)
 
     @torch.no_grad()
-    def __call__(self, tokens: torch.Tensor, intermediate_output: Optional[int] = None):
+    def __call__(self, tokens: torch.Tensor, intermediate_output: Optional[int] = None, extra_embeds: Optional[torch.Tensor] = None):
+        """tokens [B, L] ids; `extra_embeds` [E, h] fp32: the prompt's textual-inversion vectors, selected by the ids V-1 .. V-2+E with EOS
+        moved to V-1+E (CLIP.remap_textual_embeddings).  The input stage is one gather kernel on the resident table and that side table."""
+        from . import ops
+        P = "text_model.embeddings."
+        extra = None if extra_embeds is None else extra_embeds.to(self.device, torch.float32).contiguous()
+        x, tokens = ops.clip_embed(tokens, self.w[P + "token_embedding.weight"], self.w[P + "position_embedding.weight"], extra)     # [B, L, h]
+        return self._encode(x, tokens, intermediate_output)
+
+    def _encode(self, x: torch.Tensor, tokens: torch.Tensor, intermediate_output: Optional[int]):
         from . import ops
         P = "text_model."
         h, heads, nl = self.cfg["hidden_size"], self.cfg["num_attention_heads"], self.cfg["num_hidden_layers"]
-        tokens = tokens.to(self.device)
-        x = (self.w[P + "embeddings.token_embedding.weight"][tokens].float() +
-             self.w[P + "embeddings.position_embedding.weight"].float()).half().contiguous()        # [B, 77, h]
         B, L = x.shape[:2]
         stop = None if intermediate_output is None else (nl + intermediate_output if intermediate_output < 0 else intermediate_output)
         inter = None
@@ -244,7 +284,7 @@ class CLIPTextModelHIP:
         x = ln(x, P + "final_layer_norm")
         if inter is not None:
             inter = ln(inter, P + "final_layer_norm")
-        pooled = x[torch.arange(B, device=self.device), tokens.to(torch.int).argmax(dim=-1)]
+        pooled = x[torch.arange(B, device=self.device), tokens.argmax(dim=-1)]      # the first EOS: the largest id, remapped or not
         return x.float(), None if inter is None else inter.float(), pooled.float()
 
 
@@ -253,7 +293,8 @@ class CLIP:
 
     def __init__(self, text_model, tokenizer: Optional[PromptTokenizer] = None, layer_idx: Optional[int] = None):
         """text_model(tokens[B, 77] long, intermediate_output=layer_idx) -> (last hidden state, hidden state at layer_idx or None, pooled):
-        `CLIPTextModelHIP` in the product."""
+        `CLIPTextModelHIP` in the product.  A prompt with textual-inversion vectors also passes extra_embeds=[E, h] fp32 and needs the model's
+        `cfg` (vocab_size, hidden_size) for the id remap."""
         self.text_model, self.tokenizer, self.layer_idx = text_model, tokenizer, layer_idx
         self.patches: Dict[str, list] = {}              # checkpoint key -> [(strength_patch, (up, down, alpha), strength_model)]
         self.patches_uuid = None                        # None: the loaded weights
@@ -302,19 +343,48 @@ class CLIP:
             raise RuntimeError("no tokenizer attached: build one with PromptTokenizer.from_pretrained(<sd1_tokenizer dir>)")
         return {"l": self.tokenizer.tokenize_with_weights(text)}
 
-    def _encode_ids(self, ids: List[List[int]]):
+    def remap_textual_embeddings(self, tokens: Sequence[Sequence[Union[int, torch.Tensor]]]):
+        """SDClipModel.set_up_textual_embeddings (LD.py:4642-4690) over all rows of a call, without its [V + E, h] table: (ids, side table).
+        With V the rows of the token table (EOS = V-1): every accepted vector gets the id V-1, V, ... in order of appearance and a row of
+        the fp32 [E, h] side table (None when E == 0); EOS becomes V-1+E, so it stays the largest id (the pooled pick is an argmax).
+        A vector whose length is not h is dropped with a warning, and its row is padded at the end, back to its length, with the LITERAL
+        pad id V-1.  That id is not remapped — the reference's quirk, kept as it is (its recorded conditioning decides): with E > 0 such a
+        pad slot selects the first custom vector, not EOS."""
+        cfg = self.text_model.cfg
+        V, h = cfg["vocab_size"], cfg["hidden_size"]
+        vectors, rows = [], []
+        for sec in tokens:
+            row = []
+            for t in sec:
+                if not isinstance(t, torch.Tensor):
+                    row.append(-1 if t == V - 1 else int(t))
+                elif t.shape[0] == h:
+                    row.append(V - 1 + len(vectors))
+                    vectors.append(t)
+                else:
+                    logging.warning("shape mismatch when trying to apply embedding, embedding will be ignored %d != %d", t.shape[0], h)
+            rows.append(row + [V - 1] * (len(sec) - len(row)))
+        eos = V - 1 + len(vectors)
+        ids = [[eos if t == -1 else t for t in row] for row in rows]
+        return ids, (torch.stack([v.to(torch.float32) for v in vectors]) if vectors else None)
+
+    def _encode_ids(self, ids: List[List[int]], extra_embeds: Optional[torch.Tensor] = None):
         self.patch_model()
-        last, inter, pooled = self.text_model(torch.tensor(ids, dtype=torch.long), intermediate_output=self.layer_idx)
+        kw = {} if extra_embeds is None else {"extra_embeds": extra_embeds}
+        last, inter, pooled = self.text_model(torch.tensor(ids, dtype=torch.long), intermediate_output=self.layer_idx, **kw)
         return (last if inter is None else inter).float(), pooled.float()
 
     def encode_from_tokens(self, tokens, return_pooled: bool = False):
-        pairs: Sequence[Sequence[Tuple[int, float]]] = tokens["l"] if isinstance(tokens, dict) else tokens
+        pairs: Sequence[Sequence[Tuple[Union[int, torch.Tensor], float]]] = tokens["l"] if isinstance(tokens, dict) else tokens
         ids = [[t for t, _ in sec] for sec in pairs]
         weighted = any(w != 1.0 for sec in pairs for _, w in sec)
         n = len(ids)
         if weighted or n == 0:
             ids = ids + [[START_TOKEN, END_TOKEN] + [END_TOKEN] * (max(len(s) for s in ids) - 2 if ids else 75)]
-        out, pooled = self._encode_ids(ids)
+        extra = None
+        if any(isinstance(t, torch.Tensor) for sec in ids for t in sec):       # (a prompt without embedding: words keeps its ids as they are)
+            ids, extra = self.remap_textual_embeddings(ids)
+        out, pooled = self._encode_ids(ids, extra)
         secs = []
         for k in range(n):
             z = out[k:k + 1]

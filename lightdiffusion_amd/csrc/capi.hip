@@ -587,4 +587,9 @@ int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream) {
     return f32_from_u8_launch((const uint8_t*)x, y, n, (hipStream_t)stream);
 }
 
+int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
+    op_begin();
+    return clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream);
+}
+
 }  // extern "C"

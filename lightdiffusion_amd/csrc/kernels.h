@@ -211,3 +211,10 @@ struct LoraArgs {
 int lora_merge_launch(const LoraArgs& a, hipStream_t stream);
 // resident layout -> checkpoint layout [rows][cols] (the inverse of the load-time repack; same index map as the merge)
 int lora_read_launch(const half_t* resident, const LoraLayout& lay, half_t* dst, hipStream_t stream);
+
+// ---- clip.hip
+// CLIP input stage: out[b][l] = round_fp16(float(row(ids[b][l])) + float(pos[l])); row(id) = table[id] (id < V-1), extra[id - (V-1)] (fp32 side table
+// of E textual-inversion vectors, V-1 <= id < V-1+E), table[V-1] (id == V-1+E: EOS stays the largest id); any other id: a row of zeros, no table read.
+// h a multiple of 8, pointers 16-byte aligned; pos holds at least L rows.
+int clip_embed_launch(const int* ids, const half_t* table, const float* extra, const half_t* pos, half_t* out, int B, int L, int V, int E, int h,
+                      hipStream_t stream);

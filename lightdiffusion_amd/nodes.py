@@ -301,10 +301,11 @@ def _attach(unet: MI355XUNet, device) -> ModelPatcher:
 
 
 def load_synthetic(device="cuda:0", max_batch: int = 1, max_hw=(64, 64), tiny: bool = False, seed: int = 0, tokenizer_dir: Optional[str] = None,
-                   max_tokens: int = 77):
+                   max_tokens: int = 77, embedding_directory=None):
     """(model, clip, vae) with deterministic random-init weights — the offline stand-in for a downloaded checkpoint.
     `max_batch` / `max_hw` / `max_tokens` only pre-size the workspaces: larger batches, latents (hires pass) or prompts
-    (more 77-token chunks) grow them on first use (MI355XUNet._ensure, MI355XVAE._ensure)."""
+    (more 77-token chunks) grow them on first use (MI355XUNet._ensure, MI355XVAE._ensure).  `embedding_directory`: where the tokenizer
+    looks for the textual-inversion files that `embedding:name` words name (the reference's `_internal/embeddings/`)."""
     ucfg, vcfg, ccfg = (W.tiny_unet_config(), W.tiny_vae_config(), W.tiny_clip_config()) if tiny else \
         (W.sd15_unet_config(), W.sd15_vae_config(), W.sd15_clip_config())
     if tiny:
@@ -312,7 +313,8 @@ def load_synthetic(device="cuda:0", max_batch: int = 1, max_hw=(64, 64), tiny: b
     gen = lambda name, shape: W.synth_tensor(name, shape, seed)
     unet = MI355XUNet(ucfg, gen, device=device, max_batch=2 * max_batch, max_hw=max_hw, max_tokens=max_tokens)
     vae = MI355XVAE(vcfg, gen, device=device, max_batch=max_batch, max_hw=max_hw, with_encoder=True)
-    tok = PromptTokenizer.from_pretrained(tokenizer_dir) if tokenizer_dir else None
+    tok = PromptTokenizer.from_pretrained(tokenizer_dir, embedding_directory=embedding_directory,
+                                          embedding_size=ccfg["hidden_size"]) if tokenizer_dir else None
     clip = CLIP(CLIPTextModelHIP(ccfg, W.synth_state_dict(W.clip_param_shapes(ccfg), seed), device=device), tok)
     return _attach(unet, device), clip, vae
 
@@ -322,8 +324,9 @@ class CheckpointLoaderSimple:
     architecture is detected from the keys (checkpoint.detect_*), weights are repacked on the device by the C library."""
 
     def __init__(self, device="cuda:0", max_batch: int = 1, max_hw=(64, 64), tokenizer_dir: Optional[str] = None,
-                 clip_heads: int = 12, unet_heads: int = 8, max_tokens: int = 77):
+                 clip_heads: int = 12, unet_heads: int = 8, max_tokens: int = 77, embedding_directory=None):
         self.device, self.max_batch, self.max_hw, self.tokenizer_dir = device, max_batch, max_hw, tokenizer_dir
+        self.embedding_directory = embedding_directory      # textual-inversion files for `embedding:name` (SD1ClipModel's embedding_directory, LD.py:6598)
         self.clip_heads, self.unet_heads, self.max_tokens = clip_heads, unet_heads, max_tokens
 
     def load_checkpoint(self, ckpt_name, output_vae=True, output_clip=True, lora=None, lora_strength: float = 1.0,
@@ -339,8 +342,10 @@ class CheckpointLoaderSimple:
         vcfg, has_enc = CK.detect_vae_config(sd)
         vae = MI355XVAE(vcfg, sd, device=self.device, max_batch=self.max_batch, max_hw=self.max_hw, with_encoder=has_enc)
         csd = CK.clip_state_dict(sd)
-        tok = PromptTokenizer.from_pretrained(self.tokenizer_dir) if self.tokenizer_dir else None
-        clip = CLIP(CLIPTextModelHIP(CK.detect_clip_config(csd, self.clip_heads), csd, device=self.device), tok)
+        ccfg = CK.detect_clip_config(csd, self.clip_heads)
+        tok = PromptTokenizer.from_pretrained(self.tokenizer_dir, embedding_directory=self.embedding_directory,
+                                              embedding_size=ccfg["hidden_size"]) if self.tokenizer_dir else None
+        clip = CLIP(CLIPTextModelHIP(ccfg, csd, device=self.device), tok)
         return _attach(unet, self.device), clip, vae
 
 

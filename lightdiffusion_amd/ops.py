@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import F16, F32, check, lib
+from ._lib import ERR_SHAPE, F16, F32, LDError, check, lib
 
 
 def _stream() -> int:
@@ -246,6 +246,30 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
     y = torch.empty_like(x)
     check(lib().ld_op_layernorm(_p(x), _p(gamma), _p(beta), _p(y), x.numel() // c, c, eps, _stream()), "ld_op_layernorm")
     return y
+
+
+def clip_embed(ids, table: torch.Tensor, pos: torch.Tensor, extra: Optional[torch.Tensor] = None):
+    """CLIP's input stage (CLIPEmbeddings, LD.py:4394-4410): out[b, l] = fp16(float(row(ids[b][l])) + float(pos[l])), fp16 [B, L, h].
+    `ids`: [B][L] host integers (a list or a tensor); `table` fp16 [V, h], resident; `extra` fp32 [E, h]: the prompt's textual-inversion
+    vectors.  row(id) = table[id] below V-1, extra[id - (V-1)] from V-1 to V-2+E, table[V-1] (EOS) at V-1+E.  The ids are range-checked here,
+    on the host, before they are uploaded (ValueError); nothing of V rows is allocated.  Returns (out, the ids as an int32 device tensor)."""
+    host = torch.as_tensor(ids).to("cpu", torch.int64)
+    if host.dim() != 2 or host.numel() == 0:
+        raise ValueError(f"clip_embed: ids must be [B][L], got shape {tuple(host.shape)}")
+    (V, h), E = table.shape, 0 if extra is None else extra.shape[0]
+    B, L = host.shape
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi > V - 1 + E:
+        raise ValueError(f"clip_embed: token id {lo if lo < 0 else hi} outside [0, {V - 1 + E}] (vocabulary {V}, {E} custom vectors)")
+    assert table.dtype == torch.float16 and pos.dtype == torch.float16 and pos.shape[1] == h, "fp16 token and position tables of one width"
+    if extra is not None:
+        assert extra.dtype == torch.float32 and extra.shape[1] == h, "custom vectors are fp32 [E, h]"
+    if L > pos.shape[0]:
+        raise LDError(ERR_SHAPE, f"ld_op_clip_embed: {L} tokens per row, the position table has {pos.shape[0]}")
+    dev = host.to(torch.int32).to(table.device)
+    out = torch.empty(B, L, h, dtype=torch.float16, device=table.device)
+    check(lib().ld_op_clip_embed(_p(dev), _p(table), _p(extra) if E else None, _p(pos), _p(out), B, L, V, E, h, _stream()), "ld_op_clip_embed")
+    return out, dev
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool = False) -> torch.Tensor:
