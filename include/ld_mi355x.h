@@ -357,6 +357,20 @@ int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int 
  * x, residual, y: fp16 NHWC of pitch 64; wt [64][9 * 64] as ld_op_repack_conv writes it; bias, residual may be NULL.  (h, w) is the output
  * size; up != 0: x is [n][h/2][w/2][64] and is read through a nearest-2x upsampling (h, w even).  y overlapping x or residual: LD_ERR_ARG. */
 int ld_op_taesd_conv(const void* x, int n, int h, int w, int up, const void* wt, const void* bias, const void* residual, int relu, void* y, void* stream);
+/* The end convolutions of the upscaler and of the preview decoder alone (3x3, stride 1, pad 1; the launchers ld_esrgan_forward and
+ * ld_taesd_decode call) — for parity tests.  Weights as ld_op_repack_conv writes them ([cout][ky][kx][cin]); pitches are multiples of 8 and
+ * at least 64; a NULL x, wt, bias or output: LD_ERR_ARG; n, h, w < 1, a bad pitch or more pixels than a grid holds: LD_ERR_SHAPE — both
+ * before any launch, and such a call leaves ld_op_last_kernel() as it was; a call that ran names its kernel there ("taesd_first_kernel").
+ *   esrgan_first: x fp32 NHWC [n][h][w][3], rounded to fp16 once -> y fp16 [n][h][w][0 .. 64) at pixel pitch ldy, and the same 64 values at
+ *                 y2 (pitch ldy2) when y2 != NULL.  No activation (conv_first, LD.py:7092-7099).
+ *   esrgan_last:  the first 64 channels of x fp16 NHWC (pitch ldx) -> out fp32 NHWC [n][h][w][3], unclamped (conv_last, LD.py:7141-7149).
+ *   taesd_first:  latent fp32 NHWC [n][h][w][4] -> relu(conv(round_fp16(3 tanh(x / 3))) + bias) fp16 [n][h][w][64] (LD.py:691-693, 716).
+ *   taesd_last:   x fp16 [n][h][w][64] -> out_f32 [n][h][w][3] = (conv + bias - 0.5) * 2 and, when out_u8 != NULL, the preview image
+ *                 uint8(clip(255 ((out_f32 + 1) * 0.5), 0, 255)) [n][h][w][3], truncated (LD.py:720, 753). */
+int ld_op_esrgan_first(const float* x, const void* wt, const void* bias, void* y, int ldy, void* y2, int ldy2, int n, int h, int w, void* stream);
+int ld_op_esrgan_last(const void* x, int ldx, const void* wt, const void* bias, float* out, int n, int h, int w, void* stream);
+int ld_op_taesd_first(const float* x, const void* wt, const void* bias, void* y, int n, int h, int w, void* stream);
+int ld_op_taesd_last(const void* x, const void* wt, const void* bias, float* out_f32, void* out_u8, int n, int h, int w, void* stream);
 /* tiled_scale's accumulation (LD.py:7326-7352), fp32 NHWC: out[oh][ow][c] += ps[th][tw][c] * my[y] * mx[x] at offset (y0, x0) and
  * div[oh][ow] += my[y] * mx[x] (my, mx: the tile's two 1-D feather ramps); ps == NULL: the final out /= div. */
 int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
@@ -364,6 +378,7 @@ int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, 
 /* The contraction kernel instantiations (GEMM / convolution / attention, the names the profile tables use) that the calling thread's
  * last ld_op_* call dispatched, in launch order, joined with ';' (e.g. "gemm3_kernel<64,160,conv>+splitk_reduce_kernel").  Reset at
  * the start of every ld_op_* call; "" when that call dispatched no contraction.  Valid until the thread's next ld_op_* call.
+ * (ld_op_esrgan_first / _last and ld_op_taesd_first / _last name their kernel too, and leave the string alone when they refuse a call.)
  * The two small convolutions name their instantiation too ("small_conv_in_kernel<3>", "small_conv_out_kernel<9,1>"). */
 const char* ld_op_last_kernel(void);
 /* The merge kernel of ld_unet_patch_param on a plain row-major matrix: dst[rows][cols] = round_fp16(float(base) + sum_j scale_j up_j down_j);

@@ -153,6 +153,10 @@ SIGNATURES = {
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_esrgan_conv": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P]),
     "ld_op_taesd_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
+    "ld_op_esrgan_first": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "ld_op_esrgan_last": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "ld_op_taesd_first": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ld_op_taesd_last": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ld_op_tile_blend": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
     "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),

@@ -533,6 +533,36 @@ int ld_op_taesd_conv(const void* x, int n, int h, int w, int up, const void* wt,
                  taesd_last_kernel_name());
 }
 
+// the 3- and 4-channel end convolutions of the upscaler and the preview decoder alone: for parity tests (the launchers the executors call).
+// A call the launcher refuses launched nothing and leaves ld_op_last_kernel() as it was.
+int ld_op_esrgan_first(const float* x, const void* wt, const void* bias, void* y, int ldy, void* y2, int ldy2, int n, int h, int w, void* stream) {
+    const int st = esrgan_first_launch(x, (const half_t*)wt, (const half_t*)bias, (half_t*)y, ldy, (half_t*)y2, ldy2, n, h, w, (hipStream_t)stream);
+    if (st != LD_OK) return st;
+    op_begin();
+    return noted(st, "esrgan_first_kernel");
+}
+
+int ld_op_esrgan_last(const void* x, int ldx, const void* wt, const void* bias, float* out, int n, int h, int w, void* stream) {
+    const int st = esrgan_last_launch((const half_t*)x, ldx, (const half_t*)wt, (const half_t*)bias, out, n, h, w, (hipStream_t)stream);
+    if (st != LD_OK) return st;
+    op_begin();
+    return noted(st, "esrgan_last_kernel");
+}
+
+int ld_op_taesd_first(const float* x, const void* wt, const void* bias, void* y, int n, int h, int w, void* stream) {
+    const int st = taesd_first_launch(x, (const half_t*)wt, (const half_t*)bias, (half_t*)y, n, h, w, (hipStream_t)stream);
+    if (st != LD_OK) return st;
+    op_begin();
+    return noted(st, "taesd_first_kernel");
+}
+
+int ld_op_taesd_last(const void* x, const void* wt, const void* bias, float* out_f32, void* out_u8, int n, int h, int w, void* stream) {
+    const int st = taesd_last_launch((const half_t*)x, (const half_t*)wt, (const half_t*)bias, out_f32, (uint8_t*)out_u8, n, h, w, (hipStream_t)stream);
+    if (st != LD_OK) return st;
+    op_begin();
+    return noted(st, "taesd_last_kernel");
+}
+
 int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
                      void* stream) {
     op_begin();

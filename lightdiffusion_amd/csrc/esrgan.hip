@@ -114,6 +114,26 @@ inline bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t b
 
 const char* esrgan_last_kernel_name() { return t_last_esrgan_kernel; }
 
+int esrgan_first_launch(const float* x, const half_t* wt, const half_t* bias, half_t* y, int ldy, half_t* y2, int ldy2, int n, int h, int w, hipStream_t stream) {
+    if (x == nullptr || wt == nullptr || bias == nullptr || y == nullptr) return LD_ERR_ARG;
+    if (n < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
+    if (ldy < 64 || (ldy & 7) || (y2 != nullptr && (ldy2 < 64 || (ldy2 & 7)))) return LD_ERR_SHAPE;
+    unsigned blocks = 0;
+    if (!end_conv_grid(n, h, w, 8, &blocks)) return LD_ERR_SHAPE;
+    hipLaunchKernelGGL(esrgan_first_kernel, dim3(blocks), dim3(256), 0, stream, x, wt, bias, y, ldy, y2, ldy2, n, h, w);
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
+int esrgan_last_launch(const half_t* x, int ldx, const half_t* wt, const half_t* bias, float* out, int n, int h, int w, hipStream_t stream) {
+    if (x == nullptr || wt == nullptr || bias == nullptr || out == nullptr) return LD_ERR_ARG;
+    if (n < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
+    if (ldx < 64 || (ldx & 7)) return LD_ERR_SHAPE;
+    unsigned blocks = 0;
+    if (!end_conv_grid(n, h, w, 1, &blocks)) return LD_ERR_SHAPE;
+    hipLaunchKernelGGL(esrgan_last_kernel, dim3(blocks), dim3(256), 0, stream, x, ldx, wt, bias, out, n, h, w);
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
 int esrgan_conv_launch(const EsrganConvArgs& a, hipStream_t stream) {
     t_last_esrgan_kernel = "";
     if (a.x == nullptr || a.wt == nullptr || a.y == nullptr) return LD_ERR_ARG;
@@ -238,13 +258,10 @@ int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h,
         ex.launch(KC_CONV3, 2.0 * a.n * a.h * (double)a.w * a.cout * 9.0 * a.cin, a.up ? "upconv3" : "dense3", (long long)a.n * a.h * a.w, a.cout, 9 * a.cin, 1,
                   esrgan_last_kernel_name, [&] { return esrgan_conv_launch(a, stream); });
     };
-    const auto launched = [] { return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP; };
 
     // conv_first: the trunk's input, and the first RRDB's (dense buffer 0 and the outer-residual copy)
     ex.launch(KC_MISC, 2.0 * npix * nf * 27, "conv_first", (long long)npix, nf, 27, 1, "esrgan_first_kernel", [&] {
-        hipLaunchKernelGGL(esrgan_first_kernel, dim3((unsigned)((npix * 8 + 255) / 256)), dim3(256), 0, stream, x, pt.ptr(e->first_w), pt.ptr(e->first_b), dense[0],
-                           ldd, trunk_in, nf, b, h, w);
-        return launched();
+        return esrgan_first_launch(x, pt.ptr(e->first_w), pt.ptr(e->first_b), dense[0], ldd, trunk_in, nf, b, h, w, stream);
     });
     if (!dry && ex.status == LD_OK)
         ex.note(hipMemcpyAsync(rrdb_in, trunk_in, npix * nf * sizeof(half_t), hipMemcpyDeviceToDevice, stream) == hipSuccess ? LD_OK : LD_ERR_HIP);
@@ -294,8 +311,7 @@ int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h,
     }
     const long long opix = (long long)b * H * W;
     ex.launch(KC_MISC, 2.0 * opix * c.out_nc * (9 * nf), "conv_last", opix, c.out_nc, 9 * nf, 1, "esrgan_last_kernel", [&] {
-        hipLaunchKernelGGL(esrgan_last_kernel, dim3((unsigned)((opix + 255) / 256)), dim3(256), 0, stream, hr, nf, pt.ptr(e->last_w), pt.ptr(e->last_b), out, b, H, W);
-        return launched();
+        return esrgan_last_launch(hr, nf, pt.ptr(e->last_w), pt.ptr(e->last_b), out, b, H, W, stream);
     });
     if (dry_peak != nullptr) *dry_peak = ar.peak;
     if (!dry) {

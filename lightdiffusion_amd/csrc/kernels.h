@@ -113,7 +113,6 @@ int dup_halves_launch(const DupArgs& a, hipStream_t stream);
 int repack_conv3x3_launch(const void* src, int src_is_f32, int O, int I, half_t* dst, hipStream_t stream);  // OIHW -> [O][ky][kx][I]
 int repack_rows_launch(const void* src, int src_is_f32, int rows, int cols, half_t* dst, int geglu_bn, hipStream_t stream);
 int ctx_pad_launch(const void* src, int src_is_f32, int n, int T, int Tp, int D, half_t* dst, hipStream_t stream);
-int fill_half_launch(half_t* dst, size_t n, float v, hipStream_t stream);
 
 // sampler / guidance elementwise (fp32 latents)
 int cfg_combine_launch(const float* den2, float* out, float cfg, size_t n_half, hipStream_t stream);   // out = u + (c-u)*cfg, den2=[u;c]
@@ -151,6 +150,21 @@ struct EsrganConvArgs {
 };
 int esrgan_conv_launch(const EsrganConvArgs& a, hipStream_t stream);
 const char* esrgan_last_kernel_name();   // instantiation the calling thread's last esrgan_conv_launch dispatched ("" = none)
+// The 3-channel ends of RRDBNet (LD.py:7092-7099, 7141-7149), one launch each.  conv_first: x fp32 NHWC [n][h][w][3], rounded to fp16 once,
+// wt [64][ky][kx][3], to 64 channels at y (pixel pitch ldy >= 64) and, when given, a second copy at y2 (pitch ldy2); conv_last: the first 64
+// channels of x (fp16 NHWC, pitch ldx >= 64), wt [3][ky][kx][64], to out fp32 NHWC [n][h][w][3].  Pitches are multiples of 8.
+int esrgan_first_launch(const float* x, const half_t* wt, const half_t* bias, half_t* y, int ldy, half_t* y2, int ldy2, int n, int h, int w, hipStream_t stream);
+int esrgan_last_launch(const half_t* x, int ldx, const half_t* wt, const half_t* bias, float* out, int n, int h, int w, hipStream_t stream);
+// blocks of 256 threads for n * h * w pixels of `per_pixel` work items each (the end convolutions of esrgan.hip / taesd.hip); false when
+// that is more than a grid's 2^31 - 1
+static inline bool end_conv_grid(int n, int h, int w, int per_pixel, unsigned* blocks) {
+    const long long nh = (long long)n * h;
+    if (nh > 0x7fffffffLL) return false;
+    const long long px = nh * w;                                   // below 2^62
+    if (px > 0x7fffffffLL * 256 / per_pixel) return false;
+    *blocks = (unsigned)((px * per_pixel + 255) / 256);
+    return true;
+}
 // tiled_scale's blend (LD.py:7326-7352), fp32: out[oh][ow][c] += ps[th][tw][c] * my[y] * mx[x] at (y0, x0), div[oh][ow] += my[y] * mx[x];
 // ps == null: the final out /= div
 int tile_blend_launch(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,
@@ -163,6 +177,11 @@ int tile_blend_launch(const float* ps, const float* my, const float* mx, int th,
 int taesd_conv_launch(const half_t* x, int n, int h, int w, int up, const half_t* wt, const half_t* bias, const half_t* residual, int relu, half_t* y,
                       hipStream_t stream);
 const char* taesd_last_kernel_name();   // instantiation the calling thread's last taesd_conv_launch dispatched ("" = none)
+// The ends of the decoder, one launch each.  first: latent fp32 NHWC [n][h][w][4] -> 3 tanh(x / 3) rounded to fp16 once, wt [64][ky][kx][4], bias,
+// ReLU -> y [n][h][w][64].  last: x [n][h][w][64], wt [3][ky][kx][64], bias -> out fp32 NHWC [n][h][w][3] = (v - 0.5) * 2 and, when img is
+// given, the preview image uint8(clip(255 (out + 1) / 2, 0, 255)) [n][h][w][3].
+int taesd_first_launch(const float* x, const half_t* wt, const half_t* bias, half_t* y, int n, int h, int w, hipStream_t stream);
+int taesd_last_launch(const half_t* x, const half_t* wt, const half_t* bias, float* out, uint8_t* img, int n, int h, int w, hipStream_t stream);
 
 // ---- image.hip: uint8 images, HWC (masks HW) with a row pitch in bytes, bit-identical to Pillow (see the file's header)
 // separable resize of the in_w x in_h window at src to out_w x out_h: horizontal pass, then vertical, uint8 between them; a pass runs exactly when

@@ -311,10 +311,6 @@ __global__ void ctx_pad_kernel(const T* src, int n, int Tk, int Tp, int D, half_
     }
 }
 
-__global__ void fill_half_kernel(half_t* dst, size_t n, float v) {
-    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) dst[q] = (half_t)v;
-}
-
 // ------------------------------------------------------------------------------------------------ sampler elementwise
 __global__ void cfg_combine_kernel(const float* den2, float* out, float cfg, size_t n) {
     for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
@@ -454,12 +450,6 @@ int ctx_pad_launch(const void* src, int src_is_f32, int n, int T, int Tp, int D,
         hipLaunchKernelGGL(ctx_pad_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, stream, (const float*)src, n, T, Tp, D, dst);
     else
         hipLaunchKernelGGL(ctx_pad_kernel<half_t>, dim3(grid_for(total, 256)), dim3(256), 0, stream, (const half_t*)src, n, T, Tp, D, dst);
-    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
-}
-
-int fill_half_launch(half_t* dst, size_t n, float v, hipStream_t stream) {
-    if (dst == nullptr) return LD_ERR_ARG;
-    hipLaunchKernelGGL(fill_half_kernel, dim3(grid_for((long long)n, 256)), dim3(256), 0, stream, dst, n, v);
     return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
 }
 

@@ -104,6 +104,24 @@ inline bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t b
 
 const char* taesd_last_kernel_name() { return t_last_taesd_kernel; }
 
+int taesd_first_launch(const float* x, const half_t* wt, const half_t* bias, half_t* y, int n, int h, int w, hipStream_t stream) {
+    if (x == nullptr || wt == nullptr || bias == nullptr || y == nullptr) return LD_ERR_ARG;
+    if (n < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
+    unsigned blocks = 0;
+    if (!end_conv_grid(n, h, w, 8, &blocks)) return LD_ERR_SHAPE;
+    hipLaunchKernelGGL(taesd_first_kernel, dim3(blocks), dim3(256), 0, stream, x, wt, bias, y, n, h, w);
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
+int taesd_last_launch(const half_t* x, const half_t* wt, const half_t* bias, float* out, uint8_t* img, int n, int h, int w, hipStream_t stream) {
+    if (x == nullptr || wt == nullptr || bias == nullptr || out == nullptr) return LD_ERR_ARG;
+    if (n < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
+    unsigned blocks = 0;
+    if (!end_conv_grid(n, h, w, 1, &blocks)) return LD_ERR_SHAPE;
+    hipLaunchKernelGGL(taesd_last_kernel, dim3(blocks), dim3(256), 0, stream, x, wt, bias, out, img, n, h, w);
+    return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
 int taesd_conv_launch(const half_t* x, int n, int h, int w, int up, const half_t* wt, const half_t* bias, const half_t* residual, int relu, half_t* y,
                       hipStream_t stream) {
     t_last_taesd_kernel = "";
@@ -192,7 +210,6 @@ int taesd_run(ld_taesd* t, bool dry, const float* latent, float* out, uint8_t* i
     const ParamTable& pt = t->pt;
     const size_t opix = (size_t)b * h * w * 64;
     half_t* buf[3] = {ar.halfs(opix * 64), ar.halfs(opix * 64), ar.halfs(opix * 64)};
-    const auto launched = [] { return hipGetLastError() == hipSuccess ? LD_OK : LD_ERR_HIP; };
     int H = h, W = w, cur = 0;
 
     auto conv = [&](const half_t* x, int up, int wslot, int bslot, const half_t* res, int relu, half_t* y) {
@@ -209,9 +226,7 @@ int taesd_run(ld_taesd* t, bool dry, const float* latent, float* out, uint8_t* i
 
     const long long npix = (long long)b * h * w;
     ex.launch(KC_MISC, 2.0 * npix * 64 * 36, "conv_first", npix, 64, 36, 1, "taesd_first_kernel", [&] {
-        hipLaunchKernelGGL(taesd_first_kernel, dim3((unsigned)((npix * 8 + 255) / 256)), dim3(256), 0, stream, latent, pt.ptr(t->first_w), pt.ptr(t->first_b),
-                           buf[0], b, h, w);
-        return launched();
+        return taesd_first_launch(latent, pt.ptr(t->first_w), pt.ptr(t->first_b), buf[0], b, h, w, stream);
     });
     int k = 0;
     for (int s = 0; s < 3; ++s) {
@@ -223,9 +238,7 @@ int taesd_run(ld_taesd* t, bool dry, const float* latent, float* out, uint8_t* i
     block(k);
     const long long lpix = (long long)b * H * W;
     ex.launch(KC_MISC, 2.0 * lpix * 3 * 576, "conv_last", lpix, 3, 576, 1, "taesd_last_kernel", [&] {
-        hipLaunchKernelGGL(taesd_last_kernel, dim3((unsigned)((lpix + 255) / 256)), dim3(256), 0, stream, buf[cur], pt.ptr(t->last_w), pt.ptr(t->last_b), out, img,
-                           b, H, W);
-        return launched();
+        return taesd_last_launch(buf[cur], pt.ptr(t->last_w), pt.ptr(t->last_b), out, img, b, H, W, stream);
     });
     if (dry_peak != nullptr) *dry_peak = ar.peak;
     if (!dry) {

@@ -456,14 +456,52 @@ def axpby_(x: torch.Tensor, a: float, y: Optional[torch.Tensor] = None, b: float
     return x
 
 
-def bislerp(samples: torch.Tensor, width: int, height: int) -> torch.Tensor:
-    """bislerp(samples, width, height) of LD.py:429-518 on the device: [n,c,h,w] -> [n,c,height,width] (fp32 math)."""
+def bislerp(samples: torch.Tensor, width: int, height: int, tmp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bislerp(samples, width, height) of LD.py:429-518 on the device: [n,c,h,w] -> [n,c,height,width] (fp32 math).  tmp: an fp32 [n,c,h,width]
+    tensor that receives the width pass's result (the height pass's input), for a caller that wants to look at it."""
     x = samples.float().contiguous()
     n, c, h, w = x.shape
-    tmp = torch.empty(n, c, h, width, dtype=torch.float32, device=x.device)
+    if tmp is None:
+        tmp = torch.empty(n, c, h, width, dtype=torch.float32, device=x.device)
+    assert tmp.dtype == torch.float32 and tuple(tmp.shape) == (n, c, h, width)
     y = torch.empty(n, c, height, width, dtype=torch.float32, device=x.device)
     check(lib().ld_op_bislerp(_p(x), _p(tmp), _p(y), n, c, h, w, height, width, _stream()), "ld_op_bislerp")
     return y.to(samples.dtype)
+
+
+# ------------------------------------------------------------------ the end convolutions of the upscaler and the preview decoder, for parity tests
+# Weights fp16 [cout][9 cin], tap-major and channel-minor (what repack_conv_weight writes); x and the results NHWC.
+def esrgan_first(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, y: torch.Tensor, y2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_first of RRDBNet: x fp32 [n,h,w,3] -> channels [0, 64) of y fp16 [n,h,w,ldy] (the rest of y untouched), and y2 [n,h,w,ldy2] likewise."""
+    n, h, w, _ = x.shape
+    check(lib().ld_op_esrgan_first(_p(x), _p(wt), _p(bias), _p(y), y.shape[-1], _p(y2), 0 if y2 is None else y2.shape[-1], n, h, w, _stream()),
+          "ld_op_esrgan_first")
+    return y
+
+
+def esrgan_last(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """conv_last of RRDBNet: the first 64 channels of x fp16 [n,h,w,ldx] -> fp32 [n,h,w,3]."""
+    n, h, w, ldx = x.shape
+    out = torch.empty(n, h, w, 3, dtype=torch.float32, device=x.device)
+    check(lib().ld_op_esrgan_last(_p(x), ldx, _p(wt), _p(bias), _p(out), n, h, w, _stream()), "ld_op_esrgan_last")
+    return out
+
+
+def taesd_first(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """TAESD's clamp + first convolution + ReLU: latent fp32 [n,h,w,4] -> fp16 [n,h,w,64]."""
+    n, h, w, _ = x.shape
+    y = torch.empty(n, h, w, 64, dtype=torch.float16, device=x.device)
+    check(lib().ld_op_taesd_first(_p(x), _p(wt), _p(bias), _p(y), n, h, w, _stream()), "ld_op_taesd_first")
+    return y
+
+
+def taesd_last(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, image: bool = True):
+    """TAESD's last convolution and output map: x fp16 [n,h,w,64] -> (fp32 [n,h,w,3] in [-1, 1] nominally, uint8 [n,h,w,3] or None)."""
+    n, h, w, _ = x.shape
+    out = torch.empty(n, h, w, 3, dtype=torch.float32, device=x.device)
+    img = torch.empty(n, h, w, 3, dtype=torch.uint8, device=x.device) if image else None
+    check(lib().ld_op_taesd_last(_p(x), _p(wt), _p(bias), _p(out), _p(img), n, h, w, _stream()), "ld_op_taesd_last")
+    return out, img
 
 
 # ------------------------------------------------------------------ 8-bit image ops (image.hip): UltimateSDUpscale's tile plumbing

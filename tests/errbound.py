@@ -594,3 +594,195 @@ def wsum_ref(w_out):
     """fp64 row sums of the device's fp16 W' and the bound of their fp32 sum: c_acc(K) sum|W'| (+ 1e-30: an all-zero row is exact)."""
     wd = w_out.double()
     return wd.sum(-1), c_acc(wd.shape[1]) * wd.abs().sum(-1) + 1e-30
+
+
+# ------------------------------------------------------------------ the end convolutions of the upscaler and the preview decoder (esrgan.hip, taesd.hip)
+# Weights are fp16 [Cout][9 Cin], tap-major and channel-minor, as the kernels read them; results [n h w][Cout].
+
+def _end_conv(a, w, b, cin):
+    """fp64 conv3x3 (pad 1) of a [n][h][w][>= cin] + b: (pre, sum |a w|) as [n h w][Cout]."""
+    cols = im2col(a[..., :cin], 3)
+    wm = tapmajor_to_oihw(w.to(a.device), cin).double().reshape(w.shape[0], -1)
+    return cols @ wm.t() + b.double().to(a.device), cols.abs() @ wm.abs().t(), wm
+
+
+def esrgan_first_ref(x, w, b):
+    """fp64 reference of esrgan_first_kernel: x fp32 NHWC [n][h][w][3], rounded to fp16 once (the kernel's own rounding, reproduced exactly: no
+    allowance), K = 27 fp32 chain from the bias, one fp16 store:  U |y| + c_acc(27) sum|a w| + 2^-23 |pre| + TINY.
+    Observed on the MI355X (tests/test_end_convs_gpu.py): worst error / bound 0.993 (the store), signed bias below 5e-6; the fp32 emulation 0.994."""
+    pre, absdot, _ = _end_conv(x.half().double(), w, b, 3)
+    return pre, U * pre.abs() + c_acc(27) * absdot + 2.0 ** -23 * pre.abs() + TINY
+
+
+TANH_FP32_REL = 2.0 ** -21      # 3 tanhf(x / 3) against 3 tanh(x / 3): the quotient, tanhf within two ulps, the product
+
+
+def taesd_clamp_ref(x):
+    """a = round_fp16(3 tanh(x / 3)) with tanh in fp64, and what the kernel's fp32 tanhf may change of it: where the fp64 value lies within
+    TANH_FP32_REL |t| of a rounding boundary of fp16 the device's operand may be the neighbouring fp16 number — one fp16 ulp there, 0 elsewhere."""
+    t = 3.0 * torch.tanh(x.double() / 3.0)
+    a = t.half().double()
+    ulp = torch.maximum(_fp16_ulp(t), _fp16_ulp(a))
+    flip = (0.5 * ulp - (t - a).abs()) <= TANH_FP32_REL * t.abs()
+    return a, flip.double() * ulp * (t != 0).double()
+
+
+def taesd_first_ref(x, w, b):
+    """fp64 reference of taesd_first_kernel: latent fp32 NHWC [n][h][w][4] -> relu(conv(a) + b), a = taesd_clamp_ref(x); K = 36:
+        U |y| + c_acc(36) sum|a w| + im2col(e_a) |w|^T + 2^-23 |pre| + TINY      (ReLU has Lipschitz constant 1).
+    Observed on the MI355X (tests/test_end_convs_gpu.py): worst error / bound 0.991 (the store), signed bias over the positive outputs below 9e-6;
+    the fp32 emulation 0.995."""
+    a, e_a = taesd_clamp_ref(x)
+    pre, absdot, wm = _end_conv(a, w, b, 4)
+    y = pre.clamp_min(0.0)
+    return y, U * y.abs() + c_acc(36) * absdot + im2col(e_a, 3) @ wm.abs().t() + 2.0 ** -23 * pre.abs() + TINY
+
+
+def esrgan_last_ref(x, w, b):
+    """fp64 reference of esrgan_last_kernel: the first 64 channels of x fp16 NHWC (any pitch) -> [n h w][3] fp32, K = 576 as packed fp16 dot
+    products accumulated in fp32 from the bias; no fp16 rounding anywhere:  c_acc(576) sum|a w|  (+ 1e-30: an all-zero patch returns the bias).
+    Observed on the MI355X (tests/test_end_convs_gpu.py): worst error / bound 0.59, signed bias below 7e-8; the fp32 emulation 0.48."""
+    pre, absdot, _ = _end_conv(x.double(), w, b, 64)
+    return pre, c_acc(576) * absdot + 1e-30
+
+
+def taesd_last_ref(x, w, b):
+    """fp64 reference of taesd_last_kernel's fp32 output d = (v - 0.5) * 2: the doubled bound of esrgan_last_ref plus the fp32 subtraction
+    (the doubling is exact): 2 c_acc(576) sum|a w| + 2^-23 |d|.  Also the image value floor(clip(255 (d + 1) / 2, 0, 255)) of the fp64 d.
+    Observed on the MI355X (tests/test_end_convs_gpu.py): worst error / bound 0.62, signed bias below 1.1e-7; every image byte equal to the truncation of
+    the device's own d and within one count of the fp64 byte."""
+    pre, absdot, _ = _end_conv(x.double(), w, b, 64)
+    d = (pre - 0.5) * 2.0
+    img = (255.0 * ((d + 1.0) * 0.5)).clamp(0.0, 255.0).floor()
+    return d, 2.0 * c_acc(576) * absdot + 2.0 ** -23 * d.abs() + 1e-30, img
+
+
+# ------------------------------------------------------------------ tiled_scale's blend (esrgan.hip: tile_blend_kernel, tile_divide_kernel)
+
+def tile_blend_ref(oh, ow, c, tiles, out0=None, div0=None):
+    """fp64 accumulation of `tiles` = [(ps [th][tw][c], my [th], mx [tw], y0, x0), ...] in the given order into out [oh][ow][c] and div [oh][ow]
+    (from out0 / div0 or zeros), and the quotient out / div:  (out, b_out, div, b_div, quot, b_quot).  Per tile the kernel rounds m = my mx, then
+    ps m, then the sum (or fuses the last two): 2^-23 on each magnitude involved —  b_out += 2^-23 (2 |ps m| + |out|),  b_div += 2^-23 (|m| + |div|).
+    The divide: b_out / div + |quot| b_div / div, and one fp32 ulp of the quotient.
+    Observed on the MI355X (tests/test_blend_gpu.py): worst error / bound 0.41 (out), 0.44 (div), 0.18 (quotient), 0.49 of one ulp for the divide alone;
+    the fp32 emulation 0.33, 0.32, 0.21."""
+    out = torch.zeros(oh, ow, c, dtype=torch.float64) if out0 is None else out0.double().clone().cpu()
+    div = torch.zeros(oh, ow, dtype=torch.float64) if div0 is None else div0.double().clone().cpu()
+    b_out, b_div = torch.zeros_like(out), torch.zeros_like(div)
+    for ps, my, mx, y0, x0 in tiles:
+        th, tw = ps.shape[0], ps.shape[1]
+        m = my.double().cpu().reshape(th, 1) * mx.double().cpu().reshape(1, tw)
+        p = ps.double().cpu() * m.unsqueeze(-1)
+        sy, sx = slice(y0, y0 + th), slice(x0, x0 + tw)
+        out[sy, sx] += p
+        div[sy, sx] += m
+        b_out[sy, sx] += 2.0 ** -23 * (2.0 * p.abs() + out[sy, sx].abs())
+        b_div[sy, sx] += 2.0 ** -23 * (m.abs() + div[sy, sx].abs())
+    quot = out / div.unsqueeze(-1)
+    b_quot = b_out / div.abs().unsqueeze(-1) + quot.abs() * (b_div / div.abs()).unsqueeze(-1) + 2.0 ** -23 * quot.abs()
+    return out, b_out + 1e-30, div, b_div + 1e-30, quot, b_quot + 1e-30
+
+
+# ------------------------------------------------------------------ bislerp (misc.hip: bislerp_axis_kernel), one axis pass
+
+BISLERP_EPS = 1e-5            # the reference's branch thresholds: dot > 1 - 1e-5 copies a, dot < 1e-5 - 1 lerps (LD.py:455-462)
+
+
+def bislerp_axis_ref(x, len_new, axis_w):
+    """fp64 reference of ONE pass of bislerp (LD.py:429-518) over fp32 NCHW x, taken as exact: the resize of the width (axis_w) or of the height to
+    len_new.  -> (y_hat, bound, dot), dot [n][ho][wo] the fp64 cosine of every tap pair (NaN-free: 0 for a zero tap).
+    The taps (lo, hi, r) are the oracle's _bilinear_taps in fp32: the tap rule is part of the operation's definition.  Per pair a, b (C-vectors):
+        na = |a|, nb = |b|, ua = a / na, ub = b / nb (0 for a zero vector), d = ua . ub, om = acos d, s = sin om, M = na (1 - r) + nb r,
+        v = M (ga ua + gb ub), ga = sin((1 - r) om) / s, gb = sin(r om) / s;   d > 1 - 1e-5: v = a;   d < 1e-5 - 1: v = a (1 - r) + b r.
+    The branch is chosen by the fp64 d.  Bound, to first order, of the kernel's fp32 evaluation:
+      * the fp32 sums: e(sum a b) = c_acc(C) sum|a b|, rel(na) = rel(nb) = c_acc(C) / 2 + 2^-23 (the sum of squares, sqrtf, the reciprocal), so
+        e_d = c_acc(C) sum|a b| / (na nb) + |d| (c_acc(C) + 2^-21);
+      * om = acosf(d): e_om = e_d / s + 2^-22 om, reaching v through |dv/dom| = M |ga' ua + gb' ub| with
+        ga' = ((1 - r) cos((1 - r) om) s - sin((1 - r) om) cos om) / s^2 (gb' likewise with r): COMPUTED, it grows without limit towards the poles;
+      * r: pos is one fp32 expression of size up to len_old, so e_r = ulp32(len_old), through
+        |dv/dr| = |(nb - na)(ga ua + gb ub) + M om (cos(r om) ub - cos((1 - r) om) ua) / s|;
+      * the norms in M and in ua, ub: |v| (rel(na) + rel(nb));
+      * the remaining operations, 2^-23 each on the magnitudes they act on: the two sines' arguments and values (2^-22 (|sin| + arg) / s each),
+        sinf(om) and the quotient, the products and the sum of v = (wa a + wb b) M: 2^-21 M (|ga ua| + |gb ub|) + 2^-22 |v|;
+      * the copy branch is exact (bound 1e-300: any difference fails); the lerp branch has 2^-22 (|a (1 - r)| + |b r|) + |b - a| e_r.
+    Observed on the MI355X (tests/test_bislerp_gpu.py): worst error / bound 0.22 (C = 1, 6 x 5 -> 9 x 11), signed bias below 6.1e-6; the oracle's fp32
+    run on the same inputs 0.097 (tests/test_errbound_cpu.py)."""
+    from oracle import sd15_ref as O
+    xd = x.double().cpu()
+    n, c, h, w = xd.shape
+    len_old = w if axis_w else h
+    lo, hi, fr = O._bilinear_taps(len_old, len_new)
+    r = fr.double()
+    if axis_w:
+        a, b = xd[:, :, :, lo], xd[:, :, :, hi]
+        r = r.view(1, 1, 1, -1)
+    else:
+        a, b = xd[:, :, lo, :], xd[:, :, hi, :]
+        r = r.view(1, 1, -1, 1)
+    ssum = lambda t: t.sum(1, keepdim=True)
+    na, nb = ssum(a * a).sqrt(), ssum(b * b).sqrt()
+    safe = lambda t: torch.where(t > 0, t, torch.ones_like(t))
+    ua, ub = a / safe(na), b / safe(nb)
+    d = ssum(ua * ub).clamp(-1.0, 1.0)
+    om = torch.acos(d)
+    s = torch.sin(om)
+    ss = torch.where(s > 0, s, torch.ones_like(s))                     # s = 0 only inside the two branches, which do not use it
+    sa, sb, ca, cb = torch.sin((1 - r) * om), torch.sin(r * om), torch.cos((1 - r) * om), torch.cos(r * om)
+    ga, gb = sa / ss, sb / ss
+    M = na * (1 - r) + nb * r
+    v = M * (ga * ua + gb * ub)
+    cc = c_acc(c)
+    rel_n = 0.5 * cc + 2.0 ** -23
+    e_d = cc * ssum((a * b).abs()) / (safe(na) * safe(nb)) + d.abs() * (cc + 2.0 ** -21)
+    e_om = e_d / ss + 2.0 ** -22 * om
+    dga = ((1 - r) * ca * ss - sa * torch.cos(om)) / (ss * ss)
+    dgb = (r * cb * ss - sb * torch.cos(om)) / (ss * ss)
+    dv_dom = M * (dga * ua + dgb * ub).abs()
+    e_r = 2.0 ** (math.floor(math.log2(len_old)) - 23)
+    dv_dr = ((nb - na) * (ga * ua + gb * ub) + M * om * (cb * ub - ca * ua) / ss).abs()
+    rest = 2.0 ** -22 * M * (((sa.abs() + (1 - r) * om) * ua.abs() + (sb.abs() + r * om) * ub.abs()) / ss) \
+        + 2.0 ** -21 * M * ((ga * ua).abs() + (gb * ub).abs()) + 2.0 ** -22 * v.abs()
+    bound = dv_dom * e_om + dv_dr * e_r + 2.0 * rel_n * v.abs() + rest + 1e-30
+    same, opp = d > 1.0 - BISLERP_EPS, d < BISLERP_EPS - 1.0
+    lerp = a * (1 - r) + b * r
+    v = torch.where(same, a, torch.where(opp, lerp, v))
+    b_lerp = 2.0 ** -22 * ((a * (1 - r)).abs() + (b * r).abs()) + (b - a).abs() * e_r + 1e-30
+    bound = torch.where(same, torch.full_like(bound, 1e-300), torch.where(opp, b_lerp, bound))
+    return v, bound, d[:, 0]
+
+
+def bislerp_dots_clear_of_the_thresholds(dot):
+    """The input condition of a bislerp case: no pair's fp64 |dot| inside (1 - 2e-5, 1 - 5e-6), where an fp32 evaluation may take the other branch —
+    the reference's own discontinuity."""
+    a = dot.abs()
+    return not bool(((a > 1.0 - 2e-5) & (a < 1.0 - 5e-6)).any())
+
+
+# ------------------------------------------------------------------ the samplers' elementwise arithmetic (misc.hip: cfg_combine_kernel, axpby_kernel)
+
+def cfg_combine_ref(den2, cfg):
+    """fp64 u + (c - u) cfg of den2 = [u ; c] (fp32): the difference, the product and the sum round once each (the last two may fuse):
+    2^-23 (|c - u| |cfg| + |(c - u) cfg| + |out|) — one fp32 ulp per operation on its own magnitude, whatever the cancellation in the sum.
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): worst error / bound 0.50 over two laps of the grid; cfg = 0 returns u bit for bit."""
+    half = den2.shape[0] // 2
+    u, c = den2[:half].double(), den2[half:].double()
+    t = (c - u) * cfg
+    out = u + t
+    return out, 2.0 ** -23 * (2.0 * t.abs() + out.abs()) + 1e-30
+
+
+def axpby_ref(x, a, y=None, b=0.0, z=None, c=0.0):
+    """fp64 a x + b y + c z (y, z optional) of fp32 tensors and fp32 scalars: every product and every partial sum rounds once:
+    2^-23 (|a x| + |b y| + |c z| + |a x + b y| + |out|).
+    Observed on the MI355X (tests/test_small_kernels_gpu.py): worst error / bound 0.46 in all four pointer arms; a = 1, b = c = 0 leaves x bit for bit."""
+    t = float(a) * x.double()
+    bound = t.abs()
+    if y is not None:
+        p = float(b) * y.double()
+        t = t + p
+        bound = bound + p.abs() + t.abs()
+    if z is not None:
+        p = float(c) * z.double()
+        t = t + p
+        bound = bound + p.abs() + t.abs()
+    return t, 2.0 ** -23 * bound + 1e-30

@@ -11,6 +11,8 @@ from conftest import GOLDEN, load_golden, rel_l2
 from embedding_files import write_embedding_files
 
 pytestmark = pytest.mark.gpu
+# the kernel of clip.hip and the tests that hold it bitwise (tests/test_errbound_cpu.py keeps the ledger)
+KERNELS = {"clip_embed_kernel": ["test_clip_embed_kernel_bitwise", "test_clip_embed_every_id_class_in_one_row"]}
 DEV = "cuda:0"
 E2E_BOUND = 5e-3           # this text model against the reference: tests/test_models_gpu.py::test_clip_text_model_on_hip_kernels
 V_CLIP = 49408

@@ -526,29 +526,352 @@ def test_pointwise_finish_and_timestep_refs():
     assert t6.tolist() == [3, 100] * 3
 
 
+# ------------------------------------------------------------------ the references of the end convolutions, the tile blend, bislerp and the sampler helpers
+def _one_ulp_off(y16, ref):
+    """y16 with ONE element moved one fp16 ulp further from ref: the first element in the lower half of its binade (where U |y_hat| < 0.75 ulp, so
+    the move — at least one ulp of error — is outside a bound that is the store's rounding plus a few 1e-7).  -> (perturbed copy, flat index)."""
+    m, _ = torch.frexp(ref.flatten().abs())
+    idx = int(torch.nonzero((m < 0.75) & (ref.flatten().abs() > 0.05))[0])
+    bad = y16.clone().flatten()
+    away = 1 if abs(float(bad[idx])) >= abs(float(ref.flatten()[idx])) else -1
+    bits = bad.view(torch.int16)
+    bits[idx] += away                                   # sign-magnitude: +1 is one step away from zero
+    return bad.view(y16.shape), idx
+
+
+def _end_inputs(n, h, w, cin, cout, seed, pitch=None):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, h, w, cin if pitch is None else pitch, generator=g)
+    wt = (torch.randn(cout, 9 * cin, generator=g) / math.sqrt(9 * cin)).half()
+    b = (torch.randn(cout, generator=g) * 0.5).half()
+    return x, wt, b
+
+
+def _conv32(a_nhwc, wt, b, cin):
+    """The fp32 convolution of the first cin channels, [n h w][Cout]."""
+    return F.conv2d(a_nhwc[..., :cin].float().permute(0, 3, 1, 2), _oihw(wt, cin).float(), b.float(), padding=1).permute(0, 2, 3, 1).reshape(-1, wt.shape[0])
+
+
+@pytest.mark.parametrize("kind", ["esrgan_first", "taesd_first"])
+def test_first_conv_refs_and_bounds(kind):
+    n, h, w, cin = 2, 16, 16, 3 if kind == "esrgan_first" else 4
+    x, wt, b = _end_inputs(n, h, w, cin, 64, cin)
+    if kind == "taesd_first":
+        x = x * 4.0
+        x[0, 0, :4] = torch.tensor([[30.0, -30.0, 0.0, -0.0], [12.0, -12.0, 1e-3, -1e-3], [0.0] * 4, [3.0, -3.0, 9.0, -9.0]])
+        ref, bound = EB.taesd_first_ref(x, wt, b)
+        a64, e_a = EB.taesd_clamp_ref(x)
+        assert a64[0, 0, 0].tolist() == [3.0, -3.0, 0.0, 0.0] and float(e_a[0, 0, 0].max()) == 0.0     # saturated and zero: no allowance
+        big = torch.randn(200000, generator=torch.Generator().manual_seed(9)) * 3.0
+        a_big, e_big = EB.taesd_clamp_ref(big)
+        assert 0.0 < float((e_big > 0).double().mean()) < 0.01                                            # the flip allowance is rare
+        assert float((((torch.tanh(big / 3.0) * 3.0).half().double() - a_big).abs() - e_big).max()) <= 0.0   # and fp32 tanh stays inside it
+        a32 = (torch.tanh(x / 3.0) * 3.0).half()
+        assert float(((a32.double() - a64).abs() - e_a).max()) <= 0.0
+        ind = F.conv2d(a64.permute(0, 3, 1, 2), _oihw(wt, cin).double(), b.double(), padding=1).clamp_min(0).permute(0, 2, 3, 1).reshape(-1, 64)
+        y32 = _conv32(a32, wt, b, cin).clamp_min(0)
+        keep = ref > 0
+    else:
+        ref, bound = EB.esrgan_first_ref(x, wt, b)
+        ind = F.conv2d(x.half().double().permute(0, 3, 1, 2), _oihw(wt, cin).double(), b.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, 64)
+        y32 = _conv32(x.half(), wt, b, cin)
+        keep = None
+    assert float((ref - ind).abs().max()) < 1e-12
+    r, s = EB.check(y32.half(), ref, bound, "fp32 emulation, RTN", image_rows=h * w, width=w, keep=keep)
+    print(f"{kind}: fp32 emulation error / bound {r:.3f}, signed bias {s:+.2e}")
+    with pytest.raises(AssertionError, match="signed bias"):
+        EB.check(_rtz(y32.double()), ref, bound, "RTZ", keep=keep)
+    bad, idx = _one_ulp_off(y32.half(), ref)
+    pix, ch = divmod(idx, 64)
+    with pytest.raises(AssertionError, match=rf"element bound: 1 of .*image {pix // (h * w)}, row {pix % (h * w) // w}, column {pix % w}; channel {ch}\)"):
+        EB.check(bad, ref, bound, "one ulp", image_rows=h * w, width=w, keep=keep)
+    if kind == "esrgan_first":                            # the input NOT rounded to fp16 first: outside the bound
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(_conv32(x, wt, b, cin).half(), ref, bound, "unrounded input")
+    # image 1's first row reading image 0's last row (the border test dropped for ky = 0)
+    a = (x.half() if kind == "esrgan_first" else (torch.tanh(x / 3.0) * 3.0).half()).float()
+    leak = y32.clone().reshape(n, h, w, 64)
+    wo = _oihw(wt, cin).float()
+    leak[1, 0] += F.conv2d(a[0:1, h - 1:h].permute(0, 3, 1, 2), wo[:, :, 0:1, :], padding=(0, 1))[0, :, 0].t()
+    leak = leak.clamp_min(0) if kind == "taesd_first" else leak
+    with pytest.raises(AssertionError, match=r"element bound: .*image 1, row 0, column"):
+        EB.check(leak.reshape(-1, 64).half(), ref, bound, "batch leak", image_rows=h * w, width=w, keep=keep)
+
+
+@pytest.mark.parametrize("kind", ["esrgan_last", "taesd_last"])
+def test_last_conv_refs_and_bounds(kind):
+    """The two 64 -> 3 kernels write fp32: there is no store rounding for a round-toward-zero variant to bias, and one fp32 ulp is inside any bound of a
+    576-long fp32 chain.  The defects here: one missing tap at one pixel, one channel without its bias, one output one fp16 ulp off; for the image, a
+    rounding instead of the truncation."""
+    n, h, w = 2, 9, 11
+    x, wt, b = _end_inputs(n, h, w, 64, 3, 64, pitch=72)
+    x = x.half()
+    if kind == "taesd_last":
+        b = torch.tensor([0.5, -0.25, 1.5]).half()
+        ref, bound, img = EB.taesd_last_ref(x, wt, b)
+        fin = lambda v: (v - 0.5) * 2.0
+        assert float((ref < -1).double().mean()) > 0.05 and float((ref > 1).double().mean()) > 0.05
+    else:
+        ref, bound = EB.esrgan_last_ref(x, wt, b)
+        fin = lambda v: v
+    v64 = F.conv2d(x[..., :64].double().permute(0, 3, 1, 2), _oihw(wt, 64).double(), b.double(), padding=1).permute(0, 2, 3, 1).reshape(-1, 3)
+    assert float((ref - fin(v64)).abs().max()) < 1e-12
+    v32 = _conv32(x, wt, b, 64)
+    keep = torch.ones_like(ref, dtype=torch.bool)
+    r, s = EB.check(fin(v32), ref, bound, "fp32 emulation", image_rows=h * w, width=w, keep=keep)
+    print(f"{kind}: fp32 emulation error / bound {r:.3f}, signed bias {s:+.2e}")
+    tap = v32.clone()                                     # image 1's first pixel without its (ky, kx) = (2, 2) tap
+    tap[h * w] -= _oihw(wt, 64).float()[:, :, 2, 2] @ x[1, 1, 1, :64].float()
+    with pytest.raises(AssertionError, match=r"element bound: [1-3] of .*image 1, row 0, column 0"):
+        EB.check(fin(tap), ref, bound, "missing tap", image_rows=h * w, width=w, keep=keep)
+    with pytest.raises(AssertionError, match=r"element bound: .*channel 1\)"):
+        EB.check(fin(_conv32(x, wt, b * torch.tensor([1.0, 0.0, 1.0]).half(), 64)), ref, bound, "channel 1 without bias", image_rows=h * w, width=w, keep=keep)
+    off = fin(v32).clone()
+    off[37, 2] *= 1.0 + 2.0 ** -10
+    with pytest.raises(AssertionError, match=r"element bound: 1 of .*image 0, row 3, column 4; channel 2"):
+        EB.check(off, ref, bound, "one fp16 ulp", image_rows=h * w, width=w, keep=keep)
+    with pytest.raises(AssertionError, match="element bound"):          # the pad channels behind channel 64 read as data
+        EB.check(fin(v32 + 1e-3 * x[..., 64:].float().sum(-1).reshape(-1, 1)), ref, bound, "pitch", keep=keep)
+    if kind == "taesd_last":
+        import numpy as np
+        import usdu_ref
+        d32 = fin(v32)
+        u8 = torch.from_numpy(usdu_ref.to_u8(((d32 + 1.0) * 0.5).numpy())).double()
+        assert float((u8 - img).abs().max()) <= 1.0 and set(u8.flatten().tolist()) >= {0.0, 255.0}
+        rounded = (255.0 * ((ref + 1.0) * 0.5)).clamp(0, 255).round()   # round to nearest: half of the bytes one count up
+        assert float((rounded != img).double().mean()) > 0.1
+
+
+def _blend_tiles(oh, ow, c, rects, seed):
+    g = torch.Generator().manual_seed(seed)
+    tiles = []
+    for (y0, x0, th, tw) in rects:
+        ramp = lambda n: torch.minimum(torch.arange(1, n + 1), torch.arange(n, 0, -1)).float().clamp_max(4) / 4.0 * (0.5 + torch.rand(1, generator=g))
+        tiles.append((torch.randn(th, tw, c, generator=g), ramp(th), ramp(tw), y0, x0))
+    return tiles
+
+
+def _blend32(oh, ow, c, tiles, skip=None, shift=0):
+    out, div = torch.zeros(oh, ow, c), torch.zeros(oh, ow)
+    for k, (ps, my, mx, y0, x0) in enumerate(tiles):
+        if k == skip:
+            continue
+        th, tw = ps.shape[:2]
+        m = my.reshape(th, 1) * (mx.roll(shift) if k == 1 else mx).reshape(1, tw)
+        out[y0:y0 + th, x0:x0 + tw] += ps * m.unsqueeze(-1)
+        div[y0:y0 + th, x0:x0 + tw] += m
+    return out, div
+
+
+def test_tile_blend_ref_and_bound():
+    """fp32 accumulation in the kernel's order is inside the bound (out, div and the quotient); a feather ramp shifted by one sample in one tile, a
+    tile left out, and one element 2^-20 off are outside it.  (An fp32 result has no store rounding to bias, and one fp32 ulp is inside a bound that
+    counts three roundings per tile.)"""
+    oh, ow, c = 40, 56, 3
+    rects = [(0, 0, 24, 32), (0, 24, 24, 32), (16, 0, 24, 32), (16, 24, 24, 32), (23, 37, 17, 19), (5, 9, 17, 19)]
+    tiles = _blend_tiles(oh, ow, c, rects, 1)
+    out, b_out, div, b_div, quot, b_quot = EB.tile_blend_ref(oh, ow, c, tiles)
+    assert float(div.min()) > 0
+    o32, d32 = _blend32(oh, ow, c, tiles)
+    keep = torch.ones_like(out, dtype=torch.bool)
+    r = [EB.check(o32, out, b_out, "out", keep=keep)[0], EB.check(d32, div, b_div, "div", keep=keep[..., 0])[0],
+         EB.check(o32 / d32.unsqueeze(-1), quot, b_quot, "quotient", keep=keep)[0]]
+    print(f"tile blend fp32 emulation: error / bound {r[0]:.3f} (out), {r[1]:.3f} (div), {r[2]:.3f} (quotient)")
+    for defect in (dict(shift=1), dict(skip=5)):
+        o_bad, d_bad = _blend32(oh, ow, c, tiles, **defect)
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(o_bad, out, b_out, str(defect), keep=keep)
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(d_bad, div, b_div, str(defect), keep=keep[..., 0])
+    bad = o32 / d32.unsqueeze(-1)
+    bad[39, 55, 2] *= 1.0 + 2.0 ** -16
+    with pytest.raises(AssertionError, match=r"element bound: 1 of .*\(39, 55, 2\)"):
+        EB.check(bad, quot, b_quot, "one element", keep=keep)
+
+
+def _oracle_pass(x, len_new, axis_w):
+    """One pass of the oracle's bislerp in fp32 (its _slerp_rows on its _bilinear_taps), NCHW -> NCHW."""
+    from oracle import sd15_ref as O
+    xp = x.float().permute(0, 2, 3, 1)
+    n, h, w, c = xp.shape
+    if axis_w:
+        lo, hi, fr = O._bilinear_taps(w, len_new)
+        y = O._slerp_rows(xp[:, :, lo].reshape(-1, c), xp[:, :, hi].reshape(-1, c), fr.view(1, 1, -1, 1).expand(n, h, -1, 1).reshape(-1, 1)).view(n, h, len_new, c)
+    else:
+        lo, hi, fr = O._bilinear_taps(h, len_new)
+        y = O._slerp_rows(xp[:, lo].reshape(-1, c), xp[:, hi].reshape(-1, c), fr.view(1, -1, 1, 1).expand(n, -1, w, 1).reshape(-1, 1)).view(n, len_new, w, c)
+    return y.permute(0, 3, 1, 2).contiguous()
+
+
+def test_bislerp_ref_and_bound():
+    """The oracle's fp32 bislerp passes bislerp_axis_ref's bound, pass by pass, on every input of tests/test_bislerp_gpu.py (its inputs meet the
+    threshold condition and its planted pairs come out at their closed-form values), and so does the recorded fixture of the reference's own run
+    (tests/golden/bislerp.npz: both passes at once, so the width pass's bound is carried through the height pass with the slerp's Lipschitz constant
+    away from the poles, 2 per tap, on the channel norm).  Dropping the zero-tap arm (1 / 0 instead of 0) or swapping the two taps is outside it.
+    This run: worst error / bound 0.097 over the GPU test's inputs (C = 1, 6 x 5 -> 9 x 11, width pass), 0.085 for the fixture."""
+    import test_bislerp_gpu as TB
+    from oracle import sd15_ref as O
+    everything = lambda t: torch.ones_like(t, dtype=torch.bool)
+    worst = 0.0
+    for case in TB.cases():
+        c, h, w, hn, wn = case
+        x, plants = TB.make_input(*case)
+        ref1, b1, d1 = EB.bislerp_axis_ref(x, wn, True)
+        t = _oracle_pass(x, wn, True)
+        ref2, b2, d2 = EB.bislerp_axis_ref(t, hn, False)
+        assert EB.bislerp_dots_clear_of_the_thresholds(d1) and EB.bislerp_dots_clear_of_the_thresholds(d2), case
+        y = _oracle_pass(t, hn, False)
+        assert torch.equal(y, O.bislerp(x, wn, hn))
+        worst = max(worst, EB.check(t, ref1, b1, f"{case} width pass", keep=everything(ref1))[0], EB.check(y, ref2, b2, f"{case} height pass", keep=everything(ref2))[0])
+        seen = TB.check_planted(t, x, plants, wn, True, str(case)) | TB.check_planted(y, t, plants, hn, False, str(case))
+        assert seen == {k for k, *_ in plants}, case
+        if c == 4 and h * w >= 30:
+            assert seen == set(TB.KINDS), case
+            # the defects, on the pass that holds the planted pairs
+            with pytest.raises(AssertionError, match="element bound"):
+                EB.check(_swapped_pass(x, wn), ref1, b1, "taps swapped", keep=everything(ref1))
+            with pytest.raises(AssertionError, match="non-finite|element bound"):
+                EB.check(_no_zero_arm_pass(x, wn), ref1, b1, "zero arm dropped", keep=everything(ref1))
+    print(f"bislerp: the oracle's fp32 run, worst error / bound {worst:.3f}")
+    assert worst < 1.0
+    g = load_golden_("bislerp")
+    for key, (wn, hn) in (("y2x", (12, 16)), ("y_odd", (9, 11))):
+        x = g["x"]
+        ref1, b1, d1 = EB.bislerp_axis_ref(x, wn, True)
+        t = _oracle_pass(x, wn, True)
+        EB.check(t, ref1, b1, f"fixture {key} width pass", keep=everything(ref1))
+        ref2, b2, d2 = EB.bislerp_axis_ref(t, hn, False)
+        assert EB.bislerp_dots_clear_of_the_thresholds(d1) and EB.bislerp_dots_clear_of_the_thresholds(d2), key
+        lo, hi, _ = O._bilinear_taps(x.shape[2], hn)
+        n1 = (b1 * b1).sum(1, keepdim=True).sqrt()
+        carried = 2.0 * (n1[:, :, lo] + n1[:, :, hi]).expand_as(ref2)
+        r, _ = EB.check(g[key], ref2, b2 + carried, f"fixture {key}", keep=everything(ref2))
+        print(f"bislerp fixture {key}: error / bound {r:.3f}")
+
+
+def _swapped_pass(x, len_new):
+    """The width pass with r and 1 - r exchanged."""
+    from oracle import sd15_ref as O
+    xp = x.float().permute(0, 2, 3, 1)
+    n, h, w, c = xp.shape
+    lo, hi, fr = O._bilinear_taps(w, len_new)
+    y = O._slerp_rows(xp[:, :, lo].reshape(-1, c), xp[:, :, hi].reshape(-1, c), (1.0 - fr).view(1, 1, -1, 1).expand(n, h, -1, 1).reshape(-1, 1))
+    return y.view(n, h, len_new, c).permute(0, 3, 1, 2).contiguous()
+
+
+def _no_zero_arm_pass(x, len_new):
+    """The width pass normalising a zero tap by 1 / 0 (what the kernel would do without its `na > 0 ? 1 / na : 0`)."""
+    from oracle import sd15_ref as O
+    xp = x.float().permute(0, 2, 3, 1)
+    n, h, w, c = xp.shape
+    lo, hi, fr = O._bilinear_taps(w, len_new)
+    a, b, r = xp[:, :, lo].reshape(-1, c), xp[:, :, hi].reshape(-1, c), fr.view(1, 1, -1, 1).expand(n, h, -1, 1).reshape(-1, 1)
+    na, nb = a.norm(dim=1, keepdim=True), b.norm(dim=1, keepdim=True)
+    ua, ub = a / na, b / nb
+    cosw = (ua * ub).sum(1, keepdim=True)
+    om = torch.acos(cosw)
+    out = (torch.sin((1 - r) * om) / torch.sin(om) * ua + torch.sin(r * om) / torch.sin(om) * ub) * (na * (1 - r) + nb * r)
+    out = torch.where(cosw > 1 - 1e-5, a, out)
+    out = torch.where(cosw < 1e-5 - 1, a * (1 - r) + b * r, out)
+    return out.view(n, h, len_new, c).permute(0, 3, 1, 2).contiguous()
+
+
+def load_golden_(name):
+    from conftest import load_golden
+    return load_golden(name)
+
+
+def test_sampler_elementwise_refs():
+    """fp32 evaluation is inside cfg_combine_ref / axpby_ref in every pointer arm; a second lap that re-reads the first lap's elements, and a term
+    dropped, are outside."""
+    g = torch.Generator().manual_seed(21)
+    den2 = torch.randn(2, 1000, generator=g) * 3.0
+    everything = lambda t: torch.ones_like(t, dtype=torch.bool)
+    for cfg in (0.0, 1.0, 7.5, -2.0):
+        ref, bound = EB.cfg_combine_ref(den2, cfg)
+        u, c = den2[0], den2[1]
+        EB.check(u + (c - u) * cfg, ref[0], bound[0], f"cfg {cfg}", keep=everything(ref[0]))
+        if cfg == 0.0:
+            assert torch.equal(ref[0], u.double())
+        else:
+            with pytest.raises(AssertionError, match="element bound"):
+                EB.check(torch.cat([(u + (c - u) * cfg)[:900], (u + (c - u) * cfg)[:100]]), ref[0], bound[0], "second lap repeats the first", keep=everything(ref[0]))
+    x, y, z = (torch.randn(1000, generator=g) for _ in range(3))
+    a, b, c = 0.7, -1.3, 2.5
+    f = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    for yy, zz in ((y, z), (y, None), (None, z), (None, None)):
+        ref, bound = EB.axpby_ref(x, f(a), yy, f(b), zz, f(c))
+        v = f(a) * x
+        if yy is not None:
+            v = v + f(b) * yy
+        if zz is not None:
+            v = v + f(c) * zz
+        EB.check(v, ref, bound, "axpby", keep=everything(ref))
+        if zz is not None:
+            with pytest.raises(AssertionError, match="element bound"):
+                EB.check(v - f(c) * zz, ref, bound, "z dropped", keep=everything(ref))
+
+
+KERNEL_PAT = r"__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+_kernel)\s*\("
+# the contraction families: held by name through the pinned routes of tests/test_routes_gpu.py
+CONTRACTION_FILES = ("gemm.hip", "gemm3.hip", "gemm5.hip", "conv6.hip", "gemm7.hip", "conv8.hip", "attention.hip")
+# every other translation unit with a kernel -> the test modules whose KERNELS tables hold its kernels
+HOLDERS = {
+    "norm.hip": ("test_norm_gpu",),
+    "misc.hip": ("test_small_kernels_gpu", "test_bislerp_gpu"),
+    "esrgan.hip": ("test_esrgan_conv_gpu", "test_end_convs_gpu", "test_blend_gpu"),
+    "taesd.hip": ("test_taesd_conv_gpu", "test_end_convs_gpu"),
+    "image.hip": ("test_usdu_gpu",),
+    "lora.hip": ("test_lora_patch_gpu",),
+    "clip.hip": ("test_embeddings_gpu",),
+}
+
+
 def test_every_norm_and_misc_kernel_is_held_by_a_gpu_test():
-    """A __global__ kernel in norm.hip or misc.hip cannot land without a row in the KERNELS table of tests/test_norm_gpu.py or
-    tests/test_small_kernels_gpu.py that names a test of that module.  Exempt, each held element-wise or bitwise elsewhere:"""
+    """A __global__ kernel anywhere under csrc cannot land without a test that holds it element-wise or bitwise.
+      * norm.hip, misc.hip, esrgan.hip, taesd.hip, image.hip, lora.hip, clip.hip: a row in the KERNELS table of one of the file's test modules
+        (HOLDERS) that names tests of that module; no row for a kernel that no longer exists;
+      * the contraction files: every kernel name is a prefix of a pinned route of tests/test_routes_gpu.py;
+      * a source file with a kernel that is in neither list fails here.
+    Exempt, each held element-wise or bitwise by the test its reason names:"""
+    import importlib
     exempt = {
         "upconv_fold_kernel": "test_upconv_fold_gpu.py holds the folded weights and the route element-wise",
-        "upconv_reduce_kernel": "test_upconv_fold_gpu.py (the split-K finish of the same route)",
+        "upconv_reduce_kernel": "test_upconv_fold_gpu.py (the split-K finish of the same route, held element-wise with it)",
         "skip_fold_kernel": "a copy and one fp16 add; test_conv6_skip_gpu.py holds its consumer element-wise against [w | wskip], b + bskip",
-        "repack_rows_kernel": "a row permutation in front of every GEGLU route of test_routes_gpu.py",
-        "fill_half_kernel": "a constant fill",
-        "cfg_combine_kernel": "fp32 elementwise, test_ops_gpu.py::test_sampler_elementwise",
-        "axpby_kernel": "fp32 elementwise, test_ops_gpu.py::test_sampler_elementwise",
-        "bislerp_axis_kernel": "test_configs_gpu.py::test_bislerp_on_device",
+        "repack_rows_kernel": "a row permutation in front of every GEGLU route of test_routes_gpu.py, held element-wise there",
+        "conv8_repack_kernel": "the weight-layout copy behind conv8, not a contraction: every conv8_kernel route of test_routes_gpu.py reads its output element-wise",
     }
-    import test_norm_gpu as TN
-    import test_small_kernels_gpu as TS
+    for k, why in exempt.items():
+        assert re.search(r"test_\w+\.py", why) and re.search(r"element-wise|bitwise", why), (k, why)
+    import test_routes_gpu as R
     csrc = os.path.join(ROOT, "lightdiffusion_amd", "csrc")
-    pat = r"__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(\w+_kernel)\s*\("
-    for f, mod in (("norm.hip", TN), ("misc.hip", TS)):
-        names = set(re.findall(pat, open(os.path.join(csrc, f)).read()))
-        assert names, f
-        missing = names - set(mod.KERNELS) - set(exempt)
+    kernels_of = lambda f: set(re.findall(KERNEL_PAT, open(os.path.join(csrc, f)).read()))
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    with_kernels = {f for f in sources if kernels_of(f)}
+    assert with_kernels == set(HOLDERS) | set(CONTRACTION_FILES), f"source files whose kernels nobody holds: {sorted(with_kernels ^ (set(HOLDERS) | set(CONTRACTION_FILES)))}"
+    held_anywhere = set()
+    for f, mods in HOLDERS.items():
+        names = kernels_of(f)
+        tables = {}
+        for m in mods:
+            mod = importlib.import_module(m)
+            for k, tests in mod.KERNELS.items():
+                assert tests and all(callable(getattr(mod, t, None)) for t in tests), (m, k, tests)
+                tables.setdefault(k, []).append(m)
+        here = {k for k in tables if k in names}
+        missing = names - here - set(exempt)
         assert not missing, f"{f}: kernels without an element-wise GPU test: {sorted(missing)}"
-        assert not set(mod.KERNELS) - names, f"{f}: rows for kernels that no longer exist: {sorted(set(mod.KERNELS) - names)}"
-        for k, tests in mod.KERNELS.items():
-            assert tests and all(callable(getattr(mod, t, None)) for t in tests), (k, tests)
-    assert not set(exempt) & (set(TN.KERNELS) | set(TS.KERNELS))
+        held_anywhere |= here
+    every = set().union(*(kernels_of(f) for f in HOLDERS))
+    for mods in HOLDERS.values():
+        for m in mods:
+            gone = set(importlib.import_module(m).KERNELS) - every
+            assert not gone, f"{m}: rows for kernels that no longer exist: {sorted(gone)}"
+    assert not set(exempt) & held_anywhere
+    pinned = {n.split("<")[0] for n in R.route_names()}
+    for f in CONTRACTION_FILES:
+        for k in kernels_of(f) - set(exempt):
+            assert any(p.startswith(k) for p in pinned), f"{f}: {k} is on no pinned route of tests/test_routes_gpu.py"
+    assert not {"bislerp_axis_kernel", "cfg_combine_kernel", "axpby_kernel"} & set(exempt)
+    assert every | set().union(*(kernels_of(f) for f in CONTRACTION_FILES)) == set().union(*(kernels_of(f) for f in sources))

@@ -19,6 +19,8 @@ from errbound import TINY, U, c_acc, check, im2col
 from lightdiffusion_amd._lib import ERR_ARG, ERR_SHAPE, OK, lib
 
 pytestmark = pytest.mark.gpu
+# the kernels of esrgan.hip this module holds (tests/test_errbound_cpu.py keeps the ledger; the end convolutions: tests/test_end_convs_gpu.py, the blend: tests/test_blend_gpu.py)
+KERNELS = {"esrgan_conv_kernel": ["test_dense_conv_in_place", "test_conv5_residuals", "test_upconv_nearest2x"]}
 
 TILE_H, TILE_W = 16, 32
 SIZES = [(1, 5, 7), (1, 8, 32), (1, 32, 8), (1, 33, 47), (2, 9, 11)]

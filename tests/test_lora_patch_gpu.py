@@ -18,6 +18,8 @@ from conftest import load_golden, rel_l2
 from lightdiffusion_amd import weights as W
 
 pytestmark = pytest.mark.gpu
+# the kernels of lora.hip and the tests that hold them, element-wise and bitwise (tests/test_errbound_cpu.py keeps the ledger)
+KERNELS = {"lora_merge_kernel": ["test_lora_merge_elementwise_against_fp64"], "lora_read_kernel": ["test_layout_round_trip_patch_read_unpatch"]}
 DEV = "cuda:0"
 UNET_TOL = 5e-3          # tests/test_configs_gpu.py: test_lora_merged_unet_and_clip_match_reference
 CLIP_TOL = 5e-3

@@ -1,4 +1,4 @@
-"""GPU: the boundary convolutions, the timestep embedding, the CFG-pair plumbing and the weight folds of misc.hip, each held element-wise
+"""GPU: the boundary convolutions, the timestep embedding, the CFG-pair plumbing, the samplers' elementwise arithmetic and the weight folds of misc.hip, each held element-wise
 (tests/errbound.py) against an fp64 reference from the same inputs, or bitwise where the kernel only moves or compares data.  The two small
 convolutions pin the instantiation they ran through ld_op_last_kernel.  Each case prints its worst error / bound and signed bias.
 
@@ -27,6 +27,8 @@ KERNELS = {
     "ln_fold_kernel": ["test_ln_fold"],
     "mlp_out_fold_kernel": ["test_mlp_out_fold"],
     "repack_conv3x3_kernel": ["test_repack_conv_is_a_permutation"],
+    "cfg_combine_kernel": ["test_cfg_combine"],
+    "axpby_kernel": ["test_axpby"],
 }
 
 
@@ -378,3 +380,39 @@ def test_ln_fold(ops, n, k, bias):
     held(b_out, b_ref, b_b, f"ln_fold b' N={n} K={k} bias={bias}", keep=torch.ones_like(b_ref, dtype=torch.bool))
     s_ref, s_b = EB.wsum_ref(w_out)
     held(wsum, s_ref, s_b, f"ln_fold wsum N={n} K={k}", keep=torch.ones_like(s_ref, dtype=torch.bool))
+
+
+# ------------------------------------------------------------------ the samplers' elementwise arithmetic
+# grid_for caps these launches at 4096 blocks of 256 threads: 4096 * 256 + 3 elements are a full first lap and a second one of three elements
+LAP = 4096 * 256
+everything = lambda t: torch.ones_like(t, dtype=torch.bool)
+
+
+@pytest.mark.parametrize("n_half", [5, LAP + 3])
+def test_cfg_combine(ops, n_half):
+    g = torch.Generator().manual_seed(n_half)
+    den2 = rnd((2, n_half), g, 3.0, torch.float32)
+    for cfg in (0.0, 1.0, 7.5, -2.0):
+        out = ops.cfg_combine(den2, cfg)
+        assert tuple(out.shape) == (1, n_half)
+        ref, bound = EB.cfg_combine_ref(den2, cfg)
+        held(out, ref, bound, f"cfg_combine n_half={n_half} cfg={cfg}", keep=everything(ref))
+        if cfg == 0.0:
+            assert torch.equal(out.view(torch.int32), den2[:1].view(torch.int32))       # u + (c - u) * 0 is u, bit for bit
+
+
+@pytest.mark.parametrize("n", [5, LAP + 3])
+def test_axpby(ops, n):
+    """All four pointer arms (y / z present or null), fp32 scalars; a = 1, b = c = 0 leaves x as it is bit for bit in every arm."""
+    g = torch.Generator().manual_seed(n + 1)
+    x0, y, z = (rnd((n,), g, 2.0, torch.float32) for _ in range(3))
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    a, b, c = f32(0.7), f32(-1.3), f32(2.5)
+    for yy, zz in ((y, z), (y, None), (None, z), (None, None)):
+        x = x0.clone()
+        assert ops.axpby_(x, a, yy, b, zz, c) is x
+        ref, bound = EB.axpby_ref(x0, a, yy, b, zz, c)
+        held(x, ref, bound, f"axpby n={n} y={yy is not None} z={zz is not None}", keep=everything(ref))
+        x = x0.clone()
+        ops.axpby_(x, 1.0, yy, 0.0, zz, 0.0)
+        assert torch.equal(x.view(torch.int32), x0.view(torch.int32)), (n, yy is not None, zz is not None)

@@ -23,6 +23,8 @@ from errbound import TINY, U, c_acc, check, im2col
 from lightdiffusion_amd._lib import ERR_ARG, ERR_SHAPE, OK, lib
 
 pytestmark = pytest.mark.gpu
+# the kernel of taesd.hip this module holds (tests/test_errbound_cpu.py keeps the ledger; the end convolutions: tests/test_end_convs_gpu.py)
+KERNELS = {"taesd_conv_kernel": ["test_conv_64_to_64"]}
 
 SIZES = [(1, 5, 7), (1, 33, 47), (2, 9, 11)]
 F23 = 2.0 ** -23

@@ -53,7 +53,19 @@ def test_ref_equals_pillow_live():
         want = np.array(im.resize(size, {"lanczos": Image.LANCZOS, "bicubic": Image.BICUBIC}[filt]))
         assert np.array_equal(ref_resample((src, box, size, filt)), want), name
     rng = np.random.default_rng(0)
-    for (h, w, r) in [(50, 70, 2.5), (96, 120, 16), (64, 64, 8), (20, 10, 16)]:        # the last: a radius beyond the image
+    filt = {"lanczos": Image.LANCZOS, "bicubic": Image.BICUBIC}
+    # four channels as CMYK and two as a pair of "L" bands (Pillow premultiplies LA and RGBA before it resizes them; its resampling itself
+    # treats every band alike), up and down, and an 8x lanczos downscale: the longest tap rows
+    for (h, w, c, size, f) in [(37, 53, 4, (72, 24), "lanczos"), (40, 31, 4, (17, 55), "bicubic"), (37, 53, 2, (72, 24), "lanczos"),
+                               (33, 29, 2, (11, 50), "bicubic"), (64, 96, 3, (12, 8), "lanczos"), (64, 96, 4, (12, 8), "lanczos")]:
+        src = rng.integers(0, 256, (h, w, c), dtype=np.uint8)
+        if c == 2:
+            want = np.stack([np.array(Image.fromarray(src[..., k]).resize(size, filt[f])) for k in range(2)], axis=-1)
+        else:
+            want = np.array(Image.fromarray(src, "CMYK" if c == 4 else "RGB").resize(size, filt[f]))
+        assert np.array_equal(R.resample(src, size[0], size[1], f), want), (h, w, c, size, f)
+    # the last three: a radius beyond the image's width, its height, both
+    for (h, w, r) in [(50, 70, 2.5), (96, 120, 16), (64, 64, 8), (20, 10, 16), (9, 50, 16), (50, 9, 16), (7, 5, 16)]:
         m = rng.integers(0, 256, (h, w), dtype=np.uint8)
         assert np.array_equal(R.gaussian_blur(m, r), np.array(Image.fromarray(m).filter(ImageFilter.GaussianBlur(r)))), (h, w, r)
 

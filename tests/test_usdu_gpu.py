@@ -1,5 +1,7 @@
-"""GPU: UltimateSDUpscale on the device.  The 8-bit image kernels (image.hip) against Pillow's recorded outputs (tests/golden/usdu_ops.npz):
-0 differing bytes; the node with the stand-in stages against the reference's recorded run (usdu_flow.npz): every canvas byte for byte; the
+"""GPU: UltimateSDUpscale on the device.  The 8-bit image kernels (image.hip) against Pillow's recorded outputs (tests/golden/usdu_ops.npz) and,
+beyond one lap of their grid-stride loops, on two and four channels, on every alignment path and with a blur radius beyond the image, against the
+NumPy restatement of Pillow's arithmetic (tests/usdu_ref.py, which tests/test_usdu_cpu.py holds to Pillow itself): 0 differing bytes; KERNELS names
+the tests that hold each kernel (tests/test_errbound_cpu.py keeps the ledger); the node with the stand-in stages against the reference's recorded run (usdu_flow.npz): every canvas byte for byte; the
 node with the real stages against the same job loop written here from usdu_ref and the package's existing nodes: identical bytes; and a
 full-size run (544 x 544 redraw tiles) on SD1.5-sized synthetic weights."""
 import os
@@ -102,6 +104,147 @@ def test_conversions():
     got = ops.f32_from_u8(dev(b)).cpu().numpy()
     assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), R.to_f32(b).view(np.uint32))      # a division, bit for bit
     assert np.array_equal(ops.f32_from_u8(dev(b)[3:250]).cpu().numpy(), R.to_f32(b[3:250]))
+
+
+# ------------------------------------------------------------------ the ops beyond one lap of their grid-stride loops, and their other paths
+# Every kernel of image.hip is a grid-stride loop of at most 4096 blocks of 256 lanes: LAP work items are one lap, and a 2048^2 canvas laps them
+# several times.  Each case below passes LAP items by a few rows, so a wrong stride shows in the rows of the second lap; the other axis is short.
+LAP = 4096 * 256
+
+KERNELS = {
+    "resample_h_kernel": ["test_resample", "test_resample_h_second_lap", "test_resample_channels_and_long_taps"],
+    "resample_v_kernel": ["test_resample", "test_resample_v_second_lap", "test_resample_channels_and_long_taps", "test_resample_v_alignment_paths"],
+    "box_h_kernel": ["test_blur", "test_blur_and_mask_second_lap", "test_blur_radius_beyond_the_image_and_in_place"],
+    "box_v_kernel": ["test_blur", "test_blur_and_mask_second_lap", "test_blur_radius_beyond_the_image_and_in_place"],
+    "mask_kernel": ["test_blur_weights_and_window", "test_blur_and_mask_second_lap", "test_mask_pattern_over_the_left_and_top_edges"],
+    "composite_kernel": ["test_composite", "test_composite_second_lap"],
+    "u8_from_f32_kernel": ["test_conversions", "test_conversions_second_lap"],
+    "f32_from_u8_kernel": ["test_conversions", "test_conversions_second_lap"],
+}
+
+
+def same_at(got, want, what):
+    """Byte for byte, naming the first differing pixel."""
+    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{what}: {len(bad)} differing bytes, the first at {tuple(int(v) for v in bad[0])}: got {got[tuple(bad[0])]}, want {want[tuple(bad[0])]}"
+
+
+def rand_u8(seed, shape):
+    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+
+
+def test_composite_second_lap():
+    h, w = 1025, 1024                                                            # 1 049 600 pixels: LAP and one row
+    assert h * w > LAP
+    canvas, tile, alpha = rand_u8(20, (h + 2, w + 3, 3)), rand_u8(21, (h, w, 3)), rand_u8(22, (h, w))
+    got = ops.u8_composite_(dev(canvas), dev(tile), dev(alpha), 3, 2)
+    same_at(got, R.composite(canvas.copy(), tile, alpha, 3, 2), "composite 1025 x 1024 x 3")
+
+
+def test_blur_and_mask_second_lap():
+    h = w = 2052                                                                 # 513 words a row: 1 052 676 items, LAP and eight rows
+    assert h * ((w + 3) // 4) > LAP
+    pat = rand_u8(23, (2040, 2040))
+    mask = ops.u8_mask(h, w, (7, 9, 2040, 2040), dev(pat))
+    want = np.zeros((h, w), np.uint8)
+    want[9:2049, 7:2047] = pat
+    same_at(mask, want, "mask 2052 x 2052")
+    same_at(ops.u8_gaussian_blur(mask, 2.5), R.gaussian_blur(want, 2.5), "blur 2052 x 2052, radius 2.5")
+
+
+def test_resample_h_second_lap():
+    src = rand_u8(24, (1024, 64, 3))                                             # 1024 rows of 64 -> 1025 pixels: 1 049 600 items
+    assert 1024 * 1025 > LAP
+    same_at(ops.u8_resample(dev(src), (1025, 1024)), R.resample(src, 1025, 1024), "horizontal resample 1024 x (64 -> 1025) x 3")
+
+
+def test_resample_v_second_lap():
+    src = rand_u8(25, (64, 1024, 3))                                             # 64 -> 1367 rows of 768 words: 1 049 856 items
+    assert 1367 * (1024 * 3 // 4) > LAP
+    same_at(ops.u8_resample(dev(src), (1024, 1367)), R.resample(src, 1024, 1367), "vertical resample (64 -> 1367) x 1024 x 3")
+
+
+def test_conversions_second_lap():
+    n = 4 * LAP + 3                                                              # four elements a lane: one full lap and a ragged word of the second
+    rng = np.random.default_rng(26)
+    x = (rng.random(n, dtype=np.float32) * np.float32(1.2) - np.float32(0.1))
+    same_at(ops.u8_from_f32(dev(x)), R.to_u8(x), "fp32 -> u8, 4 LAP + 3 elements")
+    b = rand_u8(27, (n,))
+    got = ops.f32_from_u8(dev(b)).cpu().numpy()
+    same_at(got.view(np.uint32), R.to_f32(b).view(np.uint32), "u8 -> fp32, 4 LAP + 3 elements")
+
+
+@pytest.mark.parametrize("c,shape,size,filt", [(2, (37, 53), (72, 24), "lanczos"), (4, (37, 53), (72, 24), "lanczos"), (2, (33, 29), (11, 50), "bicubic"),
+                                               (4, (40, 31), (17, 55), "bicubic"), (3, (64, 96), (12, 8), "lanczos"), (4, (64, 96), (12, 8), "lanczos")])
+def test_resample_channels_and_long_taps(c, shape, size, filt):
+    """Two and four channels, and an 8x lanczos downscale (49 taps a sample: the longest rows)."""
+    src = rand_u8(30 + c + size[0], shape + (c,))
+    same_at(ops.u8_resample(dev(src), size, filt), R.resample(src, size[0], size[1], filt), f"resample {shape} x {c} -> {size} {filt}")
+
+
+def _resample_v_into(src_view, dst_view, filt="lanczos"):
+    """The vertical pass alone (the width does not change) from one uint8 view into another, through the C ABI."""
+    from lightdiffusion_amd._lib import check, lib
+    sp, spitch, h, w, c = ops._u8_image(src_view)
+    dp, dpitch, oh, ow, dc = ops._u8_image(dst_view)
+    assert (w, c) == (ow, dc) and oh != h
+    vco, vk = ops._coeffs_on(src_view.device, h, oh, filt)
+    check(lib().ld_op_u8_resample(sp, spitch, w, h, c, dp, dpitch, ow, oh, None, 0, vco.data_ptr(), vk, None, torch.cuda.current_stream().cuda_stream), "ld_op_u8_resample")
+
+
+@pytest.mark.parametrize("src_off,dst_off", [(0, 1), (1, 0), (3, 3), (0, 0)], ids=lambda v: str(v))
+def test_resample_v_alignment_paths(src_off, dst_off):
+    """resample_v_kernel moves a word per lane where pointer and pitch allow and bytes where they do not, separately for source and destination:
+    an aligned source into a window at an odd byte offset of a larger tensor, the reverse, both unaligned, both aligned.  The bytes around the
+    destination window stay as they were."""
+    h, oh, w = 23, 37, 50                                                        # 50 bytes a row: twelve words and a ragged one
+    big = rand_u8(40 + src_off, (h, 64))
+    src = big[:, src_off:src_off + w]
+    canvas = rand_u8(41 + dst_off, (oh + 2, 64))
+    d = dev(canvas)
+    _resample_v_into(dev(big)[:, src_off:src_off + w], d[1:1 + oh, dst_off:dst_off + w])
+    want = canvas.copy()
+    want[1:1 + oh, dst_off:dst_off + w] = R.resample(src, w, oh)
+    same_at(d, want, f"vertical resample, source offset {src_off}, destination offset {dst_off}")
+
+
+def _blur_into(src_view, dst_view, radius):
+    from lightdiffusion_amd._lib import check, lib
+    sp, spitch, h, w, _ = ops._u8_image(src_view)
+    dp, dpitch, dh, dw, _ = ops._u8_image(dst_view)
+    assert (h, w) == (dh, dw)
+    tmp = torch.empty(lib().ld_op_u8_blur_tmp_bytes(w, h), dtype=torch.uint8, device=src_view.device)
+    check(lib().ld_op_u8_gaussian_blur(sp, spitch, dp, dpitch, w, h, float(radius), tmp.data_ptr(), torch.cuda.current_stream().cuda_stream), "ld_op_u8_gaussian_blur")
+
+
+@pytest.mark.parametrize("h,w", [(9, 50), (50, 9), (7, 5)])
+def test_blur_radius_beyond_the_image_and_in_place(h, w):
+    """Radius 16 is a box radius of 15: beyond the width - 1, the height - 1 or both, so every tap of some pass is the clamped border.  Then the
+    same blur in place (dst is src), in a window at an odd offset of a larger tensor whose other bytes must not change."""
+    assert ops.u8_box_weights(16)[0] == 15 and 15 >= min(h, w) - 1
+    mask = rand_u8(50 + h, (h, w))
+    want = R.gaussian_blur(mask, 16)
+    same_at(ops.u8_gaussian_blur(dev(mask), 16), want, f"blur {h} x {w}, radius 16")
+    canvas = rand_u8(51 + h, (h + 4, w + 9))
+    canvas[2:2 + h, 5:5 + w] = mask
+    d = dev(canvas)
+    win = d[2:2 + h, 5:5 + w]
+    _blur_into(win, win, 16)
+    canvas[2:2 + h, 5:5 + w] = want
+    same_at(d, canvas, f"blur {h} x {w} in place, radius 16")
+
+
+def test_mask_pattern_over_the_left_and_top_edges():
+    pat = rand_u8(60, (30, 41))
+    for (h, w, x, y) in [(25, 33, -7, -4), (25, 33, -7, 3), (25, 33, 5, -29), (10, 10, -3, -2)]:
+        want = np.zeros((h, w), np.uint8)
+        y1, y2, x1, x2 = max(y, 0), min(y + 30, h), max(x, 0), min(x + 41, w)
+        want[y1:y2, x1:x2] = pat[y1 - y:y2 - y, x1 - x:x2 - x]
+        same_at(ops.u8_mask(h, w, (x, y, 41, 30), dev(pat)), want, f"mask {h} x {w}, pattern at ({x}, {y})")
+        want[y1:y2, x1:x2] = 255
+        same_at(ops.u8_mask(h, w, (x, y, 41, 30), None, DEV), want, f"mask {h} x {w}, rectangle at ({x}, {y})")
 
 
 # ------------------------------------------------------------------ the node
