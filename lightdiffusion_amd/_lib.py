@@ -45,17 +45,27 @@ class LDError(RuntimeError):
 _lib = None
 _P, _I, _F, _Z = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 
+# what every resident model exports alike, as ld_<family>_<op> (csrc/runtime.h `Model`)
+_MODEL_OPS = {
+    "destroy": (None, [_P]),
+    "param_count": (_I, [_P]),
+    "param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
+    "workspace_bytes": (_Z, [_P]),
+    "last_launches": (_I, [_P]),
+    "last_flops": (C.c_double, [_P]),
+    "profile_launches": (_I, [_P, C.c_char_p, _Z]),
+}
+_SIZED_OPS = {"reserve": (_I, [_P, _I, _I, _I]), "plan_bytes": (_Z, [_P, _I, _I, _I])}   # (batch, h, w): all but the UNet, whose reserve adds the tokens
+
 # name -> (restype, argtypes): every symbol include/ld_mi355x.h declares
 SIGNATURES = {
+    **{f"ld_{fam}_{op}": sig for fam in ("unet", "vae", "esrgan", "taesd") for op, sig in _MODEL_OPS.items()},
+    **{f"ld_{fam}_{op}": sig for fam in ("vae", "esrgan", "taesd") for op, sig in _SIZED_OPS.items()},
     "ld_version": (C.c_char_p, []),
     "ld_status_string": (C.c_char_p, [_I]),
     "ld_unet_create": (_I, [C.POINTER(UNetConfig), C.POINTER(_P)]),
-    "ld_unet_destroy": (None, [_P]),
-    "ld_unet_param_count": (_I, [_P]),
-    "ld_unet_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
-    "ld_unet_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
     "ld_unet_reserve": (_I, [_P, _I, _I, _I, _I]),
-    "ld_unet_workspace_bytes": (_Z, [_P]),
     "ld_unet_weight_bytes": (_Z, [_P]),
     "ld_unet_set_context": (_I, [_P, _P, _I, _I, _I, _P]),
     "ld_unet_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -63,54 +73,21 @@ SIGNATURES = {
     "ld_unet_profile_pair": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_unet_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_unet_profile_kernels": (_I, [_P, C.c_char_p, _Z]),
-    "ld_unet_profile_launches": (_I, [_P, C.c_char_p, _Z]),
     "ld_unet_patch_param": (_I, [_P, C.c_char_p, C.POINTER(LoraTerm), _I, _P]),
     "ld_unet_unpatch": (_I, [_P, C.c_char_p, _P]),
     "ld_unet_read_param": (_I, [_P, C.c_char_p, _P, _P]),
     "ld_unet_refresh_derived": (_I, [_P, _P]),
     "ld_unet_patch_bytes": (_Z, [_P]),
-    "ld_unet_last_launches": (_I, [_P]),
-    "ld_unet_last_flops": (C.c_double, [_P]),
     "ld_vae_create": (_I, [C.POINTER(VAEConfig), C.POINTER(_P)]),
-    "ld_vae_destroy": (None, [_P]),
-    "ld_vae_param_count": (_I, [_P]),
-    "ld_vae_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
-    "ld_vae_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
-    "ld_vae_reserve": (_I, [_P, _I, _I, _I]),
-    "ld_vae_workspace_bytes": (_Z, [_P]),
-    "ld_vae_plan_bytes": (_Z, [_P, _I, _I, _I]),
     "ld_vae_decode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ld_vae_profile_launches": (_I, [_P, C.c_char_p, _Z]),
-    "ld_vae_last_launches": (_I, [_P]),
-    "ld_vae_last_flops": (C.c_double, [_P]),
     "ld_esrgan_create": (_I, [C.POINTER(ESRGANConfig), C.POINTER(_P)]),
-    "ld_esrgan_destroy": (None, [_P]),
-    "ld_esrgan_param_count": (_I, [_P]),
-    "ld_esrgan_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
-    "ld_esrgan_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
-    "ld_esrgan_reserve": (_I, [_P, _I, _I, _I]),
-    "ld_esrgan_workspace_bytes": (_Z, [_P]),
-    "ld_esrgan_plan_bytes": (_Z, [_P, _I, _I, _I]),
     "ld_esrgan_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_esrgan_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ld_esrgan_profile_launches": (_I, [_P, C.c_char_p, _Z]),
-    "ld_esrgan_last_launches": (_I, [_P]),
-    "ld_esrgan_last_flops": (C.c_double, [_P]),
     "ld_taesd_create": (_I, [C.POINTER(_P)]),
-    "ld_taesd_destroy": (None, [_P]),
-    "ld_taesd_param_count": (_I, [_P]),
-    "ld_taesd_param_info": (_I, [_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(C.c_int64)]),
-    "ld_taesd_load_param": (_I, [_P, C.c_char_p, _P, _I, _P]),
-    "ld_taesd_reserve": (_I, [_P, _I, _I, _I]),
-    "ld_taesd_workspace_bytes": (_Z, [_P]),
-    "ld_taesd_plan_bytes": (_Z, [_P, _I, _I, _I]),
     "ld_taesd_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ld_taesd_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ld_taesd_profile_launches": (_I, [_P, C.c_char_p, _Z]),
-    "ld_taesd_last_launches": (_I, [_P]),
-    "ld_taesd_last_flops": (C.c_double, [_P]),
     "ld_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _Z, _P]),
     "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_groupnorm_conv_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),

@@ -182,20 +182,12 @@ int tile_blend_launch(const float* ps, const float* my, const float* mx, int th,
 // writes the next block's first 64 channels into the other buffer), the RRDB input (the outer residual), the trunk input (the
 // ShortcutBlock's residual), one 64-channel stage per up-convolution and one for the HR convolution.
 // =====================================================================================================================
-struct ld_esrgan {
+struct ld_esrgan : Model {
     ld_esrgan_config cfg;
-    ParamTable pt;
     int first_w = -1, first_b = -1, trunk_w = -1, trunk_b = -1, hr_w = -1, hr_b = -1, last_w = -1, last_b = -1;
     std::vector<int> rdb_w, rdb_b;   // [(block * 3 + rdb) * 5 + conv]
     std::vector<int> up_w, up_b;
     int n_up = 0;
-    Arena arena;
-    char* ws_base = nullptr;
-    size_t ws_bytes = 0;
-    int last_launches = 0;
-    double last_flops = 0.0;
-    Timing timing;
-    bool want_timing = false;
 };
 
 namespace {
@@ -233,17 +225,9 @@ int esrgan_build(ld_esrgan* e) {
 int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h, int w, hipStream_t stream, size_t* dry_peak = nullptr) {
     const ld_esrgan_config& c = e->cfg;
     if ((long long)b * h * w * c.scale * c.scale > 0x7fffffffLL) return LD_ERR_SHAPE;
-    Exec ex;
-    ex.stream = stream;
-    ex.dry = dry;
     Arena plan;
-    ex.arena = dry ? &plan : &e->arena;
-    if (e->want_timing && !dry) {
-        e->timing.reset();
-        ex.timing = &e->timing;
-    }
+    Exec ex = e->begin(dry, stream, plan);
     Arena& ar = *ex.arena;
-    ar.release(0);
     const ParamTable& pt = e->pt;
     const int nf = c.nf, gc = c.gc, ldd = nf + 4 * gc;
     const size_t npix = (size_t)b * h * w;
@@ -313,12 +297,7 @@ int esrgan_run(ld_esrgan* e, bool dry, const float* x, float* out, int b, int h,
     ex.launch(KC_MISC, 2.0 * opix * c.out_nc * (9 * nf), "conv_last", opix, c.out_nc, 9 * nf, 1, "esrgan_last_kernel", [&] {
         return esrgan_last_launch(hr, nf, pt.ptr(e->last_w), pt.ptr(e->last_b), out, b, H, W, stream);
     });
-    if (dry_peak != nullptr) *dry_peak = ar.peak;
-    if (!dry) {
-        e->last_launches = ex.launches;
-        e->last_flops = ex.flops;
-    }
-    return ex.status;
+    return e->end(ex, dry_peak, !dry);
 }
 
 }  // namespace
@@ -331,8 +310,7 @@ int ld_esrgan_create(const ld_esrgan_config* cfg, ld_esrgan** out) {
     e->cfg = *cfg;
     const int st = esrgan_build(e);
     if (st != LD_OK) {
-        e->pt.destroy();
-        delete e;
+        ld_esrgan_destroy(e);
         return st;
     }
     *out = e;
@@ -341,75 +319,38 @@ int ld_esrgan_create(const ld_esrgan_config* cfg, ld_esrgan** out) {
 
 void ld_esrgan_destroy(ld_esrgan* e) {
     if (e == nullptr) return;
-    e->pt.destroy();
-    e->timing.destroy();
-    if (e->ws_base) (void)hipFree(e->ws_base);
+    e->destroy_common();
     delete e;
 }
 
-int ld_esrgan_param_count(const ld_esrgan* e) { return e ? (int)e->pt.slots.size() : 0; }
-
-int ld_esrgan_param_info(const ld_esrgan* e, int i, const char** name, int* ndim, int64_t shape[4]) {
-    return abi_param_info(e ? &e->pt : nullptr, i, name, ndim, shape);
-}
-
-int ld_esrgan_load_param(ld_esrgan* e, const char* name, const void* src, int dtype, void* stream) {
-    return abi_load_param(e ? &e->pt : nullptr, name, src, dtype, stream);
-}
+int ld_esrgan_param_count(const ld_esrgan* e) { return abi_param_count(e); }
+int ld_esrgan_param_info(const ld_esrgan* e, int i, const char** name, int* ndim, int64_t shape[4]) { return abi_param_info(e, i, name, ndim, shape); }
+int ld_esrgan_load_param(ld_esrgan* e, const char* name, const void* src, int dtype, void* stream) { return abi_load_param(e, name, src, dtype, stream); }
+size_t ld_esrgan_workspace_bytes(const ld_esrgan* e) { return abi_workspace_bytes(e); }
+int ld_esrgan_last_launches(const ld_esrgan* e) { return abi_last_launches(e); }
+double ld_esrgan_last_flops(const ld_esrgan* e) { return abi_last_flops(e); }
+int ld_esrgan_profile_launches(const ld_esrgan* e, char* buf, size_t buf_bytes) { return abi_profile_launches(e, buf, buf_bytes); }
 
 size_t ld_esrgan_plan_bytes(ld_esrgan* e, int b, int h, int w) {
-    if (e == nullptr || b < 1 || h < 1 || w < 1) return 0;
-    size_t peak = 0;
-    if (esrgan_run(e, true, nullptr, nullptr, b, h, w, nullptr, &peak) != LD_OK) return 0;
-    return (peak + 4095) / 4096 * 4096 + 4096;
+    return abi_plan_bytes(e, b, h, w, [&](size_t* peak) { return esrgan_run(e, true, nullptr, nullptr, b, h, w, nullptr, peak); });
 }
 
 int ld_esrgan_reserve(ld_esrgan* e, int max_b, int max_h, int max_w) {
     if (e == nullptr || max_b < 1 || max_h < 1 || max_w < 1) return LD_ERR_ARG;
-    const size_t bytes = ld_esrgan_plan_bytes(e, max_b, max_h, max_w);
+    const size_t bytes = ld_esrgan_plan_bytes(e, max_b, max_h, max_w);   // (planned before the old workspace goes)
     if (bytes == 0) return LD_ERR_SHAPE;
-    if (e->ws_base) {
-        (void)hipFree(e->ws_base);
-        e->ws_base = nullptr;
-    }
-    e->arena = Arena();
-    e->ws_bytes = 0;
-    if (hipMalloc((void**)&e->ws_base, bytes) != hipSuccess) {
-        e->ws_base = nullptr;
-        return LD_ERR_HIP;
-    }
-    e->ws_bytes = bytes;
-    e->arena.base = e->ws_base;
-    e->arena.cap = bytes - 4096;
-    return LD_OK;
+    return e->set_workspace(bytes, bytes - 4096);
 }
-
-size_t ld_esrgan_workspace_bytes(const ld_esrgan* e) { return e ? e->ws_bytes : 0; }
 
 int ld_esrgan_forward(ld_esrgan* e, const float* x, float* out, int b, int h, int w, void* stream) {
     if (e == nullptr || x == nullptr || out == nullptr) return LD_ERR_ARG;
-    if (e->ws_base == nullptr || !e->pt.all_loaded()) return LD_ERR_STATE;
-    if (b < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
-    size_t peak = 0;
-    const int st = esrgan_run(e, true, nullptr, nullptr, b, h, w, nullptr, &peak);
-    if (st != LD_OK) return st;
-    if (peak > e->arena.cap) return LD_ERR_SHAPE;
-    return esrgan_run(e, false, x, out, b, h, w, (hipStream_t)stream);
+    return abi_checked_run(*e, true, b >= 1 && h >= 1 && w >= 1,
+                           [&](size_t* peak) { return esrgan_run(e, true, nullptr, nullptr, b, h, w, nullptr, peak); },
+                           [&] { return esrgan_run(e, false, x, out, b, h, w, (hipStream_t)stream); });
 }
 
 int ld_esrgan_profile(ld_esrgan* e, const float* x, float* out, int b, int h, int w, void* stream) {
-    if (e == nullptr) return LD_ERR_ARG;
-    e->want_timing = true;
-    const int st = ld_esrgan_forward(e, x, out, b, h, w, stream);
-    e->want_timing = false;
-    return st != LD_OK ? st : abi_profile_collect(e->timing, stream);
+    return abi_profile(e, stream, [&] { return ld_esrgan_forward(e, x, out, b, h, w, stream); });
 }
-
-int ld_esrgan_profile_launches(const ld_esrgan* e, char* buf, size_t buf_bytes) {
-    return abi_profile_launches(e ? &e->timing : nullptr, buf, buf_bytes);
-}
-
-int ld_esrgan_last_launches(const ld_esrgan* e) { return e ? e->last_launches : 0; }
-double ld_esrgan_last_flops(const ld_esrgan* e) { return e ? e->last_flops : 0.0; }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Host-side runtime shared by the UNet and VAE executors: resident weight table (checkpoint names -> repacked
+// Host-side runtime shared by the executors (UNet, VAE, ESRGAN, TAESD): resident weight table (checkpoint names -> repacked
 // fp16 device tensors), a bump arena for activations with mark/release (stack discipline, deterministic addresses
 // so a whole forward can be captured into a hipGraph), and an Exec context that counts launches / FLOPs and
 // doubles as a dry-run planner (sizes the arena without touching the GPU).
@@ -327,27 +327,131 @@ struct Exec {
     }
 };
 
-// ---- the tails of the C ABI that the three executors (ld_unet_*, ld_vae_*, ld_esrgan_*) share; `pt` / `t`: the handle's table / timing, null for a null handle
-inline int abi_param_info(const ParamTable* pt, int i, const char** name, int* ndim, int64_t shape[4]) {
-    if (pt == nullptr || i < 0 || i >= (int)pt->slots.size()) return LD_ERR_ARG;
-    const ParamSlot& s = pt->slots[i];
+constexpr size_t SPLITK_BYTES = (size_t)96 << 20;   // the scratch of the contractions the UNet and the VAE carve behind their activations
+
+// ---- What the four resident models (ld_unet, ld_vae, ld_esrgan, ld_taesd) share: the weight table, the reserved workspace, the last run's
+// counts and the timing of a profiled run.  Each family derives its handle from this, adds its own slots and state, and walks its own blocks.
+struct Model {
+    ParamTable pt;
+    Arena arena;                     // activations: the front of the workspace
+    char* ws_base = nullptr;
+    size_t ws_bytes = 0;
+    float* splitk_ws = nullptr;      // scratch of the contractions inside the workspace (UNet, VAE); null: the family has none
+    size_t splitk_bytes = 0;
+    int* sync_ws = nullptr;          // LD_SYNC_INTS zeroed ints for the in-launch reductions (gemm.h GemmParams::sync); UNet only
+    int last_launches = 0;
+    double last_flops = 0.0;
+    Timing timing;
+    bool want_timing = false;
+
+    // the opening of every run: a dry run bumps the caller's private arena (no base: sizes only), a real one the reserved workspace
+    Exec begin(bool dry, hipStream_t stream, Arena& dry_arena) {
+        Exec ex;
+        ex.stream = stream;
+        ex.dry = dry;
+        ex.arena = dry ? &dry_arena : &arena;
+        ex.splitk_ws = splitk_ws;
+        ex.splitk_bytes = splitk_bytes;
+        ex.sync_ws = sync_ws;
+        if (want_timing && !dry) {
+            timing.reset();
+            ex.timing = &timing;
+        }
+        ex.arena->release(0);
+        return ex;
+    }
+    // ... and its close.  `record`: keep the run's counts as last_*; the UNet and the VAE do so on every run, ESRGAN and TAESD on real runs only
+    int end(const Exec& ex, size_t* dry_peak, bool record) {
+        if (record) {
+            last_launches = ex.launches;
+            last_flops = ex.flops;
+        }
+        if (dry_peak != nullptr) *dry_peak = ex.arena->peak;
+        return ex.status;
+    }
+
+    // bytes of a workspace whose activations peak at `peak`: rounded up to 4096, the family's regions behind them (`extra`), a 4096-byte guard
+    static size_t padded(size_t peak, size_t extra = 0) { return (peak + 4095) / 4096 * 4096 + extra + 4096; }
+    void free_workspace() {
+        if (ws_base) (void)hipFree(ws_base);
+        ws_base = nullptr;
+        arena = Arena();
+    }
+    // replaces the workspace: `total_bytes` in all, the first `act_bytes` of them the arena
+    int set_workspace(size_t total_bytes, size_t act_bytes) {
+        free_workspace();
+        ws_bytes = 0;
+        if (hipMalloc((void**)&ws_base, total_bytes) != hipSuccess) {
+            ws_base = nullptr;
+            return LD_ERR_HIP;
+        }
+        ws_bytes = total_bytes;
+        arena.base = ws_base;
+        arena.cap = act_bytes;
+        return LD_OK;
+    }
+    void destroy_common() {
+        pt.destroy();
+        timing.destroy();
+        free_workspace();
+    }
+};
+
+// ---- the C ABI the four families export alike, over the handle's base (null for a null handle)
+inline int abi_param_count(const Model* m) { return m ? (int)m->pt.slots.size() : 0; }
+inline size_t abi_workspace_bytes(const Model* m) { return m ? m->ws_bytes : 0; }
+inline int abi_last_launches(const Model* m) { return m ? m->last_launches : 0; }
+inline double abi_last_flops(const Model* m) { return m ? m->last_flops : 0.0; }
+inline int abi_profile_launches(const Model* m, char* buf, size_t buf_bytes) { return m ? m->timing.format_launches(buf, buf_bytes) : LD_ERR_ARG; }
+inline int abi_param_info(const Model* m, int i, const char** name, int* ndim, int64_t shape[4]) {
+    if (m == nullptr || i < 0 || i >= (int)m->pt.slots.size()) return LD_ERR_ARG;
+    const ParamSlot& s = m->pt.slots[i];
     if (name) *name = s.name.c_str();
     if (ndim) *ndim = s.ndim;
     if (shape)
         for (int k = 0; k < 4; ++k) shape[k] = s.shape[k];
     return LD_OK;
 }
-inline int abi_load_param(ParamTable* pt, const char* name, const void* src, int dtype, void* stream) {
-    if (pt == nullptr || name == nullptr) return LD_ERR_ARG;
-    return pt->load(name, src, dtype, (hipStream_t)stream);
+inline int abi_load_param(Model* m, const char* name, const void* src, int dtype, void* stream) {
+    if (m == nullptr || name == nullptr) return LD_ERR_ARG;
+    return m->pt.load(name, src, dtype, (hipStream_t)stream);
 }
-inline int abi_profile_launches(const Timing* t, char* buf, size_t buf_bytes) {
-    if (t == nullptr) return LD_ERR_ARG;
-    return t->format_launches(buf, buf_bytes);
+// the workspace a (b, h, w) run needs; dry_run(&peak): the family's host-only dry run(s).  0: no handle, no such shape
+template <class Dry>
+size_t abi_plan_bytes(const Model* m, int b, int h, int w, Dry&& dry_run, size_t extra_bytes = 0) {
+    size_t peak = 0;
+    if (m == nullptr || b < 1 || h < 1 || w < 1 || dry_run(&peak) != LD_OK) return 0;
+    return Model::padded(peak, extra_bytes);
 }
-// behind a profiled run that returned LD_OK: wait for its launches, then read their events
-inline int abi_profile_collect(Timing& t, void* stream) {
+// the last shape (and route) a family validated against the reserved arena, so that a repeated call skips the dry run; zeros: none
+struct PlanKey {
+    int v[4] = {0, 0, 0, 0};
+    bool operator==(const PlanKey& o) const { return v[0] == o.v[0] && v[1] == o.v[1] && v[2] == o.v[2] && v[3] == o.v[3]; }
+};
+// a real run behind the family's argument check: the handle's state, the shape, a dry run against the reserved arena (unless `planned`
+// already holds `shape`), then real()
+template <class Dry, class Real>
+int abi_checked_run(Model& m, bool state_ok, bool shape_ok, Dry&& dry_run, Real&& real, PlanKey* planned = nullptr, PlanKey shape = PlanKey()) {
+    if (m.ws_base == nullptr || !m.pt.all_loaded() || !state_ok) return LD_ERR_STATE;
+    if (!shape_ok) return LD_ERR_SHAPE;
+    if (planned == nullptr || !(*planned == shape)) {   // new shape: plan it on the host before touching the GPU
+        size_t peak = 0;
+        const int st = dry_run(&peak);
+        if (st != LD_OK) return st;
+        if (peak > m.arena.cap) return LD_ERR_SHAPE;
+        if (planned != nullptr) *planned = shape;
+    }
+    return real();
+}
+// run() with HIP events around every launch; behind one that returned LD_OK: wait for its launches, then read their events
+template <class Run>
+int abi_profile(Model* m, void* stream, Run&& run) {
+    if (m == nullptr) return LD_ERR_ARG;
+    m->want_timing = true;
+    const int st = run();
+    m->want_timing = false;
+    if (st != LD_OK) return st;
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
-    t.collect();
+    m->timing.collect();
     return LD_OK;
 }

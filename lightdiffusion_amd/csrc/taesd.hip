@@ -153,18 +153,10 @@ int taesd_conv_launch(const half_t* x, int n, int h, int w, int up, const half_t
 // Workspace: three 64-channel buffers of the OUTPUT resolution that rotate: a Block reads its input, writes its two intermediates into the
 // other two, and its result over the first intermediate; an upsampling convolution writes the next buffer.
 // =====================================================================================================================
-struct ld_taesd {
-    ParamTable pt;
+struct ld_taesd : Model {
     int first_w = -1, first_b = -1, last_w = -1, last_b = -1;
     int blk_w[10][3], blk_b[10][3];
     int up_w[3];
-    Arena arena;
-    char* ws_base = nullptr;
-    size_t ws_bytes = 0;
-    int last_launches = 0;
-    double last_flops = 0.0;
-    Timing timing;
-    bool want_timing = false;
 };
 
 namespace {
@@ -196,17 +188,9 @@ int taesd_build(ld_taesd* t) {
 
 int taesd_run(ld_taesd* t, bool dry, const float* latent, float* out, uint8_t* img, int b, int h, int w, hipStream_t stream, size_t* dry_peak = nullptr) {
     if ((long long)b * h * w * 64 > 0x7fffffffLL) return LD_ERR_SHAPE;
-    Exec ex;
-    ex.stream = stream;
-    ex.dry = dry;
     Arena plan;
-    ex.arena = dry ? &plan : &t->arena;
-    if (t->want_timing && !dry) {
-        t->timing.reset();
-        ex.timing = &t->timing;
-    }
+    Exec ex = t->begin(dry, stream, plan);
     Arena& ar = *ex.arena;
-    ar.release(0);
     const ParamTable& pt = t->pt;
     const size_t opix = (size_t)b * h * w * 64;
     half_t* buf[3] = {ar.halfs(opix * 64), ar.halfs(opix * 64), ar.halfs(opix * 64)};
@@ -240,12 +224,7 @@ int taesd_run(ld_taesd* t, bool dry, const float* latent, float* out, uint8_t* i
     ex.launch(KC_MISC, 2.0 * lpix * 3 * 576, "conv_last", lpix, 3, 576, 1, "taesd_last_kernel", [&] {
         return taesd_last_launch(buf[cur], pt.ptr(t->last_w), pt.ptr(t->last_b), out, img, b, H, W, stream);
     });
-    if (dry_peak != nullptr) *dry_peak = ar.peak;
-    if (!dry) {
-        t->last_launches = ex.launches;
-        t->last_flops = ex.flops;
-    }
-    return ex.status;
+    return t->end(ex, dry_peak, !dry);
 }
 
 }  // namespace
@@ -257,8 +236,7 @@ int ld_taesd_create(ld_taesd** out) {
     ld_taesd* t = new ld_taesd();
     const int st = taesd_build(t);
     if (st != LD_OK) {
-        t->pt.destroy();
-        delete t;
+        ld_taesd_destroy(t);
         return st;
     }
     *out = t;
@@ -267,75 +245,38 @@ int ld_taesd_create(ld_taesd** out) {
 
 void ld_taesd_destroy(ld_taesd* t) {
     if (t == nullptr) return;
-    t->pt.destroy();
-    t->timing.destroy();
-    if (t->ws_base) (void)hipFree(t->ws_base);
+    t->destroy_common();
     delete t;
 }
 
-int ld_taesd_param_count(const ld_taesd* t) { return t ? (int)t->pt.slots.size() : 0; }
-
-int ld_taesd_param_info(const ld_taesd* t, int i, const char** name, int* ndim, int64_t shape[4]) {
-    return abi_param_info(t ? &t->pt : nullptr, i, name, ndim, shape);
-}
-
-int ld_taesd_load_param(ld_taesd* t, const char* name, const void* src, int dtype, void* stream) {
-    return abi_load_param(t ? &t->pt : nullptr, name, src, dtype, stream);
-}
+int ld_taesd_param_count(const ld_taesd* t) { return abi_param_count(t); }
+int ld_taesd_param_info(const ld_taesd* t, int i, const char** name, int* ndim, int64_t shape[4]) { return abi_param_info(t, i, name, ndim, shape); }
+int ld_taesd_load_param(ld_taesd* t, const char* name, const void* src, int dtype, void* stream) { return abi_load_param(t, name, src, dtype, stream); }
+size_t ld_taesd_workspace_bytes(const ld_taesd* t) { return abi_workspace_bytes(t); }
+int ld_taesd_last_launches(const ld_taesd* t) { return abi_last_launches(t); }
+double ld_taesd_last_flops(const ld_taesd* t) { return abi_last_flops(t); }
+int ld_taesd_profile_launches(const ld_taesd* t, char* buf, size_t buf_bytes) { return abi_profile_launches(t, buf, buf_bytes); }
 
 size_t ld_taesd_plan_bytes(ld_taesd* t, int b, int h, int w) {
-    if (t == nullptr || b < 1 || h < 1 || w < 1) return 0;
-    size_t peak = 0;
-    if (taesd_run(t, true, nullptr, nullptr, nullptr, b, h, w, nullptr, &peak) != LD_OK) return 0;
-    return (peak + 4095) / 4096 * 4096 + 4096;
+    return abi_plan_bytes(t, b, h, w, [&](size_t* peak) { return taesd_run(t, true, nullptr, nullptr, nullptr, b, h, w, nullptr, peak); });
 }
 
 int ld_taesd_reserve(ld_taesd* t, int max_b, int max_h, int max_w) {
     if (t == nullptr || max_b < 1 || max_h < 1 || max_w < 1) return LD_ERR_ARG;
-    const size_t bytes = ld_taesd_plan_bytes(t, max_b, max_h, max_w);
+    const size_t bytes = ld_taesd_plan_bytes(t, max_b, max_h, max_w);   // (planned before the old workspace goes)
     if (bytes == 0) return LD_ERR_SHAPE;
-    if (t->ws_base) {
-        (void)hipFree(t->ws_base);
-        t->ws_base = nullptr;
-    }
-    t->arena = Arena();
-    t->ws_bytes = 0;
-    if (hipMalloc((void**)&t->ws_base, bytes) != hipSuccess) {
-        t->ws_base = nullptr;
-        return LD_ERR_HIP;
-    }
-    t->ws_bytes = bytes;
-    t->arena.base = t->ws_base;
-    t->arena.cap = bytes - 4096;
-    return LD_OK;
+    return t->set_workspace(bytes, bytes - 4096);
 }
-
-size_t ld_taesd_workspace_bytes(const ld_taesd* t) { return t ? t->ws_bytes : 0; }
 
 int ld_taesd_decode(ld_taesd* t, const float* latent, float* out_f32, void* out_u8, int b, int h, int w, void* stream) {
     if (t == nullptr || latent == nullptr || out_f32 == nullptr) return LD_ERR_ARG;
-    if (t->ws_base == nullptr || !t->pt.all_loaded()) return LD_ERR_STATE;
-    if (b < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
-    size_t peak = 0;
-    const int st = taesd_run(t, true, nullptr, nullptr, nullptr, b, h, w, nullptr, &peak);
-    if (st != LD_OK) return st;
-    if (peak > t->arena.cap) return LD_ERR_SHAPE;
-    return taesd_run(t, false, latent, out_f32, (uint8_t*)out_u8, b, h, w, (hipStream_t)stream);
+    return abi_checked_run(*t, true, b >= 1 && h >= 1 && w >= 1,
+                           [&](size_t* peak) { return taesd_run(t, true, nullptr, nullptr, nullptr, b, h, w, nullptr, peak); },
+                           [&] { return taesd_run(t, false, latent, out_f32, (uint8_t*)out_u8, b, h, w, (hipStream_t)stream); });
 }
 
 int ld_taesd_profile(ld_taesd* t, const float* latent, float* out_f32, void* out_u8, int b, int h, int w, void* stream) {
-    if (t == nullptr) return LD_ERR_ARG;
-    t->want_timing = true;
-    const int st = ld_taesd_decode(t, latent, out_f32, out_u8, b, h, w, stream);
-    t->want_timing = false;
-    return st != LD_OK ? st : abi_profile_collect(t->timing, stream);
+    return abi_profile(t, stream, [&] { return ld_taesd_decode(t, latent, out_f32, out_u8, b, h, w, stream); });
 }
-
-int ld_taesd_profile_launches(const ld_taesd* t, char* buf, size_t buf_bytes) {
-    return abi_profile_launches(t ? &t->timing : nullptr, buf, buf_bytes);
-}
-
-int ld_taesd_last_launches(const ld_taesd* t) { return t ? t->last_launches : 0; }
-double ld_taesd_last_flops(const ld_taesd* t) { return t ? t->last_flops : 0.0; }
 
 }  // extern "C"

@@ -48,9 +48,8 @@ struct Feat {
 
 }  // namespace
 
-struct ld_unet {
+struct ld_unet : Model {
     ld_unet_config cfg;
-    ParamTable pt;
     std::vector<ResW> res;
     std::vector<StW> st;
     std::vector<ConvW> convs;
@@ -58,22 +57,13 @@ struct ld_unet {
     std::vector<Layer> mid_block;
     int te0_w, te0_b, te2_w, te2_b, outn_g, outn_b, outc_w, outc_b;
     int emb_total = 0, ted = 0;
-    // workspace
-    Arena arena;
-    char* ws_base = nullptr;
-    size_t ws_bytes = 0;
-    float* splitk_ws = nullptr;
-    size_t splitk_bytes = 0;
     float* log_sigmas = nullptr;   // 1000-entry table, device
     // context (cross-attention K / V^T per transformer, hoisted out of the step)
     int max_n = 0, max_h = 0, max_w = 0, max_tok = 0;
     half_t* ctx16 = nullptr;
     std::vector<half_t*> ctx_k, ctx_vt;
     int ctx_n = 0, ctx_tok = 0, ctx_tpad = 0;
-    int plan_n = 0, plan_h = 0, plan_w = 0, plan_pair = 0;   // last shape (and route) validated against the reserved arena
-    int last_launches = 0;
-    double last_flops = 0.0;
-    int* sync_ws = nullptr;        // LD_SYNC_INTS zeroed ints for the in-launch reductions (gemm.h GemmParams::sync)
+    PlanKey planned;               // (n, h, w, pair) validated last
     // derived copies of the 3x3 convolution weights in the row-resident kernel's layout (conv8.hip), re-derived with the LayerNorm folds
     struct W8 { int slot, N, Cin; size_t off; };
     std::vector<W8> w8_list;
@@ -88,8 +78,6 @@ struct ld_unet {
         w8_list.push_back({slot, N, Cin, w8_bytes});
         w8_bytes += (conv8_weight_bytes(N, Cin) + 255) / 256 * 256;
     }
-    Timing timing;
-    bool want_timing = false;
     char* fold_base = nullptr;     // LN-folded copies of the LN-consuming projections (see StW)
     size_t fold_bytes = 0;
     bool fold_dirty = true;        // set by every ld_unet_load_param / patch / unpatch; cleared when the fold kernels have run
@@ -547,20 +535,9 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     R.u = u;
     R.n = n;
     R.n_alloc = n;
-    Exec& ex = R.ex;
-    ex.stream = stream;
-    ex.dry = dry;
-    Arena plan;   // dry runs bump a private arena (no base): sizes only
-    ex.arena = dry ? &plan : &u->arena;
-    ex.splitk_ws = u->splitk_ws;
-    ex.splitk_bytes = u->splitk_bytes;
-    ex.sync_ws = u->sync_ws;
-    if (u->want_timing && !dry) {
-        u->timing.reset();
-        ex.timing = &u->timing;
-    }
+    Arena plan;
+    Exec& ex = R.ex = u->begin(dry, stream, plan);
     Arena& ar = *ex.arena;
-    ar.release(0);
     const ld_unet_config& c = u->cfg;
     const int mc = c.model_channels, ted = u->ted;
     const int in_mod = pair ? n / 2 : 0;   // CFG pair: x / sigma hold n / 2 samples; the kernels that read them per sample index n % in_mod
@@ -666,10 +643,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         a.x_in = x; a.sigma = sigma; a.out = out; a.in_mod = in_mod;
         ex.launch(KC_MISC, 2.0 * n * f.H * f.W * f.C * 9.0 * c.out_channels, "", 0, 0, 0, 0, "small_conv_out_kernel", [&] { return small_conv_out_launch(a, stream); });
     }
-    u->last_launches = ex.launches;
-    u->last_flops = ex.flops;
-    if (dry_peak) *dry_peak = ar.peak;
-    return ex.status;
+    return u->end(ex, dry_peak, true);
 }
 
 }  // namespace
@@ -704,8 +678,7 @@ int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
     u->cfg = *cfg;
     const int st = build(u);
     if (st != LD_OK) {
-        u->pt.destroy();
-        delete u;
+        ld_unet_destroy(u);
         return st;
     }
     // sigma table of ModelSamplingDiscrete (LD.py:1300-1326): scaled-linear betas in fp64, log taken in fp64
@@ -722,16 +695,11 @@ int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
     u->w8_of_slot.assign(u->pt.slots.size(), -1);
     for (const ld_unet::W8& w : u->w8_list) u->w8_of_slot[w.slot] = (long long)w.off;
     if (u->w8_bytes > 0 && hipMalloc((void**)&u->w8_base, u->w8_bytes) != hipSuccess) u->w8_base = nullptr;   // (without the copies the general kernels run)
-    if (u->fold_bytes > 0 && hipMalloc((void**)&u->fold_base, u->fold_bytes) != hipSuccess) {
-        u->pt.destroy();
-        delete u;
-        return LD_ERR_HIP;
-    }
-    if (hipMalloc((void**)&u->sync_ws, LD_SYNC_INTS * sizeof(int)) != hipSuccess || hipMemset(u->sync_ws, 0, LD_SYNC_INTS * sizeof(int)) != hipSuccess ||
+    if ((u->fold_bytes > 0 && hipMalloc((void**)&u->fold_base, u->fold_bytes) != hipSuccess) ||
+        hipMalloc((void**)&u->sync_ws, LD_SYNC_INTS * sizeof(int)) != hipSuccess || hipMemset(u->sync_ws, 0, LD_SYNC_INTS * sizeof(int)) != hipSuccess ||
         hipMalloc((void**)&u->log_sigmas, 1000 * sizeof(float)) != hipSuccess ||
         hipMemcpy(u->log_sigmas, ls.data(), 1000 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        u->pt.destroy();
-        delete u;
+        ld_unet_destroy(u);
         return LD_ERR_HIP;
     }
     *out = u;
@@ -740,9 +708,7 @@ int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
 
 void ld_unet_destroy(ld_unet* u) {
     if (u == nullptr) return;
-    u->pt.destroy();
-    u->timing.destroy();
-    if (u->ws_base) (void)hipFree(u->ws_base);
+    u->destroy_common();
     if (u->log_sigmas) (void)hipFree(u->log_sigmas);
     if (u->sync_ws) (void)hipFree(u->sync_ws);
     if (u->w8_base) (void)hipFree(u->w8_base);
@@ -751,11 +717,12 @@ void ld_unet_destroy(ld_unet* u) {
     delete u;
 }
 
-int ld_unet_param_count(const ld_unet* u) { return u ? (int)u->pt.slots.size() : 0; }
-
-int ld_unet_param_info(const ld_unet* u, int i, const char** name, int* ndim, int64_t shape[4]) {
-    return abi_param_info(u ? &u->pt : nullptr, i, name, ndim, shape);
-}
+int ld_unet_param_count(const ld_unet* u) { return abi_param_count(u); }
+int ld_unet_param_info(const ld_unet* u, int i, const char** name, int* ndim, int64_t shape[4]) { return abi_param_info(u, i, name, ndim, shape); }
+size_t ld_unet_workspace_bytes(const ld_unet* u) { return abi_workspace_bytes(u); }
+int ld_unet_last_launches(const ld_unet* u) { return abi_last_launches(u); }
+double ld_unet_last_flops(const ld_unet* u) { return abi_last_flops(u); }
+int ld_unet_profile_launches(const ld_unet* u, char* buf, size_t buf_bytes) { return abi_profile_launches(u, buf, buf_bytes); }
 
 int ld_unet_load_param(ld_unet* u, const char* name, const void* src, int dtype, void* stream) {
     if (u == nullptr || name == nullptr) return LD_ERR_ARG;
@@ -765,7 +732,7 @@ int ld_unet_load_param(ld_unet* u, const char* name, const void* src, int dtype,
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return LD_ERR_HIP;
         u->drop_backup(it->second);
     }
-    return abi_load_param(&u->pt, name, src, dtype, stream);
+    return abi_load_param(u, name, src, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------- LoRA patches (load-class calls)
@@ -844,18 +811,13 @@ int ld_unet_refresh_derived(ld_unet* u, void* stream) {
     return refresh_derived(u, (hipStream_t)stream);
 }
 
-size_t ld_unet_workspace_bytes(const ld_unet* u) { return u ? u->ws_bytes : 0; }
 size_t ld_unet_weight_bytes(const ld_unet* u) { return u ? u->pt.bytes + (u->fold_base ? u->fold_bytes : 0) + (u->w8_base ? u->w8_bytes : 0) : 0; }
 
 int ld_unet_reserve(ld_unet* u, int max_n, int max_h, int max_w, int max_tok) {
     if (u == nullptr || max_n < 1 || max_h < 1 || max_w < 1 || max_tok < 1) return LD_ERR_ARG;
-    if (u->ws_base) {
-        (void)hipFree(u->ws_base);
-        u->ws_base = nullptr;
-    }
+    u->free_workspace();   // (the old workspace goes before the new one is planned)
     // plan: dry-run the executor to find the activation peak
-    u->arena = Arena();
-    u->plan_n = u->plan_h = u->plan_w = u->plan_pair = 0;
+    u->planned = PlanKey();
     u->ctx_tok = max_tok;
     u->ctx_tpad = (max_tok + 7) & ~7;
     u->ctx_k.assign(u->st.size(), nullptr);
@@ -869,21 +831,14 @@ int ld_unet_reserve(ld_unet* u, int max_n, int max_h, int max_w, int max_tok) {
         if (st != LD_OK) return st;
         if (peak2 > peak) peak = peak2;
     }
-    const size_t act = (peak + 4095) / 4096 * 4096;
     const size_t tpad = (size_t)u->ctx_tpad;
     size_t ctxb = ((size_t)max_n * tpad * u->cfg.context_dim * sizeof(half_t) + 255) / 256 * 256;
     for (const StW& s : u->st) ctxb += 2 * (((size_t)max_n * tpad * s.c * sizeof(half_t) + 255) / 256 * 256);
-    u->splitk_bytes = (size_t)96 << 20;
-    u->ws_bytes = act + ctxb + u->splitk_bytes + 4096;
-    if (hipMalloc((void**)&u->ws_base, u->ws_bytes) != hipSuccess) {
-        u->ws_base = nullptr;
-        return LD_ERR_HIP;
-    }
-    char* p = u->ws_base;
-    u->arena.base = p;
-    u->arena.cap = act;
-    u->arena.off = u->arena.peak = 0;
-    p += act;
+    u->splitk_bytes = SPLITK_BYTES;
+    const size_t bytes = Model::padded(peak, SPLITK_BYTES + ctxb), act = bytes - SPLITK_BYTES - ctxb - 4096;
+    st = u->set_workspace(bytes, act);
+    if (st != LD_OK) return st;
+    char* p = u->ws_base + act;   // behind the activations: the contractions' scratch, then the context and its projections
     u->splitk_ws = reinterpret_cast<float*>(p);
     p += u->splitk_bytes;
     u->ctx16 = reinterpret_cast<half_t*>(p);
@@ -932,21 +887,10 @@ int ld_unet_set_context(ld_unet* u, const void* ctx, int dtype, int n, int token
 
 static int forward_checked(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream, bool pair) {
     if (u == nullptr || x == nullptr || sigma == nullptr || out == nullptr) return LD_ERR_ARG;
-    if (u->ws_base == nullptr || !u->pt.all_loaded() || u->ctx_n == 0) return LD_ERR_STATE;
-    if (n != u->ctx_n) return LD_ERR_SHAPE;
-    if (n > u->max_n || h < 1 || w < 1) return LD_ERR_SHAPE;
-    int st = LD_OK;
-    if (n != u->plan_n || h != u->plan_h || w != u->plan_w || (int)pair != u->plan_pair) {   // new shape: plan it on the host before touching the GPU
-        size_t peak = 0;
-        st = run_forward(u, true, nullptr, nullptr, nullptr, n, h, w, eps_only, nullptr, &peak, pair);
-        if (st != LD_OK) return st;
-        if (peak > u->arena.cap) return LD_ERR_SHAPE;
-        u->plan_n = n;
-        u->plan_h = h;
-        u->plan_w = w;
-        u->plan_pair = (int)pair;
-    }
-    return run_forward(u, false, x, sigma, out, n, h, w, eps_only, (hipStream_t)stream, nullptr, pair);
+    return abi_checked_run(*u, u->ctx_n != 0, n == u->ctx_n && n <= u->max_n && h >= 1 && w >= 1,
+                           [&](size_t* peak) { return run_forward(u, true, nullptr, nullptr, nullptr, n, h, w, eps_only, nullptr, peak, pair); },
+                           [&] { return run_forward(u, false, x, sigma, out, n, h, w, eps_only, (hipStream_t)stream, nullptr, pair); },
+                           &u->planned, PlanKey{{n, h, w, (int)pair}});
 }
 
 int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream) {
@@ -974,10 +918,7 @@ int ld_unet_profile_pair(ld_unet* u, const float* x, const float* sigma, float* 
 static int profile_any(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6], double flops[6],
                        int launches[6], bool pair) {
     if (u == nullptr || ms == nullptr || flops == nullptr || launches == nullptr) return LD_ERR_ARG;
-    u->want_timing = true;
-    int st = forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair);
-    u->want_timing = false;
-    if (st == LD_OK) st = abi_profile_collect(u->timing, stream);
+    const int st = abi_profile(u, stream, [&] { return forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair); });
     if (st != LD_OK) return st;
     for (int i = 0; i < KC_COUNT; ++i) {
         ms[i] = u->timing.ms[i];
@@ -998,12 +939,5 @@ int ld_unet_profile_kernels(const ld_unet* u, char* buf, size_t buf_bytes) {
     }
     return LD_OK;
 }
-
-int ld_unet_profile_launches(const ld_unet* u, char* buf, size_t buf_bytes) {
-    return abi_profile_launches(u ? &u->timing : nullptr, buf, buf_bytes);
-}
-
-int ld_unet_last_launches(const ld_unet* u) { return u ? u->last_launches : 0; }
-double ld_unet_last_flops(const ld_unet* u) { return u ? u->last_flops : 0.0; }
 
 }  // extern "C"

@@ -19,9 +19,8 @@ struct VAttnW {
 };
 }  // namespace
 
-struct ld_vae {
+struct ld_vae : Model {
     ld_vae_config cfg;
-    ParamTable pt;
     int pq_w, pq_b, cin_w, cin_b;
     VResW mid1, mid2;
     VAttnW mid_attn;
@@ -35,16 +34,7 @@ struct ld_vae {
     std::vector<int> ups_w, ups_b;        // [level] (-1 at level 0)
     int no_g, no_b, co_w, co_b;
     int block_in0 = 0;
-    Arena arena;
-    char* ws_base = nullptr;
-    size_t ws_bytes = 0;
-    float* splitk_ws = nullptr;
-    size_t splitk_bytes = 0;
-    int plan_b = 0, plan_h = 0, plan_w = 0;
-    int last_launches = 0;
-    double last_flops = 0.0;
-    Timing timing;
-    bool want_timing = false;
+    PlanKey planned;                      // the decode shape validated last
     half_t* co_pad = nullptr;             // conv_out weights zero-padded to 32 output rows + 32 biases (MFMA output conv)
 };
 
@@ -299,19 +289,9 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
     VRun R;
     R.v = v;
     R.n = b;
-    Exec& ex = R.ex;
-    ex.stream = stream;
-    ex.dry = dry;
     Arena plan;
-    ex.arena = dry ? &plan : &v->arena;
-    ex.splitk_ws = v->splitk_ws;
-    ex.splitk_bytes = v->splitk_bytes;
-    if (v->want_timing && !dry) {
-        v->timing.reset();
-        ex.timing = &v->timing;
-    }
+    Exec& ex = R.ex = v->begin(dry, stream, plan);
     Arena& ar = *ex.arena;
-    ar.release(0);
     const ld_vae_config& c = v->cfg;
     int H = h, W = w;
     int C = v->block_in0;
@@ -373,10 +353,7 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
                       [&] { return small_conv_out_launch(a, stream); });
         }
     }
-    v->last_launches = ex.launches;
-    v->last_flops = ex.flops;
-    if (dry_peak) *dry_peak = ar.peak;
-    return ex.status;
+    return v->end(ex, dry_peak, true);
 }
 
 // VAE.encode's device part (LD.py:6383-6410 → AutoencodingEngine.encode 3475-3481 → Encoder.forward 3731-3758 → quant_conv):
@@ -385,15 +362,9 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
     VRun R;
     R.v = v;
     R.n = b;
-    Exec& ex = R.ex;
-    ex.stream = stream;
-    ex.dry = dry;
     Arena plan;
-    ex.arena = dry ? &plan : &v->arena;
-    ex.splitk_ws = v->splitk_ws;
-    ex.splitk_bytes = v->splitk_bytes;
+    Exec& ex = R.ex = v->begin(dry, stream, plan);   // (no entry point profiles an encode: want_timing is never set here)
     Arena& ar = *ex.arena;
-    ar.release(0);
     const ld_vae_config& c = v->cfg;
     int H = h, W = w;
     for (int l = 1; l < c.num_levels; ++l) {
@@ -438,10 +409,7 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
                   [&] { return small_pointwise_launch(m, v->pt.ptr(v->e_q_w), v->pt.ptr(v->e_q_b), moments, b, H * W, Z2, stream); });
     }
     if (H != h || W != w) ex.note(LD_ERR_SHAPE);
-    v->last_launches = ex.launches;
-    v->last_flops = ex.flops;
-    if (dry_peak) *dry_peak = ar.peak;
-    return ex.status;
+    return v->end(ex, dry_peak, true);
 }
 
 }  // namespace
@@ -459,9 +427,7 @@ int ld_vae_create(const ld_vae_config* cfg, ld_vae** out) {
         if (hipMalloc((void**)&v->co_pad, bytes) != hipSuccess || hipMemset(v->co_pad, 0, bytes) != hipSuccess) st = LD_ERR_HIP;
     }
     if (st != LD_OK) {
-        v->pt.destroy();
-        if (v->co_pad) (void)hipFree(v->co_pad);
-        delete v;
+        ld_vae_destroy(v);
         return st;
     }
     *out = v;
@@ -470,113 +436,68 @@ int ld_vae_create(const ld_vae_config* cfg, ld_vae** out) {
 
 void ld_vae_destroy(ld_vae* v) {
     if (v == nullptr) return;
-    v->pt.destroy();
-    v->timing.destroy();
+    v->destroy_common();
     if (v->co_pad) (void)hipFree(v->co_pad);
-    if (v->ws_base) (void)hipFree(v->ws_base);
     delete v;
 }
 
-int ld_vae_param_count(const ld_vae* v) { return v ? (int)v->pt.slots.size() : 0; }
+int ld_vae_param_count(const ld_vae* v) { return abi_param_count(v); }
+int ld_vae_param_info(const ld_vae* v, int i, const char** name, int* ndim, int64_t shape[4]) { return abi_param_info(v, i, name, ndim, shape); }
+int ld_vae_load_param(ld_vae* v, const char* name, const void* src, int dtype, void* stream) { return abi_load_param(v, name, src, dtype, stream); }
+size_t ld_vae_workspace_bytes(const ld_vae* v) { return abi_workspace_bytes(v); }
+int ld_vae_last_launches(const ld_vae* v) { return abi_last_launches(v); }
+double ld_vae_last_flops(const ld_vae* v) { return abi_last_flops(v); }
+int ld_vae_profile_launches(const ld_vae* v, char* buf, size_t buf_bytes) { return abi_profile_launches(v, buf, buf_bytes); }
 
-int ld_vae_param_info(const ld_vae* v, int i, const char** name, int* ndim, int64_t shape[4]) {
-    return abi_param_info(v ? &v->pt : nullptr, i, name, ndim, shape);
-}
-
-int ld_vae_load_param(ld_vae* v, const char* name, const void* src, int dtype, void* stream) {
-    return abi_load_param(v ? &v->pt : nullptr, name, src, dtype, stream);
-}
-
-size_t ld_vae_workspace_bytes(const ld_vae* v) { return v ? v->ws_bytes : 0; }
-
-// host-only dry run of the executor: the workspace a (b, h, w) decode (and encode, when the encoder is loaded) needs, without allocating
-static int vae_plan(ld_vae* v, int b, int h, int w, size_t* bytes) {
-    size_t peak = 0;
-    int st = run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, &peak);
-    if (st != LD_OK) return st;
-    if (v->cfg.with_encoder) {
+// host-only dry runs of the executor: the activation peak of a (b, h, w) decode (and encode, when the encoder is loaded), without allocating
+static int vae_plan(ld_vae* v, int b, int h, int w, size_t* peak) {
+    int st = run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, peak);
+    if (st == LD_OK && v->cfg.with_encoder) {
         size_t pe = 0;
         st = run_encode(v, true, nullptr, nullptr, b, h, w, nullptr, &pe);
-        if (st != LD_OK) return st;
-        if (pe > peak) peak = pe;
+        if (pe > *peak) *peak = pe;
     }
-    v->plan_b = v->plan_h = v->plan_w = 0;          // (the dry run re-planned the arena marks: the next real call plans its own shape)
-    *bytes = (peak + 4095) / 4096 * 4096 + ((size_t)96 << 20) + 4096;
-    return LD_OK;
+    if (st == LD_OK) v->planned = PlanKey();        // (the dry run re-planned the arena marks: the next real call plans its own shape)
+    return st;
+}
+
+size_t ld_vae_plan_bytes(ld_vae* v, int b, int h, int w) {
+    return abi_plan_bytes(v, b, h, w, [&](size_t* peak) { return vae_plan(v, b, h, w, peak); }, SPLITK_BYTES);
 }
 
 int ld_vae_reserve(ld_vae* v, int max_b, int max_h, int max_w) {
     if (v == nullptr || max_b < 1 || max_h < 1 || max_w < 1) return LD_ERR_ARG;
-    if (v->ws_base) {
-        (void)hipFree(v->ws_base);
-        v->ws_base = nullptr;
-    }
-    v->arena = Arena();
-    v->plan_b = v->plan_h = v->plan_w = 0;
-    size_t bytes = 0;
-    const int st = vae_plan(v, max_b, max_h, max_w, &bytes);
+    v->free_workspace();                            // (the old workspace goes before the new one is planned)
+    v->planned = PlanKey();
+    size_t peak = 0;
+    const int st = vae_plan(v, max_b, max_h, max_w, &peak);
     if (st != LD_OK) return st;
-    v->ws_bytes = bytes;
-    v->splitk_bytes = (size_t)96 << 20;
-    const size_t act = v->ws_bytes - v->splitk_bytes - 4096;
-    if (hipMalloc((void**)&v->ws_base, v->ws_bytes) != hipSuccess) {
-        v->ws_base = nullptr;
-        return LD_ERR_HIP;
-    }
-    v->arena.base = v->ws_base;
-    v->arena.cap = act;
-    v->splitk_ws = reinterpret_cast<float*>(v->ws_base + act);
-    return LD_OK;
-}
-
-size_t ld_vae_plan_bytes(ld_vae* v, int b, int h, int w) {
-    size_t bytes = 0;
-    if (v == nullptr || b < 1 || h < 1 || w < 1 || vae_plan(v, b, h, w, &bytes) != LD_OK) return 0;
-    return bytes;
+    const size_t bytes = Model::padded(peak, SPLITK_BYTES), act = bytes - SPLITK_BYTES - 4096;
+    v->splitk_bytes = SPLITK_BYTES;
+    const int ws = v->set_workspace(bytes, act);
+    if (ws == LD_OK) v->splitk_ws = reinterpret_cast<float*>(v->ws_base + act);
+    return ws;
 }
 
 int ld_vae_decode(ld_vae* v, const float* z, float* out, int b, int h, int w, void* stream) {
     if (v == nullptr || z == nullptr || out == nullptr) return LD_ERR_ARG;
-    if (v->ws_base == nullptr || !v->pt.all_loaded()) return LD_ERR_STATE;
-    if (b < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
-    if (b != v->plan_b || h != v->plan_h || w != v->plan_w) {
-        size_t peak = 0;
-        const int st = run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, &peak);
-        if (st != LD_OK) return st;
-        if (peak > v->arena.cap) return LD_ERR_SHAPE;
-        v->plan_b = b;
-        v->plan_h = h;
-        v->plan_w = w;
-    }
-    return run_decode(v, false, z, out, b, h, w, (hipStream_t)stream);
+    return abi_checked_run(*v, true, b >= 1 && h >= 1 && w >= 1,
+                           [&](size_t* peak) { return run_decode(v, true, nullptr, nullptr, b, h, w, nullptr, peak); },
+                           [&] { return run_decode(v, false, z, out, b, h, w, (hipStream_t)stream); }, &v->planned, PlanKey{{b, h, w, 0}});
 }
 
 int ld_vae_encode(ld_vae* v, const float* pixels_nchw, float* moments, int b, int h, int w, void* stream) {
     if (v == nullptr || pixels_nchw == nullptr || moments == nullptr) return LD_ERR_ARG;
-    if (!v->cfg.with_encoder) return LD_ERR_STATE;
-    if (v->ws_base == nullptr || !v->pt.all_loaded()) return LD_ERR_STATE;
-    if (b < 1 || h < 1 || w < 1) return LD_ERR_SHAPE;
-    size_t peak = 0;
-    int st = run_encode(v, true, nullptr, nullptr, b, h, w, nullptr, &peak);
-    if (st != LD_OK) return st;
-    if (peak > v->arena.cap) return LD_ERR_SHAPE;
-    v->plan_b = v->plan_h = v->plan_w = 0;   // the decode plan cache does not cover encode shapes
-    return run_encode(v, false, pixels_nchw, moments, b, h, w, (hipStream_t)stream);
+    return abi_checked_run(*v, v->cfg.with_encoder != 0, b >= 1 && h >= 1 && w >= 1,
+                           [&](size_t* peak) { return run_encode(v, true, nullptr, nullptr, b, h, w, nullptr, peak); },
+                           [&] {
+                               v->planned = PlanKey();   // the decode plan cache does not cover encode shapes
+                               return run_encode(v, false, pixels_nchw, moments, b, h, w, (hipStream_t)stream);
+                           });
 }
 
 int ld_vae_profile(ld_vae* v, const float* z, float* out, int b, int h, int w, void* stream) {
-    if (v == nullptr) return LD_ERR_ARG;
-    v->want_timing = true;
-    const int st = ld_vae_decode(v, z, out, b, h, w, stream);
-    v->want_timing = false;
-    return st != LD_OK ? st : abi_profile_collect(v->timing, stream);
+    return abi_profile(v, stream, [&] { return ld_vae_decode(v, z, out, b, h, w, stream); });
 }
-
-int ld_vae_profile_launches(const ld_vae* v, char* buf, size_t buf_bytes) {
-    return abi_profile_launches(v ? &v->timing : nullptr, buf, buf_bytes);
-}
-
-int ld_vae_last_launches(const ld_vae* v) { return v ? v->last_launches : 0; }
-double ld_vae_last_flops(const ld_vae* v) { return v ? v->last_flops : 0.0; }
 
 }  // extern "C"

@@ -10,7 +10,6 @@ PLANES, so that what it shows is the last plane as a grey image.  That loop's ar
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Callable, Dict, Optional, Union
 
@@ -18,7 +17,7 @@ import torch
 
 from . import weights as W
 from ._lib import check, lib
-from .unet import WeightSource, _load_params, _parse_launches, _stream
+from ._model import ResidentModel, WeightSource, _stream
 
 _PREFIX = "taesd_decoder."
 
@@ -45,10 +44,12 @@ def load_decoder_file(path: str) -> Dict[str, torch.Tensor]:
     return decoder_state_dict(CK.load_state_dict(os.fspath(path)))
 
 
-class MI355XTAESD:
+class MI355XTAESD(ResidentModel):
     """TAESD's decoder resident on one MI355X.  `weights`: a state dict (any spelling `decoder_state_dict` accepts), a callable
     (name, shape) -> tensor, or the path of a safetensors file.  The latent is what the sampler loop holds: the model-space x the reference
     passes to `taesd_preview` (LD.py:764), [B, 4, h, w], with no `process_out` applied."""
+
+    family = "taesd"
 
     def __init__(self, weights: Union[WeightSource, str, os.PathLike], device="cuda:0", max_batch: int = 1, max_hw=(64, 64)):
         self.device = torch.device(device)
@@ -56,45 +57,8 @@ class MI355XTAESD:
             weights = load_decoder_file(weights)
         elif not callable(weights):
             weights = decoder_state_dict(weights)
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().ld_taesd_create(C.byref(self._h)), "ld_taesd_create")
-            _load_params(self._h, lib().ld_taesd_param_count, lib().ld_taesd_param_info, lib().ld_taesd_load_param, weights, self.device)
-        self._reserved = (0, 0, 0)
-        self.reserve_epoch = 0               # bumped when the workspace moves: a captured decode bakes its addresses in
+        self._create(weights)
         self._ensure(max_batch, max_hw[0], max_hw[1])
-
-    def _ensure(self, b: int, h: int, w: int) -> None:
-        """Grow the workspace when a call exceeds the plan (batch or latent size)."""
-        mb, mh, mw = self._reserved
-        if b > mb or h > mh or w > mw:
-            self._reserved = (max(b, mb), max(h, mh), max(w, mw))
-            with torch.cuda.device(self.device):
-                check(lib().ld_taesd_reserve(self._h, *self._reserved), "ld_taesd_reserve")
-            self.reserve_epoch += 1
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                lib().ld_taesd_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def workspace_bytes(self) -> int:
-        return lib().ld_taesd_workspace_bytes(self._h)
-
-    def plan_bytes(self, b: int, h: int, w: int) -> int:
-        return lib().ld_taesd_plan_bytes(self._h, b, h, w)
-
-    @property
-    def last_flops(self) -> float:
-        return lib().ld_taesd_last_flops(self._h)
-
-    @property
-    def last_launches(self) -> int:
-        return lib().ld_taesd_last_launches(self._h)
 
     def _nhwc(self, latent: torch.Tensor) -> torch.Tensor:
         if latent.dim() != 4 or latent.shape[1] != 4:
@@ -129,7 +93,7 @@ class MI355XTAESD:
     def profile(self, latent: torch.Tensor) -> list:
         """One decode with HIP events around every launch -> [(what, dims, flops, microseconds, kernel)] in launch order."""
         self._run(latent, True, profile=True)
-        return _parse_launches(lib().ld_taesd_profile_launches, self._h)
+        return self.profile_launches()
 
     def to(self, device):
         """The reference builds a TAESD per preview and leaves it where it loads; the weights here stay resident in the C handle."""

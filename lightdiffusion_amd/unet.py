@@ -12,43 +12,13 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Callable, Dict, Optional, Union
+from typing import Dict, Optional
 
 import torch
 
 from . import weights as W
 from ._lib import ERR_SHAPE, F16, F32, LDError, LoraTerm, UNetConfig, VAEConfig, check, lib
-
-WeightSource = Union[Dict[str, torch.Tensor], Callable[[str, tuple], torch.Tensor]]
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _load_params(handle, count_fn, info_fn, load_fn, src: WeightSource, device, prefixes=("",)):
-    name, ndim, shape = C.c_char_p(), C.c_int(), (C.c_int64 * 4)()
-    for i in range(count_fn(handle)):
-        check(info_fn(handle, i, C.byref(name), C.byref(ndim), shape), "param_info")
-        key = name.value.decode()
-        shp = tuple(int(shape[k]) for k in range(ndim.value))
-        if callable(src):
-            t = src(key, shp)
-        else:
-            t = None
-            for p in prefixes:
-                if p + key in src:
-                    t = src[p + key]
-                    break
-            if t is None:
-                raise KeyError(f"checkpoint is missing '{key}'")
-        if tuple(t.shape) != shp:
-            raise ValueError(f"'{key}': expected shape {shp}, got {tuple(t.shape)}")
-        if t.dtype not in (torch.float16, torch.float32):
-            t = t.float()
-        t = t.to(device).contiguous()
-        check(load_fn(handle, key.encode(), t.data_ptr(), F32 if t.dtype == torch.float32 else F16, _stream()), f"load_param({key})")
-    torch.cuda.synchronize(device)
+from ._model import ResidentModel, WeightSource, _stream
 
 
 def lora_factor_mismatch(shape, up, down) -> Optional[str]:
@@ -83,18 +53,10 @@ def lora_terms(terms, device, shape):
     return arr, keep
 
 
-def _parse_launches(fn, handle) -> list:
-    buf = C.create_string_buffer(1 << 18)
-    check(fn(handle, buf, len(buf)), "profile_launches")
-    out = []
-    for line in buf.value.decode().splitlines():
-        what, a, b, c, d, fl, us, kern = line.split("\t")
-        out.append((what, (int(a), int(b), int(c), int(d)), float(fl), float(us), kern))
-    return out
-
-
-class MI355XUNet:
+class MI355XUNet(ResidentModel):
     """SD1.x UNet resident on one MI355X.  `cfg` as in `weights.sd15_unet_config()`."""
+
+    family, key_prefixes, reserve_rank = "unet", ("", "model.diffusion_model."), 4
 
     def __init__(self, cfg: dict, weights: WeightSource, device="cuda:0", max_batch: int = 2, max_hw=(64, 64), max_tokens: int = 77):
         self.cfg = dict(cfg)
@@ -112,13 +74,7 @@ class MI355XUNet:
             c.transformer_depth_output[i] = v
         c.transformer_depth_middle = cfg["transformer_depth_middle"]
         c.context_dim, c.num_heads = cfg["context_dim"], cfg["num_heads"]
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().ld_unet_create(C.byref(c), C.byref(self._h)), "ld_unet_create")
-            _load_params(self._h, lib().ld_unet_param_count, lib().ld_unet_param_info, lib().ld_unet_load_param, weights,
-                         self.device, ("", "model.diffusion_model."))
-        self._reserved = (0, 0, 0, 0)
-        self.reserve_epoch = 0           # bumped whenever the workspace moves: captured hipGraphs of older epochs are stale
+        self._create(weights, C.byref(c))
         self.reserve(max_batch, max_hw, max_tokens)
         self._ctx_ref = None             # device copy of the context the resident K / V^T were projected from
         self._ctx_token = None           # per-run token of our own sampling stack (sampling.sampling_function)
@@ -130,33 +86,16 @@ class MI355XUNet:
         self._hook_event = None
         self._hook_epoch = 0
         self.applied_patches_uuid = None  # identity of the LoRA patch set merged into the resident weights (None: the loaded weights)
-        self._param_shapes = None        # {parameter name: checkpoint shape}, read from the library on first use
 
     def reserve(self, max_batch: int, max_hw=(64, 64), max_tokens: int = 77) -> None:
         """(Re)size the activation workspace.  Growing it frees and reallocates: the context must be set again and every
         captured graph is stale (`reserve_epoch`)."""
-        with torch.cuda.device(self.device):
-            check(lib().ld_unet_reserve(self._h, max_batch, max_hw[0], max_hw[1], max_tokens), "ld_unet_reserve")
-        self._reserved = (max_batch, max_hw[0], max_hw[1], max_tokens)
-        self.reserve_epoch += 1
+        self._reserve(max_batch, max_hw[0], max_hw[1], max_tokens)
+
+    def _workspace_moved(self) -> None:
         self._ctx_ref = self._ctx_token = self.ctx_shape = None
         self._denoisers = {}
         self._hook = {}
-
-    def _ensure(self, n: int, h: int, w: int, tokens: int) -> None:
-        """Lazy re-reserve (the reference accepts any batch, latent size and number of 77-token chunks): grow the plan when a
-        call exceeds it instead of failing with ERR_SHAPE."""
-        mn, mh, mw, mt = self._reserved
-        if n > mn or h > mh or w > mw or tokens > mt:
-            self.reserve(max(n, mn), (max(h, mh), max(w, mw)), max(tokens, mt))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                lib().ld_unet_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     # -- sizes
     @property
@@ -170,17 +109,6 @@ class MI355XUNet:
         return lib().ld_unet_patch_bytes(self._h)
 
     # -- parameters and LoRA patches of the resident weights
-    def param_shapes(self) -> Dict[str, tuple]:
-        """{parameter name (checkpoint key minus 'model.diffusion_model.'): shape as the checkpoint stores it}"""
-        if self._param_shapes is None:
-            name, ndim, shape = C.c_char_p(), C.c_int(), (C.c_int64 * 4)()
-            out = {}
-            for i in range(lib().ld_unet_param_count(self._h)):
-                check(lib().ld_unet_param_info(self._h, i, C.byref(name), C.byref(ndim), shape), "param_info")
-                out[name.value.decode()] = tuple(int(shape[k]) for k in range(ndim.value))
-            self._param_shapes = out
-        return dict(self._param_shapes)
-
     def read_param(self, name: str) -> torch.Tensor:
         """The resident value of one parameter, back in checkpoint layout (fp16, device)."""
         shapes = self.param_shapes()
@@ -231,18 +159,6 @@ class MI355XUNet:
         self.applied_patches_uuid = uuid
         if changed:
             self._weights_changed()
-
-    @property
-    def workspace_bytes(self) -> int:
-        return lib().ld_unet_workspace_bytes(self._h)
-
-    @property
-    def last_launches(self) -> int:
-        return lib().ld_unet_last_launches(self._h)
-
-    @property
-    def last_flops(self) -> float:
-        return lib().ld_unet_last_flops(self._h)
 
     # -- hot path
     def set_context(self, ctx: torch.Tensor) -> None:
@@ -321,10 +237,6 @@ class MI355XUNet:
             name, n, ms, fl = line.split("\t")
             out[name] = (float(ms), float(fl), int(n))
         return out
-
-    def profile_launches(self) -> list:
-        """Per launch of the last `profile()` call: [(what, (a, b, c, d), flops, microseconds, kernel)] in launch order."""
-        return _parse_launches(lib().ld_unet_profile_launches, self._h)
 
     # -- the reference's plugin seam
     def _sync_context(self, ctx: torch.Tensor, n: int, h: int, w: int, token=None) -> None:
@@ -442,9 +354,10 @@ class MI355XUNet:
         return self
 
 
-class MI355XVAE:
+class MI355XVAE(ResidentModel):
     """KL-VAE decoder resident on one MI355X.  `cfg` as in `weights.sd15_vae_config()`."""
 
+    family, key_prefixes = "vae", ("", "first_stage_model.")
     downscale_ratio = 8
     latent_channels = 4
 
@@ -458,41 +371,8 @@ class MI355XVAE:
         for i, v in enumerate(cfg["ch_mult"]):
             c.ch_mult[i] = v
         c.num_res_blocks, c.out_ch = cfg["num_res_blocks"], cfg["out_ch"]
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().ld_vae_create(C.byref(c), C.byref(self._h)), "ld_vae_create")
-            _load_params(self._h, lib().ld_vae_param_count, lib().ld_vae_param_info, lib().ld_vae_load_param, weights,
-                         self.device, ("", "first_stage_model."))
-        self._reserved = (0, 0, 0)
+        self._create(weights, C.byref(c))
         self._ensure(max_batch, max_hw[0], max_hw[1])
-
-    def _ensure(self, b: int, h: int, w: int) -> None:
-        """Grow the workspace when a call exceeds the plan (batch or latent size), e.g. the 1024^2 decode of a hires pass."""
-        mb, mh, mw = self._reserved
-        if b > mb or h > mh or w > mw:
-            self._reserved = (max(b, mb), max(h, mh), max(w, mw))
-            with torch.cuda.device(self.device):
-                check(lib().ld_vae_reserve(self._h, *self._reserved), "ld_vae_reserve")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                lib().ld_vae_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def workspace_bytes(self) -> int:
-        return lib().ld_vae_workspace_bytes(self._h)
-
-    @property
-    def last_flops(self) -> float:
-        return lib().ld_vae_last_flops(self._h)
-
-    @property
-    def last_launches(self) -> int:
-        return lib().ld_vae_last_launches(self._h)
 
     memory_fraction = 0.9          # share of the free device memory a decode's workspace may take
     memory_budget = None           # bytes; None: ask the driver (torch.cuda.mem_get_info) — tests set it to force the split
@@ -507,9 +387,10 @@ class MI355XVAE:
         if budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             budget = self.memory_fraction * (free + (self.workspace_bytes if any(self._reserved) else 0))   # (a re-reserve frees the old one first)
+        _, ph, pw = self._grown(b, h, w)                          # (the sizes `_ensure` will reserve)
         n = b
         while n > 1:
-            need = lib().ld_vae_plan_bytes(self._h, n, max(h, mh), max(w, mw))
+            need = self.plan_bytes(n, ph, pw)
             if 0 < need <= budget:
                 break
             n = (n + 1) // 2
@@ -535,7 +416,7 @@ class MI355XVAE:
         out = torch.empty(b, 8 * h, 8 * w, self.cfg["out_ch"], dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             check(lib().ld_vae_profile(self._h, z.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_vae_profile")
-        return _parse_launches(lib().ld_vae_profile_launches, self._h)
+        return self.profile_launches()
 
     def decode(self, samples_in: torch.Tensor) -> torch.Tensor:
         """VAE.decode (LD.py:6357-6381): returns [B, 8h, 8w, 3] fp32 in [0,1] on the CPU (`intermediate_device`)."""

@@ -11,7 +11,7 @@ import torch
 
 from . import weights as W
 from ._lib import ESRGANConfig, check, lib
-from .unet import WeightSource, _load_params, _parse_launches, _stream
+from ._model import ResidentModel, WeightSource, _stream
 
 
 def tile_plan(height: int, width: int, tile: int, overlap: int) -> List[Tuple[int, int, int, int]]:
@@ -33,9 +33,11 @@ def feather_ramp(n: int, feather: int) -> torch.Tensor:
     return m
 
 
-class MI355XUpscaler:
+class MI355XUpscaler(ResidentModel):
     """RRDBNet resident on one MI355X.  `cfg`: in_nc, out_nc, nf, gc, nb, scale (checkpoint.detect_esrgan_config); `weights`: a state
     dict with old-arch keys (checkpoint.normalize_esrgan_keys) or a callable (name, shape) -> tensor."""
+
+    family = "esrgan"
 
     def __init__(self, cfg: dict, weights: WeightSource, device="cuda:0", max_batch: int = 1, max_hw=(64, 64)):
         self.cfg = dict(cfg)
@@ -43,43 +45,8 @@ class MI355XUpscaler:
         c = ESRGANConfig()
         c.in_nc, c.out_nc, c.nf, c.gc, c.nb, c.scale = (int(cfg[k]) for k in ("in_nc", "out_nc", "nf", "gc", "nb", "scale"))
         self.scale = int(cfg["scale"])
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().ld_esrgan_create(C.byref(c), C.byref(self._h)), "ld_esrgan_create")
-            _load_params(self._h, lib().ld_esrgan_param_count, lib().ld_esrgan_param_info, lib().ld_esrgan_load_param, weights, self.device)
-        self._reserved = (0, 0, 0)
+        self._create(weights, C.byref(c))
         self._ensure(max_batch, max_hw[0], max_hw[1])
-
-    def _ensure(self, b: int, h: int, w: int) -> None:
-        """Grow the workspace when a call exceeds the plan (batch or image size)."""
-        mb, mh, mw = self._reserved
-        if b > mb or h > mh or w > mw:
-            self._reserved = (max(b, mb), max(h, mh), max(w, mw))
-            with torch.cuda.device(self.device):
-                check(lib().ld_esrgan_reserve(self._h, *self._reserved), "ld_esrgan_reserve")
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                lib().ld_esrgan_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    @property
-    def workspace_bytes(self) -> int:
-        return lib().ld_esrgan_workspace_bytes(self._h)
-
-    def plan_bytes(self, b: int, h: int, w: int) -> int:
-        return lib().ld_esrgan_plan_bytes(self._h, b, h, w)
-
-    @property
-    def last_flops(self) -> float:
-        return lib().ld_esrgan_last_flops(self._h)
-
-    @property
-    def last_launches(self) -> int:
-        return lib().ld_esrgan_last_launches(self._h)
 
     def _io(self, image: torch.Tensor):
         x = image.to(self.device, torch.float32).contiguous()
@@ -101,7 +68,7 @@ class MI355XUpscaler:
         x, out, b, h, w = self._io(image)
         with torch.cuda.device(self.device):
             check(lib().ld_esrgan_profile(self._h, x.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_esrgan_profile")
-        return _parse_launches(lib().ld_esrgan_profile_launches, self._h)
+        return self.profile_launches()
 
     def to(self, device):
         """The reference moves the model to the device before and to the CPU after an upscale (LD.py:7365, 7393); the weights here stay
