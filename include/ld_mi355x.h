@@ -220,11 +220,14 @@ int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int
                void* ws, size_t ws_bytes, void* stream);
 /* GroupNorm(32) + SiLU + 3x3 conv (stride 1, pad 1) over the channel concat of two NHWC sources — ResBlock1.in_layers /
  * out_layers (LD.py:5224-5262).  Where the conv runs on the halo-tile kernel the normalisation is fused into its A operand
- * (statistics pass only, no normalised tensor in HBM).  ws >= ld_op_groupnorm_conv_ws_bytes(...). */
+ * (statistics pass only, no normalised tensor in HBM).  in_part / in_chunks (optional, one source only): the GroupNorm partial statistics
+ * of x1 that its producer wrote, [n][in_chunks][32][2] floats — the statistics pass is skipped, as the UNet executor does behind a convolution
+ * that emitted them.  part / chunks (both or neither): the partial statistics of y, as ld_op_conv_gn_partials.
+ * ws >= ld_op_groupnorm_conv_ws_bytes(...). */
 size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int cout);
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
-                         const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
-                         size_t ws_bytes, void* stream);
+                         const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, float* in_part,
+                         int in_chunks, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
 int ld_op_repack_conv(const void* src_oihw, int dtype, int cout, int cin, void* dst, void* stream);
 /* ResBlock1's out_layers convolution and its 1x1 skip_connection as ONE contraction (LD.py:5267, 5273-5287; the UNet executor's "skip
  * fold"):  y = conv3x3(x; wt) + bias + conv1x1(cat(s1, s2); wskip) + bskip (+ rowvec per image), stride 1, pad 1.  x [n][h][w][c];
@@ -237,11 +240,16 @@ int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, c
 /* The same behind out_layers' GroupNorm(32) + SiLU, as the UNet executor runs a ResBlock's second half:
  *   y = conv3x3(SiLU(GroupNorm(x)); wt) + bias + conv1x1(cat(s1, s2); wskip) + bskip (+ rowvec per image).
  * The skip sources enter RAW.  gamma / beta NULL: no normalisation (ld_op_conv_skip).  part / chunks (both or neither): the GroupNorm partial
- * statistics of y, as ld_op_conv_gn_partials.  ws >= ld_op_groupnorm_conv_skip_ws_bytes(...). */
+ * statistics of y, as ld_op_conv_gn_partials; in_part / in_chunks: those of x from its producer, as ld_op_groupnorm_conv.
+ * ws >= ld_op_groupnorm_conv_skip_ws_bytes(...). */
 size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int n, int h, int w);
 int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const void* gamma, const void* beta, float eps, const void* wt, const void* bias,
                               const void* s1, int sc1, const void* s2, int sc2, const void* wskip, const void* bskip, const void* rowvec, void* y, int cout,
-                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
+                              float* in_part, int in_chunks, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
+/* Host only: does the UNet executor run the 3x3 stride-1 convolution [n][h][w][c] -> cout of a ResBlock's out_layers on a kernel that takes the
+ * 1x1 skip_connection as a second K segment (ld_op_groupnorm_conv_skip), 1, or does the skip run as a launch of its own in front (0)?  The
+ * answer of the route planner under the executors' scratch. */
+int ld_op_conv_takes_skip_segment(int c, int n, int h, int w, int cout);
 /* Upsample1 (nearest resize to hv x wv, then 3x3 conv, stride 1, pad 1; LD.py:5141-5152) with the resize folded into the weights: for an exact
  * 2x resize the layer is four 2x2 convolutions of the SOURCE image, one per output phase (2y + py, 2x + px), whose weights are sums of the 3x3
  * taps.  ld_op_upconv2x_fold derives them once from wt [cout][9 cin] (ld_op_repack_conv's layout): wfold [py*2+px][cout][a*2+b][cin], 16 cout cin
@@ -250,14 +258,14 @@ int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const v
 int ld_op_upconv2x_fold(const void* wt, int cout, int cin, void* wfold, void* stream);
 int ld_op_upconv2x(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* wfold, const void* bias, void* y, int cout,
                    void* ws, size_t ws_bytes, void* stream);
-/* 3x3 stride-1 convolution (hv = 2h: behind a nearest-2x upsampling) that also returns the GroupNorm(32) partial statistics of its OUTPUT
+/* Convolution (ksize 1 or 3, any stride, two optional sources, hv = 2h: behind a nearest-2x upsampling; ld_op_conv's arguments) that also returns the GroupNorm(32) partial statistics of its OUTPUT
  * where the kernel that runs the shape writes them (the halo convolution's generic epilogue, the row-resident kernel, the split-K second
  * pass) — what lets the GroupNorm that follows (ResBlock1 out_layers / the next block's in_layers, LD.py:5224-5262; the VAE's ResnetBlock,
  * LD.py:3560-3576) skip its statistics pass.  part: [n][*chunks][32][2] floats (sum, sum of squares per image, pixel chunk, group), sized
  * ld_op_conv_gn_partials_floats(n, hv*wv); *chunks = 0 when this shape's kernel does not write them.  For parity tests. */
 size_t ld_op_conv_gn_partials_floats(int n, int hw);
-int ld_op_conv_gn_partials(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* bias,
-                           const void* residual, void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
+int ld_op_conv_gn_partials(const void* x, int c, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize, const void* wt,
+                           const void* bias, const void* residual, void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
 /* GroupNorm(32) over the channel concat of two NHWC sources (+ optional SiLU); ws >= ld_op_groupnorm_ws_bytes */
 size_t ld_op_groupnorm_ws_bytes(int n, int hw);
 int ld_op_groupnorm(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta,
@@ -323,6 +331,9 @@ int ld_op_timestep_embed_mod(const float* sigma, const float* log_sigmas, int n_
 int ld_op_dup_halves(void* base0, size_t bytes0, void* base1, size_t bytes1, void* base2, size_t bytes2, int count, void* stream);
 /* src [n][t][d] (dtype LD_F16 / LD_F32) -> dst fp16 [n][tp][d], rows t .. tp-1 zero */
 int ld_op_ctx_pad(const void* src, int dtype, int n, int t, int tp, int d, void* dst, void* stream);
+/* the cross-attention operands ld_unet_set_context projects once per context, per transformer: k_out [n][tp][c] = ctx16 wk^T and
+ * vt_out [n][c][tp] = wv ctx16_b^T from the padded context ctx16 [n][tp][d] (ld_op_ctx_pad), wk / wv [c][d] */
+int ld_op_ctx_kv(const void* ctx16, const void* wk, const void* wv, int n, int tp, int d, int c, void* k_out, void* vt_out, void* stream);
 /* w_out [c][5c] = [wpo w2 | wpo], b_out = wpo b2 + bpo  (wpo [c][c], w2 [c][4c]): fp32 sums, one rounding to fp16 */
 int ld_op_mlp_out_fold(const void* wpo, const void* w2, const void* b2, const void* bpo, int c, void* w_out, void* b_out, void* stream);
 /* w_out [n][k] = fp16(w * gamma), b_out [n] = fp16(bias + w beta) (bias optional), wsum [n] = fp32 row sums of the ROUNDED w_out */
@@ -332,13 +343,14 @@ int ld_op_ln_fold(const void* w, int n, int k, const void* gamma, const void* be
 /* The LayerNorm fold of the UNet's transformer blocks (BasicTransformerBlock, LD.py:4117-4162: every attention / GEGLU
  * projection reads LayerNorm(x)) as an operator pair, for parity tests: t[M][C] = x · w_prod^T + b_prod (the GEMM that writes the
  * residual stream, emitting per-row statistics) and y[M][N] = LayerNorm(t; gamma, beta, eps) · w^T + bias, finished on the fp32
- * accumulators of t · (w diag(gamma))^T.  ws: >= 2*N*C + 8*N + 8*((C+63)/64)*M + 1024 bytes. */
-int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
+ * accumulators of t · (w diag(gamma))^T.  residual [M][C] (optional) is added to t: the residual stream's own update, t += x · w_prod^T + b_prod.
+ * ws: >= 2*N*C + 8*N + 8*((C+63)/64)*M + 1024 bytes. */
+int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* residual, const void* gamma, const void* beta, const void* w,
                     const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream);
 /* The same pair with the GEGLU of FeedForward.net[0] as the consumer (LD.py:4513-4515, 4524-4540): y[M][N/2] = a * gelu(g) with
  * [a | g] = LayerNorm(t) · w^T + bias — the transformer block's MLP input exactly as the executor runs it (row-panel kernel at C = 320).
  * ws: >= 4*N*C + 12*N + 8*((C+63)/64)*M + 2048 bytes. */
-int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
+int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* residual, const void* gamma, const void* beta, const void* w,
                           const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream);
 /* bislerp (LD.py:429-518, LatentUpscale.upscale 6639-6654): fp32 NCHW latents [n][c][h][w] -> [n][c][h_new][w_new];
  * tmp: n*c*h*w_new floats of scratch (the width pass runs first, as in the reference) */
@@ -381,6 +393,10 @@ int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, 
  * (ld_op_esrgan_first / _last and ld_op_taesd_first / _last name their kernel too, and leave the string alone when they refuse a call.)
  * The two small convolutions name their instantiation too ("small_conv_in_kernel<3>", "small_conv_out_kernel<9,1>"). */
 const char* ld_op_last_kernel(void);
+/* EVERY launch of the calling thread's last ld_op_* call, in launch order and joined with ';', under the names the executors' launch tables
+ * (ld_unet_profile_launches) print: the contractions as above, and the norm and boundary launches ("gn_stats_kernel+gn_finalize_kernel",
+ * "gn_apply_kernel", "timestep_embed_kernel", "small_conv_in_kernel", "dup_halves_kernel", ...).  Operators outside the UNet's forward leave it "". */
+const char* ld_op_last_launches(void);
 /* The merge kernel of ld_unet_patch_param on a plain row-major matrix: dst[rows][cols] = round_fp16(float(base) + sum_j scale_j up_j down_j);
  * dst may alias base.  Also what the host's text model patches its weights with. */
 int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream);

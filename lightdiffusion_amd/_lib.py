@@ -91,20 +91,21 @@ SIGNATURES = {
     "ld_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _Z, _P]),
     "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_groupnorm_conv_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "ld_op_groupnorm_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "ld_op_groupnorm_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
     "ld_op_repack_conv": (_I, [_P, _I, _I, _I, _P, _P]),
     "ld_op_upconv2x_fold": (_I, [_P, _I, _I, _P, _P]),
     "ld_op_upconv2x": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_conv_skip_ws_bytes": (_Z, [_I, _I, _I, _I]),
     "ld_op_conv_skip": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "ld_op_groupnorm_conv_skip_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
-    "ld_op_groupnorm_conv_skip": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "ld_op_groupnorm_conv_skip": (_I, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "ld_op_conv_takes_skip_segment": (_I, [_I, _I, _I, _I, _I]),
     "ld_op_groupnorm_ws_bytes": (_Z, [_I, _I]),
     "ld_op_groupnorm": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _I, _P, _P, _P]),
     "ld_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "ld_op_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "ld_op_conv_gn_partials_floats": (_Z, [_I, _I]),
-    "ld_op_conv_gn_partials": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "ld_op_conv_gn_partials": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     "ld_op_attention_rowv": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "ld_op_softmax_rows": (_I, [_P, _I, _I, _P]),
     "ld_op_timestep_embed": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
@@ -123,10 +124,11 @@ SIGNATURES = {
     "ld_op_timestep_embed_mod": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "ld_op_dup_halves": (_I, [_P, _Z, _P, _Z, _P, _Z, _I, _P]),
     "ld_op_ctx_pad": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "ld_op_ctx_kv": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ld_op_mlp_out_fold": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
     "ld_op_ln_fold": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
-    "ld_op_linear_ln": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
-    "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
+    "ld_op_linear_ln": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
+    "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_esrgan_conv": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P]),
     "ld_op_taesd_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
@@ -136,6 +138,7 @@ SIGNATURES = {
     "ld_op_taesd_last": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ld_op_tile_blend": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_last_kernel": (C.c_char_p, []),
+    "ld_op_last_launches": (C.c_char_p, []),
     "ld_op_lora_merge": (_I, [_P, _P, _I, _I, C.POINTER(LoraTerm), _I, _P]),
     "ld_op_u8_resample": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P]),
     "ld_op_u8_resample_tmp_bytes": (_Z, [_I, _I, _I]),

@@ -10,9 +10,19 @@ inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // ld_op_last_kernel: the contraction instantiations the calling thread's last ld_op_* call dispatched, in launch order, joined with ';'
 thread_local std::string t_op_kernels;
-inline void op_begin() { t_op_kernels.clear(); }
+// ld_op_last_launches: every launch of that call under the name the executors' profile tables print for it, norm and misc launches included
+thread_local std::string t_op_launches;
+inline void op_begin() {
+    t_op_kernels.clear();
+    t_op_launches.clear();
+}
 inline int noted(int st, const char* name) {
     note_kernel(&t_op_kernels, name);
+    return st;
+}
+// a launcher called directly (no Exec): the name the executors time that launch under
+inline int launched(int st, const char* table_name) {
+    if (st == LD_OK) note_kernel(&t_op_launches, table_name);
     return st;
 }
 
@@ -35,6 +45,7 @@ struct Op {
         ex.arena = &arena;
         ex.stream = (hipStream_t)stream;
         ex.names = &t_op_kernels;
+        ex.all_names = &t_op_launches;
     }
     Op(const Op&) = delete;
     bool fits() const { return align256(arena.peak) <= arena.cap; }   // everything carved so far lies inside the caller's buffer
@@ -70,6 +81,8 @@ extern "C" {
 const char* ld_version(void) { return "ld_mi355x 0.1 (gfx950)"; }
 
 const char* ld_op_last_kernel(void) { return t_op_kernels.c_str(); }
+
+const char* ld_op_last_launches(void) { return t_op_launches.c_str(); }
 
 const char* ld_status_string(int s) {
     switch (s) {
@@ -162,12 +175,28 @@ size_t ld_op_conv_gn_partials_floats(int n, int hw) {
     return groupnorm_workspace_bytes(n, hw) / sizeof(float);
 }
 
-int ld_op_conv_gn_partials(const void* x, int c, int n, int h, int w, int hv, int wv, const void* wt, const void* bias, const void* residual,
-                           void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+int ld_op_conv_gn_partials(const void* x, int c, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize, const void* wt,
+                           const void* bias, const void* residual, void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
     if (part == nullptr || chunks == nullptr) return LD_ERR_ARG;
     *chunks = 0;
-    return op_conv(x, c, nullptr, 0, n, h, w, hv, wv, 1, 3, wt, bias, nullptr, residual, y, cout, ws, ws_bytes, stream, part, chunks);
+    return op_conv(x, c, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, nullptr, residual, y, cout, ws, ws_bytes, stream, part, chunks);
+}
+
+int ld_op_conv_takes_skip_segment(int c, int n, int h, int w, int cout) {
+    op_begin();
+    // what unet.hip Run::resblock asks of out_layers' convolution as it stands before the skip joins it (Exec::conv_takes_skip_segment), under
+    // the scratch every executor launch has: split partials, counters and, where the shape can have one, the row-resident kernel's weight copy.
+    // Host only: the plan reads no operand, so any non-null address stands for them.
+    if (c <= 0 || n <= 0 || h <= 0 || w <= 0 || cout <= 0) return 0;
+    static const half_t any[8] = {};
+    GemmParams p = conv_params(any, c, nullptr, 0, n, h, w, h, w, 1, 3, any, any, cout, const_cast<half_t*>(any));
+    p.W8 = conv8_weight_eligible(cout, c) ? any : nullptr;
+    Exec ex;
+    ex.splitk_ws = reinterpret_cast<float*>(const_cast<half_t*>(any));
+    ex.splitk_bytes = kCompositeSplitBytes;
+    ex.sync_ws = reinterpret_cast<int*>(const_cast<half_t*>(any));
+    return ex.conv_takes_skip_segment(p) ? 1 : 0;
 }
 
 size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int cout) {
@@ -178,9 +207,13 @@ size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int co
 }
 
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
-                         const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws, size_t ws_bytes,
-                         void* stream) {
+                         const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, float* in_part, int in_chunks,
+                         float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
+    // in_part / in_chunks: GroupNorm partial statistics of x1 that its producer wrote ([n][in_chunks][32][2]; one source only): the statistics
+    // pass is skipped, as in Run::resblock.  part / chunks (both or neither): the partial statistics of y, as ld_op_conv_gn_partials.
+    if ((part == nullptr) != (chunks == nullptr) || in_chunks < 0 || (in_part != nullptr && (in_chunks == 0 || c2 != 0))) return LD_ERR_ARG;
+    if (chunks != nullptr) *chunks = 0;
     // GroupNorm(32) + SiLU + 3x3 convolution (stride 1, pad 1): the reference's ResBlock1.in_layers / out_layers (LD.py:5224-5262), by
     // Exec::gn_silu_conv — fused into the halo tile's loader where the plan says so, else the two-pass GroupNorm (which the row-resident kernel
     // takes too), then the convolution.  The scratch: normalised tensor | counters | weight copy | split partials | statistics, scale, shift.
@@ -191,8 +224,9 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
     GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, h, w, 1, 3, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
     p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
     p.R = (const half_t*)residual;
+    if (part != nullptr) want_gn_partials(p, n, h * w, part, chunks);
     op.conv8_scratch(p, wt, kCompositeSplitBytes);
-    op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g);
+    op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g, in_part, in_chunks);
     return op.ex.status;
 }
 
@@ -207,7 +241,7 @@ size_t ld_op_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout) {
 // them (as ld_op_conv_gn_partials).  The scratch: folded weights | folded bias | [normalised tensor] | split partials | [statistics, scale, shift].
 static int op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, const void* bias, const void* s1, int sc1, const void* s2, int sc2,
                         const void* wskip, const void* bskip, const void* rowvec, const void* gamma, const void* beta, float eps, void* y, int cout,
-                        float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+                        float* in_part, int in_chunks, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
     Op op(ws, ws_bytes, stream);
     const int K9 = 9 * c, SC = sc1 + sc2, HW = h * w;
     half_t* wf = op.arena.halfs((size_t)cout * (K9 + SC));
@@ -224,7 +258,7 @@ static int op_conv_skip(const void* x, int c, int n, int h, int w, const void* w
     } else {
         half_t* g = op.arena.halfs((size_t)n * HW * c);
         op.splitk(kCompositeSplitBytes);
-        op.ex.gn_silu_conv(p, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, g);
+        op.ex.gn_silu_conv(p, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, g, in_part, in_chunks);
     }
     return op.ex.status;
 }
@@ -235,7 +269,7 @@ int ld_op_conv_skip(const void* x, int c, int n, int h, int w, const void* wt, c
     if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
     if (ws_bytes < ld_op_conv_skip_ws_bytes(c, sc1, sc2, cout)) return LD_ERR_ARG;
-    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, nullptr, nullptr, 0.f, y, cout, nullptr, nullptr, ws, ws_bytes, stream);
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, nullptr, nullptr, 0.f, y, cout, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int n, int h, int w) {
@@ -247,14 +281,16 @@ size_t ld_op_groupnorm_conv_skip_ws_bytes(int c, int sc1, int sc2, int cout, int
 
 int ld_op_groupnorm_conv_skip(const void* x, int c, int n, int h, int w, const void* gamma, const void* beta, float eps, const void* wt, const void* bias,
                               const void* s1, int sc1, const void* s2, int sc2, const void* wskip, const void* bskip, const void* rowvec, void* y, int cout,
-                              float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+                              float* in_part, int in_chunks, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
+    // in_part / in_chunks: GroupNorm partial statistics of x from its producer ([n][in_chunks][32][2]), as ld_op_groupnorm_conv
+    if (in_chunks < 0 || (in_part != nullptr && (in_chunks == 0 || gamma == nullptr))) return LD_ERR_ARG;
     if (x == nullptr || wt == nullptr || bias == nullptr || s1 == nullptr || wskip == nullptr || bskip == nullptr || y == nullptr || ws == nullptr) return LD_ERR_ARG;
     if (c <= 0 || sc1 <= 0 || sc2 < 0 || (sc2 > 0 && s2 == nullptr) || cout <= 0 || n <= 0 || h <= 0 || w <= 0) return LD_ERR_ARG;
     if ((gamma == nullptr) != (beta == nullptr) || (part == nullptr) != (chunks == nullptr)) return LD_ERR_ARG;
     if (ws_bytes < ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w)) return LD_ERR_ARG;
     if (chunks != nullptr) *chunks = 0;
-    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, gamma, beta, eps, y, cout, part, chunks, ws, ws_bytes, stream);
+    return op_conv_skip(x, c, n, h, w, wt, bias, s1, sc1, s2, sc2, wskip, bskip, rowvec, gamma, beta, eps, y, cout, in_part, in_chunks, part, chunks, ws, ws_bytes, stream);
 }
 
 int ld_op_repack_conv(const void* src, int dtype, int cout, int cin, void* dst, void* stream) {
@@ -270,8 +306,8 @@ size_t ld_op_groupnorm_ws_bytes(int n, int hw) {
 int ld_op_groupnorm(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
                     int silu, void* y, void* ws, void* stream) {
     op_begin();
-    return groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps,
-                            silu, (half_t*)y, (float*)ws, (hipStream_t)stream);
+    return launched(groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps,
+                                     silu, (half_t*)y, (float*)ws, (hipStream_t)stream), "gn_stats_kernel+gn_apply_kernel");
 }
 
 int ld_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int c, float eps, void* stream) {
@@ -360,8 +396,8 @@ int ld_op_groupnorm_from_partials(const void* x1, int c1, const void* x2, int c2
                                   int silu, void* y, float* part, int pstat, void* stream) {
     op_begin();
     if (pstat < 1) return LD_ERR_ARG;
-    return groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps, silu, (half_t*)y, part,
-                            (hipStream_t)stream, pstat);
+    return launched(groupnorm_launch((const half_t*)x1, c1, (const half_t*)x2, c2, n, hw, (const half_t*)gamma, (const half_t*)beta, eps, silu, (half_t*)y, part,
+                                     (hipStream_t)stream, pstat), "gn_apply_kernel");
 }
 
 int ld_op_groupnorm_scale_shift(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta, float eps,
@@ -380,7 +416,7 @@ int ld_op_small_conv_in(const float* x, const float* scale_sigma, const void* pr
     a.x = x; a.scale_sigma = scale_sigma; a.pre_w = (const half_t*)pre_w; a.pre_b = (const half_t*)pre_b;
     a.w = (const half_t*)wt; a.b = (const half_t*)bias; a.y = (half_t*)y;
     a.N = n; a.Cin = cin; a.H = h; a.W = w; a.Cout = cout; a.dup_off = dup_off;
-    const int st = small_conv_in_launch(a, (hipStream_t)stream);
+    const int st = launched(small_conv_in_launch(a, (hipStream_t)stream), "small_conv_in_kernel");
     return noted(st, small_conv_last_kernel_name());
 }
 
@@ -392,7 +428,7 @@ int ld_op_small_conv_out(const void* x, const void* wt, const void* bias, int n,
     a.x = (const half_t*)x; a.w = (const half_t*)wt; a.b = (const half_t*)bias;
     a.N = n; a.H = h; a.W = w; a.Cin = cin; a.Cout = cout; a.mode = mode;
     a.x_in = x_in; a.sigma = sigma; a.in_mod = in_mod; a.out = out;
-    const int st = small_conv_out_launch(a, (hipStream_t)stream);
+    const int st = launched(small_conv_out_launch(a, (hipStream_t)stream), "small_conv_out_kernel");
     return noted(st, small_conv_last_kernel_name());
 }
 
@@ -409,7 +445,7 @@ int ld_op_vae_out_finish(const void* t8, float* out, long long npix, int cout, v
 int ld_op_timestep_embed_mod(const float* sigma, const float* log_sigmas, int n_sigmas, int n, int dim, void* out, float* t_out, int sigma_mod,
                              void* stream) {
     op_begin();
-    return timestep_embed_launch(sigma, log_sigmas, n_sigmas, n, dim, (half_t*)out, t_out, (hipStream_t)stream, sigma_mod);
+    return launched(timestep_embed_launch(sigma, log_sigmas, n_sigmas, n, dim, (half_t*)out, t_out, (hipStream_t)stream, sigma_mod), "timestep_embed_kernel");
 }
 
 int ld_op_dup_halves(void* base0, size_t bytes0, void* base1, size_t bytes1, void* base2, size_t bytes2, int count, void* stream) {
@@ -419,13 +455,26 @@ int ld_op_dup_halves(void* base0, size_t bytes0, void* base1, size_t bytes1, voi
     a.base[1] = (char*)base1; a.bytes[1] = bytes1;
     a.base[2] = (char*)base2; a.bytes[2] = bytes2;
     a.count = count;
-    return dup_halves_launch(a, (hipStream_t)stream);
+    return launched(dup_halves_launch(a, (hipStream_t)stream), "dup_halves_kernel");
 }
 
 int ld_op_ctx_pad(const void* src, int dtype, int n, int t, int tp, int d, void* dst, void* stream) {
     op_begin();
     if ((dtype != LD_F16 && dtype != LD_F32) || n <= 0 || t <= 0 || d <= 0) return LD_ERR_ARG;
     return ctx_pad_launch(src, dtype == LD_F32, n, t, tp, d, (half_t*)dst, (hipStream_t)stream);
+}
+
+int ld_op_ctx_kv(const void* ctx16, const void* wk, const void* wv, int n, int tp, int d, int c, void* k_out, void* vt_out, void* stream) {
+    op_begin();
+    // the two launches ld_unet_set_context makes per transformer, by the same builders: K = ctx Wk^T [n tp][c] and, per sample, V^T = Wv ctx^T [c][tp]
+    if (ctx16 == nullptr || wk == nullptr || wv == nullptr || k_out == nullptr || vt_out == nullptr || n <= 0 || tp <= 0 || d <= 0 || c <= 0) return LD_ERR_ARG;
+    int st = gemm_launch(linear_params((const half_t*)ctx16, d, (const half_t*)wk, nullptr, n * tp, c, d, (half_t*)k_out), (hipStream_t)stream);
+    if (st != LD_OK) return st;
+    note_kernel(&t_op_kernels, gemm_last_kernel_name());
+    GemmParams v = linear_params((const half_t*)wv, d, (const half_t*)ctx16, nullptr, c, tp, d, (half_t*)vt_out);
+    v.batch = n; v.sW = (long long)tp * d; v.sC = (long long)c * tp;
+    st = gemm_launch(v, (hipStream_t)stream);
+    return noted(st, gemm_last_kernel_name());
 }
 
 int ld_op_mlp_out_fold(const void* wpo, const void* w2, const void* b2, const void* bpo, int c, void* w_out, void* b_out, void* stream) {
@@ -446,7 +495,7 @@ int ld_op_ln_fold(const void* w, int n, int k, const void* gamma, const void* be
 //   y = LayerNorm(t; gamma, beta, eps) · w^T + bias   computed as rstd * (t · W'^T - mu * wsum) + b' on the accumulators
 // geglu: the transformer block's MLP input — y[M][N/2] = a * gelu(g), [a | g] = LayerNorm(t) · w^T + bias (GEGLU, LD.py:4513-4515); w rows are
 // repacked into the tile-interleaved [value | gate] order first, then folded (the fold is row-wise).
-static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w, const void* bias,
+static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* residual, const void* gamma, const void* beta, const void* w, const void* bias,
                         void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream, bool geglu) {
     if (x == nullptr || w_prod == nullptr || gamma == nullptr || beta == nullptr || w == nullptr || (geglu && bias == nullptr) || t_out == nullptr ||
         y == nullptr || ws == nullptr)
@@ -474,6 +523,7 @@ static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, c
     if (st != LD_OK) return st;
     int parts = 0;
     GemmParams a = linear_params((const half_t*)x, C, (const half_t*)w_prod, (const half_t*)b_prod, M, C, C, (half_t*)t_out);
+    a.R = (const half_t*)residual;   // (the residual stream itself in Run::transformer: t += ...)
     ln_producer(a, stat, &parts);
     op.ex.gemm(a);
     GemmParams b = linear_params((const half_t*)t_out, C, w2, b2, M, N, C, (half_t*)y, geglu ? 2 : 0, bn);
@@ -482,16 +532,16 @@ static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, c
     return op.ex.status;
 }
 
-int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
+int ld_op_linear_ln(const void* x, const void* w_prod, const void* b_prod, const void* residual, const void* gamma, const void* beta, const void* w,
                     const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    return op_linear_ln(x, w_prod, b_prod, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, false);
+    return op_linear_ln(x, w_prod, b_prod, residual, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, false);
 }
 
-int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* gamma, const void* beta, const void* w,
+int ld_op_linear_ln_geglu(const void* x, const void* w_prod, const void* b_prod, const void* residual, const void* gamma, const void* beta, const void* w,
                           const void* bias, void* t_out, void* y, int M, int C, int N, float eps, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    return op_linear_ln(x, w_prod, b_prod, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, true);
+    return op_linear_ln(x, w_prod, b_prod, residual, gamma, beta, w, bias, t_out, y, M, C, N, eps, ws, ws_bytes, stream, true);
 }
 
 int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, const ld_lora_term* terms, int n_terms, void* stream) {

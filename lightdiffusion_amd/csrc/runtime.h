@@ -195,6 +195,7 @@ struct Exec {
     size_t splitk_bytes = 0;
     int* sync_ws = nullptr;          // LD_SYNC_INTS zeroed ints for the in-launch reductions (gemm.h GemmParams::sync); null: those kernels are not used
     std::string* names = nullptr;    // optional: receives the contraction and attention kernels this Exec dispatched (ld_op_last_kernel)
+    std::string* all_names = nullptr;   // optional: receives the name of EVERY launch, as the profile tables print it (ld_op_last_launches)
     // optional: runs in front of a contraction's kernel, once its plan is known, with before_gemm_arg; a status other than LD_OK takes the
     // launch's place (capi.hip: what the row-resident kernel needs from a caller's scratch)
     int (*before_gemm)(const GemmParams&, const GemmPlan&, const void* arg, hipStream_t) = nullptr;
@@ -233,14 +234,20 @@ struct Exec {
     // failed, notes the status and closes the record under the kernel's name.
     template <class F>
     void launch(int cls, double fl, const char* what, long long a, long long b, long long d, long long e, const char* kernel_name, F&& fn, int nl = 1) {
-        if (open(cls, fl, nl, what, a, b, d, e)) note(fn());
+        if (open(cls, fl, nl, what, a, b, d, e)) {
+            note(fn());
+            note_kernel(all_names, kernel_name);
+        }
         t_end(kernel_name);
     }
     // ... under the name one of the launchers' last-kernel functions (gemm_last_kernel_name ...) gives after fn ran
     template <class F>
     void launch(int cls, double fl, const char* what, long long a, long long b, long long d, long long e, const char* (*last_kernel)(), F&& fn) {
         const bool run = open(cls, fl, 1, what, a, b, d, e);
-        if (run) note(fn());
+        if (run) {
+            note(fn());
+            note_kernel(all_names, last_kernel());
+        }
         t_end(run ? last_kernel() : "");
     }
     bool open(int cls, double fl, int nl, const char* what, long long a, long long b, long long d, long long e) {

@@ -32,6 +32,13 @@ def last_kernel() -> str:
     return lib().ld_op_last_kernel().decode()
 
 
+def last_launches() -> str:
+    """EVERY launch of the last operator call on this thread, in launch order and joined with ';', under the names the executors' launch
+    tables print (`profile_launches`): the contractions as `last_kernel`, and the norm / boundary launches ("gn_stats_kernel+gn_finalize_kernel",
+    "gn_apply_kernel", "timestep_embed_kernel", ...)."""
+    return lib().ld_op_last_launches().decode()
+
+
 _WS = {}
 
 
@@ -72,21 +79,21 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 
 
 def linear_ln(x: torch.Tensor, w_prod: torch.Tensor, b_prod: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
-              weight: torch.Tensor, bias: Optional[torch.Tensor], eps: float = 1e-5):
-    """The UNet's LayerNorm fold as an operator pair: t = x @ w_prod.T + b_prod;  y = LayerNorm(t) @ weight.T + bias with the
+              weight: torch.Tensor, bias: Optional[torch.Tensor], eps: float = 1e-5, residual: Optional[torch.Tensor] = None):
+    """The UNet's LayerNorm fold as an operator pair: t = x @ w_prod.T + b_prod (+ residual);  y = LayerNorm(t) @ weight.T + bias with the
     normalisation finished on the GEMM accumulators (no LayerNorm launch, no normalised tensor).  Returns (t, y)."""
     M, C = x.shape
     N = weight.shape[0]
     t = torch.empty(M, C, dtype=torch.float16, device=x.device)
     y = torch.empty(M, N, dtype=torch.float16, device=x.device)
     ws = _ws(2 * N * C + 8 * N + 8 * ((C + 63) // 64) * M + 4096, x.device)
-    check(lib().ld_op_linear_ln(_p(x), _p(w_prod), _p(b_prod), _p(gamma), _p(beta), _p(weight), _p(bias), _p(t), _p(y), M, C, N, eps,
+    check(lib().ld_op_linear_ln(_p(x), _p(w_prod), _p(b_prod), _p(residual), _p(gamma), _p(beta), _p(weight), _p(bias), _p(t), _p(y), M, C, N, eps,
                                 _p(ws), ws.numel(), _stream()), "ld_op_linear_ln")
     return t, y
 
 
 def linear_ln_geglu(x: torch.Tensor, w_prod: torch.Tensor, b_prod: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
-                    weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5):
+                    weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5, residual: Optional[torch.Tensor] = None):
     """linear_ln with the GEGLU of FeedForward.net[0] as the consumer: t = x @ w_prod.T + b_prod;  [a | g] = LayerNorm(t) @ weight.T + bias;
     y = a * gelu(g) — the transformer block's MLP input as the executor runs it.  Returns (t, y) with y of width N / 2."""
     M, C = x.shape
@@ -94,7 +101,7 @@ def linear_ln_geglu(x: torch.Tensor, w_prod: torch.Tensor, b_prod: Optional[torc
     t = torch.empty(M, C, dtype=torch.float16, device=x.device)
     y = torch.empty(M, N // 2, dtype=torch.float16, device=x.device)
     ws = _ws(4 * N * C + 12 * N + 8 * ((C + 63) // 64) * M + 4096, x.device)
-    check(lib().ld_op_linear_ln_geglu(_p(x), _p(w_prod), _p(b_prod), _p(gamma), _p(beta), _p(weight), _p(bias), _p(t), _p(y), M, C, N, eps,
+    check(lib().ld_op_linear_ln_geglu(_p(x), _p(w_prod), _p(b_prod), _p(residual), _p(gamma), _p(beta), _p(weight), _p(bias), _p(t), _p(y), M, C, N, eps,
                                       _p(ws), ws.numel(), _stream()), "ld_op_linear_ln_geglu")
     return t, y
 
@@ -171,11 +178,12 @@ def conv2d_skip(x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, s1:
 
 def group_norm_silu_conv2d_skip(x: torch.Tensor, gamma: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, w_packed: torch.Tensor,
                                 bias: torch.Tensor, s1: torch.Tensor, s2: Optional[torch.Tensor], w_skip: torch.Tensor, b_skip: torch.Tensor,
-                                rowvec: Optional[torch.Tensor] = None, partials: bool = False):
+                                rowvec: Optional[torch.Tensor] = None, partials: bool = False, in_part: Optional[torch.Tensor] = None):
     """A ResBlock's second half as the UNet executor runs it (LD.py:5267, 5273-5287):
     y = conv3x3(SiLU(GroupNorm32(x)); w_packed) + bias + conv1x1(cat(s1, s2); w_skip) + b_skip, the raw skip sources a second K segment of
     the one contraction.  gamma / beta None: x is taken as it is (conv2d_skip).  partials: also return the GroupNorm(32) partial statistics
-    the launch wrote for y ([n, chunks, 32, 2] fp32, or None where this shape's kernel writes none), as conv2d_gn_partials."""
+    the launch wrote for y ([n, chunks, 32, 2] fp32, or None where this shape's kernel writes none), as conv2d_gn_partials.  in_part: the
+    partial statistics of x from its producer ([n, chunks, 32, 2]): the GroupNorm skips its statistics pass."""
     import ctypes
     n, h, w, c = x.shape
     sc1 = s1.shape[-1]
@@ -186,7 +194,8 @@ def group_norm_silu_conv2d_skip(x: torch.Tensor, gamma: Optional[torch.Tensor], 
     chunks = ctypes.c_int(0)
     ws = _ws(lib().ld_op_groupnorm_conv_skip_ws_bytes(c, sc1, sc2, cout, n, h, w), x.device)
     check(lib().ld_op_groupnorm_conv_skip(_p(x), c, n, h, w, _p(gamma), _p(beta), eps, _p(w_packed), _p(bias), _p(s1), sc1, _p(s2), sc2, _p(w_skip),
-                                          _p(b_skip), _p(rowvec), _p(y), cout, _p(part), ctypes.byref(chunks) if partials else None, _p(ws), ws.numel(),
+                                          _p(b_skip), _p(rowvec), _p(y), cout, _p(in_part), 0 if in_part is None else in_part.shape[1], _p(part),
+                                          ctypes.byref(chunks) if partials else None, _p(ws), ws.numel(),
                                           _stream()), "ld_op_groupnorm_conv_skip")
     if not partials:
         return y
@@ -194,20 +203,23 @@ def group_norm_silu_conv2d_skip(x: torch.Tensor, gamma: Optional[torch.Tensor], 
 
 
 def conv2d_gn_partials(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out_hw: Optional[tuple] = None,
-                       residual: Optional[torch.Tensor] = None):
-    """3x3 stride-1 NHWC conv that also returns the GroupNorm(32) partial statistics its kernel wrote for the OUTPUT:
+                       residual: Optional[torch.Tensor] = None, ksize: int = 3, stride: int = 1, x2: Optional[torch.Tensor] = None):
+    """NHWC conv (conv2d's arguments; 3x3 stride 1 by default) that also returns the GroupNorm(32) partial statistics its kernel wrote for the OUTPUT:
     (y, part [n, chunks, 32, 2] fp32 or None when this shape's kernel writes none) — what the executors hand to the next GroupNorm
     (ResBlock1, LD.py:5224-5262; ResnetBlock, LD.py:3560-3576) instead of a statistics pass."""
     import ctypes
     n, h, w, c = x.shape
+    c2 = 0 if x2 is None else x2.shape[-1]
     hv, wv = (h, w) if out_hw is None else out_hw
     cout = w_packed.shape[0]
-    y = torch.empty(n, hv, wv, cout, dtype=torch.float16, device=x.device)
-    part = torch.zeros(lib().ld_op_conv_gn_partials_floats(n, hv * wv), dtype=torch.float32, device=x.device)
+    ho = (hv - 1) // stride + 1 if ksize == 3 else hv
+    wo = (wv - 1) // stride + 1 if ksize == 3 else wv
+    y = torch.empty(n, ho, wo, cout, dtype=torch.float16, device=x.device)
+    part = torch.zeros(lib().ld_op_conv_gn_partials_floats(n, ho * wo), dtype=torch.float32, device=x.device)
     chunks = ctypes.c_int(0)
     ws = _ws(192 << 20, x.device)
-    check(lib().ld_op_conv_gn_partials(_p(x), c, n, h, w, hv, wv, _p(w_packed), _p(bias), _p(residual), _p(y), cout, _p(part), ctypes.byref(chunks),
-                                       _p(ws), ws.numel(), _stream()), "ld_op_conv_gn_partials")
+    check(lib().ld_op_conv_gn_partials(_p(x), c, _p(x2), c2, n, h, w, hv, wv, stride, ksize, _p(w_packed), _p(bias), _p(residual), _p(y), cout, _p(part),
+                                       ctypes.byref(chunks), _p(ws), ws.numel(), _stream()), "ld_op_conv_gn_partials")
     if chunks.value == 0:
         return y, None
     return y, part[: n * chunks.value * 64].view(n, chunks.value, 32, 2)
@@ -215,17 +227,31 @@ def conv2d_gn_partials(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[t
 
 def group_norm_silu_conv2d(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w_packed: torch.Tensor,
                            bias: Optional[torch.Tensor], x2: Optional[torch.Tensor] = None, rowvec: Optional[torch.Tensor] = None,
-                           residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+                           residual: Optional[torch.Tensor] = None, partials: bool = False, in_part: Optional[torch.Tensor] = None):
     """conv3x3(SiLU(GroupNorm32(cat(x, x2)))) + rowvec + residual on NHWC fp16 — ResBlock1.in_layers / out_layers (LD.py:5224-5262)
-    as ONE operator: on the halo-tile convolution kernel the normalisation happens inside the conv's A operand."""
+    as ONE operator: on the halo-tile convolution kernel the normalisation happens inside the conv's A operand.  in_part: the GroupNorm
+    partial statistics of x from its producer ([n, chunks, 32, 2]; x2 must be None): no statistics pass.  partials: returns (y, the partial
+    statistics the launch wrote for y, or None where this shape's kernel writes none), as conv2d_gn_partials."""
+    import ctypes
     n, h, w, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[-1]
     cout = w_packed.shape[0]
     y = torch.empty(n, h, w, cout, dtype=torch.float16, device=x.device)
+    part = torch.zeros(lib().ld_op_conv_gn_partials_floats(n, h * w), dtype=torch.float32, device=x.device) if partials else None
+    chunks = ctypes.c_int(0)
     ws = _ws(lib().ld_op_groupnorm_conv_ws_bytes(c1, c2, n, h, w, cout), x.device)
     check(lib().ld_op_groupnorm_conv(_p(x), c1, _p(x2), c2, n, h, w, _p(gamma), _p(beta), eps, _p(w_packed), _p(bias), _p(rowvec), _p(residual),
-                                     _p(y), cout, _p(ws), ws.numel(), _stream()), "ld_op_groupnorm_conv")
-    return y
+                                     _p(y), cout, _p(in_part), 0 if in_part is None else in_part.shape[1], _p(part),
+                                     ctypes.byref(chunks) if partials else None, _p(ws), ws.numel(), _stream()), "ld_op_groupnorm_conv")
+    if not partials:
+        return y
+    return y, (None if chunks.value == 0 else part[: n * chunks.value * 64].view(n, chunks.value, 32, 2))
+
+
+def conv_takes_skip_segment(c: int, n: int, h: int, w: int, cout: int) -> bool:
+    """Host only: does the UNet executor fold a ResBlock's 1x1 skip_connection into out_layers' 3x3 convolution [n, h, w, c] -> cout
+    (group_norm_silu_conv2d_skip), or run it as a launch of its own in front (conv2d with ksize 1, then the residual)?"""
+    return bool(lib().ld_op_conv_takes_skip_segment(c, n, h, w, cout))
 
 
 def group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, silu: bool = False,
@@ -283,6 +309,17 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, cau
     vt[:, :, :lk] = v.transpose(1, 2)
     o = torch.empty_like(q)
     check(lib().ld_op_attention(_p(q), c, _p(k.contiguous()), c, _p(vt), lkp, _p(o), c, b, heads, lq, lk, d, 1.0 / math.sqrt(d), int(causal), _stream()),
+          "ld_op_attention")
+    return o
+
+
+def attention_vt(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, heads: int) -> torch.Tensor:
+    """attention() on operands projected once per context (context_kv): k [b, Lk, heads*d], vt [b, heads*d, Lk padded to 8] = V transposed."""
+    b, lq, c = q.shape
+    lk = k.shape[1]
+    o = torch.empty_like(q)
+    d = c // heads
+    check(lib().ld_op_attention(_p(q), c, _p(k), c, _p(vt), vt.shape[2], _p(o), c, b, heads, lq, lk, d, 1.0 / math.sqrt(d), 0, _stream()),
           "ld_op_attention")
     return o
 
@@ -422,6 +459,29 @@ def ctx_pad(src: torch.Tensor, tp: int) -> torch.Tensor:
     dst = torch.empty(n, tp, d, dtype=torch.float16, device=src.device)
     check(lib().ld_op_ctx_pad(_p(src), F32 if src.dtype == torch.float32 else F16, n, t, tp, d, _p(dst), _stream()), "ld_op_ctx_pad")
     return dst
+
+
+def context_kv(ctx16: torch.Tensor, wk: torch.Tensor, wv: torch.Tensor):
+    """The cross-attention operands the UNet projects once per context: ctx16 [n, tp, d] (ctx_pad), wk / wv [c, d] ->
+    (k [n, tp, c], vt [n, c, tp]) by the launches of ld_unet_set_context."""
+    n, tp, d = ctx16.shape
+    c = wk.shape[0]
+    k = torch.empty(n, tp, c, dtype=torch.float16, device=ctx16.device)
+    vt = torch.empty(n, c, tp, dtype=torch.float16, device=ctx16.device)
+    check(lib().ld_op_ctx_kv(_p(ctx16), _p(wk), _p(wv), n, tp, d, c, _p(k), _p(vt), _stream()), "ld_op_ctx_kv")
+    return k, vt
+
+
+def dup_halves_(*tensors: torch.Tensor) -> None:
+    """Up to three contiguous tensors whose dim 0 is even: the first half of each is copied onto its second half, in one launch (the CFG pair's
+    hand-over in front of the first cross-attention)."""
+    assert 1 <= len(tensors) <= 3
+    args = []
+    for t in tensors:
+        assert t.is_cuda and t.is_contiguous() and t.shape[0] % 2 == 0
+        args += [t.data_ptr(), t.numel() * t.element_size() // 2]
+    args += [None, 0] * (3 - len(tensors))
+    check(lib().ld_op_dup_halves(*args, len(tensors), _stream()), "ld_op_dup_halves")
 
 
 def mlp_out_fold(wpo: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, bpo: torch.Tensor):

@@ -596,6 +596,40 @@ def wsum_ref(w_out):
     return wd.sum(-1), c_acc(wd.shape[1]) * wd.abs().sum(-1) + 1e-30
 
 
+# ------------------------------------------------------------------ a ResBlock half as the UNet executor runs it (tests/test_unet_chain_gpu.py)
+
+def gn_silu_conv_ref(x, gamma, beta, eps, w_oihw, bias, x2=None, rowvec=None, residual=None, skip=None):
+    """fp64 conv3x3(SiLU(GroupNorm32(cat(x, x2))); w) + bias (+ rowvec per image) (+ residual) of NHWC fp16 x [n][h][w][C1], x2 [n][h][w][C2], and
+    with skip = (s1, s2 or None, wskip [Cout][SC], bskip) the 1x1 convolution of the RAW sources cat(s1, s2) as a second K segment
+    (ResBlock1's skip_connection folded into out_layers, LD.py:5267): y_hat [n h w][Cout], bound.
+    A composition of references this module already has, nothing new in it:
+      * the normalised, activated operand a = SiLU(GN(x)) and ITS element bound e_a from groupnorm_ref (fp32 statistics — a producer's partials
+        are fp32 sums of the same fp16 values — the fp32 affine map and SiLU, ONE fp16 rounding: the store of the two-pass route, the halo
+        loader's conversion where the norm is fused);
+      * the contraction over columns [im2col(a) | s1 | s2] against [w | wskip] with bias b + bskip, by epilogue_ref with K = 9 C + SC, as
+        test_routes_gpu.py's skip and GroupNorm routes build it; the operand's error enters as extra = im2col(e_a) |w|^T (the raw skip columns
+        carry none), in place of those routes' (2^-11 + 1e-5) |a| |w|^T: the same rounding, with the statistics' share taken from groupnorm_ref's
+        model, cancellation term included, instead of a constant."""
+    n, h, wd = x.shape[0], x.shape[1], x.shape[2]
+    a, e_a = groupnorm_ref(x, x2, gamma, beta, eps, True)
+    C = a.shape[-1]
+    cout = w_oihw.shape[0]
+    cols = im2col(a.reshape(n, h, wd, C), 3)
+    ecols = im2col(e_a.reshape(n, h, wd, C), 3)
+    wm = w_oihw.double().reshape(cout, -1)
+    extra = ecols @ wm.abs().t()
+    b = None if bias is None else bias.double()
+    if skip is not None:
+        s1, s2, wskip, bskip = skip
+        sk = (s1 if s2 is None else torch.cat([s1, s2], dim=-1)).double()
+        cols = torch.cat([cols, sk.reshape(-1, sk.shape[-1])], dim=1)
+        wm = torch.cat([wm, wskip.double().reshape(cout, -1)], dim=1)
+        b = (0.0 if b is None else b) + bskip.double()
+    rv = None if rowvec is None else rowvec.double().repeat_interleave(h * wd, dim=0)
+    res = None if residual is None else residual.reshape(-1, cout)
+    return epilogue_ref(cols @ wm.t(), cols.abs() @ wm.abs().t(), wm.shape[1], b, res, extra=extra, rowvec=rv)
+
+
 # ------------------------------------------------------------------ the end convolutions of the upscaler and the preview decoder (esrgan.hip, taesd.hip)
 # Weights are fp16 [Cout][9 Cin], tap-major and channel-minor, as the kernels read them; results [n h w][Cout].
 

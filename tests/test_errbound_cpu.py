@@ -875,3 +875,132 @@ def test_every_norm_and_misc_kernel_is_held_by_a_gpu_test():
             assert any(p.startswith(k) for p in pinned), f"{f}: {k} is on no pinned route of tests/test_routes_gpu.py"
     assert not {"bislerp_axis_kernel", "cfg_combine_kernel", "axpby_kernel"} & set(exempt)
     assert every | set().union(*(kernels_of(f) for f in CONTRACTION_FILES)) == set().union(*(kernels_of(f) for f in sources))
+
+
+# ------------------------------------------------------------------ a ResBlock half on the executor's routes, and the UNet chain's module list (tests/unet_chain.py)
+
+def _res_half_fp32(x, x2, ga, be, eps, wt, b, rowvec, residual, skip, stats_from=None, drop_rowvec=False, halve_tap=False):
+    """The ResBlock half in torch fp32 with the kernels' fp16 rounding points: GroupNorm + SiLU rounded to fp16 once, fp32 convolution (+ the raw
+    skip columns), the staged fp16 tile, then rowvec and residual as fp16 adds.  Defects: stats_from = (i, j): sample i is normalised with
+    the statistics of sample j; drop_rowvec; halve_tap: the tap (ky, kx) = (1, 0) counts half in the image's first row (a border row's tap)."""
+    xin = x if x2 is None else torch.cat([x, x2], -1)
+    n, h, w, c = xin.shape
+    src = xin.reshape(n, h * w, c)
+    if stats_from is not None:
+        i, j = stats_from
+        cpg = c // 32
+        g = src.float().reshape(n, h * w, 32, cpg)
+        mu = g.mean(dim=(1, 3))
+        var = (g * g).mean(dim=(1, 3)) - mu * mu
+        mu[i], var[i] = mu[j], var[j]
+        per_c = lambda t: t.repeat_interleave(cpg, dim=1).unsqueeze(1)
+        y = (src.float() - per_c(mu)) * per_c(torch.rsqrt(var + eps)) * ga.float() + be.float()
+        a = F.silu(y).half()
+    else:
+        a = _gn_fp32(src, ga, be, eps, True).half()
+    a = a.reshape(n, h, w, c).permute(0, 3, 1, 2).float()
+    acc = F.conv2d(a, wt.float(), None, padding=1)
+    if halve_tap:
+        first = F.conv2d(F.pad(a, (1, 1, 1, 1))[:, :, 1:2, :-2], wt.float()[:, :, 1:2, 0:1])      # tap (1, 0) of row 0: the pixel to the left (zero padding at column 0)
+        acc[:, :, 0:1, :] -= 0.5 * first
+    bias = b.float()
+    if skip is not None:
+        s1, s2, wsk, bsk = skip
+        s = (s1 if s2 is None else torch.cat([s1, s2], -1)).permute(0, 3, 1, 2).float()
+        acc = acc + F.conv2d(s, wsk.float()[:, :, None, None])
+        bias = (b.float() + bsk.float()).half().float()
+    y = (acc + bias.view(1, -1, 1, 1)).half()
+    if rowvec is not None and not drop_rowvec:
+        y = (y.float() + rowvec.float()[:, :, None, None]).half()
+    if residual is not None:
+        y = (y.float() + residual.permute(0, 3, 1, 2).float()).half()
+    return y.permute(0, 2, 3, 1).reshape(n * h * w, -1)
+
+
+@pytest.mark.parametrize("two_sources,with_skip", [(False, False), (True, False), (False, True)], ids=["in_layers", "in_layers_concat", "out_layers_skip"])
+def test_gn_silu_conv_ref_and_bound(two_sources, with_skip):
+    """errbound.gn_silu_conv_ref: equal to an independent fp64 evaluation; accepts the fp32 emulation under round to nearest; rejects a dropped
+    row vector, the statistics of the neighbouring sample, a halved border tap, a dropped skip segment and round toward zero."""
+    g = torch.Generator().manual_seed(11)
+    n, h, w, c1, c2, cout = 2, 5, 7, 64, 32 if two_sources else 0, 64
+    C = c1 + c2
+    r = lambda *s, scale=1.0, off=0.0: (torch.randn(*s, generator=g) * scale + off).half()
+    x = r(n, h, w, c1, off=0.3)
+    x[1] = (x[1].float() * 1.7 - 0.8).half()                     # the two samples' statistics differ
+    x2 = r(n, h, w, c2, scale=2.0, off=-0.5) if c2 else None
+    ga, be = r(C, scale=0.2, off=1.0), r(C, scale=0.2)
+    wt, b = r(cout, C, 3, 3, scale=1 / math.sqrt(9 * C)), r(cout, scale=0.5)
+    rowvec = r(n, cout, scale=0.5)
+    residual = None if with_skip else r(n, h, w, cout)
+    skip = (r(n, h, w, 64, scale=2.0), None, r(cout, 64, scale=1 / math.sqrt(64)), r(cout, scale=0.5)) if with_skip else None
+    ref, bound = EB.gn_silu_conv_ref(x, ga, be, 1e-5, wt, b, x2=x2, rowvec=rowvec, residual=residual, skip=skip)
+    xin = (x if x2 is None else torch.cat([x, x2], -1)).double().permute(0, 3, 1, 2)
+    a = F.silu(F.group_norm(xin, 32, ga.double(), be.double(), 1e-5))
+    ind = F.conv2d(a, wt.double(), b.double(), padding=1) + rowvec.double()[:, :, None, None]
+    if residual is not None:
+        ind = ind + residual.double().permute(0, 3, 1, 2)
+    if skip is not None:
+        ind = ind + F.conv2d(skip[0].double().permute(0, 3, 1, 2), skip[2].double()[:, :, None, None], skip[3].double())
+    assert float((ref - ind.permute(0, 2, 3, 1).reshape(-1, cout)).abs().max()) < 1e-11
+    emu = lambda **kw: _res_half_fp32(x, x2, ga, be, 1e-5, wt, b, rowvec, residual, skip, **kw)
+    rr, s = EB.check(emu(), ref, bound, "fp32 emulation, RTN", image_rows=h * w, width=w)
+    assert rr < 1.0 and abs(s) < EB.BIAS_TOL
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check(emu(drop_rowvec=True), ref, bound, "row vector dropped", image_rows=h * w, width=w)
+    with pytest.raises(AssertionError, match=r"element bound: .*image 0"):
+        EB.check(emu(stats_from=(0, 1)), ref, bound, "sample 0 normalised with sample 1's statistics", image_rows=h * w, width=w)
+    with pytest.raises(AssertionError, match=r"element bound: .*image \d, row 0"):
+        EB.check(emu(halve_tap=True), ref, bound, "a border tap halved", image_rows=h * w, width=w)
+    if skip is not None:
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(_res_half_fp32(x, x2, ga, be, 1e-5, wt, b, rowvec, residual, (torch.zeros_like(skip[0]),) + skip[1:]), ref, bound, "skip segment dropped")
+    with pytest.raises(AssertionError, match="signed bias"):
+        EB.check(_rtz(ref), ref, bound, "RTZ")
+
+
+@pytest.mark.parametrize("config", ["tiny", "sd15"])
+def test_unet_chain_has_one_stage_per_reference_module(config):
+    """The chain's module list (tests/unet_chain.py `modules`, what its forward walks) against counts derived from the config alone:
+    UNetModel1.__init__ (LD.py:5379-5686) builds num_res_blocks[l] ResBlocks per level on the way down, one Downsample between levels, two in the
+    middle, num_res_blocks[l] + 1 per level on the way up with one Upsample between levels; a SpatialTransformer behind each ResBlock whose
+    transformer_depth entry is positive (transformer_depth_output read from its END).  Every name is a prefix of checkpoint keys, each key is owned
+    by exactly one module, and the channels are those of the parameter shapes."""
+    from lightdiffusion_amd import weights as W
+    import unet_chain as UC
+    cfg = W.tiny_unet_config() if config == "tiny" else W.sd15_unet_config()
+    blocks = UC.modules(cfg)
+    flat = [l for _, layers in blocks for l in layers]
+    kinds = lambda k: [l for l in flat if l[0] == k]
+    nrb, levels = cfg["num_res_blocks"], len(cfg["channel_mult"])
+    n_in, n_out = sum(nrb), sum(r + 1 for r in nrb)
+    assert len(kinds("conv_in")) == 1 and flat[0][0] == "conv_in"
+    assert len(kinds("res")) == n_in + 2 + n_out
+    assert len(kinds("down")) == levels - 1 and len(kinds("up")) == levels - 1
+    n_st = sum(1 for d in cfg["transformer_depth"][:n_in] if d > 0) + (1 if cfg["transformer_depth_middle"] > 0 else 0) + \
+        sum(1 for d in cfg["transformer_depth_output"][:n_out] if d > 0)
+    assert len(kinds("st")) == n_st
+    where = [b[0] for b, _ in blocks]
+    assert where.count("input") == 1 + n_in + levels - 1 and where.count("middle") == 1 and where.count("output") == n_out
+    # the output blocks pop the input blocks' channels in reverse: every ResBlock's cin is its in_layers norm's width, concat included
+    shapes = W.unet_param_shapes(cfg)
+    owned = {}
+    for kind, name, cin, cout in flat:
+        keys = [k for k in shapes if k.startswith(name + ".")]
+        assert keys, name
+        for k in keys:
+            assert k not in owned, (k, name, owned.get(k))
+            owned[k] = name
+        if kind == "res":
+            assert shapes[name + ".in_layers.0.weight"] == (cin,) and shapes[name + ".out_layers.3.weight"][0] == cout
+            assert ((name + ".skip_connection.weight") in shapes) == (cin != cout)
+        elif kind == "st":
+            assert shapes[name + ".norm.weight"] == (cin,) and cin == cout
+        else:
+            assert shapes[name + ".weight"][:2] == (cout, cin)
+    rest = set(shapes) - set(owned)
+    assert rest == {"time_embed.0.weight", "time_embed.0.bias", "time_embed.2.weight", "time_embed.2.bias", "out.0.weight", "out.0.bias",
+                    "out.2.weight", "out.2.bias"}, sorted(rest)
+    # the transformers sit where the depth lists say: the last transformer_depth_output entries belong to the FIRST output blocks
+    out_blocks = [layers for (w_, _), layers in blocks if w_ == "output"]
+    tdo = cfg["transformer_depth_output"][:n_out]
+    assert [any(l[0] == "st" for l in layers) for layers in out_blocks] == [d > 0 for d in reversed(tdo)]

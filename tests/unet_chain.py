@@ -1,0 +1,307 @@
+"""The SD1.x UNet forward as a chain of operator calls (helper module of tests/test_unet_chain_gpu.py).
+
+A plain restatement of UNetModel1.forward (LD.py:5688-5767) over the module list UNetModel1.__init__ builds (LD.py:5379-5686), with
+ResBlock1._forward (LD.py:5273-5287), SpatialTransformer.forward (LD.py:4239-4262) around BasicTransformerBlock._forward (LD.py:4117-4162),
+Downsample1 / Upsample1 (LD.py:5141-5186), EPS.calculate_input / calculate_denoised around it (BaseModel.apply_model, LD.py:5828-5860) and the
+CFG pair of calc_cond_batch (LD.py:2515-2547) — every step ONE call of the operator seam (lightdiffusion_amd/ops.py), on weights taken from
+the synthetic checkpoint and brought into the resident layouts by the seam's own repack / fold operators.  Nothing here reads the executor:
+the chain is what tests/test_unet_chain_gpu.py diffs the executor against, launch by launch and bit by bit, and every call leaves a tap
+(stage kind, layer name, inputs, parameters, output, launches) from which the test recomputes that one stage in fp64.
+
+`modules(cfg)` is the host-only walk of the constructor: the list of (kind, name, ...) the forward runs over.
+"""
+from __future__ import annotations
+
+import torch
+
+from lightdiffusion_amd import weights as W
+
+
+# ------------------------------------------------------------------ the module list (host only)
+
+def modules(cfg: dict):
+    """[(block, [(kind, name, cin, cout)])] for block in ('input', i) / ('middle', 0) / ('output', i), kind in conv_in, res, st, down, up:
+    the walk of UNetModel1.__init__ (LD.py:5379-5686).  For 'res' cin counts the skip concat of an output block."""
+    mc, cm, nrb = cfg["model_channels"], cfg["channel_mult"], cfg["num_res_blocks"]
+    td_in, td_out = list(cfg["transformer_depth"]), list(cfg["transformer_depth_output"])
+    blocks = [(("input", 0), [("conv_in", "input_blocks.0.0", cfg["in_channels"], mc)])]
+    ch, chans, idx = mc, [mc], 1
+    for level, mult in enumerate(cm):
+        for _ in range(nrb[level]):
+            layers = [("res", f"input_blocks.{idx}.0", ch, mult * mc)]
+            ch = mult * mc
+            if td_in.pop(0) > 0:
+                layers.append(("st", f"input_blocks.{idx}.1", ch, ch))
+            blocks.append((("input", idx), layers))
+            chans.append(ch)
+            idx += 1
+        if level != len(cm) - 1:
+            blocks.append((("input", idx), [("down", f"input_blocks.{idx}.0.op", ch, ch)]))
+            chans.append(ch)
+            idx += 1
+    mid = [("res", "middle_block.0", ch, ch)]
+    if cfg["transformer_depth_middle"] > 0:
+        mid.append(("st", "middle_block.1", ch, ch))
+    mid.append(("res", "middle_block.2", ch, ch))
+    blocks.append((("middle", 0), mid))
+    idx = 0
+    for level in reversed(range(len(cm))):
+        for i in range(nrb[level] + 1):
+            layers = [("res", f"output_blocks.{idx}.0", ch + chans.pop(), mc * cm[level])]
+            ch = mc * cm[level]
+            j = 1
+            if td_out.pop() > 0:
+                layers.append(("st", f"output_blocks.{idx}.{j}", ch, ch))
+                j += 1
+            if level and i == nrb[level]:
+                layers.append(("up", f"output_blocks.{idx}.{j}.conv", ch, ch))
+            blocks.append((("output", idx), layers))
+            idx += 1
+    return blocks
+
+
+def log_sigma_table() -> torch.Tensor:
+    """ModelSamplingDiscrete's table (LD.py:1300-1326): scaled-linear betas and the logarithm in fp64, rounded to fp32 once."""
+    betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, 1000, dtype=torch.float64) ** 2
+    ac = torch.cumprod(1.0 - betas, dim=0)
+    return (((1 - ac) / ac) ** 0.5).log().float()
+
+
+# ------------------------------------------------------------------ the chain
+
+class Feat:
+    """An activation [n][H][W][C] and, where its producer wrote them, the GroupNorm partial statistics of it."""
+
+    def __init__(self, t, part=None):
+        self.t, self.part = t, part
+
+
+class UNetChain:
+    def __init__(self, cfg: dict, device="cuda:0", seed: int = 0):
+        from lightdiffusion_amd import ops
+        self.ops, self.cfg, self.dev, self.seed = ops, dict(cfg), torch.device(device), seed
+        self.shapes = W.unet_param_shapes(cfg)
+        self.blocks = modules(cfg)
+        self.heads = cfg["num_heads"]
+        self._w = {}
+        self.taps = []
+        self.ctx = None
+        self.log_sigmas = log_sigma_table().to(self.dev)
+        res = [l for _, layers in self.blocks for l in layers if l[0] == "res"]
+        # every ResBlock's emb_layers Linear as rows of one matrix, in the order the blocks run (one projection per step)
+        self.emb_off, off = {}, 0
+        for _, name, _, cout in res:
+            self.emb_off[name] = off
+            off += cout
+        self.emb_total = off
+        self.emb_w = torch.cat([self.mat(n + ".emb_layers.1.weight") for _, n, _, _ in res]).contiguous()
+        self.emb_b = torch.cat([self.vec(n + ".emb_layers.1.bias") for _, n, _, _ in res]).contiguous()
+
+    # -- weights: the checkpoint's fp32 masters -> fp16, in the layouts the kernels read, by the seam's own operators
+    def master(self, name):
+        return W.synth_tensor(name, self.shapes[name], self.seed)
+
+    def _cached(self, key, make):
+        if key not in self._w:
+            self._w[key] = make()
+        return self._w[key]
+
+    def vec(self, name):
+        return self._cached(name, lambda: self.master(name).half().to(self.dev).contiguous())
+
+    def mat(self, name):
+        """[O][I] (a Linear, or a 1x1 convolution's [O][I][1][1])."""
+        return self._cached(name, lambda: self.master(name).half().reshape(self.shapes[name][0], -1).to(self.dev).contiguous())
+
+    def oihw(self, name):
+        """fp16 [O][I][k][k], the checkpoint's layout (what the fp64 references take)."""
+        return self._cached(("oihw", name), lambda: self.master(name).half().to(self.dev).contiguous())
+
+    def conv3(self, name):
+        """[O][9 I] tap-major from the fp32 master, as a load repacks it."""
+        return self._cached(("c3", name), lambda: self.ops.repack_conv_weight(self.master(name).to(self.dev)))
+
+    def tap(self, kind, name, inp, par, out, **more):
+        self.taps.append(dict(kind=kind, name=name, inp=inp, par=par, out=out, kernel=self.ops.last_kernel(), launches=self.ops.last_launches(), **more))
+        return out
+
+    # -- the context: K / V^T of every cross-attention, projected once (CrossAttention.forward's to_k / to_v, LD.py:4028-4036)
+    def set_context(self, ctx: torch.Tensor):
+        ops = self.ops
+        ctx = ctx.to(self.dev)
+        n, T, _ = ctx.shape
+        ctx16 = ops.ctx_pad(ctx.contiguous(), (T + 7) // 8 * 8)
+        self.ctx = {}
+        for _, layers in self.blocks:
+            for kind, name, _, _ in layers:
+                if kind == "st":
+                    b = name + ".transformer_blocks.0.attn2"
+                    k, vt = ops.context_kv(ctx16, self.mat(b + ".to_k.weight"), self.mat(b + ".to_v.weight"))
+                    self.ctx[name] = (k[:, :T].contiguous(), vt, ctx16)
+        self.ctx_n, self.ctx_tokens = n, T
+
+    # -- ResBlock1._forward (LD.py:5273-5287): in_layers (+ emb_layers' row), out_layers, skip_connection
+    def resblock(self, name, f: Feat, skip, emb_all, n):
+        ops = self.ops
+        x1 = f.t[:n]
+        x2 = None if skip is None else skip[:n]
+        c1, c2 = x1.shape[-1], 0 if x2 is None else x2.shape[-1]
+        H, Wd = x1.shape[1], x1.shape[2]
+        cout = self.shapes[name + ".in_layers.2.weight"][0]
+        in_part = f.part if x2 is None else None
+        rv = emb_all[:n, self.emb_off[name]:self.emb_off[name] + cout].contiguous()
+        g1, b1 = self.vec(name + ".in_layers.0.weight"), self.vec(name + ".in_layers.0.bias")
+        g2, b2 = self.vec(name + ".out_layers.0.weight"), self.vec(name + ".out_layers.0.bias")
+        w1, bias1 = self.conv3(name + ".in_layers.2.weight"), self.vec(name + ".in_layers.2.bias")
+        w2, bias2 = self.conv3(name + ".out_layers.3.weight"), self.vec(name + ".out_layers.3.bias")
+        has_skip = (name + ".skip_connection.weight") in self.shapes
+        fold = has_skip and ops.conv_takes_skip_segment(cout, n, H, Wd, cout)
+        res = x1
+        if has_skip:
+            wsk, bsk = self.mat(name + ".skip_connection.weight"), self.vec(name + ".skip_connection.bias")
+            if not fold:
+                res = ops.conv2d(x1, wsk, bsk, ksize=1, x2=x2)
+                self.tap("conv", name + ".skip_connection", dict(x=x1, x2=x2), dict(w=self.oihw(name + ".skip_connection.weight"), b=bsk), res)
+        h1, p1 = ops.group_norm_silu_conv2d(x1, g1, b1, 1e-5, w1, bias1, x2=x2, rowvec=rv, partials=True, in_part=in_part)
+        self.tap("gn_conv", name + ".in_layers", dict(x=x1, x2=x2, rowvec=rv, in_part=in_part),
+                 dict(gamma=g1, beta=b1, eps=1e-5, w=self.oihw(name + ".in_layers.2.weight"), b=bias1), h1, part=p1)
+        if fold:
+            out, po = ops.group_norm_silu_conv2d_skip(h1, g2, b2, 1e-5, w2, bias2, x1, x2, wsk, bsk, partials=True, in_part=p1)
+            self.tap("gn_conv", name + ".out_layers+skip", dict(x=h1, x2=None, rowvec=None, in_part=p1, s1=x1, s2=x2),
+                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2, wskip=wsk, bskip=bsk), out, part=po)
+        else:
+            out, po = ops.group_norm_silu_conv2d(h1, g2, b2, 1e-5, w2, bias2, residual=res, partials=True, in_part=p1)
+            self.tap("gn_conv", name + ".out_layers", dict(x=h1, x2=None, rowvec=None, in_part=p1, residual=res),
+                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2), out, part=po)
+        return out, po
+
+    # -- SpatialTransformer.forward (LD.py:4239-4262) around BasicTransformerBlock._forward (LD.py:4117-4162)
+    def transformer(self, name, f: Feat, n, n_all, pending):
+        """n samples run up to the cross-attention's K / V; `pending`: a CFG pair whose halves still share everything — the residual stream, the
+        query of attn2 and the block's input are copied to the second half in front of the cross-attention, which runs on all n_all."""
+        ops, heads = self.ops, self.heads
+        x = f.t[:n]
+        _, H, Wd, C = x.shape
+        L = H * Wd
+        b = name + ".transformer_blocks.0"
+        gng, gnb = self.vec(name + ".norm.weight"), self.vec(name + ".norm.bias")
+        if f.part is not None:
+            g = ops.group_norm_from_partials(x, f.part, gng, gnb, 1e-6)
+        else:
+            g = ops.group_norm(x, gng, gnb, 1e-6)
+        self.tap("groupnorm", name + ".norm", dict(x=x, in_part=f.part), dict(gamma=gng, beta=gnb, eps=1e-6, silu=False), g)
+        # proj_in, then [q | k | v] of attn1 on LayerNorm1 of it
+        wqkv = self._cached(("qkv", b), lambda: torch.cat([self.mat(b + ".attn1.to_q.weight"), self.mat(b + ".attn1.to_k.weight"),
+                                                           self.mat(b + ".attn1.to_v.weight")]).contiguous())
+        pin_w, pin_b = self.mat(name + ".proj_in.weight"), self.vec(name + ".proj_in.bias")
+        ln = lambda i: (self.vec(f"{b}.norm{i}.weight"), self.vec(f"{b}.norm{i}.bias"))
+        g2d = g.reshape(n * L, C)
+        t, qkv = ops.linear_ln(g2d, pin_w, pin_b, *ln(1), wqkv, None)
+        self.tap("linear_ln", name + ".proj_in>attn1.qkv", dict(x=g2d, residual=None), dict(w_prod=pin_w, b_prod=pin_b, gamma=ln(1)[0], beta=ln(1)[1], w=wqkv, b=None,
+                                                                                         geglu=False), (t, qkv))
+        ao = ops.attention_qkv(qkv.view(n, L, 3 * C), heads)
+        self.tap("attention", b + ".attn1", dict(q=qkv.view(n, L, 3 * C)[..., :C], k=qkv.view(n, L, 3 * C)[..., C:2 * C], v=qkv.view(n, L, 3 * C)[..., 2 * C:]), {}, ao)
+        o1w, o1b, q2w = self.mat(b + ".attn1.to_out.0.weight"), self.vec(b + ".attn1.to_out.0.bias"), self.mat(b + ".attn2.to_q.weight")
+        ao2d = ao.reshape(n * L, C)
+        t_in = t
+        t, q2 = ops.linear_ln(ao2d, o1w, o1b, *ln(2), q2w, None, residual=t_in)
+        self.tap("linear_ln", b + ".attn1.to_out>attn2.to_q", dict(x=ao2d, residual=t_in), dict(w_prod=o1w, b_prod=o1b, gamma=ln(2)[0], beta=ln(2)[1], w=q2w, b=None,
+                                                                                                geglu=False), (t, q2))
+        if pending:
+            full = lambda *shape: torch.empty((n_all,) + shape, dtype=torch.float16, device=self.dev)
+            tf, qf, xf = full(L, C), full(L, C), full(H, Wd, C)
+            tf[:n].copy_(t.view(n, L, C))
+            qf[:n].copy_(q2.view(n, L, C))
+            xf[:n].copy_(x)
+            ops.dup_halves_(tf, qf, xf)
+            self.tap("dup", name + " (pair split)", dict(t=t, q2=q2, x=x), {}, (tf, qf, xf))
+            t, q2, x, n = tf.view(n_all * L, C), qf.view(n_all * L, C), xf, n_all
+        k, vt, _ = self.ctx[name]
+        ao = ops.attention_vt(q2.view(n, L, C), k, vt, heads)
+        self.tap("attention", b + ".attn2", dict(q=q2.view(n, L, C), k=k, v=vt[:, :, :k.shape[1]].transpose(1, 2)), {}, ao)
+        o2w, o2b = self.mat(b + ".attn2.to_out.0.weight"), self.vec(b + ".attn2.to_out.0.bias")
+        f1w, f1b = self.mat(b + ".ff.net.0.proj.weight"), self.vec(b + ".ff.net.0.proj.bias")
+        ao2d = ao.reshape(n * L, C)
+        t_in = t
+        t, ff = ops.linear_ln_geglu(ao2d, o2w, o2b, *ln(3), f1w, f1b, residual=t_in)
+        self.tap("linear_ln", b + ".attn2.to_out>ff.net.0", dict(x=ao2d, residual=t_in), dict(w_prod=o2w, b_prod=o2b, gamma=ln(3)[0], beta=ln(3)[1], w=f1w, b=f1b,
+                                                                                              geglu=True), (t, ff))
+        # ff.net.2, the block's residual, proj_out and the transformer's residual: one contraction over [ff | t] on [Wpo W2 | Wpo]
+        wmo, bmo = self._cached(("mo", name), lambda: ops.mlp_out_fold(self.mat(name + ".proj_out.weight"), self.mat(b + ".ff.net.2.weight"),
+                                                                       self.vec(b + ".ff.net.2.bias"), self.vec(name + ".proj_out.bias")))
+        ff4, t4 = ff.view(n, H, Wd, 4 * C), t.view(n, H, Wd, C)
+        out, po = ops.conv2d_gn_partials(ff4, wmo, bmo, residual=x, ksize=1, x2=t4)
+        self.tap("conv", name + ".ff.net.2>proj_out", dict(x=ff4, x2=t4, residual=x), dict(w=wmo.view(C, 5 * C, 1, 1), b=bmo), out, part=po)
+        return out, po, n
+
+    # -- apply_model: calculate_input, UNetModel1.forward, calculate_denoised
+    def forward(self, x: torch.Tensor, sigma: torch.Tensor, eps_only: bool = False, pair: bool = False):
+        """x [n][4][h][w] fp32, sigma [n] (pair: both hold n / 2 samples, run against the 2 x (n / 2)-row context) -> denoised (eps) [n or 2 (n / 2)] fp32."""
+        ops, cfg = self.ops, self.cfg
+        self.taps = []
+        mc = cfg["model_channels"]
+        nb, _, h, w = x.shape
+        n_all = 2 * nb if pair else nb
+        assert self.ctx is not None and self.ctx_n == n_all
+        in_mod = nb if pair else 0
+        n = nb                                       # samples the layers run on: all of them, or the first half of a pair up to the first cross-attention
+        pending = pair
+        # time embedding (timestep_embedding LD.py:803-812, time_embed, every ResBlock's emb_layers)
+        temb, _ = ops.timestep_embed_mod(sigma, self.log_sigmas, mc, n_all, in_mod)
+        self.tap("timestep", "timestep_embedding", dict(sigma=sigma), dict(dim=mc, n=n_all, sigma_mod=in_mod), temb)
+        lin = lambda what, a, wn, bn_, act: self.tap("linear", what, dict(x=a), dict(w=wn, b=bn_, act=act), ops.linear(a, wn, bn_, act=act))
+        e1 = lin("time_embed.0", temb, self.mat("time_embed.0.weight"), self.vec("time_embed.0.bias"), "silu")
+        semb = lin("time_embed.2", e1, self.mat("time_embed.2.weight"), self.vec("time_embed.2.bias"), "silu")   # (every emb_layers starts with SiLU)
+        emb_all = lin("emb_layers (all ResBlocks)", semb, self.emb_w, self.emb_b, "none")
+
+        hs = []
+        f = None
+        for (where, bi), layers in self.blocks:
+            skip = None
+            if where == "output":
+                skip = hs.pop()
+                assert skip.shape[1:3] == f.t.shape[1:3]
+            for kind, name, cin, cout in layers:
+                if kind == "conv_in":
+                    y = torch.empty(n_all, h, w, mc, dtype=torch.float16, device=self.dev)
+                    wi, bi_ = self.conv3(name + ".weight"), self.vec(name + ".bias")
+                    ops.small_conv_in(x, wi, bi_, scale_sigma=sigma, y=y, dup_off=nb * h * w * mc if pair else 0)
+                    self.tap("conv_in", name, dict(x=x, sigma=sigma), dict(w=wi, b=bi_), y)
+                    f = Feat(y)
+                elif kind == "res":
+                    out, po = self.resblock(name, f, skip, emb_all, n)
+                    skip = None
+                    f = Feat(out, po)
+                elif kind == "st":
+                    out, po, n_now = self.transformer(name, f, n, n_all, pending)
+                    if pending:
+                        pending, n = False, n_now
+                    f = Feat(out, po)
+                elif kind == "down":
+                    assert not pending, "a CFG pair is split at the first cross-attention, in front of every resampling of the supported layouts"
+                    wd, bd = self.conv3(name + ".weight"), self.vec(name + ".bias")
+                    out, po = ops.conv2d_gn_partials(f.t, wd, bd, stride=2)
+                    self.tap("conv", name, dict(x=f.t, stride=2), dict(w=self.oihw(name + ".weight"), b=bd), out, part=po)
+                    f = Feat(out, po)
+                elif kind == "up":
+                    hv, wv = (hs[-1].shape[1], hs[-1].shape[2]) if hs else (2 * f.t.shape[1], 2 * f.t.shape[2])
+                    wu, bu = self.conv3(name + ".weight"), self.vec(name + ".bias")
+                    wf = self._cached(("up", name), lambda: ops.upconv2x_fold(wu))
+                    out = ops.upconv2x(f.t, wu, wf, bu, out_hw=(hv, wv))
+                    self.tap("upconv", name, dict(x=f.t, out_hw=(hv, wv)), dict(w=self.oihw(name + ".weight"), b=bu), out)
+                    f = Feat(out)
+            if where == "input":
+                assert not (pending and bi >= 1), "first input block without a transformer: not a layout of this chain"
+                hs.append(f.t)
+        # out: GroupNorm + SiLU, the 3x3 convolution to the latent's channels, calculate_denoised
+        og, ob = self.vec("out.0.weight"), self.vec("out.0.bias")
+        if f.part is not None:
+            g = ops.group_norm_from_partials(f.t, f.part, og, ob, 1e-5, silu=True)
+        else:
+            g = ops.group_norm(f.t, og, ob, 1e-5, silu=True)
+        self.tap("groupnorm", "out.0", dict(x=f.t, in_part=f.part), dict(gamma=og, beta=ob, eps=1e-5, silu=True), g)
+        wo, bo = self.conv3("out.2.weight"), self.vec("out.2.bias")
+        mode = 2 if eps_only else 0
+        out = ops.small_conv_out(g, wo, bo, mode, x_in=x, sigma=sigma, in_mod=in_mod)
+        self.tap("conv_out", "out.2", dict(x=g, x_in=x, sigma=sigma), dict(w=wo, b=bo, mode=mode, in_mod=in_mod), out)
+        return out
