@@ -39,6 +39,11 @@ extern "C" {
 #define LD_F16 0
 #define LD_F32 1
 
+/* whose launch a convolution operator reproduces (ld_op_conv, ld_op_conv_gn_partials, ld_op_groupnorm_conv): the scratch it plans under and the
+ * form in which it asks for the GroupNorm statistics of its output */
+#define LD_FORM_UNET 0  /* split partials, the counters and weight copy of the row-resident kernel; statistics with the chunk geometry (split-K second pass included) */
+#define LD_FORM_VAE 1   /* 96 MB of split partials only; statistics from the kernels that sum what they store (the halo tile's epilogue), or none */
+
 const char* ld_version(void);
 const char* ld_status_string(int status);
 
@@ -145,6 +150,8 @@ int ld_vae_encode(ld_vae* v, const float* pixels_nchw, float* moments, int b, in
 /* ld_vae_decode with a HIP-event pair around every launch (recorded on `stream`; synchronises it), and the per-launch table of that
  * run in the format of ld_unet_profile_launches: the per-layer VAE table of profiles/ (TFLOP/s and bytes per stage) is built from it */
 int ld_vae_profile(ld_vae* v, const float* z, float* out, int b, int h, int w, void* stream);
+/* ld_vae_encode with a HIP-event pair around every launch (synchronises the stream); its table is read by ld_vae_profile_launches too */
+int ld_vae_profile_encode(ld_vae* v, const float* pixels_nchw, float* moments, int b, int h, int w, void* stream);
 int ld_vae_profile_launches(const ld_vae* v, char* buf, size_t buf_bytes);
 int ld_vae_last_launches(const ld_vae* v);
 double ld_vae_last_flops(const ld_vae* v);
@@ -213,21 +220,33 @@ double ld_taesd_last_flops(const ld_taesd* t);
  * checkpoint row order [value | gate]; y is [M][N/2]).  ws/ws_bytes: optional split-K scratch. */
 int ld_op_linear(const void* x, const void* w, const void* bias, const void* residual, void* y, int M, int N, int K,
                  float alpha, int act, void* ws, size_t ws_bytes, void* stream);
-/* NHWC conv, ksize 1 or 3 (pad ksize/2), w in [Cout][ky][kx][Cin] order (see ld_op_repack_conv).  Two optional
- * NHWC sources are concatenated along channels; (hv, wv) != (h, w) resizes the input nearest-neighbour first. */
+/* y[batch][M][N] = alpha * x[batch][M][K] · w[batch][N][K]^T + bias[N] + bias_m[M], one problem per batch element at the element strides sA, sW, sC
+ * (0: shared), row pitches lda, ldw (0 = K) and N.  Rows n_valid .. N-1 of w (n_valid 0 = N) read as zeros: those columns of y are stored as
+ * bias + bias_m alone.  The three contractions of the VAE's AttnBlock at a width without a flash kernel.  ws/ws_bytes: split-K scratch (batch 1). */
+int ld_op_linear_batched(const void* x, int lda, const void* w, int ldw, const void* bias, const void* bias_m, void* y, int M, int N, int K, int n_valid,
+                         float alpha, int batch, long long sA, long long sW, long long sC, void* ws, size_t ws_bytes, void* stream);
+/* NHWC conv, ksize 1 or 3, w in [Cout][ky][kx][Cin] order (see ld_op_repack_conv).  Two optional
+ * NHWC sources are concatenated along channels; (hv, wv) != (h, w) resizes the input nearest-neighbour first.
+ * pad: zeros above / left of the image, -1 = ksize / 2; ho, wo: the output's size, 0 = what pad ksize / 2 gives at this stride — the zeros below /
+ * right of the image follow from it (pad 0 with ho = (h - 2) / 2 + 1 at stride 2: the VAE encoder's Downsample, F.pad (0, 1, 0, 1)).
+ * n_valid (0 = cout): rows of wt that are read, the others count as zeros; ldc (0 = cout): row pitch of y, a multiple of 8 >= n_valid — the
+ * VAE's output convolution on weights padded to 32 rows stores 8 columns.  form: LD_FORM_UNET or LD_FORM_VAE (ws >= 96 MB + 256 there). */
 int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
-               const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout,
-               void* ws, size_t ws_bytes, void* stream);
+               const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, int pad, int ho, int wo, int n_valid,
+               int ldc, int form, void* ws, size_t ws_bytes, void* stream);
+/* Host only: does the VAE executor run its output convolution [n][h][w][c] -> out_ch on the halo-tile kernel (ld_op_conv on weights zero-padded
+ * to 32 rows with n_valid = 8, ldc = 8 and LD_FORM_VAE, then ld_op_vae_out_finish), 1, or on ld_op_small_conv_out (mode 1), 0? */
+int ld_op_vae_conv_out_takes_halo_tile(int c, int n, int h, int w, int out_ch);
 /* GroupNorm(32) + SiLU + 3x3 conv (stride 1, pad 1) over the channel concat of two NHWC sources — ResBlock1.in_layers /
  * out_layers (LD.py:5224-5262).  Where the conv runs on the halo-tile kernel the normalisation is fused into its A operand
  * (statistics pass only, no normalised tensor in HBM).  in_part / in_chunks (optional, one source only): the GroupNorm partial statistics
  * of x1 that its producer wrote, [n][in_chunks][32][2] floats — the statistics pass is skipped, as the UNet executor does behind a convolution
- * that emitted them.  part / chunks (both or neither): the partial statistics of y, as ld_op_conv_gn_partials.
- * ws >= ld_op_groupnorm_conv_ws_bytes(...). */
+ * that emitted them.  part / chunks (both or neither): the partial statistics of y, as ld_op_conv_gn_partials.  form: LD_FORM_UNET, or
+ * LD_FORM_VAE for a ResnetBlock half as the VAE executor launches it.  ws >= ld_op_groupnorm_conv_ws_bytes(...). */
 size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int cout);
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
                          const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, float* in_part,
-                         int in_chunks, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
+                         int in_chunks, float* part, int* chunks, int form, void* ws, size_t ws_bytes, void* stream);
 int ld_op_repack_conv(const void* src_oihw, int dtype, int cout, int cin, void* dst, void* stream);
 /* ResBlock1's out_layers convolution and its 1x1 skip_connection as ONE contraction (LD.py:5267, 5273-5287; the UNet executor's "skip
  * fold"):  y = conv3x3(x; wt) + bias + conv1x1(cat(s1, s2); wskip) + bskip (+ rowvec per image), stride 1, pad 1.  x [n][h][w][c];
@@ -262,10 +281,12 @@ int ld_op_upconv2x(const void* x, int c, int n, int h, int w, int hv, int wv, co
  * where the kernel that runs the shape writes them (the halo convolution's generic epilogue, the row-resident kernel, the split-K second
  * pass) — what lets the GroupNorm that follows (ResBlock1 out_layers / the next block's in_layers, LD.py:5224-5262; the VAE's ResnetBlock,
  * LD.py:3560-3576) skip its statistics pass.  part: [n][*chunks][32][2] floats (sum, sum of squares per image, pixel chunk, group), sized
- * ld_op_conv_gn_partials_floats(n, hv*wv); *chunks = 0 when this shape's kernel does not write them.  For parity tests. */
+ * ld_op_conv_gn_partials_floats(n, hv*wv); *chunks = 0 when this shape's kernel does not write them — under LD_FORM_VAE whenever the halo tile
+ * does not take the shape: the caller then runs the two-pass GroupNorm.  pad .. form: as ld_op_conv.  For parity tests. */
 size_t ld_op_conv_gn_partials_floats(int n, int hw);
 int ld_op_conv_gn_partials(const void* x, int c, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize, const void* wt,
-                           const void* bias, const void* residual, void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream);
+                           const void* bias, const void* residual, void* y, int cout, int pad, int ho, int wo, int n_valid, int ldc, int form, float* part,
+                           int* chunks, void* ws, size_t ws_bytes, void* stream);
 /* GroupNorm(32) over the channel concat of two NHWC sources (+ optional SiLU); ws >= ld_op_groupnorm_ws_bytes */
 size_t ld_op_groupnorm_ws_bytes(int n, int hw);
 int ld_op_groupnorm(const void* x1, int c1, const void* x2, int c2, int n, int hw, const void* gamma, const void* beta,

@@ -82,6 +82,7 @@ SIGNATURES = {
     "ld_vae_decode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_vae_profile_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_esrgan_create": (_I, [C.POINTER(ESRGANConfig), C.POINTER(_P)]),
     "ld_esrgan_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_esrgan_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
@@ -89,9 +90,11 @@ SIGNATURES = {
     "ld_taesd_decode": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ld_taesd_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ld_op_linear": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _Z, _P]),
-    "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "ld_op_linear_batched": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, C.c_longlong, C.c_longlong, C.c_longlong, _P, _Z, _P]),
+    "ld_op_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "ld_op_vae_conv_out_takes_halo_tile": (_I, [_I, _I, _I, _I, _I]),
     "ld_op_groupnorm_conv_ws_bytes": (_Z, [_I, _I, _I, _I, _I, _I]),
-    "ld_op_groupnorm_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
+    "ld_op_groupnorm_conv": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P, _Z, _P]),
     "ld_op_repack_conv": (_I, [_P, _I, _I, _I, _P, _P]),
     "ld_op_upconv2x_fold": (_I, [_P, _I, _I, _P, _P]),
     "ld_op_upconv2x": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
@@ -105,7 +108,7 @@ SIGNATURES = {
     "ld_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "ld_op_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "ld_op_conv_gn_partials_floats": (_Z, [_I, _I]),
-    "ld_op_conv_gn_partials": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "ld_op_conv_gn_partials": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "ld_op_attention_rowv": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "ld_op_softmax_rows": (_I, [_P, _I, _I, _P]),
     "ld_op_timestep_embed": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),

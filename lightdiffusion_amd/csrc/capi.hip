@@ -122,14 +122,64 @@ int ld_op_linear(const void* x, const void* w, const void* bias, const void* res
     return op.ex.status;
 }
 
+// What ld_op_conv / ld_op_conv_gn_partials take beyond the symmetric convolution: pad (top / left zeros, -1 = ksize / 2) with an explicit
+// output size ho x wo (0 = what pad ksize / 2 gives; the bottom / right zeros follow from it — the VAE encoder's Downsample), n_valid rows of
+// wt that exist (0 = cout) stored at a row pitch of ldc (0 = cout) — the VAE's padded output convolution — and the executor whose launch it is.
+struct ConvGeom {
+    int pad = -1, ho = 0, wo = 0, n_valid = 0, ldc = 0, form = LD_FORM_UNET;
+    bool ok(int ksize, int cout) const {
+        if (pad < -1 || pad > ksize / 2 || ho < 0 || wo < 0 || (ho == 0) != (wo == 0)) return false;
+        if (n_valid < 0 || n_valid > cout || ldc < 0 || (ldc & 7) || (ldc > 0 && ldc < (n_valid > 0 ? n_valid : cout))) return false;
+        return form == LD_FORM_UNET || form == LD_FORM_VAE;
+    }
+};
+
+int ld_op_linear_batched(const void* x, int lda, const void* w, int ldw, const void* bias, const void* bias_m, void* y, int M, int N, int K, int n_valid,
+                         float alpha, int batch, long long sA, long long sW, long long sC, void* ws, size_t ws_bytes, void* stream) {
+    op_begin();
+    // the batched contractions of the VAE's attention at a width without a flash kernel (vae.hip VRun::attn), by the same builder: rows
+    // n_valid .. N-1 of w read as zeros, a bias along the rows of y, one problem per batch element at the three strides
+    if (x == nullptr || w == nullptr || y == nullptr || batch < 1 || n_valid < 0 || n_valid > N || sA < 0 || sW < 0 || sC < 0) return LD_ERR_ARG;
+    GemmParams p = linear_params((const half_t*)x, lda, (const half_t*)w, (const half_t*)bias, M, N, K, (half_t*)y, 0, 0, ldw);
+    p.n_valid = n_valid; p.bias_m = (const half_t*)bias_m; p.alpha = alpha;
+    p.batch = batch; p.sA = sA; p.sW = sW; p.sC = sC;
+    Op op(ws, ws_bytes, stream);
+    op.splitk_rest();
+    op.ex.gemm(p);
+    return op.ex.status;
+}
+
 static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
                    const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
-                   size_t ws_bytes, void* stream, float* gn_part, int* gn_chunks, const void* wup = nullptr) {
+                   size_t ws_bytes, void* stream, float* gn_part, int* gn_chunks, const void* wup = nullptr, const ConvGeom& g = ConvGeom()) {
     if (stride < 1 || (ksize != 1 && ksize != 3)) return LD_ERR_ARG;
-    GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, hv, wv, stride, ksize, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
+    if (!g.ok(ksize, cout)) return LD_ERR_ARG;
+    GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, hv, wv, stride, ksize, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y,
+                               g.pad, g.ho, g.wo);
     p.Wup = (const half_t*)wup;
     p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
     p.R = (const half_t*)residual;
+    if (g.n_valid > 0) p.n_valid = g.n_valid;
+    if (g.ldc > 0) p.ldc = p.ldr = g.ldc;
+    if (g.form == LD_FORM_VAE) {
+        // the VAE executor's launch (vae.hip VRun::conv): statistics from the kernels that sum what they store only, no chunk geometry; its scratch
+        // is the split partials alone — no counters and no weight copy, so the row-resident kernel is never offered
+        if (gn_part != nullptr) want_gn_tile_partials(p, gn_part, gn_chunks);
+        Op op(ws, ws_bytes, stream);
+        op.splitk(kCompositeSplitBytes);
+        if (ws == nullptr || !op.fits()) return LD_ERR_ARG;
+        if (p.ldc < p.N) {
+            // fewer stored columns than weight rows: only the halo tile's 32-column tile stores n_valid columns; every other kernel stores all N
+            // at the pitch ldc (the executor asks the plan first, and so does this)
+            const GemmPlan pl = op.ex.plan(p);
+            if (!(pl.halo_tile && pl.bn == 32 && p.n_valid > 0 && p.n_valid <= p.ldc)) return LD_ERR_SHAPE;
+            op.ex.gemm(p, &pl);
+            return op.ex.status;
+        }
+        op.ex.gemm(p);
+        return op.ex.status;
+    }
+    if (p.ldc < p.N) return LD_ERR_SHAPE;   // (the narrow store is the VAE output convolution's)
     if (gn_part != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, gn_part, gn_chunks);   // (as the executors ask)
     const size_t head = conv8_scratch_head(cout, c1 + c2);
     if (ws != nullptr && ksize == 3 && conv8_weight_eligible(cout, c1 + c2) && ws_bytes > head + ((size_t)8 << 20)) {
@@ -150,10 +200,12 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
 }
 
 int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
-               const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, void* ws,
-               size_t ws_bytes, void* stream) {
+               const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, int pad, int ho, int wo, int n_valid,
+               int ldc, int form, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
-    return op_conv(x1, c1, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, rowvec, residual, y, cout, ws, ws_bytes, stream, nullptr, nullptr);
+    ConvGeom g;
+    g.pad = pad; g.ho = ho; g.wo = wo; g.n_valid = n_valid; g.ldc = ldc; g.form = form;
+    return op_conv(x1, c1, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, rowvec, residual, y, cout, ws, ws_bytes, stream, nullptr, nullptr, nullptr, g);
 }
 
 int ld_op_upconv2x_fold(const void* wt, int cout, int cin, void* wfold, void* stream) {
@@ -176,11 +228,28 @@ size_t ld_op_conv_gn_partials_floats(int n, int hw) {
 }
 
 int ld_op_conv_gn_partials(const void* x, int c, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize, const void* wt,
-                           const void* bias, const void* residual, void* y, int cout, float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+                           const void* bias, const void* residual, void* y, int cout, int pad, int ho, int wo, int n_valid, int ldc, int form, float* part,
+                           int* chunks, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
     if (part == nullptr || chunks == nullptr) return LD_ERR_ARG;
     *chunks = 0;
-    return op_conv(x, c, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, nullptr, residual, y, cout, ws, ws_bytes, stream, part, chunks);
+    ConvGeom g;
+    g.pad = pad; g.ho = ho; g.wo = wo; g.n_valid = n_valid; g.ldc = ldc; g.form = form;
+    return op_conv(x, c, x2, c2, n, h, w, hv, wv, stride, ksize, wt, bias, nullptr, residual, y, cout, ws, ws_bytes, stream, part, chunks, nullptr, g);
+}
+
+int ld_op_vae_conv_out_takes_halo_tile(int c, int n, int h, int w, int out_ch) {
+    op_begin();
+    // what vae.hip run_decode asks of its output convolution: the weights zero-padded to 32 rows, 8 stored columns, planned under the VAE's
+    // scratch.  Host only: the plan reads no operand, so any non-null address stands for them.
+    if (c <= 0 || n <= 0 || h <= 0 || w <= 0 || out_ch <= 0 || out_ch > 8) return 0;
+    static const half_t any[8] = {};
+    GemmParams q = conv_params(any, c, nullptr, 0, n, h, w, h, w, 1, 3, any, any, 32, const_cast<half_t*>(any));
+    q.n_valid = 8; q.ldc = 8;
+    Exec ex;
+    ex.splitk_ws = reinterpret_cast<float*>(const_cast<half_t*>(any));
+    ex.splitk_bytes = kCompositeSplitBytes;
+    return ex.plan(q).halo_tile ? 1 : 0;
 }
 
 int ld_op_conv_takes_skip_segment(int c, int n, int h, int w, int cout) {
@@ -208,8 +277,9 @@ size_t ld_op_groupnorm_conv_ws_bytes(int c1, int c2, int n, int h, int w, int co
 
 int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, const void* gamma, const void* beta, float eps,
                          const void* wt, const void* bias, const void* rowvec, const void* residual, void* y, int cout, float* in_part, int in_chunks,
-                         float* part, int* chunks, void* ws, size_t ws_bytes, void* stream) {
+                         float* part, int* chunks, int form, void* ws, size_t ws_bytes, void* stream) {
     op_begin();
+    if (form != LD_FORM_UNET && form != LD_FORM_VAE) return LD_ERR_ARG;
     // in_part / in_chunks: GroupNorm partial statistics of x1 that its producer wrote ([n][in_chunks][32][2]; one source only): the statistics
     // pass is skipped, as in Run::resblock.  part / chunks (both or neither): the partial statistics of y, as ld_op_conv_gn_partials.
     if ((part == nullptr) != (chunks == nullptr) || in_chunks < 0 || (in_part != nullptr && (in_chunks == 0 || c2 != 0))) return LD_ERR_ARG;
@@ -224,8 +294,13 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
     GemmParams p = conv_params((const half_t*)x1, c1, (const half_t*)x2, c2, n, h, w, h, w, 1, 3, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
     p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
     p.R = (const half_t*)residual;
-    if (part != nullptr) want_gn_partials(p, n, h * w, part, chunks);
-    op.conv8_scratch(p, wt, kCompositeSplitBytes);
+    if (form == LD_FORM_VAE) {   // vae.hip VRun::gn_conv: the tile epilogue's statistics or none, split partials as the only scratch
+        if (part != nullptr) want_gn_tile_partials(p, part, chunks);
+        op.splitk(kCompositeSplitBytes);
+    } else {
+        if (part != nullptr) want_gn_partials(p, n, h * w, part, chunks);
+        op.conv8_scratch(p, wt, kCompositeSplitBytes);
+    }
     op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g, in_part, in_chunks);
     return op.ex.status;
 }
@@ -379,7 +454,7 @@ int ld_op_axpby(float* x, float a, const float* y, float b, const float* z, floa
 int ld_op_softmax_rows_ld(void* s, int rows, int cols, long long ld, int valid, void* stream) {
     op_begin();
     if (valid < 0 || ld < cols) return LD_ERR_SHAPE;
-    return softmax_rows_launch((half_t*)s, rows, cols, ld, (hipStream_t)stream, valid);
+    return launched(softmax_rows_launch((half_t*)s, rows, cols, ld, (hipStream_t)stream, valid), "softmax_rows_kernel");
 }
 
 int ld_op_groupnorm_chunks(int n, int hw) {
@@ -434,12 +509,12 @@ int ld_op_small_conv_out(const void* x, const void* wt, const void* bias, int n,
 
 int ld_op_small_pointwise(const void* x, const void* wt, const void* bias, float* out, int n, int hw, int c, void* stream) {
     op_begin();
-    return small_pointwise_launch((const half_t*)x, (const half_t*)wt, (const half_t*)bias, out, n, hw, c, (hipStream_t)stream);
+    return launched(small_pointwise_launch((const half_t*)x, (const half_t*)wt, (const half_t*)bias, out, n, hw, c, (hipStream_t)stream), "small_pointwise_kernel");
 }
 
 int ld_op_vae_out_finish(const void* t8, float* out, long long npix, int cout, void* stream) {
     op_begin();
-    return vae_out_finish_launch((const half_t*)t8, out, npix, cout, (hipStream_t)stream);
+    return launched(vae_out_finish_launch((const half_t*)t8, out, npix, cout, (hipStream_t)stream), "vae_out_finish_kernel");
 }
 
 int ld_op_timestep_embed_mod(const float* sigma, const float* log_sigmas, int n_sigmas, int n, int dim, void* out, float* t_out, int sigma_mod,

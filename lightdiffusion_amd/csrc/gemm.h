@@ -29,7 +29,9 @@ struct GemmParams {
     const half_t* W = nullptr;
     int ldw = 0;
     int M = 0, N = 0, K = 0;
-    int n_valid = 0;             // rows of W that exist (0 = N); rows n_valid..N-1 read as zeros (padded outputs)
+    int n_valid = 0;             // rows of W that exist (0 = N); rows n_valid..N-1 are never read.  The tap-major kernels load row n_valid - 1 in their
+                                 // place and store all N columns: the pad columns repeat column n_valid - 1 (finite, not zero).  The halo tile's
+                                 // 32-column tile stores n_valid columns only (its caller pads W with zero rows)
     // ---- batching over blockIdx.z (element strides)
     int batch = 1;
     long long sA = 0, sW = 0, sC = 0, sR = 0;

@@ -363,7 +363,7 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
     R.v = v;
     R.n = b;
     Arena plan;
-    Exec& ex = R.ex = v->begin(dry, stream, plan);   // (no entry point profiles an encode: want_timing is never set here)
+    Exec& ex = R.ex = v->begin(dry, stream, plan);   // (timed under ld_vae_profile_encode)
     Arena& ar = *ex.arena;
     const ld_vae_config& c = v->cfg;
     int H = h, W = w;
@@ -498,6 +498,10 @@ int ld_vae_encode(ld_vae* v, const float* pixels_nchw, float* moments, int b, in
 
 int ld_vae_profile(ld_vae* v, const float* z, float* out, int b, int h, int w, void* stream) {
     return abi_profile(v, stream, [&] { return ld_vae_decode(v, z, out, b, h, w, stream); });
+}
+
+int ld_vae_profile_encode(ld_vae* v, const float* pixels_nchw, float* moments, int b, int h, int w, void* stream) {
+    return abi_profile(v, stream, [&] { return ld_vae_encode(v, pixels_nchw, moments, b, h, w, stream); });
 }
 
 }  // extern "C"

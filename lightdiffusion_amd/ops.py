@@ -119,21 +119,68 @@ def repack_conv_weight(w_oihw: torch.Tensor) -> torch.Tensor:
     return out
 
 
+FORM_UNET, FORM_VAE = 0, 1      # LD_FORM_*: whose launch a convolution operator reproduces (include/ld_mi355x.h)
+_VAE_WS = (96 << 20) + 4096     # the VAE executor's split partials, and room for the operator's alignment
+
+
+def _conv_out_size(hv, wv, ksize, stride, pad, out_size):
+    """(ho, wo) and the (pad, ho, wo) arguments of the C entry points: out_size is only meaningful beside an explicit pad."""
+    if pad is None:
+        assert out_size is None
+        return ((hv - 1) // stride + 1 if ksize == 3 else hv), ((wv - 1) // stride + 1 if ksize == 3 else wv), (-1, 0, 0)
+    if out_size is None:
+        out_size = ((hv + pad + ksize // 2 - ksize) // stride + 1, (wv + pad + ksize // 2 - ksize) // stride + 1)
+    ho, wo = out_size
+    # every tap row / column the output reads lies at most one zero row / column outside the image (the loader's bounds check supplies those)
+    assert 1 <= ho and (ho - 1) * stride - pad + ksize - 1 <= hv and 1 <= wo and (wo - 1) * stride - pad + ksize - 1 <= wv, "output larger than the padded image"
+    return ho, wo, (pad, ho, wo)
+
+
 def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], ksize: int = 3, stride: int = 1,
            x2: Optional[torch.Tensor] = None, out_hw: Optional[tuple] = None, rowvec: Optional[torch.Tensor] = None,
-           residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+           residual: Optional[torch.Tensor] = None, pad: Optional[int] = None, out_size: Optional[tuple] = None, n_valid: int = 0, ldc: int = 0,
+           form: int = FORM_UNET) -> torch.Tensor:
     """NHWC conv (pad ksize//2) over the channel concat of x [N,H,W,C1] and optional x2 [N,H,W,C2];
-    `out_hw` first resizes the input nearest-neighbour (Upsample1, LD.py:5141-5152); rowvec [N,Cout] is added per image."""
+    `out_hw` first resizes the input nearest-neighbour (Upsample1, LD.py:5141-5152); rowvec [N,Cout] is added per image.
+    pad / out_size: zeros above and left of the image and the output's (ho, wo) — the zeros below and right follow from it (pad=0 at stride 2:
+    the VAE encoder's Downsample, F.pad (0, 1, 0, 1), LD.py:3514-3528).  n_valid / ldc: only the first n_valid rows of w_packed are read and y
+    has ldc columns (the VAE's output convolution on weights zero-padded to 32 rows: n_valid = ldc = 8).  form: FORM_VAE plans the launch under
+    the VAE executor's scratch."""
     n, h, w, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[-1]
     hv, wv = (h, w) if out_hw is None else out_hw
     cout = w_packed.shape[0]
-    ho = (hv - 1) // stride + 1 if ksize == 3 else hv
-    wo = (wv - 1) // stride + 1 if ksize == 3 else wv
-    y = torch.empty(n, ho, wo, cout, dtype=torch.float16, device=x.device)
-    ws = _ws(192 << 20, x.device)
+    ho, wo, geom = _conv_out_size(hv, wv, ksize, stride, pad, out_size)
+    y = torch.empty(n, ho, wo, ldc or cout, dtype=torch.float16, device=x.device)
+    ws = _ws(_VAE_WS if form == FORM_VAE else 192 << 20, x.device)
     check(lib().ld_op_conv(_p(x), c1, _p(x2), c2, n, h, w, hv, wv, stride, ksize, _p(w_packed), _p(bias), _p(rowvec), _p(residual),
-                           _p(y), cout, _p(ws), ws.numel(), _stream()), "ld_op_conv")
+                           _p(y), cout, *geom, n_valid, ldc, form, _p(ws), ws.numel(), _stream()), "ld_op_conv")
+    return y
+
+
+def vae_conv_out_takes_halo_tile(c: int, n: int, h: int, w: int, out_ch: int) -> bool:
+    """Host only: does the VAE executor run its output convolution [n, h, w, c] -> out_ch on the halo-tile kernel (conv2d on weights padded to
+    32 rows with n_valid = ldc = 8 and FORM_VAE, then vae_out_finish) or on small_conv_out (mode 1)?"""
+    return bool(lib().ld_op_vae_conv_out_takes_halo_tile(c, n, h, w, out_ch))
+
+
+def linear_batched(x: torch.Tensor, w: torch.Tensor, M: int, N: int, K: int, batch: int, strides: tuple, lda: int, ldw: int = 0,
+                   bias: Optional[torch.Tensor] = None, bias_m: Optional[torch.Tensor] = None, n_valid: int = 0, alpha: float = 1.0) -> torch.Tensor:
+    """y [batch, M, N] = alpha * x_b @ w_b[:n_valid].T (+ bias[N]) (+ bias_m[M] along the rows); columns n_valid .. N-1 hold the biases alone.
+    x, w: tensors (or views into one) read as [M, lda] / [N, ldw] per batch element at the element strides (sA, sW) = strides (0: shared) — the
+    three contractions of the VAE's AttnBlock where no flash kernel takes the width (V^T = Wv g^T + bv, S = Q K^T / sqrt(C), O = P V)."""
+    sA, sW = strides
+    ldw = ldw or K
+    nv = n_valid or N
+    assert x.is_cuda and w.is_cuda and x.dtype == w.dtype == torch.float16
+    room = lambda t: (t.untyped_storage().nbytes() - t.storage_offset() * 2) // 2          # halfs from the view's first element to the end of its storage
+    assert (batch - 1) * sA + (M - 1) * lda + K <= room(x) and (batch - 1) * sW + (nv - 1) * ldw + K <= room(w), "operand smaller than the problem"
+    assert bias is None or bias.numel() >= N
+    assert bias_m is None or bias_m.numel() >= M
+    y = torch.empty(batch, M, N, dtype=torch.float16, device=x.device)
+    ws = _ws(_VAE_WS, x.device)
+    check(lib().ld_op_linear_batched(x.data_ptr(), lda, w.data_ptr(), ldw, _p(bias), _p(bias_m), _p(y), M, N, K, n_valid, alpha, batch, sA, sW, M * N,
+                                     _p(ws), 96 << 20, _stream()), "ld_op_linear_batched")
     return y
 
 
@@ -203,23 +250,24 @@ def group_norm_silu_conv2d_skip(x: torch.Tensor, gamma: Optional[torch.Tensor], 
 
 
 def conv2d_gn_partials(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], out_hw: Optional[tuple] = None,
-                       residual: Optional[torch.Tensor] = None, ksize: int = 3, stride: int = 1, x2: Optional[torch.Tensor] = None):
+                       residual: Optional[torch.Tensor] = None, ksize: int = 3, stride: int = 1, x2: Optional[torch.Tensor] = None,
+                       pad: Optional[int] = None, out_size: Optional[tuple] = None, form: int = FORM_UNET):
     """NHWC conv (conv2d's arguments; 3x3 stride 1 by default) that also returns the GroupNorm(32) partial statistics its kernel wrote for the OUTPUT:
     (y, part [n, chunks, 32, 2] fp32 or None when this shape's kernel writes none) — what the executors hand to the next GroupNorm
-    (ResBlock1, LD.py:5224-5262; ResnetBlock, LD.py:3560-3576) instead of a statistics pass."""
+    (ResBlock1, LD.py:5224-5262; ResnetBlock, LD.py:3560-3576) instead of a statistics pass.  pad / out_size / form: as conv2d; under FORM_VAE
+    only the halo tile's epilogue writes statistics (the VAE executor's request), so `part` is None wherever another kernel takes the shape."""
     import ctypes
     n, h, w, c = x.shape
     c2 = 0 if x2 is None else x2.shape[-1]
     hv, wv = (h, w) if out_hw is None else out_hw
     cout = w_packed.shape[0]
-    ho = (hv - 1) // stride + 1 if ksize == 3 else hv
-    wo = (wv - 1) // stride + 1 if ksize == 3 else wv
+    ho, wo, geom = _conv_out_size(hv, wv, ksize, stride, pad, out_size)
     y = torch.empty(n, ho, wo, cout, dtype=torch.float16, device=x.device)
     part = torch.zeros(lib().ld_op_conv_gn_partials_floats(n, ho * wo), dtype=torch.float32, device=x.device)
     chunks = ctypes.c_int(0)
-    ws = _ws(192 << 20, x.device)
-    check(lib().ld_op_conv_gn_partials(_p(x), c, _p(x2), c2, n, h, w, hv, wv, stride, ksize, _p(w_packed), _p(bias), _p(residual), _p(y), cout, _p(part),
-                                       ctypes.byref(chunks), _p(ws), ws.numel(), _stream()), "ld_op_conv_gn_partials")
+    ws = _ws(_VAE_WS if form == FORM_VAE else 192 << 20, x.device)
+    check(lib().ld_op_conv_gn_partials(_p(x), c, _p(x2), c2, n, h, w, hv, wv, stride, ksize, _p(w_packed), _p(bias), _p(residual), _p(y), cout, *geom, 0, 0,
+                                       form, _p(part), ctypes.byref(chunks), _p(ws), ws.numel(), _stream()), "ld_op_conv_gn_partials")
     if chunks.value == 0:
         return y, None
     return y, part[: n * chunks.value * 64].view(n, chunks.value, 32, 2)
@@ -227,11 +275,13 @@ def conv2d_gn_partials(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[t
 
 def group_norm_silu_conv2d(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, w_packed: torch.Tensor,
                            bias: Optional[torch.Tensor], x2: Optional[torch.Tensor] = None, rowvec: Optional[torch.Tensor] = None,
-                           residual: Optional[torch.Tensor] = None, partials: bool = False, in_part: Optional[torch.Tensor] = None):
+                           residual: Optional[torch.Tensor] = None, partials: bool = False, in_part: Optional[torch.Tensor] = None,
+                           form: int = FORM_UNET):
     """conv3x3(SiLU(GroupNorm32(cat(x, x2)))) + rowvec + residual on NHWC fp16 — ResBlock1.in_layers / out_layers (LD.py:5224-5262)
     as ONE operator: on the halo-tile convolution kernel the normalisation happens inside the conv's A operand.  in_part: the GroupNorm
     partial statistics of x from its producer ([n, chunks, 32, 2]; x2 must be None): no statistics pass.  partials: returns (y, the partial
-    statistics the launch wrote for y, or None where this shape's kernel writes none), as conv2d_gn_partials."""
+    statistics the launch wrote for y, or None where this shape's kernel writes none), as conv2d_gn_partials.  form: FORM_VAE for a
+    ResnetBlock half (LD.py:3560-3576) as the VAE executor launches it."""
     import ctypes
     n, h, w, c1 = x.shape
     c2 = 0 if x2 is None else x2.shape[-1]
@@ -242,7 +292,7 @@ def group_norm_silu_conv2d(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Ten
     ws = _ws(lib().ld_op_groupnorm_conv_ws_bytes(c1, c2, n, h, w, cout), x.device)
     check(lib().ld_op_groupnorm_conv(_p(x), c1, _p(x2), c2, n, h, w, _p(gamma), _p(beta), eps, _p(w_packed), _p(bias), _p(rowvec), _p(residual),
                                      _p(y), cout, _p(in_part), 0 if in_part is None else in_part.shape[1], _p(part),
-                                     ctypes.byref(chunks) if partials else None, _p(ws), ws.numel(), _stream()), "ld_op_groupnorm_conv")
+                                     ctypes.byref(chunks) if partials else None, form, _p(ws), ws.numel(), _stream()), "ld_op_groupnorm_conv")
     if not partials:
         return y
     return y, (None if chunks.value == 0 else part[: n * chunks.value * 64].view(n, chunks.value, 32, 2))

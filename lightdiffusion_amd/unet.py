@@ -418,13 +418,20 @@ class MI355XVAE(ResidentModel):
             check(lib().ld_vae_profile(self._h, z.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_vae_profile")
         return self.profile_launches()
 
+    def profile_encode(self, pixel_samples: torch.Tensor) -> list:
+        """One encode_moments with HIP events around every launch -> the launch table, as profile_decode."""
+        px, (b, h, w) = self._encoder_input(pixel_samples)
+        out = torch.empty(b, 2 * self.cfg["z_channels"], h, w, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().ld_vae_profile_encode(self._h, px.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_vae_profile_encode")
+        return self.profile_launches()
+
     def decode(self, samples_in: torch.Tensor) -> torch.Tensor:
         """VAE.decode (LD.py:6357-6381): returns [B, 8h, 8w, 3] fp32 in [0,1] on the CPU (`intermediate_device`)."""
         return self.decode_device(samples_in).cpu()
 
-    def encode_moments(self, pixel_samples: torch.Tensor) -> torch.Tensor:
-        """pixels [B, H, W, 3] in [0,1] -> moments [B, 2z, H/8, W/8] fp32 on the device (mean | logvar): everything of
-        VAE.encode (LD.py:6383-6410) up to, but excluding, the regularizer's random sample."""
+    def _encoder_input(self, pixel_samples: torch.Tensor):
+        """pixels [B, H, W, 3] in [0,1] -> (fp32 NCHW in [-1, 1] on the device, (B, H/8, W/8)), the workspace grown to that shape."""
         if not self.with_encoder:
             raise RuntimeError("this MI355XVAE was created without the encoder (with_encoder=True)")
         px = pixel_samples[..., :3].to(self.device, torch.float32).movedim(-1, 1)
@@ -434,6 +441,12 @@ class MI355XVAE(ResidentModel):
         if h * 8 != H or w * 8 != W:
             raise ValueError("image sides must be multiples of 8")
         self._ensure(b, h, w)
+        return px, (b, h, w)
+
+    def encode_moments(self, pixel_samples: torch.Tensor) -> torch.Tensor:
+        """pixels [B, H, W, 3] in [0,1] -> moments [B, 2z, H/8, W/8] fp32 on the device (mean | logvar): everything of
+        VAE.encode (LD.py:6383-6410) up to, but excluding, the regularizer's random sample."""
+        px, (b, h, w) = self._encoder_input(pixel_samples)
         out = torch.empty(b, 2 * self.cfg["z_channels"], h, w, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             check(lib().ld_vae_encode(self._h, px.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_vae_encode")

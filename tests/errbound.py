@@ -189,26 +189,39 @@ def linear_ref(x, w, bias=None, residual=None, alpha=1.0, act="none"):
     return epilogue_ref(acc, absdot, x.shape[-1], bias, residual, alpha, act)
 
 
-def im2col(x_nhwc: torch.Tensor, ksize: int, stride: int = 1, out_hw=None) -> torch.Tensor:
+DOWNSAMPLE_PAD = (0, 1, 0, 1)     # the VAE encoder's Downsample (LD.py:3514-3528): F.pad's (left, right, top, bottom), then a 3x3 stride-2 conv, no padding
+
+
+def conv_out_hw(hv: int, wv: int, ksize: int, stride: int, pad=None):
+    """(ho, wo) of a ksize x ksize convolution at `stride` over an hv x wv image padded by pad = (left, right, top, bottom), None = ksize // 2 all round."""
+    l, r, t, b = (ksize // 2,) * 4 if pad is None else pad
+    return (hv + t + b - ksize) // stride + 1, (wv + l + r - ksize) // stride + 1
+
+
+def im2col(x_nhwc: torch.Tensor, ksize: int, stride: int = 1, out_hw=None, pad=None) -> torch.Tensor:
     """fp64 im2col of an NHWC fp16 tensor (after an optional nearest resize to out_hw): [n * ho * wo][C * k * k], columns (c, ky, kx) —
-    the order of a [Cout][C][k][k] weight reshaped to [Cout][C k k]."""
+    the order of a [Cout][C][k][k] weight reshaped to [Cout][C k k].  pad: (left, right, top, bottom) zeros as F.pad takes them (None: k // 2)."""
     x = x_nhwc.permute(0, 3, 1, 2).double()
     if out_hw is not None and tuple(out_hw) != tuple(x.shape[-2:]):
         x = torch.nn.functional.interpolate(x, size=tuple(out_hw), mode="nearest")
-    cols = torch.nn.functional.unfold(x, ksize, padding=ksize // 2, stride=stride)     # [n][C k k][L]
+    if pad is None:
+        cols = torch.nn.functional.unfold(x, ksize, padding=ksize // 2, stride=stride)     # [n][C k k][L]
+    else:
+        cols = torch.nn.functional.unfold(torch.nn.functional.pad(x, tuple(pad)), ksize, padding=0, stride=stride)
     return cols.transpose(1, 2).reshape(-1, cols.shape[1])
 
 
-def conv_ref(x, w_oihw, bias=None, residual=None, stride=1, out_hw=None, x2=None, rowvec=None):
-    """fp64 reference of ld_op_conv (NHWC, pad k // 2) as explicit im2col + matmul on the device: y_hat [n*ho*wo][Cout], bound, (ho, wo)."""
+def conv_ref(x, w_oihw, bias=None, residual=None, stride=1, out_hw=None, x2=None, rowvec=None, pad=None):
+    """fp64 reference of ld_op_conv (NHWC, pad k // 2, or pad = (left, right, top, bottom)) as explicit im2col + matmul on the device:
+    y_hat [n*ho*wo][Cout], bound, (ho, wo)."""
     xin = x if x2 is None else torch.cat([x, x2], dim=-1)
     k = w_oihw.shape[-1]
-    cols = im2col(xin, k, stride, out_hw)
+    cols = im2col(xin, k, stride, out_hw, pad)
     wm = w_oihw.double().reshape(w_oihw.shape[0], -1)
     acc = cols @ wm.t()
     absdot = cols.abs() @ wm.abs().t()
     hv, wv = (x.shape[1], x.shape[2]) if out_hw is None else out_hw
-    ho, wo = ((hv - 1) // stride + 1, (wv - 1) // stride + 1) if k == 3 else (hv, wv)
+    ho, wo = conv_out_hw(hv, wv, k, stride, pad) if pad is not None else ((hv - 1) // stride + 1, (wv - 1) // stride + 1) if k == 3 else (hv, wv)
     rv = None if rowvec is None else rowvec.double().repeat_interleave(ho * wo, dim=0)
     res = None if residual is None else residual.reshape(-1, residual.shape[-1])
     y, bd = epilogue_ref(acc, absdot, wm.shape[1], bias, res, rowvec=rv)
@@ -236,13 +249,15 @@ def cpu_rows_linear(x, w, rows):
     return x[rows].cpu().double() @ w.cpu().double().t()
 
 
-def cpu_rows_conv(x, w_oihw, rows, stride=1, out_hw=None, x2=None):
-    """CPU fp64 convolution at the sampled output pixels (rows of the [n*ho*wo] result), by explicit patch gathering."""
+def cpu_rows_conv(x, w_oihw, rows, stride=1, out_hw=None, x2=None, pad=None):
+    """CPU fp64 convolution at the sampled output pixels (rows of the [n*ho*wo] result), by explicit patch gathering.
+    pad = (left, right, top, bottom): the zeros around the image (None: k // 2 all round)."""
     xin = (x if x2 is None else torch.cat([x, x2], dim=-1)).cpu()
     n, h, wd, c = xin.shape
     hv, wv = (h, wd) if out_hw is None else out_hw
     k = w_oihw.shape[-1]
-    ho, wo = ((hv - 1) // stride + 1, (wv - 1) // stride + 1) if k == 3 else (hv, wv)
+    ho, wo = conv_out_hw(hv, wv, k, stride, pad) if pad is not None else ((hv - 1) // stride + 1, (wv - 1) // stride + 1) if k == 3 else (hv, wv)
+    left, top = (k // 2, k // 2) if pad is None else (pad[0], pad[2])
     wm = w_oihw.cpu().double()
     out = []
     for r in rows:
@@ -251,12 +266,49 @@ def cpu_rows_conv(x, w_oihw, rows, stride=1, out_hw=None, x2=None):
         acc = torch.zeros(wm.shape[0], dtype=torch.float64)
         for ky in range(k):
             for kx in range(k):
-                vy, vx = oy * stride + ky - k // 2, ox * stride + kx - k // 2
+                vy, vx = oy * stride + ky - top, ox * stride + kx - left
                 if 0 <= vy < hv and 0 <= vx < wv:
                     sy, sx = (vy * h) // hv, (vx * wd) // wv           # nearest resize: source pixel floor(v * in / out)
                     acc += wm[:, :, ky, kx] @ xin[img, sy, sx].double()
         out.append(acc)
     return torch.stack(out)
+
+
+def linear_batched_ref(x, w, bias=None, bias_m=None, n_valid=None, alpha=1.0):
+    """fp64 reference of ld_op_linear_batched: x [b][M][K], w [b][N][K] (or [N][K], shared), bias [N], bias_m [M] (along the rows of y),
+    only the first n_valid rows of w exist -> y_hat [b][M][n_valid], bound (epilogue_ref's, bias_m as a second bias of the staged tile).
+    The stored columns n_valid .. N-1 are NOT part of the reference; what they hold is fixed by the kernels (gemm3.hip gemm3_kernel /
+    gemm4_kernel loaders: `n = n0 + row < p.n_valid ? n0 + row : p.n_valid - 1`; the epilogue stores every n < N): the loader reads row
+    n_valid - 1 in place of a row that does not exist, so each pad column repeats column n_valid - 1 — a finite value, bit for bit that column
+    when there is no per-column bias (pad_columns_held).  They are never zeros of their own, and nothing behind may count on that: the softmax
+    over `valid` keys overwrites the scores' pad columns with exact zeros, and P V then runs over all Lp columns of P against a finite V^T."""
+    xd, wd = x.double(), w.double()
+    nv = wd.shape[-2] if n_valid is None else n_valid
+    wd = wd[..., :nv, :]
+    acc = xd @ wd.transpose(-1, -2)
+    absdot = xd.abs() @ wd.abs().transpose(-1, -2)
+    b = None
+    if bias is not None:
+        b = bias.double()[:nv]
+    if bias_m is not None:
+        b = (0.0 if b is None else b) + bias_m.double().reshape(-1, 1)
+    return epilogue_ref(acc, absdot, x.shape[-1], b, None, alpha)
+
+
+def pad_columns_held(y, n_valid, what):
+    """The stored pad columns of a batched linear without a per-column bias: each a bitwise repeat of column n_valid - 1 (linear_batched_ref)."""
+    if y.shape[-1] > n_valid:
+        last = y[..., n_valid - 1:n_valid]
+        assert bool(torch.isfinite(y[..., n_valid:].float()).all()) and torch.equal(y[..., n_valid:], last.expand_as(y[..., n_valid:])), \
+            f"{what}: the {y.shape[-1] - n_valid} pad columns do not repeat column {n_valid - 1}"
+
+
+def pv_ref(p, vt, valid):
+    """fp64 O = P V for P [b][L][Lp] (softmax rows whose columns valid .. Lp-1 MUST be exactly zero: asserted) and V^T [b][C][Lp], over the
+    valid keys only — the pad columns of V^T may hold anything finite: y_hat [b][L][C], bound."""
+    assert bool((p[..., valid:] == 0).all()), "P's pad columns are not exactly zero"
+    assert bool(torch.isfinite(vt.float()).all()), "V^T holds a non-finite value (0 * inf in the pad columns)"
+    return linear_batched_ref(p[..., :valid], vt[..., :valid])
 
 
 def attention_ref(q, k, v, heads, causal=False, ones=None, p_subnormal=False):

@@ -162,7 +162,7 @@ def test_vae_decode_non_square_bands_against_oracle():
             "conv6_kernel<W128,halo,32x512>"} <= kinds, kinds
     ref = O.vae_decode(W.synth_state_dict(W.vae_decoder_param_shapes(cfg)), cfg, z[:1])
     assert float((img[:1] - ref).abs().max()) < 2.0 / 255.0
-    img1 = v.decode(z[1:])                                     # batch 1: other tile counts (the output conv falls back below 192 tiles)
+    img1 = v.decode(z[1:])                                     # batch 1: other tile counts (the output conv keeps the halo tile at exactly 192 tiles; tests/test_vae_chain_gpu.py)
     assert float((img1 - img[1:]).abs().max()) < 1.0 / 255.0
     del v
     torch.cuda.empty_cache()

@@ -1004,3 +1004,211 @@ def test_unet_chain_has_one_stage_per_reference_module(config):
     out_blocks = [layers for (w_, _), layers in blocks if w_ == "output"]
     tdo = cfg["transformer_depth_output"][:n_out]
     assert [any(l[0] == "st" for l in layers) for layers in out_blocks] == [d > 0 for d in reversed(tdo)]
+
+
+# ------------------------------------------------------------------ what the VAE chain adds (tests/vae_chain.py, tests/test_vae_chain_gpu.py)
+
+def _down_fp32(xpadded_nchw, wt, b):
+    """The encoder's downsample in torch fp32 from an already padded fp16 image [n][C][H + 1][W + 1]: fp32 sums, one fp16 rounding."""
+    return (F.conv2d(xpadded_nchw.float(), wt.float(), None, stride=2) + b.float().view(1, -1, 1, 1)).half().permute(0, 2, 3, 1).reshape(-1, wt.shape[0])
+
+
+@pytest.mark.parametrize("hw", [(8, 6), (7, 5)], ids=["even", "odd"])
+def test_asymmetric_pad_conv_reference(hw):
+    """errbound.im2col / conv_ref / cpu_rows_conv with the pad (0, 1, 0, 1) of the VAE encoder's Downsample (LD.py:3514-3528): equal to fp64
+    F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2); the fp32 emulation passes; a symmetric pad, a bottom row whose out-of-image taps read the next
+    image's first row and a right column whose out-of-image taps read the next pixel row's first pixel (what a loader without a bounds check
+    finds at those addresses in NHWC memory) are rejected, each at the row or column it spoils."""
+    g = torch.Generator().manual_seed(23)
+    n, (h, w), c, cout = 2, hw, 64, 32
+    x = torch.randn(n, h, w, c, generator=g).half()
+    x[1, 0] = (x[1, 0].float() * 8.0).half()                       # large values in the second image's first pixel row
+    x[:, :, 0] = (x[:, :, 0].float() * 4.0).half()                 # ... and in every row's first pixel
+    wt = (torch.randn(cout, c, 3, 3, generator=g) / math.sqrt(9 * c)).half()
+    b = (torch.randn(cout, generator=g) * 0.5).half()
+    ref, bound, (ho, wo) = EB.conv_ref(x, wt, b, stride=2, pad=EB.DOWNSAMPLE_PAD)
+    assert (ho, wo) == ((h + 1 - 3) // 2 + 1, (w + 1 - 3) // 2 + 1) == EB.conv_out_hw(h, w, 3, 2, EB.DOWNSAMPLE_PAD)
+    xn = x.permute(0, 3, 1, 2)
+    ind = F.conv2d(F.pad(xn.double(), (0, 1, 0, 1)), wt.double(), b.double(), stride=2)
+    assert float((ref - ind.permute(0, 2, 3, 1).reshape(-1, cout)).abs().max()) < 1e-11
+    rows = list(range(ref.shape[0]))
+    cpu = EB.cpu_rows_conv(x, wt, rows, 2, pad=EB.DOWNSAMPLE_PAD) + b.double()
+    assert torch.allclose(cpu, ref, rtol=1e-12, atol=1e-12)
+    where = dict(image_rows=ho * wo, width=wo)
+    r, s = EB.check(_down_fp32(F.pad(xn, (0, 1, 0, 1)), wt, b), ref, bound, "fp32 emulation, RTN", **where)
+    assert r < 1.0 and abs(s) < EB.BIAS_TOL + EB.rtn_noise(ref.numel())
+    if h % 2 == 0:                                                  # (pad 1 all round gives the same output size at an even size only)
+        sym = (F.conv2d(xn.float(), wt.float(), b.float(), stride=2, padding=1)).half().permute(0, 2, 3, 1).reshape(-1, cout)
+        assert sym.shape == ref.shape
+        with pytest.raises(AssertionError, match="element bound"):
+            EB.check(sym, ref, bound, "pad 1 on all sides", **where)
+    # the row below the image: the next image's first row (image 0 only: nothing of the test lies behind the last image)
+    below = torch.zeros(n, c, 1, w, dtype=torch.float16)
+    below[0] = xn[1, :, 0:1]
+    spoiled = F.pad(torch.cat([xn, below], dim=2), (0, 1, 0, 0))
+    if (h + 1 - 3) % 2 == 0:                                        # (the last output row reads the pad row: an even height)
+        with pytest.raises(AssertionError, match=rf"element bound: .*image 0, row {ho - 1}, "):
+            EB.check(_down_fp32(spoiled, wt, b), ref, bound, "bottom taps read the next image", **where)
+    # the column right of the image: the first pixel of the next pixel row
+    flat = torch.cat([xn.permute(0, 2, 3, 1).reshape(-1, c), torch.zeros(1, c, dtype=torch.float16)])          # NHWC memory, then one pixel of zeros
+    right = flat[torch.arange(n * h * w).reshape(n, h, w)[:, :, -1] + 1].permute(0, 2, 1).unsqueeze(-1)            # [n][C][h][1]
+    spoiled = F.pad(torch.cat([xn, right], dim=3), (0, 0, 0, 1))
+    if (w + 1 - 3) % 2 == 0:
+        with pytest.raises(AssertionError, match=rf"element bound: .*column {wo - 1}; "):
+            EB.check(_down_fp32(spoiled, wt, b), ref, bound, "right taps read the next row", **where)
+
+
+def test_linear_batched_reference_and_pad_columns():
+    """errbound.linear_batched_ref (bias along the rows, n_valid), pad_columns_held and pv_ref: equal to an independent fp64 evaluation; the fp32
+    emulation passes; a bias added along the columns instead, one batch element read at its neighbour's stride and scores over the pad keys
+    (n_valid = Lp: the softmax's denominator then counts them) are rejected; P with a non-zero pad column is refused outright."""
+    g = torch.Generator().manual_seed(31)
+    n, C, L = 2, 64, 35
+    Lp = (L + 7) // 8 * 8
+    r = lambda *s, scale=1.0: (torch.randn(*s, generator=g) * scale).half()
+    wv, bv, x = r(C, C, scale=1 / math.sqrt(C)), r(C, scale=0.5), r(n, L, C)
+    # V^T = Wv x_b^T + bv: bias along the rows
+    ref, bound = EB.linear_batched_ref(wv.unsqueeze(0).expand(n, C, C), x, bias_m=bv, n_valid=L)
+    ind = torch.einsum("ok,blk->bol", wv.double(), x.double()) + bv.double().view(1, C, 1)
+    assert ref.shape == (n, C, L) and float((ref - ind).abs().max()) < 1e-12
+    emu = (torch.einsum("ok,blk->bol", wv.float(), x.float()) + bv.float().view(1, C, 1)).half()
+    rr, s = EB.check(emu, ref, bound, "fp32 emulation, RTN")
+    assert rr < 1.0 and abs(s) < EB.BIAS_TOL + EB.rtn_noise(ref.numel())
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check((torch.einsum("ok,blk->bol", wv.float(), x.float()) + bv.float()[:L].view(1, 1, L)).half(), ref, bound, "bias along the columns")
+    with pytest.raises(AssertionError, match=r"element bound: .*element \(1, "):
+        EB.check(torch.stack([emu[0], emu[0]]), ref, bound, "batch 1 read at batch 0's address")
+    stored = torch.cat([emu, emu[..., L - 1:L].expand(n, C, Lp - L)], dim=-1)
+    EB.pad_columns_held(stored, L, "V^T")
+    with pytest.raises(AssertionError, match="pad columns"):
+        EB.pad_columns_held(torch.cat([emu, torch.zeros(n, C, Lp - L, dtype=torch.float16)], dim=-1), L, "V^T zero-filled")
+    # S = Q K^T / sqrt(C), P = softmax over the valid keys, O = P V
+    q, k = r(n, L, C), r(n, L, C)
+    sref, sbound = EB.linear_batched_ref(q, k, n_valid=L, alpha=1 / math.sqrt(C))
+    assert float((sref - q.double() @ k.double().transpose(1, 2) / math.sqrt(C)).abs().max()) < 1e-12
+    s16 = (q.float() @ k.float().transpose(1, 2) / math.sqrt(C)).half()
+    EB.check(s16, sref, sbound, "scores, fp32 emulation")
+    spad = torch.cat([s16, s16[..., L - 1:L].expand(n, L, Lp - L)], dim=-1)
+    pref, pbound = EB.softmax_ref(spad.reshape(n * L, Lp), L)
+    p16 = pref.half()
+    assert bool((p16[:, L:] == 0).all())
+    EB.check(p16, pref, pbound, "softmax over the valid keys", keep=EB.top_half_per_row(pref))
+    with pytest.raises(AssertionError, match="element bound"):           # the pad keys' repeated scores join the denominator
+        EB.check(torch.softmax(spad.float().reshape(n * L, Lp), -1).half(), pref, pbound, "softmax over all Lp keys")
+    vt = stored.clone()
+    vt[..., L:] = 3.0e4                                                   # whatever the pad columns of V^T hold, it is finite and meets zeros
+    oref, obound = EB.pv_ref(p16.view(n, L, Lp), vt, L)
+    oind = pref.view(n, L, Lp)[..., :L].half().double() @ stored.double()[..., :L].transpose(1, 2)
+    assert float((oref - oind).abs().max()) < 1e-12
+    EB.check((p16.view(n, L, Lp).float() @ vt.float().transpose(1, 2)).half(), oref, obound, "P V, fp32 emulation")
+    bad = p16.view(n, L, Lp).clone()
+    bad[1, 3, L] = 2.0 ** -20
+    with pytest.raises(AssertionError, match="not exactly zero"):
+        EB.pv_ref(bad, vt, L)
+
+
+def _gn_from(x, stats_of, ga, be, eps, silu):
+    """GroupNorm (+SiLU) of x [n][hw][C] in torch fp32 with the group statistics of ANOTHER tensor of the same shape (a handover gone wrong)."""
+    n, hw, c = x.shape
+    cpg = c // 32
+    sg = stats_of.float().reshape(n, hw, 32, cpg)
+    mu = sg.mean(dim=(1, 3))
+    var = ((sg * sg).mean(dim=(1, 3)) - mu * mu).clamp_min(0.0)
+    per_c = lambda t: t.repeat_interleave(cpg, dim=1).unsqueeze(1)
+    y = (x.float() - per_c(mu)) * per_c(torch.rsqrt(var + eps)) * ga.float() + be.float()
+    return (F.silu(y) if silu else y).half()
+
+
+@pytest.mark.parametrize("silu", [False, True], ids=["norm", "norm_silu"])
+def test_groupnorm_ref_rejects_handed_over_statistics_of_another_tensor(silu):
+    """The statistics handover of csrc/vae.hip (VRun::st_of / wrote / gn) gone wrong, on errbound.groupnorm_ref — the stage reference of norm_out
+    and, inside gn_silu_conv_ref, of every ResnetBlock half: the same arithmetic with the tensor's own statistics passes; with the statistics
+    of the tensor that lay at the same address before (the same layer's output one step earlier: 2 % larger, shifted by 0.01 — a plausible
+    image) or of the neighbouring sample it is rejected.  (gn_silu_conv_ref's neighbour control: test_gn_silu_conv_ref_and_bound.)"""
+    x, ga, be = _gn_inputs(2, 60, 128, 41)
+    x[1] = (x[1].float() * 1.3 + 0.2).half()
+    ref, bound = EB.groupnorm_ref(x, None, ga, be, 1e-6, silu)
+    rr, s = EB.check(_gn_from(x, x, ga, be, 1e-6, silu), ref, bound, "own statistics")
+    assert rr < 1.0 and abs(s) < EB.BIAS_TOL
+    prev = (x.float() * 1.02 + 0.01).half()
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check(_gn_from(x, prev, ga, be, 1e-6, silu), ref, bound, "statistics of the previous tensor at this address")
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check(_gn_from(x, x.flip(0), ga, be, 1e-6, silu), ref, bound, "statistics of the neighbouring sample")
+
+
+def test_gn_silu_conv_ref_rejects_stale_statistics():
+    """... and through the convolution (errbound.gn_silu_conv_ref, the ResnetBlock half's reference): a half normalised with the statistics
+    of the previous tensor at the same address is rejected."""
+    g = torch.Generator().manual_seed(43)
+    n, h, w, c, cout = 2, 5, 7, 64, 64
+    r = lambda *s, scale=1.0, off=0.0: (torch.randn(*s, generator=g) * scale + off).half()
+    x = r(n, h, w, c, off=0.3)
+    ga, be = r(c, scale=0.2, off=1.0), r(c, scale=0.2)
+    wt, b, res = r(cout, c, 3, 3, scale=1 / math.sqrt(9 * c)), r(cout, scale=0.5), r(n, h, w, cout)
+    ref, bound = EB.gn_silu_conv_ref(x, ga, be, 1e-6, wt, b, residual=res)
+
+    def half_with(stats_of):
+        a = _gn_from(x.reshape(n, h * w, c), stats_of.reshape(n, h * w, c), ga, be, 1e-6, True).reshape(n, h, w, c).permute(0, 3, 1, 2).float()
+        y = (F.conv2d(a, wt.float(), None, padding=1) + b.float().view(1, -1, 1, 1)).half()
+        return (y.float() + res.permute(0, 3, 1, 2).float()).half().permute(0, 2, 3, 1).reshape(n * h * w, cout)
+    EB.check(half_with(x), ref, bound, "own statistics", image_rows=h * w, width=w)
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check(half_with((x.float() * 1.02 + 0.01).half()), ref, bound, "stale statistics", image_rows=h * w, width=w)
+
+
+def _vae_cfg(tag):
+    from lightdiffusion_amd import weights as W
+    return {"tiny": W.tiny_vae_config(), "sd15": W.sd15_vae_config(), "fallback": dict(z_channels=4, ch=64, ch_mult=[1, 1, 1, 1], num_res_blocks=2, out_ch=3)}[tag]
+
+
+@pytest.mark.parametrize("config", ["tiny", "sd15", "fallback"])
+@pytest.mark.parametrize("encoder", [False, True], ids=["decoder", "encoder"])
+def test_vae_chain_has_one_stage_per_reference_module(config, encoder):
+    """The chain's module list (tests/vae_chain.py `modules`) against counts derived from the config alone: Decoder.__init__ (LD.py:3761-3855)
+    builds num_res_blocks + 1 ResnetBlocks per level and one Upsample between levels, Encoder.__init__ (LD.py:3649-3729) num_res_blocks per
+    level and one Downsample between levels; two ResnetBlocks around one AttnBlock in the middle of either; nin_shortcut exactly where
+    cin != cout.  Every name is a prefix of checkpoint keys, each key is owned by exactly one module, and the channels are the parameters'."""
+    from lightdiffusion_amd import weights as W
+    import vae_chain as VC
+    cfg = _vae_cfg(config)
+    mods = VC.modules(cfg, encoder)
+    kinds = lambda k: [m for m in mods if m[0] == k]
+    levels, nrb = len(cfg["ch_mult"]), cfg["num_res_blocks"]
+    assert mods[0][0] == "conv_in" and len(kinds("conv_in")) == 1
+    assert len(kinds("res")) == levels * (nrb if encoder else nrb + 1) + 2
+    assert len(kinds("attn")) == 1 and len(kinds("down" if encoder else "up")) == levels - 1 and not kinds("up" if encoder else "down")
+    assert [m[0] for m in mods[-3:]] == ["norm_out", "conv_out", "quant"] if encoder else [m[0] for m in mods[-2:]] == ["norm_out", "conv_out"]
+    i = [m[0] for m in mods].index("attn")
+    assert mods[i - 1][0] == "res" and mods[i + 1][0] == "res" and ".mid." in mods[i][1]
+    # per level: its ResnetBlocks, then the resampling (not behind the last level of the walk)
+    walk = [m for m in mods if m[0] in ("res", "up", "down") and ".mid." not in m[1]]
+    per = nrb if encoder else nrb + 1
+    want = []
+    for step in range(levels):
+        want += ["res"] * per + ([] if step == levels - 1 else ["down" if encoder else "up"])
+    assert [m[0] for m in walk] == want
+    shapes = W.vae_encoder_param_shapes(cfg) if encoder else W.vae_decoder_param_shapes(cfg)
+    owned = {}
+    for kind, name, cin, cout in mods:
+        keys = [k for k in shapes if k.startswith(name + ".")]
+        assert keys, name
+        for k in keys:
+            assert k not in owned, (k, name, owned.get(k))
+            owned[k] = name
+        if kind == "res":
+            assert shapes[name + ".norm1.weight"] == (cin,) and shapes[name + ".conv2.weight"][:2] == (cout, cout) and shapes[name + ".conv1.weight"][:2] == (cout, cin)
+            assert ((name + ".nin_shortcut.weight") in shapes) == (cin != cout)
+        elif kind == "attn":
+            assert shapes[name + ".norm.weight"] == (cin,) and cin == cout and all(shapes[f"{name}.{t}.weight"] == (cin, cin, 1, 1) for t in ("q", "k", "v", "proj_out"))
+        elif kind == "norm_out":
+            assert shapes[name + ".weight"] == (cin,)
+        else:
+            assert shapes[name + ".weight"][:2] == (cout, cin)
+    rest = set(shapes) - set(owned)
+    assert rest == (set() if encoder else {"post_quant_conv.weight", "post_quant_conv.bias"}), sorted(rest)
+    # the chain of channels is unbroken, and the widths are the config's
+    for a, b in zip(mods, mods[1:]):
+        assert a[3] == b[2], (a, b)
+    mid = cfg["ch"] * cfg["ch_mult"][-1]
+    assert mods[i][2] == mid and (mods[0][3] == cfg["ch"] if encoder else mods[0][3] == mid)

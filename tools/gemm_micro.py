@@ -59,7 +59,7 @@ def conv_graph(n, h, w_, cin, cout, reps):
     from lightdiffusion_amd._lib import lib, check
     def fn():
         check(lib().ld_op_conv(x.data_ptr(), cin, None, 0, n, h, w_, h, w_, 1, 3, wt.data_ptr(), b.data_ptr(), None, None, y.data_ptr(), cout,
-                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "conv")
+                               -1, 0, 0, 0, 0, 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), "conv")
     ms = graph_time(fn, reps)
     print(f"[graph] conv3 n={n} {h}x{w_} {cin}->{cout}: {ms*1e3:8.1f} us  {2.0*n*h*w_*cout*9*cin/ms/1e9:7.1f} TF/s", flush=True)
 

@@ -48,7 +48,7 @@ def conv(nimg, h, cin, cout, res=False):
     r = torch.randn(nimg, h, h, cout, device=DEV, dtype=torch.float16) if res else None
     def fn():
         check(L.ld_op_conv(x.data_ptr(), cin, None, 0, nimg, h, h, h, h, 1, 3, wt.data_ptr(), b.data_ptr(), None, None if r is None else r.data_ptr(),
-                           y.data_ptr(), cout, WS.data_ptr(), WS.numel(), torch.cuda.current_stream().cuda_stream), "conv")
+                           y.data_ptr(), cout, -1, 0, 0, 0, 0, 0, WS.data_ptr(), WS.numel(), torch.cuda.current_stream().cuda_stream), "conv")
     return fn, 2.0 * nimg * h * h * cout * 9 * cin, f"conv3 {nimg * h * h}x{cout}x{9 * cin}{' +res' if res else ''}"
 
 
