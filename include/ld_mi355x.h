@@ -382,9 +382,14 @@ int ld_op_bislerp(const float* x, float* tmp, float* y, int n, int c, int h, int
  * x: NHWC with pixel pitch ldx >= cin, cin a multiple of 32 in [64, 192]; cout 32 or 64; wt [cout][9 cin] as ld_op_repack_conv writes it;
  * r1 / r2: NHWC with pitches ldr1 / ldr2, cout channels read.  y may be x (same pointer and pitch) when c_off >= cin — the dense
  * concatenation in place; any other overlap of y with x is LD_ERR_ARG.  (h, w) is the output size; up != 0: x is [n][h/2][w/2] and is read
- * through a nearest-2x upsampling (upconv_block, LD.py:6995-7022).  Pitches and c_off are multiples of 8.  LD_ERR_SHAPE otherwise. */
+ * through a nearest-2x upsampling (upconv_block, LD.py:6995-7022).  Pitches and c_off are multiples of 8.  LD_ERR_SHAPE otherwise.
+ * ld_op_esrgan_conv_y2 is the same call with a second store (ld_op_esrgan_conv passes y2 = NULL): y2 != NULL: the same cout values are also stored at y2[n][h][w][0 .. cout) (pitch ldy2 >= cout, a multiple of 8) — the RRDB's third block
+ * writes the next RRDB's outer residual there, and y2 may be r2 itself (each element is read before it is overwritten, by the same lane);
+ * y2 overlapping x: LD_ERR_ARG. */
 int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
                       float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream);
+int ld_op_esrgan_conv_y2(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off,
+                         int cout, float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* y2, int ldy2, void* stream);
 /* TAESD's 64 -> 64 convolution (stride 1, pad 1) on the same halo-tile main loop under its own epilogue (Block, LD.py:695-702):
  *   y[n][h][w][64] = relu?(conv3x3(x; wt) + bias? + residual?)     (fp32, one rounding at the store)
  * x, residual, y: fp16 NHWC of pitch 64; wt [64][9 * 64] as ld_op_repack_conv writes it; bias, residual may be NULL.  (h, w) is the output
@@ -416,7 +421,9 @@ int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, 
 const char* ld_op_last_kernel(void);
 /* EVERY launch of the calling thread's last ld_op_* call, in launch order and joined with ';', under the names the executors' launch tables
  * (ld_unet_profile_launches) print: the contractions as above, and the norm and boundary launches ("gn_stats_kernel+gn_finalize_kernel",
- * "gn_apply_kernel", "timestep_embed_kernel", "small_conv_in_kernel", "dup_halves_kernel", ...).  Operators outside the UNet's forward leave it "". */
+ * "gn_apply_kernel", "timestep_embed_kernel", "small_conv_in_kernel", "dup_halves_kernel", ...); ld_op_esrgan_conv / _first / _last and
+ * ld_op_taesd_conv / _first / _last the names of ld_esrgan_profile_launches / ld_taesd_profile_launches ("esrgan_conv_kernel<64,up>",
+ * "taesd_first_kernel").  Operators outside the four executors' forwards leave it "". */
 const char* ld_op_last_launches(void);
 /* The merge kernel of ld_unet_patch_param on a plain row-major matrix: dst[rows][cols] = round_fp16(float(base) + sum_j scale_j up_j down_j);
  * dst may alias base.  Also what the host's text model patches its weights with. */

@@ -134,6 +134,7 @@ SIGNATURES = {
     "ld_op_linear_ln_geglu": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "ld_op_bislerp": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_esrgan_conv": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P]),
+    "ld_op_esrgan_conv_y2": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _F, _P, _I, _F, _P, _I, _F, _P, _I, _P]),
     "ld_op_taesd_conv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     "ld_op_esrgan_first": (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "ld_op_esrgan_last": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P]),

@@ -637,8 +637,9 @@ int ld_op_lora_merge(const void* base_f16, void* dst_f16, int rows, int cols, co
     return lora_merge_launch(a, (hipStream_t)stream);
 }
 
-int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
-                      float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream) {
+// the 21-argument entry point every earlier caller has, and the same with the second store (y2, ldy2) that only the RRDB's third block uses
+int ld_op_esrgan_conv_y2(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off,
+                         int cout, float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* y2, int ldy2, void* stream) {
     op_begin();
     EsrganConvArgs a;
     a.x = (const half_t*)x; a.ldx = ldx; a.cin = cin;
@@ -648,14 +649,21 @@ int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int 
     a.slope = slope;
     a.r1 = (const half_t*)r1; a.ldr1 = ldr1; a.s1 = s1;
     a.r2 = (const half_t*)r2; a.ldr2 = ldr2; a.s2 = s2;
-    return noted(esrgan_conv_launch(a, (hipStream_t)stream), esrgan_last_kernel_name());
+    a.y2 = (half_t*)y2; a.ldy2 = ldy2;
+    const int st = esrgan_conv_launch(a, (hipStream_t)stream);
+    return noted(launched(st, esrgan_last_kernel_name()), esrgan_last_kernel_name());
+}
+
+int ld_op_esrgan_conv(const void* x, int ldx, int cin, int n, int h, int w, int up, const void* wt, const void* bias, void* y, int ldy, int c_off, int cout,
+                      float slope, const void* r1, int ldr1, float s1, const void* r2, int ldr2, float s2, void* stream) {
+    return ld_op_esrgan_conv_y2(x, ldx, cin, n, h, w, up, wt, bias, y, ldy, c_off, cout, slope, r1, ldr1, s1, r2, ldr2, s2, nullptr, 0, stream);
 }
 
 int ld_op_taesd_conv(const void* x, int n, int h, int w, int up, const void* wt, const void* bias, const void* residual, int relu, void* y, void* stream) {
     op_begin();
-    return noted(taesd_conv_launch((const half_t*)x, n, h, w, up, (const half_t*)wt, (const half_t*)bias, (const half_t*)residual, relu, (half_t*)y,
-                                   (hipStream_t)stream),
-                 taesd_last_kernel_name());
+    const int st = taesd_conv_launch((const half_t*)x, n, h, w, up, (const half_t*)wt, (const half_t*)bias, (const half_t*)residual, relu, (half_t*)y,
+                                     (hipStream_t)stream);
+    return noted(launched(st, taesd_last_kernel_name()), taesd_last_kernel_name());
 }
 
 // the 3- and 4-channel end convolutions of the upscaler and the preview decoder alone: for parity tests (the launchers the executors call).
@@ -664,28 +672,28 @@ int ld_op_esrgan_first(const float* x, const void* wt, const void* bias, void* y
     const int st = esrgan_first_launch(x, (const half_t*)wt, (const half_t*)bias, (half_t*)y, ldy, (half_t*)y2, ldy2, n, h, w, (hipStream_t)stream);
     if (st != LD_OK) return st;
     op_begin();
-    return noted(st, "esrgan_first_kernel");
+    return noted(launched(st, "esrgan_first_kernel"), "esrgan_first_kernel");
 }
 
 int ld_op_esrgan_last(const void* x, int ldx, const void* wt, const void* bias, float* out, int n, int h, int w, void* stream) {
     const int st = esrgan_last_launch((const half_t*)x, ldx, (const half_t*)wt, (const half_t*)bias, out, n, h, w, (hipStream_t)stream);
     if (st != LD_OK) return st;
     op_begin();
-    return noted(st, "esrgan_last_kernel");
+    return noted(launched(st, "esrgan_last_kernel"), "esrgan_last_kernel");
 }
 
 int ld_op_taesd_first(const float* x, const void* wt, const void* bias, void* y, int n, int h, int w, void* stream) {
     const int st = taesd_first_launch(x, (const half_t*)wt, (const half_t*)bias, (half_t*)y, n, h, w, (hipStream_t)stream);
     if (st != LD_OK) return st;
     op_begin();
-    return noted(st, "taesd_first_kernel");
+    return noted(launched(st, "taesd_first_kernel"), "taesd_first_kernel");
 }
 
 int ld_op_taesd_last(const void* x, const void* wt, const void* bias, float* out_f32, void* out_u8, int n, int h, int w, void* stream) {
     const int st = taesd_last_launch((const half_t*)x, (const half_t*)wt, (const half_t*)bias, out_f32, (uint8_t*)out_u8, n, h, w, (hipStream_t)stream);
     if (st != LD_OK) return st;
     op_begin();
-    return noted(st, "taesd_last_kernel");
+    return noted(launched(st, "taesd_last_kernel"), "taesd_last_kernel");
 }
 
 int ld_op_tile_blend(const float* ps, const float* my, const float* mx, int th, int tw, float* out, float* div, int oh, int ow, int y0, int x0, int c,

@@ -597,10 +597,12 @@ def esrgan_last(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor) -> torch.
     return out
 
 
-def taesd_first(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
-    """TAESD's clamp + first convolution + ReLU: latent fp32 [n,h,w,4] -> fp16 [n,h,w,64]."""
+def taesd_first(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """TAESD's clamp + first convolution + ReLU: latent fp32 [n,h,w,4] -> fp16 [n,h,w,64] (a new tensor, or the caller's y)."""
     n, h, w, _ = x.shape
-    y = torch.empty(n, h, w, 64, dtype=torch.float16, device=x.device)
+    if y is None:
+        y = torch.empty(n, h, w, 64, dtype=torch.float16, device=x.device)
+    assert y.dtype == torch.float16 and tuple(y.shape) == (n, h, w, 64)
     check(lib().ld_op_taesd_first(_p(x), _p(wt), _p(bias), _p(y), n, h, w, _stream()), "ld_op_taesd_first")
     return y
 
@@ -612,6 +614,31 @@ def taesd_last(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, image: boo
     img = torch.empty(n, h, w, 3, dtype=torch.uint8, device=x.device) if image else None
     check(lib().ld_op_taesd_last(_p(x), _p(wt), _p(bias), _p(out), _p(img), n, h, w, _stream()), "ld_op_taesd_last")
     return out, img
+
+
+# ------------------------------------------------------------------ the halo-tile 64-channel convolutions of the upscaler and the preview decoder
+# One call = one launch of the executors (esrgan.hip esrgan_run, taesd.hip taesd_run), on caller-owned NHWC fp16 buffers that the call writes
+# in place where the executor does: the dense block's append into its own input buffer, the second store over a residual.
+def esrgan_conv(x: torch.Tensor, cin: int, wt: torch.Tensor, bias: Optional[torch.Tensor], y: torch.Tensor, c_off: int, cout: int,
+                slope: float = 0.0, r1: Optional[torch.Tensor] = None, s1: float = 1.0, r2: Optional[torch.Tensor] = None, s2: float = 1.0,
+                y2: Optional[torch.Tensor] = None, up: bool = False) -> torch.Tensor:
+    """One conv_block of RRDBNet: channels [0, cin) of x [n,hs,ws,ldx] -> channels [c_off, c_off + cout) of y [n,h,w,ldy] (y may be x itself when
+    c_off >= cin), v = lrelu(conv + bias, slope) (slope 0: none), then s1 v + r1, then s2 v + r2 (the first cout channels of r1 / r2), and the
+    same values into channels [0, cout) of y2 (which may be r2).  up: x is [n,h/2,w/2,ldx], read through a nearest-2x upsampling."""
+    n, h, w, ldy = y.shape
+    ld = lambda t: 0 if t is None else t.shape[-1]
+    check(lib().ld_op_esrgan_conv_y2(_p(x), x.shape[-1], cin, n, h, w, int(up), _p(wt), _p(bias), _p(y), ldy, c_off, cout, slope, _p(r1), ld(r1), s1,
+                                     _p(r2), ld(r2), s2, _p(y2), ld(y2), _stream()), "ld_op_esrgan_conv_y2")
+    return y
+
+
+def taesd_conv(x: torch.Tensor, wt: torch.Tensor, bias: Optional[torch.Tensor], y: torch.Tensor, residual: Optional[torch.Tensor] = None,
+               relu: bool = False, up: bool = False) -> torch.Tensor:
+    """One convolution of a TAESD Block, or the one behind an nn.Upsample: x [n,hs,ws,64] -> y [n,h,w,64] = relu?(conv + bias? + residual?), written
+    into the caller's y (the executor's rotating buffers); up: x is [n,h/2,w/2,64], read through a nearest-2x upsampling."""
+    n, h, w, _ = y.shape
+    check(lib().ld_op_taesd_conv(_p(x), n, h, w, int(up), _p(wt), _p(bias), _p(residual), int(relu), _p(y), _stream()), "ld_op_taesd_conv")
+    return y
 
 
 # ------------------------------------------------------------------ 8-bit image ops (image.hip): UltimateSDUpscale's tile plumbing

@@ -17,36 +17,49 @@ def n_upconvs(scale: int) -> int:
     return int(scale).bit_length() - 1
 
 
-def dense_block(sd, prefix: str, x: torch.Tensor) -> torch.Tensor:
+def _same(t: torch.Tensor) -> torch.Tensor:
+    return t
+
+
+def half_round(t: torch.Tensor) -> torch.Tensor:
+    return t.half().to(t.dtype)
+
+
+def dense_block(sd, prefix: str, x: torch.Tensor, rnd=_same) -> torch.Tensor:
     feats = [x]
     for k in range(1, 6):
-        y = F.conv2d(torch.cat(feats, 1), sd[f"{prefix}.conv{k}.0.weight"], sd[f"{prefix}.conv{k}.0.bias"], padding=1)
+        y = rnd(F.conv2d(torch.cat(feats, 1), sd[f"{prefix}.conv{k}.0.weight"], sd[f"{prefix}.conv{k}.0.bias"], padding=1))
         if k < 5:
-            feats.append(F.leaky_relu(y, 0.2))
+            feats.append(rnd(F.leaky_relu(y, 0.2)))
     return y * 0.2 + x
 
 
-def rrdbnet(sd, x_nhwc: torch.Tensor, nb: int, scale: int, dtype=torch.float32, channels_last: bool = False) -> torch.Tensor:
-    """sd: old-arch keys; x_nhwc [B, H, W, 3] -> [B, H s, W s, 3] (unclamped) in `dtype` on x's device."""
+def rrdbnet(sd, x_nhwc: torch.Tensor, nb: int, scale: int, dtype=torch.float32, channels_last: bool = False, emulate_fp16: bool = False) -> torch.Tensor:
+    """sd: old-arch keys; x_nhwc [B, H, W, 3] -> [B, H s, W s, 3] (unclamped) in `dtype` on x's device.
+    emulate_fp16: the emulation the fixtures' `emul_rel_l2` was measured with (tools/make_upscale_golden.py): weights, the input and every
+    Conv2d / LeakyReLU output rounded to fp16 — where the device path rounds — and everything else in `dtype`."""
     dev = x_nhwc.device
-    sd = {k: v.to(dev, dtype) for k, v in sd.items()}
+    rnd = half_round if emulate_fp16 else _same
+    sd = {k: rnd(v.to(dev, dtype)) for k, v in sd.items()}
+    x_nhwc = rnd(x_nhwc.to(dtype))
     if channels_last:
         sd = {k: (v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v) for k, v in sd.items()}
     x = x_nhwc.to(dtype).permute(0, 3, 1, 2)
     x = x.contiguous(memory_format=torch.channels_last) if channels_last else x.contiguous()
-    conv = lambda t, p: F.conv2d(t, sd[p + ".weight"], sd[p + ".bias"], padding=1)
+    conv = lambda t, p: rnd(F.conv2d(t, sd[p + ".weight"], sd[p + ".bias"], padding=1))
+    lrelu = lambda t: rnd(F.leaky_relu(t, 0.2))
     fea = conv(x, "model.0")
     t = fea
     for b in range(nb):
         r = t
         for j in (1, 2, 3):
-            r = dense_block(sd, f"model.1.sub.{b}.RDB{j}", r)
+            r = dense_block(sd, f"model.1.sub.{b}.RDB{j}", r, rnd)
         t = r * 0.2 + t
     t = fea + conv(t, f"model.1.sub.{nb}")
     n_up = n_upconvs(scale)
     for u in range(n_up):
-        t = F.leaky_relu(conv(F.interpolate(t, scale_factor=2, mode="nearest"), f"model.{3 * (u + 1)}"), 0.2)
-    t = F.leaky_relu(conv(t, f"model.{3 * n_up + 2}"), 0.2)
+        t = lrelu(conv(F.interpolate(t, scale_factor=2, mode="nearest"), f"model.{3 * (u + 1)}"))
+    t = lrelu(conv(t, f"model.{3 * n_up + 2}"))
     return conv(t, f"model.{3 * n_up + 4}").permute(0, 2, 3, 1).contiguous()
 
 

@@ -20,7 +20,7 @@ from lightdiffusion_amd._lib import ERR_ARG, ERR_SHAPE, OK, lib
 
 pytestmark = pytest.mark.gpu
 # the kernels of esrgan.hip this module holds (tests/test_errbound_cpu.py keeps the ledger; the end convolutions: tests/test_end_convs_gpu.py, the blend: tests/test_blend_gpu.py)
-KERNELS = {"esrgan_conv_kernel": ["test_dense_conv_in_place", "test_conv5_residuals", "test_upconv_nearest2x"]}
+KERNELS = {"esrgan_conv_kernel": ["test_dense_conv_in_place", "test_conv5_residuals", "test_conv5_second_store", "test_upconv_nearest2x"]}
 
 TILE_H, TILE_W = 16, 32
 SIZES = [(1, 5, 7), (1, 8, 32), (1, 32, 8), (1, 33, 47), (2, 9, 11)]
@@ -71,6 +71,13 @@ def _call(x, ldx, cin, n, h, w, up, wr, b, y, ldy, c_off, cout, slope, r1=None, 
                                    _stream())
 
 
+def _call_y2(x, ldx, cin, n, h, w, up, wr, b, y, ldy, c_off, cout, slope, r1=None, ldr1=0, s1=1.0, r2=None, ldr2=0, s2=1.0, y2=None, ldy2=0):
+    """The same call with the second store (ld_op_esrgan_conv_y2)."""
+    p = lambda t: None if t is None else t.data_ptr()
+    return lib().ld_op_esrgan_conv_y2(p(x), ldx, cin, n, h, w, int(up), p(wr), p(b), p(y), ldy, c_off, cout, slope, p(r1), ldr1, s1, p(r2), ldr2, s2,
+                                      p(y2), ldy2, _stream())
+
+
 @pytest.mark.parametrize("n,h,w", SIZES)
 @pytest.mark.parametrize("cin", [64, 96, 128, 160, 192])
 def test_dense_conv_in_place(cin, n, h, w):
@@ -110,6 +117,29 @@ def test_conv5_residuals(two, n, h, w):
 
 
 @pytest.mark.parametrize("n,h,w", SIZES)
+def test_conv5_second_store(n, h, w):
+    """conv5 of an RRDB's third block: R1 + R2 and the second store y2 (halo_conv.h: the same packed values at pitch ldy2) — first into a
+    buffer of its own, then over R2 itself, the executor's aliasing (r2 == y2 == the RRDB's input): every lane reads its R2 elements before it
+    overwrites them, so the result is the same y and R2 holds y afterwards."""
+    x, wt, b = _operands(192, 64, n, h, w, 400 + h)
+    wr = _repack(wt)
+    r2 = torch.randn(n, h, w, 64, generator=torch.Generator().manual_seed(6)).half().cuda()
+    y = torch.zeros(n, h, w, 192, dtype=torch.float16, device="cuda")
+    y2 = torch.full((n, h, w, 64), -7.25, dtype=torch.float16, device="cuda")
+    st = _call_y2(x, 192, 192, n, h, w, False, wr, b, y, 192, 0, 64, 0.0, x, 192, 0.2, r2, 64, 0.2, y2, 64)
+    assert st == OK and lib().ld_op_last_kernel().decode() == "esrgan_conv_kernel<64>"
+    ref, bound = dense_conv_ref(x, wt, b, 0.0, [(0.2, x[..., :64]), (0.2, r2)])
+    check(y[..., :64].reshape(-1, 64), ref, bound, f"conv5 R1+R2 with y2 at {n}x{h}x{w}", image_rows=h * w, width=w)
+    assert torch.equal(y2.view(torch.int16), y[..., :64].contiguous().view(torch.int16)), "y2 is not y[..., :64] bit for bit"
+    assert not bool(y[..., 64:].any())
+    ya = torch.zeros_like(y)
+    alias = r2.clone()
+    assert _call_y2(x, 192, 192, n, h, w, False, wr, b, ya, 192, 0, 64, 0.0, x, 192, 0.2, alias, 64, 0.2, alias, 64) == OK
+    assert torch.equal(ya.view(torch.int16), y.view(torch.int16)), "y2 == r2 changed y"
+    assert torch.equal(alias.view(torch.int16), y2.view(torch.int16)), "r2 does not hold y after the aliased call"
+
+
+@pytest.mark.parametrize("n,h,w", SIZES)
 def test_upconv_nearest2x(n, h, w):
     """upconv_block: the source is (h, w), the output (2h, 2w): halo pixel (y, x) <- source (y >> 1, x >> 1); LeakyReLU 0.2."""
     x, wt, b = _operands(64, 64, n, h, w, 300 + h)
@@ -135,4 +165,18 @@ def test_arguments_are_checked_before_any_launch():
     assert call(cout=16) == ERR_SHAPE and call(cout=48) == ERR_SHAPE
     assert call(ldx=32) == ERR_SHAPE and call(c_off=40) == ERR_SHAPE and call(ldy=60) == ERR_SHAPE
     assert call(h=0) == ERR_SHAPE and call(up=True) == ERR_SHAPE                                      # odd output size behind a 2x upsampling
+    torch.cuda.synchronize()
+
+
+def test_second_store_arguments_are_checked_before_any_launch():
+    x, wt, b = _operands(64, 32, 1, 5, 7, 1)
+    wr = _repack(wt)
+    buf = torch.zeros(1, 5, 7, 192, dtype=torch.float16, device="cuda")
+    y = torch.zeros(1, 5, 7, 64, dtype=torch.float16, device="cuda")
+    y2 = torch.zeros(1, 5, 7, 64, dtype=torch.float16, device="cuda")
+    call = lambda **k: _call_y2(**{**dict(x=buf, ldx=192, cin=64, n=1, h=5, w=7, up=False, wr=wr, b=b, y=y, ldy=64, c_off=0, cout=32, slope=0.2), **k})
+    assert call() == OK and call(y2=y2, ldy2=64) == OK and call(y2=y2, ldy2=32) == OK
+    assert call(y2=y2, ldy2=24) == ERR_SHAPE and call(y2=y2, ldy2=36) == ERR_SHAPE                      # ldy2 < cout; ldy2 & 7
+    assert call(y2=buf, ldy2=192) == ERR_ARG and call(y2=buf[:, :, :, 64:], ldy2=192) == ERR_ARG         # y2 overlapping x
+    assert lib().ld_op_last_kernel().decode() == ""
     torch.cuda.synchronize()

@@ -65,3 +65,29 @@ def test_restatement_reproduces_the_reference(name):
     assert y.shape == g["y"].shape
     assert rel_l2(y, g["y"]) < 1e-5
     assert 1e-4 < float(g["emul_rel_l2"]) < 5e-3
+
+
+@pytest.mark.parametrize("name", ["esrgan_x2_nb1", "esrgan_x4_nb2"])
+def test_fp16_emulation_mode_reproduces_the_fixtures_emulation(name):
+    """rrdbnet(emulate_fp16=True) rounds where the fixtures' emulation rounded (weights, input, every Conv2d / LeakyReLU output): its distance from
+    the reference's fp32 output is the fixture's own `emul_rel_l2` up to fp32 summation noise — the allowance the chain tests derive from this
+    mode for the scales that have no fixture (tests/test_esrgan_chain_gpu.py) is measured the way the fixtures' was."""
+    g = load_golden(name)
+    nb, scale = int(g["nb"]), int(g["scale"])
+    sd = _sd(nb, scale, int(g["weight_seed"]))
+    mine, stored = rel_l2(ER.rrdbnet(sd, g["x"], nb, scale, emulate_fp16=True), g["y"]), float(g["emul_rel_l2"])
+    print(f"{name}: emulation rel-L2 {mine:.6e}, the fixture's emul_rel_l2 {stored:.6e}")
+    assert abs(mine - stored) <= 1e-2 * stored, (mine, stored)
+    assert rel_l2(ER.rrdbnet(sd, g["x"], nb, scale), g["y"]) < 1e-5          # the default mode is untouched
+
+
+@pytest.mark.parametrize("nb,scale,shape", [(1, 1, (2, 6, 10)), (1, 1, (1, 17, 9)), (1, 8, (1, 3, 5))])
+def test_fp16_emulation_distance_at_the_scales_without_a_fixture(nb, scale, shape):
+    """The same measurement at scale 1 and scale 8, on the chain tests' shapes: of the order the fixtures store (rand images in [0, 1])."""
+    sd = _sd(nb, scale)
+    x = torch.rand(*shape, 3, generator=torch.Generator().manual_seed(7))
+    y = ER.rrdbnet(sd, x, nb, scale)
+    assert tuple(y.shape) == (shape[0], shape[1] * scale, shape[2] * scale, 3)
+    e = rel_l2(ER.rrdbnet(sd, x, nb, scale, emulate_fp16=True), y)
+    print(f"x{scale} nb{nb} {shape}: emulation rel-L2 {e:.3e}")
+    assert 1e-4 < e < 5e-3
