@@ -60,6 +60,10 @@ __device__ __forceinline__ uint4 add8h(uint4 a, uint4 b) {
 }
 
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
+// The same on a value read back from a staged fp16 tile, which may be -inf (a pre-activation below -65504 overflowed in the tile): -inf / (1 + inf)
+// is NaN, the true value is -0, and the direct-store path (fp32 throughout) returns -0.  The numerator clamped at -FLT_MAX gives -0 there and is
+// bit-identical for every finite x (one v_max_f32 more per value); +inf stays +inf, NaN stays NaN (through the exponential).
+__device__ __forceinline__ float silu_tile_f(float x) { return fmaxf(x, -3.402823466e+38f) / (1.0f + __expf(-x)); }
 // exact (erf) GELU, as torch.nn.functional.gelu default used by the reference's GEGLU (LD.py:4513-4515):
 //   gelu(x) = x Phi(x) = max(x, 0) - |x| Phi(-|x|),   Phi(-z) = 2^P(z) on z = min(|x|, 6)
 // with P a degree-6 minimax fit of log2 Phi(-z) weighted for the absolute error of z Phi(-z) (tools/fit_gelu.py: max |error| 5.1e-7 over
@@ -72,6 +76,9 @@ __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)
 // the GATE half is masked.  A NaN-transparent form (max(x, 0) as 0.5 (x + |x|)) costs one more vector instruction per value in an epilogue
 // that is vector-issue bound; the activations of this path are finite by construction (fp16 storage would have turned an overflow into inf,
 // which both forms handle alike: gelu(+inf) = +inf, gelu(-inf) = -0).
+// The store policy as tests/test_adverse_routes_gpu.py::test_overflow_policy holds it: a stage past 65520 stores +-inf with that stage's sign, and
+// a later finite add keeps it; an activation absorbs a tile that overflowed to -inf into its true value there, -0 (gelu above, silu_tile_f /
+// quick_gelu_tile_f); there is no NaN without an infinite operand.
 #define LD_GELU_ZMAX 6.0f
 #define LD_GELU_C0 -0.999993086f
 #define LD_GELU_C1 -1.15120173f
@@ -164,6 +171,7 @@ __device__ __forceinline__ void geglu8_staged_f32(const f32x2 (&af)[4], const f3
 
 // quick_gelu of the CLIP MLP: a * sigmoid(1.702 a)  (ACTIVATIONS, LD.py:4296-4299)
 __device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.0f + __expf(-1.702f * x)); }
+__device__ __forceinline__ float quick_gelu_tile_f(float x) { return fmaxf(x, -3.402823466e+38f) / (1.0f + __expf(-1.702f * x)); }   // as silu_tile_f
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -172,8 +172,8 @@ __device__ __forceinline__ void v5_epilogue_strip(const GemmParams& p, half_t* C
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float t = v[j] + b[j] + bm + e[j];
-                if (p.act == 1) t = silu_f(t);
-                else if (p.act == 3) t = quick_gelu_f(t);
+                if (p.act == 1) t = silu_tile_f(t);
+                else if (p.act == 3) t = quick_gelu_tile_f(t);
                 v[j] = t + r[j];
             }
             const uint4 packed = pack8(v);
@@ -437,8 +437,8 @@ __device__ __forceinline__ void v6_finish(const GemmParams& p, f32x4 (&acc)[TM][
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 float t = v[j] + b[j] + bm + e[j];
-                if (p.act == 1) t = silu_f(t);
-                else if (p.act == 3) t = quick_gelu_f(t);
+                if (p.act == 1) t = silu_tile_f(t);
+                else if (p.act == 3) t = quick_gelu_tile_f(t);
                 v[j] = t + r[j];
             }
             if ((TOT % 64 == 0 || q0 < TOT) && m_base + row < p.M && n_w + cc * 8 < p.n_valid) {

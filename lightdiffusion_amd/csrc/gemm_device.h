@@ -249,8 +249,8 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const half_t*
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         float t = v[j] + b[j] + bm + e[j];
-                        if (p.act == 1) t = silu_f(t);
-                        else if (p.act == 3) t = quick_gelu_f(t);
+                        if (p.act == 1) t = silu_tile_f(t);
+                        else if (p.act == 3) t = quick_gelu_tile_f(t);
                         v[j] = t + r[j];
                     }
                     const uint4 packed = pack8(v);

@@ -49,6 +49,21 @@ def rtn_noise(n: float) -> float:
     return 4.0 * U / math.sqrt(3.0 * max(1.0, n))
 
 
+def rtn_noise_weighted(mags: torch.Tensor, ref: torch.Tensor, floor_frac: float = 1e-3) -> float:
+    """rtn_noise for an output whose roundings are NOT relative to |y_hat|: element i carries independent round-to-nearest errors of values of
+    magnitude mags_i in total (each uniform within +-U of its value: standard deviation at most U mags_i / sqrt(3)), so the bias statistic
+    sum(e_i sign_i) / sum|y_hat_i| over the kept elements has standard deviation U / sqrt(3) * sqrt(sum mags_i^2) / sum|y_hat_i|; four of
+    them.  With mags = |y_hat| this is rtn_noise(n_eff) of independent_roundings' n_eff.  It is what a residual that cancels the contraction
+    needs (tests/adverse.py cancel: the packed adds round relative to |pre| = 8 |y_hat|) and what heavy-tailed outputs need (few elements carry
+    the sum)."""
+    a = ref.double().abs().flatten()
+    m = mags.double().abs().flatten().to(a.device)
+    k = a > floor_frac * float(a.max())
+    if int(k.sum()) == 0:
+        return 0.0
+    return float(4.0 * U / math.sqrt(3.0) * (m[k] * m[k]).sum().sqrt() / a[k].sum())
+
+
 def independent_roundings(ref: torch.Tensor, keep: torch.Tensor | None = None, floor_frac: float = 1e-3) -> float:
     """The n of rtn_noise for an output.  The bias statistic is the |y_hat|-weighted mean of the kept elements' relative rounding errors, and equal
     values round equally, so its chance level is that of  n_eff = (sum W_v)^2 / sum W_v^2  independent errors, W_v the summed |y_hat| of each
@@ -156,14 +171,20 @@ def _act(t: torch.Tensor, act: str) -> torch.Tensor:
     return t
 
 
-def epilogue_ref(acc, absdot, K, bias=None, residual=None, alpha=1.0, act="none", extra=None, rowvec=None):
+def epilogue_ref(acc, absdot, K, bias=None, residual=None, alpha=1.0, act="none", extra=None, rowvec=None, staged_subnormal=True):
     """y_hat and its element bound for y = act(alpha * acc + bias) + residual (act 'geglu': acc / absdot hold [value | gate] halves).
-    acc, absdot: fp64 A W^T and |A| |W|^T; `extra`: an fp64 tensor of further input-side error of acc (e.g. a rounded normalised operand)."""
+    acc, absdot: fp64 A W^T and |A| |W|^T; `extra`: an fp64 tensor of further input-side error of acc (e.g. a rounded normalised operand).
+    The staged fp16 tile rounds to 2^-11 |pre| in fp16's normal range and to 2^-25 ABSOLUTE below 2^-14, where 2^-11 |pre| is less than that:
+    the tile's term is max(2^-11 |pre|, 2^-25) — unchanged for every |pre| >= 2^-14.  It matters where something multiplies the staged value
+    afterwards: a GEGLU whose value half is subnormal times a gate of several hundred (tests/test_adverse_cpu.py holds that the bound is wrong
+    without it and still rejects a tile flushed to zero with it).  staged_subnormal=False: the bound without that floor (that control only)."""
     e_acc = c_acc(K) * absdot * abs(alpha)
     if extra is not None:
         e_acc = e_acc + extra * abs(alpha)
     pre = alpha * acc + (0.0 if bias is None else bias.double())
     e_pre = e_acc + (U + 2.0 ** -23) * ((alpha * acc).abs() + pre.abs())      # the staged fp16 tile (and an fp16 bias add)
+    if staged_subnormal:
+        e_pre = e_pre + (2.0 ** -25 - U * pre.abs()).clamp_min(0.0)
     if act == "geglu":
         n2 = pre.shape[-1] // 2
         a, g = pre[..., :n2], pre[..., n2:]

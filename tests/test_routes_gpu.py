@@ -378,8 +378,9 @@ GN_CONV_ROUTES = [
 
 @pytest.mark.parametrize("n,h,w,c1,c2,cout,route", GN_CONV_ROUTES, ids=lambda v: str(v))
 def test_groupnorm_conv_route(ops, n, h, w, c1, c2, cout, route):
-    """conv3x3(SiLU(GroupNorm32(cat(x1, x2)))) + bias: the loader rounds the normalised, activated operand to fp16 once, so the bound
-    adds 2^-11 |SiLU(GN(x))| |W|^T (and the fp32 statistics' error, far below it) to the linear bound."""
+    """conv3x3(SiLU(GroupNorm32(cat(x1, x2)))) + bias against errbound.gn_silu_conv_ref: the loader rounds the normalised, activated operand to fp16
+    once, and the operand's error — that rounding and the fp32 statistics' share, cancellation term included — comes from groupnorm_ref's model
+    and reaches the output as im2col(e_a) |W|^T (tests/test_adverse_routes_gpu.py runs the same rows where the statistics' share is visible)."""
     C = c1 + c2
     x = r16((n, h, w, c1), 41, 1.0, 0.3)
     x2 = r16((n, h, w, c2), 42, 2.0, -0.5) if c2 else None
@@ -388,17 +389,7 @@ def test_groupnorm_conv_route(ops, n, h, w, c1, c2, cout, route):
     b = r16((cout,), 46, 0.5)
     y = ops.group_norm_silu_conv2d(x, gamma, beta, 1e-5, ops.repack_conv_weight(wt), b, x2=x2)
     assert ops.last_kernel().endswith(route)
-    xin = (x if x2 is None else torch.cat([x, x2], -1)).double()
-    g = xin.reshape(n, h * w, 32, C // 32)
-    mu = g.mean(dim=(1, 3), keepdim=True)
-    var = ((g - mu) ** 2).mean(dim=(1, 3), keepdim=True)
-    xn = ((g - mu) / torch.sqrt(var + 1e-5)).reshape(n, h, w, C) * gamma.double() + beta.double()
-    xn = xn * torch.sigmoid(xn)
-    cols = EB.im2col(xn, 3)
-    wm = wt.double().reshape(cout, -1)
-    acc = cols @ wm.t()
-    absdot = cols.abs() @ wm.abs().t()
-    ref, bound = EB.epilogue_ref(acc, absdot, 9 * C, b, None, extra=(EB.U + 1e-5) * absdot)
+    ref, bound = EB.gn_silu_conv_ref(x, gamma, beta, 1e-5, wt, b, x2=x2)
     EB.check(y.reshape(-1, cout), ref, bound, f"{route} n{n} {h}x{w} c{c1}+{c2}->{cout}", image_rows=h * w, width=w)
 
 

@@ -59,38 +59,41 @@ def inputs(name):
 
 
 class Side:
-    """One config: the executor's handle, the chain, and per case the chain's output and taps (computed once, never changed)."""
+    """One config and weight source: the executor's handle, the chain, and per case the chain's output and taps (computed once, never changed).
+    source: a WeightSource for both (None: the synthetic checkpoint); cases / inputs_of: another case table and its inputs (None: CASES / inputs)."""
 
-    def __init__(self, tag):
-        from lightdiffusion_amd.unet import synthetic_unet
+    def __init__(self, tag, source=None, cases=None, inputs_of=None):
+        from lightdiffusion_amd.unet import MI355XUNet, synthetic_unet
         from unet_chain import UNetChain
         self.tag, self.cfg = tag, config(tag)
-        mine = [c for c in CASES.values() if c[0] == tag]
-        self.unet = synthetic_unet(self.cfg, max_batch=max((2 if c[4] == "pair" else 1) * c[1] for c in mine), max_hw=(max(c[2][0] for c in mine), max(c[2][1] for c in mine)),
-                                   max_tokens=max(c[3] for c in mine))
-        self.chain = UNetChain(self.cfg, DEV)
+        self.cases, self.inputs = CASES if cases is None else cases, inputs if inputs_of is None else inputs_of
+        mine = [c for c in self.cases.values() if c[0] == tag]
+        kw = dict(max_batch=max((2 if c[4] == "pair" else 1) * c[1] for c in mine), max_hw=(max(c[2][0] for c in mine), max(c[2][1] for c in mine)),
+                  max_tokens=max(c[3] for c in mine))
+        self.unet = synthetic_unet(self.cfg, **kw) if source is None else MI355XUNet(self.cfg, source, **kw)
+        self.chain = UNetChain(self.cfg, DEV, source=source)
         self._chain_runs = {}
 
     def chain_run(self, name):
         if name not in self._chain_runs:
-            _, _, _, _, mode = CASES[name]
-            x, sigma, ctx = inputs(name)
+            _, _, _, _, mode = self.cases[name]
+            x, sigma, ctx = self.inputs(name)
             self.chain.set_context(ctx)
             out = self.chain.forward(x, sigma, eps_only=mode == "eps", pair=mode == "pair")
             self._chain_runs[name] = (out, self.chain.taps)
         return self._chain_runs[name]
 
     def executor_run(self, name):
-        _, _, _, _, mode = CASES[name]
-        x, sigma, ctx = inputs(name)
+        _, _, _, _, mode = self.cases[name]
+        x, sigma, ctx = self.inputs(name)
         self.unet.set_context(ctx)
         if mode == "pair":
             return self.unet.forward_pair(x, sigma)
         return self.unet.forward(x, sigma, eps_only=mode == "eps")
 
     def executor_table(self, name):
-        _, _, _, _, mode = CASES[name]
-        x, sigma, ctx = inputs(name)
+        _, _, _, _, mode = self.cases[name]
+        x, sigma, ctx = self.inputs(name)
         self.unet.set_context(ctx)
         (self.unet.profile_pair if mode == "pair" else self.unet.profile)(x, sigma)
         return [r[4] for r in self.unet.profile_launches()]

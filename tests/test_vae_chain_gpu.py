@@ -65,31 +65,34 @@ def inputs(name):
 
 
 class Side:
-    """One config: the executor's handle, the chain, and per case the chain's output and taps (computed once, never changed)."""
+    """One config and weight source: the executor's handle, the chain, and per case the chain's output and taps (computed once, never changed).
+    source: a WeightSource for both (None: the synthetic checkpoint); cases: another case table with CASES' names (None: CASES)."""
 
-    def __init__(self, tag):
-        from lightdiffusion_amd.unet import synthetic_vae
+    def __init__(self, tag, source=None, cases=None):
+        from lightdiffusion_amd.unet import MI355XVAE, synthetic_vae
         from vae_chain import VAEChain
         self.tag, self.cfg = tag, config(tag)
-        mine = [c[2] for c in CASES.values() if c[0] == tag]
-        self.vae = synthetic_vae(self.cfg, max_batch=max(s[0] for s in mine), max_hw=(max(s[1] for s in mine), max(s[2] for s in mine)), with_encoder=True)
-        self.chain = VAEChain(self.cfg, DEV, with_encoder=True)
+        self.cases = CASES if cases is None else cases
+        mine = [c[2] for c in self.cases.values() if c[0] == tag]
+        kw = dict(max_batch=max(s[0] for s in mine), max_hw=(max(s[1] for s in mine), max(s[2] for s in mine)), with_encoder=True)
+        self.vae = synthetic_vae(self.cfg, **kw) if source is None else MI355XVAE(self.cfg, source, **kw)
+        self.chain = VAEChain(self.cfg, DEV, with_encoder=True, source=source)
         self._chain_runs = {}
 
     def chain_run(self, name):
         if name not in self._chain_runs:
             x = inputs(name)
-            out = self.chain.decode(x) if CASES[name][1] == "decode" else self.chain.encode_moments(x)
+            out = self.chain.decode(x) if self.cases[name][1] == "decode" else self.chain.encode_moments(x)
             self._chain_runs[name] = (out, self.chain.taps)
         return self._chain_runs[name]
 
     def executor_run(self, name):
         x = inputs(name)
-        return self.vae.decode_device(x) if CASES[name][1] == "decode" else self.vae.encode_moments(x)
+        return self.vae.decode_device(x) if self.cases[name][1] == "decode" else self.vae.encode_moments(x)
 
     def executor_table(self, name):
         x = inputs(name)
-        rows = self.vae.profile_decode(x) if CASES[name][1] == "decode" else self.vae.profile_encode(x)
+        rows = self.vae.profile_decode(x) if self.cases[name][1] == "decode" else self.vae.profile_encode(x)
         return [r[4] for r in rows]
 
 

@@ -77,9 +77,10 @@ class Feat:
 
 
 class UNetChain:
-    def __init__(self, cfg: dict, device="cuda:0", seed: int = 0):
+    def __init__(self, cfg: dict, device="cuda:0", seed: int = 0, source=None):
         from lightdiffusion_amd import ops
         self.ops, self.cfg, self.dev, self.seed = ops, dict(cfg), torch.device(device), seed
+        self.source = source                  # a WeightSource (name, shape -> fp32 master); None: the synthetic checkpoint of `seed`
         self.shapes = W.unet_param_shapes(cfg)
         self.blocks = modules(cfg)
         self.heads = cfg["num_heads"]
@@ -99,6 +100,8 @@ class UNetChain:
 
     # -- weights: the checkpoint's fp32 masters -> fp16, in the layouts the kernels read, by the seam's own operators
     def master(self, name):
+        if self.source is not None:
+            return self.source(name, self.shapes[name])
         return W.synth_tensor(name, self.shapes[name], self.seed)
 
     def _cached(self, key, make):
