@@ -387,7 +387,8 @@ int ld_op_groupnorm(const void* x1, int c1, const void* x2, int c2, int n, int h
 
 int ld_op_layernorm(const void* x, const void* gamma, const void* beta, void* y, int rows, int c, float eps, void* stream) {
     op_begin();
-    return layernorm_launch((const half_t*)x, (const half_t*)gamma, (const half_t*)beta, (half_t*)y, rows, c, eps, (hipStream_t)stream);
+    return launched(layernorm_launch((const half_t*)x, (const half_t*)gamma, (const half_t*)beta, (half_t*)y, rows, c, eps, (hipStream_t)stream),
+                    "layernorm_kernel");
 }
 
 int ld_op_attention(const void* q, int ldq, const void* k, int ldk, const void* vt, int ldvt, void* o, int ldo, int b, int heads,
@@ -752,7 +753,8 @@ int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream) {
 
 int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
     op_begin();
-    return clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream);
+    return launched(clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream),
+                    "clip_embed_kernel");
 }
 
 }  // extern "C"

@@ -14,6 +14,13 @@ source(model): weights.synth_tensor with
 The convolutions that are linear in the stream (upsample.conv, downsample.conv, .op, nin_shortcut, skip_connection, proj_out) keep their synthetic
 scale: the same gain on them compounds to 1e8 and beyond.  GAIN is fixed by tests/test_adverse_cpu.py: the fp32 oracle's peak |activation| on the
 tiny cases lies in [2^13, 2^15], a factor 2 below fp16's 65504.
+
+source('clip'), the text model: the stream writers are self_attn.out_proj and mlp.fc2 (gain and x 16 rows as above), the norms layer_norm1 / 2 and
+final_layer_norm, other biases x 20; the embedding tables keep their synthetic scale except position row 0, which is x 64 — every later query then
+attends to an outlier key 0, so the causal attention sees peaked scores.  A stress profile: no checkpoint is available offline and none of these
+figures measures one.  GAIN['clip'] and CHAIN_GAIN[('clip', *)] are fixed by tests/test_clip_chain_cpu.py::test_adverse_clip_window: the fp32
+oracle's peak over the stages the product stores lies in [2^13, 2^15.5] (tiny x 64: 2.1e4; CLIP-L's width with 2 layers x 64: 1.8e4; the 12 layers
+x 32: 1.7e4 — the stream grows with depth, so the deeper model takes the smaller gain).
 """
 from __future__ import annotations
 
@@ -27,19 +34,21 @@ import torch
 from lightdiffusion_amd import weights as W
 
 # one gain per model (a power of two).  Peaks of the fp32 oracle on fp16-rounded weights with these gains: tests/test_adverse_cpu.py::test_window
-GAIN = {"unet": 16.0, "vae": 128.0}
+GAIN = {"unet": 16.0, "vae": 128.0, "clip": 32.0}
 # the gain of the executor / chain tests (tests/test_adverse_chain_gpu.py) per (model, config).  Their window is asserted on the fp64 references of
 # the stages the executor STORES, and the UNet executor never stores the oracle's hottest stage: ff.net.2 is folded into proj_out (mlp_out_fold).
 # What it stores peaks well below the oracle's figure, so the window [2^13, 2^15.5] — which that test asserts per case, and whose peaks
 # profiles/adverse_parity.json records — needs the next power of two for the tiny config and the one after for SD1.5.  At the tiny gain the fp32
 # oracle's own peak, the unstored stage included, stays below 2^15.5 (tests/test_adverse_cpu.py::test_window_at_the_chain_gain); the SD1.5 oracle
 # was not run on the CPU.
-CHAIN_GAIN = {("unet", "tiny"): 32.0, ("unet", "sd15"): 64.0, ("vae", "tiny"): 128.0, ("vae", "fallback"): 128.0, ("vae", "sd15"): 128.0}
+CHAIN_GAIN = {("unet", "tiny"): 32.0, ("unet", "sd15"): 64.0, ("vae", "tiny"): 128.0, ("vae", "fallback"): 128.0, ("vae", "sd15"): 128.0,
+              ("clip", "tiny"): 64.0, ("clip", "w2"): 64.0, ("clip", "sd15"): 32.0}
 OUTLIER_EVERY, OUTLIER_AT, OUTLIER_GAIN = 37, 5, 16.0
 BIAS_GAIN = 20.0
 
-_STREAM_WRITERS = re.compile(r"\.(conv2|out_layers\.3|to_out\.0|ff\.net\.2)\.weight$")
-_NORM = re.compile(r"(^|\.)(norm\d?|norm_out|in_layers\.0|out_layers\.0|out\.0)\.(weight|bias)$")
+_STREAM_WRITERS = re.compile(r"\.(conv2|out_layers\.3|to_out\.0|ff\.net\.2|self_attn\.out_proj|mlp\.fc2)\.weight$")
+_NORM = re.compile(r"(^|\.)(norm\d?|norm_out|in_layers\.0|out_layers\.0|out\.0|layer_norm\d|final_layer_norm)\.(weight|bias)$")
+POSITION_ROW0_GAIN = 64.0
 
 
 def is_norm(name: str) -> bool:
@@ -47,11 +56,15 @@ def is_norm(name: str) -> bool:
 
 
 def source(model: str, seed: int = 0, gain: float | None = None):
-    """A WeightSource (name, shape -> fp32 tensor) of the adverse network of `model` ('unet' or 'vae')."""
+    """A WeightSource (name, shape -> fp32 tensor) of the adverse network of `model` ('unet', 'vae' or 'clip')."""
     s = GAIN[model] if gain is None else gain
 
     def get(name, shape):
         t = W.synth_tensor(name, tuple(shape), seed)
+        if name.endswith("embedding.weight"):             # the text model's tables: synthetic scale, but position row 0 (every later query attends
+            if "position_embedding" in name:              # to an outlier key 0: the causal kernel sees peaked scores)
+                t[0] = t[0] * POSITION_ROW0_GAIN
+            return t
         if is_norm(name):
             if name.endswith(".weight"):
                 return torch.exp2(1.5 * (t - 1.0) / 0.1)

@@ -5,7 +5,7 @@ network whose residual stream reaches 2^13 .. 2^15, has outlier channels, norm g
 Held per case: the launch list equal entry by entry; torch.equal(executor, chain), also after every other adverse case of the handle (A, B, A);
 every tap on all rows inside the existing bounds with the signed-bias statistic; the producers' partials (inside the stage references); no tap
 output non-finite; and the window — the largest |fp64 stage reference| over all taps lies in [2^13, 2^15.5] (asserted on the references, not on
-the device's outputs).  ESRGAN and TAESD have no normalisation and homogeneous activations, CLIP has no chain: out of scope.
+the device's outputs).  ESRGAN and TAESD have no normalisation and homogeneous activations: out of scope; the text model on its adverse network: tests/test_clip_chain_gpu.py.
 
 Recorded, not asserted (tiny configs): rel-L2 and max-abs of the chain against the fp32 oracle on the same fp16-rounded weights — no derived
 bound exists for a 40-layer fp16 network at these statistics.  With LD_WRITE_PARITY=1 the records go to profiles/adverse_parity.json.

@@ -65,6 +65,8 @@ LINEAR_ADVERSE = _rows(R.LINEAR_ROUTES, [
     (63, 1280, 328, "gemm4_kernel<64,64,plain>"), (128, 1600, 312, "gemm4_kernel<64,160,plain>"), (2040, 640, 632, "gemm3_kernel<64,64,plain>"),
     (4160, 640, 312, "gemm3_kernel<64,160,plain>"), (300, 640, 64, "gemm4_kernel<64,160,plain>"), (16384, 960, 2560, "gemm5_kernel<256,320,plain>"),
     (24576, 640, 1280, "gemm5_kernel<256,320,geglu>"), (48897, 320, 320, "gemm7_kernel<256,K320,plain>"), (48897, 1280, 320, "gemm7_kernel<256,K320,geglu>"),
+    # the text model's fc1 + quick-GELU and fc2 + residual (K = 3072, split over K) at M = 231
+    (231, 3072, 768, "gemm4_kernel<64,128,plain>"), (231, 768, 3072, "gemm4_kernel<64,64,plain>+splitk_reduce_kernel"),
 ], (0, 1, 2, 7))
 LINEAR_CASES = [(row, prof, kind) for row in LINEAR_ADVERSE for prof in ("big", "outlier", "heavy") for kind in (("randn", "cancel") if row[4] else ("none",))]
 

@@ -215,6 +215,16 @@ LINEAR_ROUTES = [
     (48897, 1280, 320, True, False, "geglu", 1.0, "gemm7_kernel<256,K320,geglu>"),
     (4096, 1280, 320, True, False, "geglu", 1.0, "gemm4_kernel<128,160,plain>"),
     (300, 640, 64, True, False, "geglu", 1.0, "gemm4_kernel<64,160,plain>"),
+    # the CLIP-L text model's four contractions (qkv, out-proj + residual, fc1 + quick-GELU, fc2 + residual) at M = 77 B: one prompt, and B = 3
+    # (M = 231 ends 25 rows into its fourth 64-row tile).  Appended: tests/test_adverse_routes_gpu.py names rows of this table
+    (77, 2304, 768, True, False, "none", 1.0, "gemm4_kernel<64,128,plain>"),
+    (77, 768, 768, True, True, "none", 1.0, "gemm4_kernel<64,64,plain>"),
+    (77, 3072, 768, True, False, "quick_gelu", 1.0, "gemm4_kernel<64,128,plain>"),
+    (77, 768, 3072, True, True, "none", 1.0, "gemm4_kernel<64,64,plain>+splitk_reduce_kernel"),
+    (231, 2304, 768, True, False, "none", 1.0, "gemm4_kernel<64,128,plain>"),
+    (231, 768, 768, True, True, "none", 1.0, "gemm4_kernel<64,64,plain>"),
+    (231, 3072, 768, True, False, "quick_gelu", 1.0, "gemm4_kernel<64,128,plain>"),
+    (231, 768, 3072, True, True, "none", 1.0, "gemm4_kernel<64,64,plain>+splitk_reduce_kernel"),
 ]
 
 
@@ -484,5 +494,24 @@ def test_vae_decode_routes_are_pinned():
     rows = v.profile_decode(torch.randn(8, 4, 64, 64))
     seen = {r[-1] for r in rows if _contraction(r[-1])}
     assert seen
+    missing = sorted(seen - route_names())
+    assert not missing, f"dispatched but not pinned by a route row: {missing}"
+
+
+def test_clip_forward_routes_are_pinned():
+    """The same for the text model, whose operator calls come from Python (CLIPTextModelHIP._encode): every contraction the recorder of
+    tests/clip_chain.py sees at CLIP-L's width with B = 1, 2, 3 prompts (M = 77, 154, 231) has a row above."""
+    import clip_chain as C
+    from lightdiffusion_amd import ops as o
+    from lightdiffusion_amd.clip import CLIPTextModelHIP
+    cfg = C.config("w2")
+    tm = CLIPTextModelHIP(cfg, C.state_dict(cfg), device=DEV)
+    seen = set()
+    for B in (1, 2, 3):
+        calls, _ = C.run(o, tm, C.prompts(B))
+        for c in calls:
+            for part in c["launches"].split(";"):
+                seen.update(k for k in [part] + part.split("+") if _contraction(k))
+    assert any(k.startswith("gemm") for k in seen) and any(k.startswith("flash_attn") for k in seen), seen
     missing = sorted(seen - route_names())
     assert not missing, f"dispatched but not pinned by a route row: {missing}"
