@@ -462,6 +462,32 @@ int ld_op_u8_composite(void* canvas, int canvas_pitch, int cw, int ch, const voi
 int ld_op_u8_from_f32(const float* x, void* y, size_t n, void* stream);
 int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream);
 
+/* ---- fp32 image operators (the Detailer's per-segment plumbing, DetailerForEach.do_detail, LD.py:9402-9590, kept on the device).  The canvas is
+ * fp32 HWC and a mask fp32 HW, addressed by a pointer and a row pitch in FLOATS; uint8 images as above, pitch in bytes.  Sides up to 16384,
+ * channels 1 to 4.  Every argument is checked before anything is launched (LD_ERR_ARG: a NULL pointer, a size < 1, a window or origin outside
+ * the canvas; LD_ERR_SHAPE: a pitch below its row, a side or a feather beyond the limits), and no kernel touches memory outside the windows
+ * these arguments describe.
+ *
+ * tensor2pil of the window [y1, y2) x [x1, x2) of the cw x ch canvas: dst[y][x][c] = uint8(clip(255 * v, 0, 255)), one fp32 product, the clip,
+ * a truncation (the arithmetic of ld_op_u8_from_f32).  The window must lie inside the canvas; the canvas is not written. */
+int ld_op_f32_crop_u8(const float* canvas, int canvas_pitch, int cw, int ch, int channels, int x1, int y1, int x2, int y2, void* dst, int dst_pitch,
+                      void* stream);
+/* torchvision's GaussianBlur(kernel_size = 2 * feather + 1) of the w x h mask at src with reflect padding (-k -> k, n - 1 + k -> n - 1 - k): a
+ * pass along x into tmp, then a pass along y into dst, out = sum_j taps[j] * in[reflect(i + j - feather)] with every product and every sum
+ * rounded to fp32 on its own, j ascending from 0 — a result is the same bits run to run.  taps: DEVICE floats [2 * feather + 1], built by the caller
+ * as torchvision builds them (linspace(-feather, feather), exp(-0.5 (x / sigma)^2), divided by their sum, in fp32).  feather 0 is a copy
+ * (hipMemcpy2DAsync, no launch; taps and tmp may be NULL).  LD_ERR_SHAPE: feather >= min(w, h), which reflection cannot serve, or feather >
+ * ld_op_f32_blur_max_feather() = 127, the tap buffer in LDS.  tmp: ld_op_f32_blur_tmp_bytes(w, h) bytes.  dst may be src. */
+int ld_op_f32_blur_max_feather(void);
+size_t ld_op_f32_blur_tmp_bytes(int w, int h);
+int ld_op_f32_gaussian_blur(const float* src, int src_pitch, float* dst, int dst_pitch, int w, int h, int feather, const float* taps, float* tmp,
+                            void* stream);
+/* pil2tensor + tensor_paste in place: canvas[y0 + y][x0 + x][c] = (1 - a) * canvas + a * (tile / 255) with a = alpha[y][x], on the tw x th tile's
+ * window clipped to the cw x ch canvas; the subtraction, the division, the two products and the sum are each rounded to fp32 (no FMA, no
+ * reciprocal).  (x0, y0) must lie inside the canvas; floats outside the clipped window are not touched. */
+int ld_op_f32_paste_u8(float* canvas, int canvas_pitch, int cw, int ch, int channels, const void* tile, int tile_pitch, const float* alpha, int alpha_pitch,
+                       int tw, int th, int x0, int y0, void* stream);
+
 /* ---- CLIP text model input stage with textual-inversion vectors (CLIPEmbeddings + SDClipModel.set_up_textual_embeddings, LD.py:4394-4410, 4642-4690).
  * out[b][l] = round_fp16(float(row(ids[b*L + l])) + float(pos[l])), fp16 [B, L, h].  `table` is the resident fp16 token table [V, h] (EOS = row V-1),
  * `extra` the prompt's E custom vectors, fp32 [E, h] (may be NULL when E == 0), `pos` the fp16 position table (at least L rows of h).

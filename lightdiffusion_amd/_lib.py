@@ -153,6 +153,11 @@ SIGNATURES = {
     "ld_op_u8_composite": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ld_op_u8_from_f32": (_I, [_P, _P, _Z, _P]),
     "ld_op_f32_from_u8": (_I, [_P, _P, _Z, _P]),
+    "ld_op_f32_crop_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "ld_op_f32_blur_max_feather": (_I, []),
+    "ld_op_f32_blur_tmp_bytes": (_Z, [_I, _I]),
+    "ld_op_f32_gaussian_blur": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "ld_op_f32_paste_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_clip_embed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 

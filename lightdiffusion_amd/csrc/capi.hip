@@ -751,6 +751,29 @@ int ld_op_f32_from_u8(const void* x, float* y, size_t n, void* stream) {
     return f32_from_u8_launch((const uint8_t*)x, y, n, (hipStream_t)stream);
 }
 
+int ld_op_f32_crop_u8(const float* canvas, int canvas_pitch, int cw, int ch, int channels, int x1, int y1, int x2, int y2, void* dst, int dst_pitch,
+                      void* stream) {
+    op_begin();
+    return f32_crop_u8_launch(canvas, canvas_pitch, cw, ch, channels, x1, y1, x2, y2, (uint8_t*)dst, dst_pitch, (hipStream_t)stream);
+}
+
+int ld_op_f32_blur_max_feather(void) { return F32_BLUR_MAX_FEATHER; }
+
+size_t ld_op_f32_blur_tmp_bytes(int w, int h) { return f32_blur_tmp_bytes(w, h); }
+
+int ld_op_f32_gaussian_blur(const float* src, int src_pitch, float* dst, int dst_pitch, int w, int h, int feather, const float* taps, float* tmp,
+                            void* stream) {
+    op_begin();
+    return f32_gaussian_blur_launch(src, src_pitch, dst, dst_pitch, w, h, feather, taps, tmp, (hipStream_t)stream);
+}
+
+int ld_op_f32_paste_u8(float* canvas, int canvas_pitch, int cw, int ch, int channels, const void* tile, int tile_pitch, const float* alpha, int alpha_pitch,
+                       int tw, int th, int x0, int y0, void* stream) {
+    op_begin();
+    return f32_paste_u8_launch(canvas, canvas_pitch, cw, ch, channels, (const uint8_t*)tile, tile_pitch, alpha, alpha_pitch, tw, th, x0, y0,
+                               (hipStream_t)stream);
+}
+
 int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
     op_begin();
     return launched(clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream),

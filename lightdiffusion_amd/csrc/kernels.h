@@ -202,6 +202,20 @@ int u8_composite_launch(uint8_t* canvas, int cpitch, int cw, int ch, const uint8
 int u8_from_f32_launch(const float* x, uint8_t* y, size_t n, hipStream_t stream);    // uint8(clip(255 x, 0, 255)): truncation
 int f32_from_u8_launch(const uint8_t* x, float* y, size_t n, hipStream_t stream);    // x / 255, correctly rounded
 
+// ---- detail/detail_image.hip: the Detailer's fp32 canvas [H][W][C] and fp32 masks [H][W], pitches in FLOATS; uint8 images as above (see the file's header)
+constexpr int F32_IMAGE_MAX_SIDE = 16384;      // a side of a canvas, tile or mask
+constexpr int F32_BLUR_MAX_FEATHER = 127;      // 2 feather + 1 = 255 taps in LDS
+// dst[y2 - y1][x2 - x1][C] = uint8(clip(255 x, 0, 255)), a truncation, of the window [y1, y2) x [x1, x2) of the cw x ch canvas; the window lies inside it
+int f32_crop_u8_launch(const float* canvas, int cpitch, int cw, int ch, int C, int x1, int y1, int x2, int y2, uint8_t* dst, int dpitch, hipStream_t stream);
+// the (2 feather + 1)^2 Gaussian of the w x h mask at src, reflect padding: a pass along x into tmp (f32_blur_tmp_bytes(w, h)), a pass along y into
+// dst; taps: device [2 feather + 1] floats; feather 0: a copy (taps and tmp unused); feather < min(w, h) and <= F32_BLUR_MAX_FEATHER; dst may be src
+size_t f32_blur_tmp_bytes(int w, int h);
+int f32_gaussian_blur_launch(const float* src, int spitch, float* dst, int dpitch, int w, int h, int feather, const float* taps, float* tmp,
+                             hipStream_t stream);
+// canvas = (1 - a) canvas + a (tile / 255), every operation rounded, on the tw x th tile's window at (x0, y0) clipped to the cw x ch canvas
+int f32_paste_u8_launch(float* canvas, int cpitch, int cw, int ch, int C, const uint8_t* tile, int tpitch, const float* alpha, int apitch, int tw, int th, int x0,
+                        int y0, hipStream_t stream);
+
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
 // (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout

@@ -6,11 +6,12 @@ networks and stay outside this package; `segs_from_boxes` builds what the box de
 The reference does the image plumbing on the host, with numpy, PIL and torchvision, for every segment.  The loop here (`do_detail`) is
 written for a canvas that goes up once as fp32 [H, W, 3] and comes down once, over an op namespace it is handed: the Pillow-identical
 `u8_resample` / `u8_from_f32` / `f32_from_u8` of lightdiffusion_amd.ops, and three fp32 image ops — `u8_crop_from_f32` (tensor2pil of a window
-of the canvas), `f32_gaussian_blur` (the mask blur) and `f32_paste_u8_` (pil2tensor + tensor_paste).  lightdiffusion_amd.ops has no kernels
-for those three, so this package has no device Detailer: `do_detail` needs `stages` with an op namespace that implements them, and nothing
-here falls back to torch on the host.  `model_stages` builds the encode / sample / decode stages on the resident VAE and sampler for such a
-namespace.  Only the small latents cross to the host, as in usdu.py.  This module holds the geometry (pure Python / NumPy) and the segment
-loop; it imports neither PIL nor torchvision.
+of the canvas), `f32_gaussian_blur` (the mask blur) and `f32_paste_u8_` (pil2tensor + tensor_paste), HIP kernels too (csrc/detail/detail_image.hip:
+crop and paste bit-identical to the reference's fp32 arithmetic, the blur within a derived bound of torchvision's).  `model_stages` builds the
+encode / sample / decode stages on the resident VAE and sampler for such a namespace, and nodes.DetailerForEach hands `do_detail` the stages
+over lightdiffusion_amd.ops: the device Detailer.  `do_detail` itself takes its `stages` from the caller and raises without — the tests run it
+on a NumPy namespace as well — and nothing here falls back to torch on the host.  Only the small latents cross to the host, as in usdu.py.
+This module holds the geometry (pure Python / NumPy) and the segment loop; it imports neither PIL nor torchvision.
 
 THE ONE DEVIATION: the work size.  The reference encodes and denoises at (new_w, new_h) = int(side * upscale) whatever they are; its UNet
 resizes to the skip's shape on the way up.  The UNet here takes latent sides that are multiples of 8 only, so the crop is Lanczos-resized to
@@ -202,8 +203,8 @@ def do_detail(image, segs, model, clip, vae, guide_size, guide_size_for_bbox, ma
     decode(latent) -> [1, h, w, 3], ops, device, observe (or None, called after every paste).  Every detailed segment's crop, enhanced crop
     and alpha stay on `device` until the one download at the end: memory grows with the number of segments, each of crop size."""
     if stages is None:
-        raise ValueError("do_detail needs `stages`: this package has no kernels for the Detailer's three fp32 image ops, and there is no "
-                         "fall-back to the host (see the module docstring and model_stages)")
+        raise ValueError("do_detail needs `stages` (model_stages(..., ops=lightdiffusion_amd.ops) for the device; nodes.DetailerForEach builds "
+                         "them): there is no fall-back to the host (see the module docstring)")
     if image.dim() != 4 or image.shape[-1] != 3:
         raise ValueError(f"expected an image [1, H, W, 3], got {tuple(image.shape)}")
     if image.shape[0] != 1:

@@ -296,6 +296,24 @@ class SegsBitwiseAndMask:
         return (detailer.segs_bitwise_and_mask(segs, mask),)
 
 
+class DetailerForEach:
+    """doit(...) -> (image, cropped, cropped_enhanced, cropped_enhanced_alpha, cnet_pil_list) with the argument list of the reference's
+    DetailerForEachTest.doit (LD.py:9598-9670): host fp32 [1, H, W, 3] in and out, the three lists of host fp32 crops sorted by shape, largest
+    first, cnet_pil_list = [zeros(1, 64, 64, 3)] (empty_pil_tensor).  Every segment is redrawn on the model's device on a resident fp32 canvas
+    (detailer.do_detail over the image kernels of lightdiffusion_amd.ops); `wildcard` is do_detail's wildcard_opt: "" or None."""
+
+    def doit(self, image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative,
+             denoise, feather, noise_mask, force_inpaint, wildcard, detailer_hook=None, cycle=1, inpaint_model=False, noise_mask_feather=0,
+             scheduler_func_opt=None):
+        from . import detailer, ops
+        stages = detailer.model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops=ops)
+        enhanced, cropped, cropped_enhanced, cropped_enhanced_alpha, _, _ = detailer.do_detail(
+            image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative, denoise,
+            feather, noise_mask, force_inpaint, wildcard, detailer_hook, cycle=cycle, inpaint_model=inpaint_model, noise_mask_feather=noise_mask_feather,
+            scheduler_func_opt=scheduler_func_opt, stages=stages)
+        return enhanced, cropped, cropped_enhanced, cropped_enhanced_alpha, [torch.zeros(1, 64, 64, 3)]
+
+
 # ------------------------------------------------------------------ loaders
 def load_synthetic_upscaler(device="cuda:0", nb: int = 23, scale: int = 4, seed: int = 0) -> MI355XUpscaler:
     """An RRDBNet with deterministic random-init weights: the offline stand-in for RealESRGAN_x4plus.pth (LD.py:84-90)."""

@@ -809,6 +809,103 @@ def u8_composite_(canvas: torch.Tensor, tile: torch.Tensor, alpha: torch.Tensor,
     return canvas
 
 
+# ------------------------------------------------------------------ fp32 image ops (detail/detail_image.hip): the Detailer's per-segment plumbing
+# The canvas is fp32 [H, W, C] on the device, a mask fp32 [H, W]; a view whose pixels are contiguous within a row is taken as pointer + pitch (in
+# floats).  With u8_resample, u8_from_f32 and f32_from_u8 above these three are the seam detailer.py works through.  A bad argument is a
+# ValueError on the host, before anything is launched.
+def _image_view(t: torch.Tensor, dtype, dims, what: str):
+    """(pointer, row pitch in elements, h, w, c) of a device image view [H, W] or [H, W, C] of `dtype` whose rows are dense."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: a tensor on the device is needed, got {getattr(t, 'device', type(t).__name__)}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: dtype {t.dtype}, expected {dtype}")
+    if t.dim() != dims or min(t.shape) < 1:
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, expected {'[H, W]' if dims == 2 else '[H, W, C]'} with no empty side")
+    c = 1 if dims == 2 else t.shape[2]
+    dense = t.stride(1) == 1 if dims == 2 else (t.stride(2) == 1 and t.stride(1) == c)
+    if not 1 <= c <= 4 or not dense or (t.shape[0] > 1 and t.stride(0) < t.shape[1] * c):
+        raise ValueError(f"{what}: 1 to 4 channels, pixels contiguous within a row (shape {tuple(t.shape)}, strides {t.stride()})")
+    return t.data_ptr(), max(t.stride(0), t.shape[1] * c), t.shape[0], t.shape[1], c
+
+
+def u8_crop_from_f32(canvas: torch.Tensor, x1: int, y1: int, x2: int, y2: int) -> torch.Tensor:
+    """tensor2pil (LD.py:8505-8509) of canvas[y1:y2, x1:x2] without the PIL object: uint8(clip(255 x, 0, 255)), a truncation in fp32, as a dense
+    uint8 [y2 - y1, x2 - x1, C].  The canvas is not written."""
+    ptr, pitch, ch, cw, c = _image_view(canvas, torch.float32, 3, "canvas")
+    x1, y1, x2, y2 = int(x1), int(y1), int(x2), int(y2)
+    if not (0 <= x1 < x2 <= cw and 0 <= y1 < y2 <= ch):
+        raise ValueError(f"the window [{x1}, {y1}, {x2}, {y2}] does not lie inside the {cw} x {ch} canvas")
+    dst = torch.empty(y2 - y1, x2 - x1, c, dtype=torch.uint8, device=canvas.device)
+    with torch.cuda.device(canvas.device):
+        check(lib().ld_op_f32_crop_u8(ptr, pitch, cw, ch, c, x1, y1, x2, y2, dst.data_ptr(), (x2 - x1) * c, _stream()), "ld_op_f32_crop_u8")
+    return dst
+
+
+_GAUSS_TAPS = {}
+
+
+def gaussian_taps(feather: int, sigma: float = 10.0) -> torch.Tensor:
+    """torchvision's _get_gaussian_kernel1d(2 feather + 1, sigma) as it computes it, in torch fp32 on the host: [2 feather + 1]."""
+    x = torch.linspace(-float(feather), float(feather), steps=2 * feather + 1, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+def _taps_on(device, feather: int, sigma: float) -> torch.Tensor:
+    d = torch.device(device)
+    key = (feather, float(sigma), d.index if d.index is not None else torch.cuda.current_device())
+    if key not in _GAUSS_TAPS:                    # uploaded once
+        _GAUSS_TAPS[key] = gaussian_taps(feather, float(sigma)).to(d)
+    return _GAUSS_TAPS[key]
+
+
+def f32_blur_max_feather() -> int:
+    """The largest feather f32_gaussian_blur takes: its 2 feather + 1 taps are staged in LDS."""
+    return lib().ld_op_f32_blur_max_feather()
+
+
+def f32_gaussian_blur(mask: torch.Tensor, feather: int, sigma: float = 10.0) -> torch.Tensor:
+    """tensor_gaussian_blur_mask (LD.py:8979-9004): torchvision's GaussianBlur(2 feather + 1, sigma) of an fp32 mask [H, W] (or a window of one: a
+    view) with reflect padding -> a new dense fp32 [H, W].  Taps in torch fp32 as torchvision builds them, two passes, every product and sum
+    rounded to fp32 in ascending tap order.  feather 0: a copy."""
+    ptr, pitch, h, w, _ = _image_view(mask, torch.float32, 2, "mask")
+    feather = int(feather)
+    if feather < 0 or feather >= min(h, w):
+        raise ValueError(f"feather={feather} must be at least 0 and smaller than both sides of the {w} x {h} mask (the blur pads by reflection)")
+    if feather > f32_blur_max_feather():
+        raise ValueError(f"feather={feather} is above the kernel's limit of {f32_blur_max_feather()} (its taps are staged in LDS)")
+    if not float(sigma) > 0.0:
+        raise ValueError(f"sigma={sigma} must be positive")
+    dst = torch.empty(h, w, dtype=torch.float32, device=mask.device)
+    taps = tmp = None
+    if feather > 0:
+        taps = _taps_on(mask.device, feather, sigma)
+        tmp = torch.empty(lib().ld_op_f32_blur_tmp_bytes(w, h), dtype=torch.uint8, device=mask.device)
+    with torch.cuda.device(mask.device):
+        check(lib().ld_op_f32_gaussian_blur(ptr, pitch, dst.data_ptr(), w, w, h, feather, _p(taps), _p(tmp), _stream()), "ld_op_f32_gaussian_blur")
+    return dst
+
+
+def f32_paste_u8_(canvas: torch.Tensor, tile: torch.Tensor, alpha: torch.Tensor, x0: int, y0: int) -> torch.Tensor:
+    """pil2tensor + tensor_paste (LD.py:8888-8889, 9355-9373) in place: canvas[y0:y0+h, x0:x0+w] = (1 - a) canvas + a (tile / 255) on the uint8 tile's window
+    clipped to the canvas, every fp32 operation rounded on its own.  The rest of the canvas is untouched.  -> canvas"""
+    cp, cpitch, ch, cw, c = _image_view(canvas, torch.float32, 3, "canvas")
+    tp, tpitch, th, tw, tc = _image_view(tile, torch.uint8, 3, "tile")
+    ap, apitch, ah, aw, _ = _image_view(alpha, torch.float32, 2, "alpha")
+    if tile.device != canvas.device or alpha.device != canvas.device:
+        raise ValueError(f"canvas, tile and alpha must be on one device, got {canvas.device}, {tile.device}, {alpha.device}")
+    if tc != c:
+        raise ValueError(f"a tile of {tc} channels for a canvas of {c}")
+    if (ah, aw) != (th, tw):
+        raise ValueError(f"alpha of shape {(ah, aw)} for a tile of {(th, tw)}")
+    x0, y0 = int(x0), int(y0)
+    if not (0 <= x0 < cw and 0 <= y0 < ch):
+        raise ValueError(f"the tile's origin ({x0}, {y0}) does not lie inside the {cw} x {ch} canvas")
+    with torch.cuda.device(canvas.device):
+        check(lib().ld_op_f32_paste_u8(cp, cpitch, cw, ch, c, tp, tpitch, ap, apitch, tw, th, x0, y0, _stream()), "ld_op_f32_paste_u8")
+    return canvas
+
+
 # ------------------------------------------------------------------ the `operations=` namespace (secondary seam)
 # The reference builds every network from an injectable namespace (`operations=ops`: UNetModel1 LD.py:5338, ResBlock1
 # 5207, SpatialTransformer 4179, CrossAttention 4005, FeedForward 3908; BaseModel picks `manual_cast` or
