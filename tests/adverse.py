@@ -24,13 +24,12 @@ x 32: 1.7e4 — the stream grows with depth, so the deeper model takes the small
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 import re
 
 import torch
 
+import chain_harness as H
 from lightdiffusion_amd import weights as W
 
 # one gain per model (a power of two).  Peaks of the fp32 oracle on fp16-rounded weights with these gains: tests/test_adverse_cpu.py::test_window
@@ -88,14 +87,7 @@ def state_dict(model: str, shapes, seed: int = 0, gain: float | None = None, fp1
 
 def record(case: str, what: dict) -> None:
     """With LD_WRITE_PARITY=1: merge `what` into the entry `case` of profiles/adverse_parity.json (a record, not an assertion)."""
-    if os.environ.get("LD_WRITE_PARITY") != "1":
-        return
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "adverse_parity.json")
-    have = json.load(open(path)) if os.path.exists(path) else {}
-    have.setdefault(case, {}).update(what)
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
+    H.record("adverse_parity.json", case, what)
 
 
 # ------------------------------------------------------------------ operand profiles (deterministic: shape and seed -> fp16)

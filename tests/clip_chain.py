@@ -22,9 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import inspect
-import json
 import math
-import os
 
 import torch
 
@@ -339,24 +337,6 @@ def check_pooled(last, pooled, ids, eos: int, what: str):
     at = first_eos(ids, eos)
     want = last[torch.arange(last.shape[0]), at.to(last.device)]
     assert torch.equal(pooled, want), f"{what}: pooled is not last[b, first EOS] (first EOS at {at.tolist()})"
-
-
-# ------------------------------------------------------------------ the record
-
-def record(case: str, what: dict, name: str = "clip_chain_parity.json") -> None:
-    """With LD_WRITE_PARITY=1: merge `what` into the entry `case` of profiles/<name> (a record, not an assertion)."""
-    if os.environ.get("LD_WRITE_PARITY") != "1":
-        return
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", name)
-    have = json.load(open(path)) if os.path.exists(path) else {}
-    have.setdefault(case, {}).update(what)
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
-
-
-def stage_record(worst: dict) -> dict:
-    return {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1], 4)} for k, v in sorted(worst.items())}
 
 
 # ------------------------------------------------------------------ the emulation and the planted defects

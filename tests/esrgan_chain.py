@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import torch
 
+from chain_harness import ChainBase
 from lightdiffusion_amd import weights as W
 
 SLOPE = 0.2           # act("leakyrelu"): nn.LeakyReLU(0.2) (LD.py:6700-6716)
@@ -52,33 +53,10 @@ def modules(cfg: dict):
 
 # ------------------------------------------------------------------ the chain
 
-class ESRGANChain:
+class ESRGANChain(ChainBase):
     def __init__(self, cfg: dict, device="cuda:0", seed: int = 0):
-        from lightdiffusion_amd import ops
-        self.ops, self.cfg, self.dev, self.seed = ops, dict(cfg), torch.device(device), seed
-        self.shapes = W.esrgan_param_shapes(cfg)
-        self._w = {}
-        self.taps = []
-
-    # -- weights: the checkpoint's fp32 masters -> fp16, in the layout the kernels read, by the seam's own operator
-    def master(self, name):
-        return W.synth_tensor(name, self.shapes[name], self.seed)
-
-    def _cached(self, key, make):
-        if key not in self._w:
-            self._w[key] = make()
-        return self._w[key]
-
-    def vec(self, name):
-        return self._cached(name, lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def oihw(self, name):
-        """fp16 [O][I][3][3], the checkpoint's layout (what the fp64 references of the 64-channel convolutions take)."""
-        return self._cached(("oihw", name), lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def conv3(self, name):
-        """[O][9 I] tap-major from the fp32 master, as a load repacks it."""
-        return self._cached(("c3", name), lambda: self.ops.repack_conv_weight(self.master(name).to(self.dev)))
+        super().__init__(W.esrgan_param_shapes(cfg), device, seed)
+        self.cfg = dict(cfg)
 
     def _buf(self, n, h, w, c):
         return torch.full((n, h, w, c), float("nan"), dtype=torch.float16, device=self.dev)

@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import torch
 
+from chain_harness import ChainBase
 from lightdiffusion_amd import weights as W
 
 PREFIX = "taesd_decoder."       # nodes.load_synthetic_taesd seeds the synthetic tensors under the whole module's key
@@ -39,30 +40,9 @@ def modules():
     return mods
 
 
-class TAESDChain:
+class TAESDChain(ChainBase):
     def __init__(self, device="cuda:0", seed: int = 0):
-        from lightdiffusion_amd import ops
-        self.ops, self.dev, self.seed = ops, torch.device(device), seed
-        self.shapes = W.taesd_decoder_param_shapes()
-        self._w = {}
-        self.taps = []
-
-    def master(self, name):
-        return W.synth_tensor(PREFIX + name, self.shapes[name], self.seed)
-
-    def _cached(self, key, make):
-        if key not in self._w:
-            self._w[key] = make()
-        return self._w[key]
-
-    def vec(self, name):
-        return self._cached(name, lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def oihw(self, name):
-        return self._cached(("oihw", name), lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def conv3(self, name):
-        return self._cached(("c3", name), lambda: self.ops.repack_conv_weight(self.master(name).to(self.dev)))
+        super().__init__(W.taesd_decoder_param_shapes(), device, seed, prefix=PREFIX)
 
     def decode(self, latent: torch.Tensor):
         """latent [n][4][h][w] -> (TAESD.decode as NHWC [n][8h][8w][3] fp32, the preview image uint8 of the same shape) on the device."""

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import adverse as A
+import chain_harness as H
 import errbound as EB
 import test_unet_chain_gpu as TU
 import test_vae_chain_gpu as TV
@@ -46,22 +47,14 @@ def unet_inputs(name):
     return x, torch.tensor(sigmas, dtype=torch.float32, device=DEV), ctx
 
 
-_SIDES = {}
+def _side(model, tag):
+    src = A.source(model, gain=GAINS[(model, tag)])
+    if model == "unet":
+        return TU.Side(tag, source=src, cases={k: v[:5] for k, v in UNET_CASES.items()}, inputs_of=unet_inputs)
+    return TV.Side(tag, source=src, cases=VAE_CASES)
 
 
-@pytest.fixture(scope="module")
-def side():
-    def get(model, tag):
-        if (model, tag) not in _SIDES:
-            src = A.source(model, gain=GAINS[(model, tag)])
-            if model == "unet":
-                _SIDES[(model, tag)] = TU.Side(tag, source=src, cases={k: v[:5] for k, v in UNET_CASES.items()}, inputs_of=unet_inputs)
-            else:
-                _SIDES[(model, tag)] = TV.Side(tag, source=src, cases=VAE_CASES)
-        return _SIDES[(model, tag)]
-    yield get
-    _SIDES.clear()
-    torch.cuda.empty_cache()
+side = H.side_fixture(_side)
 
 
 ALL = [("unet", n) for n in UNET_CASES] + [("vae", n) for n in VAE_CASES]
@@ -71,21 +64,13 @@ def _tag(model, name):
     return (UNET_CASES if model == "unet" else VAE_CASES)[name][0]
 
 
-_record = A.record
-
-
 # ------------------------------------------------------------------ B1
 
 @pytest.mark.parametrize("model,name", ALL)
 def test_same_launches(side, model, name):
     s = side(model, _tag(model, name))
     _, taps = s.chain_run(name)
-    mine = [(t["name"], k) for t in taps for k in t["launches"].split(";") if k]
-    theirs = s.executor_table(name)
-    for i, ((layer, a), b) in enumerate(zip(mine, theirs)):
-        assert a == b, f"{name}: launch {i} differs at {layer}: the chain ran {a}, the executor {b}"
-    assert len(mine) == len(theirs), (len(mine), len(theirs))
-    assert all(t["launches"] for t in taps), [t["name"] for t in taps if not t["launches"]]
+    H.same_launches(name, taps, s.executor_table(name))
 
 
 # ------------------------------------------------------------------ B2
@@ -95,13 +80,8 @@ def test_same_bits(side, model, name):
     tag = _tag(model, name)
     s = side(model, tag)
     want, _ = s.chain_run(name)
-    got = s.executor_run(name)
-    assert got.shape == want.shape and torch.equal(got, want), f"{name}: {TU._differs(got, want)}"
-    for other in (UNET_CASES if model == "unet" else VAE_CASES):             # shape history A, B, A on the adverse handle
-        if other != name and _tag(model, other) == tag:
-            s.executor_run(other)
-            got = s.executor_run(name)
-            assert torch.equal(got, want), f"{name} after {other}: {TU._differs(got, want)}"
+    others = [o for o in (UNET_CASES if model == "unet" else VAE_CASES) if o != name and _tag(model, o) == tag]
+    H.same_bits(name, want, s.executor_run, others)                          # shape history A, B, A on the adverse handle
 
 
 # ------------------------------------------------------------------ B3 and the window
@@ -121,20 +101,11 @@ def test_every_stage_elementwise_in_the_window(side, model, name, monkeypatch):
             peak["nonfinite"].append(what)
         return check(y, ref, bound, what, **kw)
     monkeypatch.setattr(EB, "check", watched)
-    fails, worst = [], {}
-    for tap in taps:
-        what = f"{name} {tap['name']} [{tap['kernel'] or tap['launches']}]"
-        try:
-            for r, b in (TU._stage(tap, s.chain, what) if model == "unet" else TV._stage(tap, what)):
-                w = worst.setdefault(tap["kind"], [0.0, 0.0])
-                w[0], w[1] = max(w[0], r), (b if abs(b) > abs(w[1]) else w[1])
-        except AssertionError as e:
-            fails.append(str(e))
-    rec = {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / EB.BIAS_TOL, 4)} for k, v in sorted(worst.items())}
+    rec, fails = H.every_stage(name, taps, (lambda tap, what: TU._stage(tap, s.chain, what)) if model == "unet" else TV._stage)
     print(f"ADVERSE CHAIN {model} {name}: peak |fp64 stage reference| {peak['ref']:.4g} at {peak['at']}; " + json.dumps(rec))
-    _record(f"chain {model} {name}", {"stages": rec, "peak_stage_reference": round(peak["ref"], 1), "peak_at": peak["at"]})
+    A.record(f"chain {model} {name}", {"stages": rec, "peak_stage_reference": round(peak["ref"], 1), "peak_at": peak["at"]})
     assert not peak["nonfinite"], f"non-finite tap outputs: {peak['nonfinite'][:6]}"
-    assert not fails, f"{len(fails)} of {len(taps)} stages outside their bound:\n" + "\n".join(fails[:12])
+    H.stages_held(fails, taps)
     assert WINDOW[0] <= peak["ref"] <= WINDOW[1], f"{name}: the largest stage reference {peak['ref']:.4g} ({peak['at']}) is outside [2^13, 2^15.5]"
 
 
@@ -162,4 +133,4 @@ def test_record_distance_to_the_fp32_oracle(side, model, name):
     assert got.shape == ref.shape and bool(torch.isfinite(got).all())
     rl2, mx = rel_l2(got, ref), float((got - ref).abs().max())
     print(f"ADVERSE ORACLE {model} {name}: rel-L2 {rl2:.3e}, max-abs {mx:.3e} (output max {float(ref.abs().max()):.3g})")
-    _record(f"chain {model} {name}", {"rel_l2_vs_fp32_oracle": float(f"{rl2:.4g}"), "max_abs_vs_fp32_oracle": float(f"{mx:.4g}")})
+    A.record(f"chain {model} {name}", {"rel_l2_vs_fp32_oracle": float(f"{rl2:.4g}"), "max_abs_vs_fp32_oracle": float(f"{mx:.4g}")})

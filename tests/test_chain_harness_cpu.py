@@ -1,0 +1,136 @@
+"""CPU control of tests/chain_harness.py: the chain tests of five executors stand or fall with it, so each of its checks is shown to accept
+what is right and to reject one planted defect, by name.  Hand-made taps, tensors of a few dozen elements."""
+import json
+import os
+
+import pytest
+import torch
+
+import chain_harness as H
+import errbound as EB
+
+TAPS = [dict(kind="first", name="conv_in", launches="k_in"), dict(kind="conv", name="block.0", launches="k_stats;k_conv", kernel="k_conv"),
+        dict(kind="last", name="conv_out", launches="k_out")]
+TABLE = ["k_in", "k_stats", "k_conv", "k_out"]
+
+
+# ------------------------------------------------------------------ B1
+
+def test_same_launches_accepts_the_matching_list():
+    assert H.same_launches("case", TAPS, TABLE) == [("conv_in", "k_in"), ("block.0", "k_stats"), ("block.0", "k_conv"), ("conv_out", "k_out")]
+
+
+def test_same_launches_rejects():
+    with pytest.raises(AssertionError, match=r"case: launch 2 differs at block\.0: the chain ran k_conv, the executor k_other"):
+        H.same_launches("case", TAPS, TABLE[:2] + ["k_other"] + TABLE[3:])
+    with pytest.raises(AssertionError, match=r"the chain has 4 launches, the executor 3; first unmatched: \('conv_out', 'k_out'\)"):
+        H.same_launches("case", TAPS, TABLE[:3])                     # a launch the executor does not have
+    with pytest.raises(AssertionError, match=r"the chain has 4 launches, the executor 5; first unmatched: k_more"):
+        H.same_launches("case", TAPS, TABLE + ["k_more"])            # a launch the chain does not have
+    with pytest.raises(AssertionError, match=r"taps without a launch: \['idle'\]"):
+        H.same_launches("case", TAPS + [dict(kind="conv", name="idle", launches="")], TABLE)
+
+
+# ------------------------------------------------------------------ B2
+
+def _flipped(t, index=(1, 2)):
+    """t with the lowest mantissa bit of one element flipped."""
+    bits = t.clone().view(torch.int32)
+    bits[index] ^= 1
+    return bits.view(torch.float32)
+
+
+def test_same_bits():
+    want = torch.arange(24, dtype=torch.float32).reshape(4, 6) + 0.5
+    ran = []
+
+    def run(case):
+        ran.append(case)
+        return want.clone()
+    H.same_bits("A", want, run, ["B", "C"])
+    assert ran == ["A", "B", "A", "C", "A"]
+    with pytest.raises(AssertionError, match=r"^A: 1 of 24 elements differ, first at \[1, 2\]: executor 8\.5"):
+        H.same_bits("A", want, lambda case: _flipped(want), ["B"])
+    ran.clear()
+
+    def stale(case):                                                 # the handle is right until another shape has run on it
+        ran.append(case)
+        return _flipped(want, (3, 5)) if "B" in ran else want.clone()
+    with pytest.raises(AssertionError, match=r"^A after B: 1 of 24 elements differ, first at \[3, 5\]"):
+        H.same_bits("A", want, stale, ["B"])
+    ran.clear()
+    H.same_bits("A", want, stale)                                    # (without a case in between there is nothing to see)
+    image = torch.arange(12, dtype=torch.uint8).reshape(2, 6)
+    H.same_bits("A", (want, image), lambda case: (want.clone(), image.clone()))
+    with pytest.raises(AssertionError, match=r"^A, result 1: 1 of 12 elements differ, first at \[0, 4\]: executor 5\.0, chain 4\.0"):
+        H.same_bits("A", (want, image), lambda case: (want.clone(), image + (torch.arange(12).reshape(2, 6) == 4)))
+    with pytest.raises(AssertionError, match=r"A: shape \(6, 4\), the chain's \(4, 6\)"):
+        H.bits_held(want.t(), want, "A")
+
+
+# ------------------------------------------------------------------ B3
+
+def _operands(seed=0, shape=(4, 8)):
+    ref = torch.randn(shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    return ref.half(), ref, EB.U * ref.abs() + EB.TINY
+
+
+def test_every_stage_reports_the_failed_stage_and_keeps_the_others():
+    seen = []
+
+    def stage(tap, what):
+        seen.append(what)
+        y, ref, bound = _operands()
+        return [H.held(y * 1.01 if tap["kind"] == "conv" else y, ref, bound, what)]
+    rec, fails = H.every_stage("case", TAPS, stage)
+    assert seen == ["case conv_in [k_in]", "case block.0 [k_conv]", "case conv_out [k_out]"]
+    assert len(fails) == 1 and fails[0].startswith("case block.0 [k_conv]: element bound: "), fails
+    assert sorted(rec) == ["first", "last"] and all(sorted(v) == ["signed_bias_over_tolerance", "worst_error_over_bound"] for v in rec.values())
+    assert all(0.0 < v["worst_error_over_bound"] <= 1.0 for v in rec.values()), rec
+    with pytest.raises(AssertionError, match=r"^1 of 3 stages outside their bound:\ncase block\.0 \[k_conv\]: element bound"):
+        H.stages_held(fails, TAPS)
+    H.stages_held([], TAPS)
+    # the worst figures per kind: the larger ratio, the signed bias of the larger magnitude with its sign, in units of BIAS_TOL
+    pairs = {"conv_in": [(0.25, 1e-5), (0.5, -3e-5)], "block.0": [(0.125, 2e-5)], "conv_out": [(0.75, -1e-5)]}
+    rec, fails = H.every_stage("case", TAPS + [dict(kind="first", name="conv_out", launches="k")], lambda tap, what: pairs[tap["name"]])
+    assert not fails and rec == {"first": {"worst_error_over_bound": 0.75, "signed_bias_over_tolerance": round(-3e-5 / EB.BIAS_TOL, 4)},
+                                 "conv": {"worst_error_over_bound": 0.125, "signed_bias_over_tolerance": round(2e-5 / EB.BIAS_TOL, 4)},
+                                 "last": {"worst_error_over_bound": 0.75, "signed_bias_over_tolerance": round(-1e-5 / EB.BIAS_TOL, 4)}}
+
+
+def test_partials_held():
+    y = torch.randn(1, 2, 2, 64, generator=torch.Generator().manual_seed(1)).half()          # 4 pixels, 32 groups of 2 channels
+    yg = y.double().reshape(1, 4, 32, 2)
+    chunk = lambda rows: torch.stack([yg[:, rows].sum((1, 3)), (yg[:, rows] ** 2).sum((1, 3))], -1)
+    part = torch.stack([chunk(slice(0, 1)), chunk(slice(1, 4))], 1).float()                   # [n][2 chunks][32 groups][sum, sum of squares]
+    H.partials_held(part, y, "conv")
+    part[0, 1, 5, 0] += 1e-3                                                                  # (the tolerance of a sum is below 1e-5 here)
+    with pytest.raises(AssertionError, match=r"^conv: partial statistics, error / tolerance "):
+        H.partials_held(part, y, "conv")
+
+
+def test_held_goes_through_the_module_attribute_check(monkeypatch):
+    calls = []
+    monkeypatch.setattr(EB, "check", lambda y, ref, bound, what, **kw: calls.append((what, kw)) or "verdict")
+    y, ref, bound = _operands()
+    assert H.held(y, ref, bound, "small", bias_extra=0.5, image_rows=4, width=2) == "verdict"
+    big = torch.ones(10 ** 4, dtype=torch.float64)
+    assert H.held(big.half(), big, big, "big", bias_extra=0.5) == "verdict"
+    assert calls == [("small", dict(bias_extra=0.5 + EB.rtn_noise(EB.independent_roundings(ref)), keep=None, image_rows=4, width=2)),
+                     ("big", dict(bias_extra=0.5, keep=None))]
+
+
+# ------------------------------------------------------------------ the record
+
+def test_record(monkeypatch, tmp_path):
+    monkeypatch.setattr(H, "PROFILES", str(tmp_path))
+    monkeypatch.delenv("LD_WRITE_PARITY", raising=False)
+    H.record("x_parity.json", "case", {"b": 2})
+    monkeypatch.setenv("LD_WRITE_PARITY", "0")
+    H.record("x_parity.json", "case", {"b": 2})
+    assert os.listdir(tmp_path) == []
+    monkeypatch.setenv("LD_WRITE_PARITY", "1")
+    (tmp_path / "x_parity.json").write_text(json.dumps({"case": {"a": 1, "b": 0}, "other": {"z": 0}}))
+    H.record("x_parity.json", "case", {"b": 2})
+    H.record("x_parity.json", "new", {"c": 3})
+    assert (tmp_path / "x_parity.json").read_text() == '{\n "case": {\n  "a": 1,\n  "b": 2\n },\n "new": {\n  "c": 3\n },\n "other": {\n  "z": 0\n }\n}\n'

@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import errbound as EB
+import chain_harness as H
 import esrgan_chain as EC
 import taesd_chain as TC
 from lightdiffusion_amd import weights as W
@@ -65,9 +65,7 @@ def _conv32(x_nhwc, w, b, up=False):
 
 
 def _check(y32, ref, bound, what, h, w):
-    y = y32.half()
-    extra = EB.rtn_noise(EB.independent_roundings(ref)) if ref.numel() < 10 ** 4 else 0.0
-    return EB.check(y, ref, bound, what, bias_extra=extra, image_rows=h * w, width=w)
+    return H.held(y32.half(), ref, bound, what, image_rows=h * w, width=w)
 
 
 def _caught(y32, ref, bound, what, h, w):

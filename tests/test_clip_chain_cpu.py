@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import adverse as A
+import chain_harness as H
 import clip_chain as C
 import errbound as EB
 from conftest import rel_l2
@@ -255,7 +256,7 @@ def test_emulated_adverse_chain_passes_in_the_window(ops):
     C.check_sequence(calls, cfg, tm.w)
     peak = {}
     worst = C.check_stages(calls, "adverse tiny emulation", peak)
-    print(f"adverse tiny emulation: peak {peak['ref']:.4g} at {peak['at']}; {C.stage_record(worst)}")
+    print(f"adverse tiny emulation: peak {peak['ref']:.4g} at {peak['at']}; {H.stage_record(worst)}")
     assert WINDOW[0] <= peak["ref"] <= WINDOW[1] and not peak.get("nonfinite")
     with pytest.raises(AssertionError, match="signed bias"):
         with C.emulated(ops, _emul(tm, 4)):

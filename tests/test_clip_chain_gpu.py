@@ -26,6 +26,7 @@ import pytest
 import torch
 
 import adverse as A
+import chain_harness as H
 import clip_chain as C
 import errbound as EB
 from conftest import rel_l2
@@ -149,9 +150,9 @@ def test_every_stage_elementwise(world, name):
     calls, _ = world.run(name)
     peak = {}
     worst = C.check_stages(calls, name, peak)
-    rec = C.stage_record(worst)
+    rec = H.stage_record(worst)
     print(f"CLIP CHAIN {name}: peak |fp64 stage reference| {peak['ref']:.4g} at {peak['at']}; {rec}")
-    C.record(name, {"stages": rec, "peak_stage_reference": round(peak["ref"], 2), "peak_at": peak["at"]})
+    H.record("clip_chain_parity.json", name, {"stages": rec, "peak_stage_reference": round(peak["ref"], 2), "peak_at": peak["at"]})
     assert not peak.get("nonfinite"), f"non-finite stage outputs: {peak['nonfinite'][:6]}"
     if adverse:
         A.record(f"chain clip {name}", {"stages": rec, "peak_stage_reference": round(peak["ref"], 1), "peak_at": peak["at"], "gain": A.CHAIN_GAIN[("clip", tag)]})
@@ -273,7 +274,7 @@ def _end_to_end(world, name):
 
 def test_end_to_end_12_layers(world):
     fig = _end_to_end(world, "sd15_b1")
-    C.record("sd15_b1", {"end_to_end": fig})
+    H.record("clip_chain_parity.json", "sd15_b1", {"end_to_end": fig})
     for k, v in fig.items():
         if k.startswith("rel_l2"):
             assert v < 5e-3, (k, v)

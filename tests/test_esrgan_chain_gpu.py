@@ -9,7 +9,7 @@ B2  same bits: torch.equal(executor, chain) on forward_device for every case —
     workspace for the case.  No tolerance.  Layers held under an exception instead: none.
 B3  every stage element-wise, on ALL rows: for each tap the fp64 reference of that one stage from the stage's own fp16 inputs and the bounds
     that exist — dense_conv_ref (tests/test_esrgan_conv_gpu.py), EB.esrgan_first_ref, EB.esrgan_last_ref — through EB.check with the
-    signed-bias statistic (EB.rtn_noise on top below 10^4 elements, as tests/test_vae_chain_gpu.py).  What only the executor reaches: the
+    signed-bias statistic (EB.rtn_noise on top below 10^4 elements: chain_harness.held).  What only the executor reaches: the
     in-place append into a buffer with stale channels (every channel outside [c_off, c_off + cout) bit-unchanged), convolution 5's R1 out
     of its own input buffer, the second store y2 over R2 (y2 == the stored y, bit for bit), the trunk convolution's buffer by the parity
     of 3 nb, the HR convolution on the pitch-192 buffer at scale 1, three up-convolutions at scale 8.
@@ -22,14 +22,14 @@ B4  the chain is the reference's network: on the esrgan_x4_nb2 / esrgan_x2_nb1 f
 Cases: the smallest shapes that reach each path (the halo tile is 16 x 32 output pixels); images are rand in [0, 1].
 """
 import json
-import os
 
 import pytest
 import torch
 
+import chain_harness as H
 import errbound as EB
 import esrgan_ref as ER
-from conftest import ROOT, load_golden, rel_l2
+from conftest import load_golden, rel_l2
 from lightdiffusion_amd import weights as W
 from test_esrgan_conv_gpu import dense_conv_ref
 
@@ -92,18 +92,7 @@ class Side:
         return [r[4] for r in self.model.profile(inputs(name))]
 
 
-_SIDES = {}
-
-
-@pytest.fixture(scope="module")
-def side():
-    def get(tag):
-        if tag not in _SIDES:
-            _SIDES[tag] = Side(tag)
-        return _SIDES[tag]
-    yield get
-    _SIDES.clear()
-    torch.cuda.empty_cache()
+side = H.side_fixture(Side)
 
 
 # ------------------------------------------------------------------ B1
@@ -115,13 +104,7 @@ def test_same_launches(side, name):
     s = side(tag)
     nb, scale = CONFIGS[tag]
     _, taps = s.chain_run(name)
-    mine = [(t["name"], k) for t in taps for k in t["launches"].split(";") if k]
-    theirs = s.executor_table(name)
-    for i, ((layer, a), b) in enumerate(zip(mine, theirs)):
-        assert a == b, f"{name}: launch {i} differs at {layer}: the chain ran {a}, the executor {b}"
-    assert len(mine) == len(theirs), (f"{name}: the chain has {len(mine)} launches, the executor {len(theirs)}; first unmatched: "
-                                      f"{mine[len(theirs)] if len(mine) > len(theirs) else theirs[len(mine)]}")
-    assert all(t["launches"] for t in taps), [t["name"] for t in taps if not t["launches"]]
+    mine = H.same_launches(name, taps, s.executor_table(name))
     assert len(mine) == len(taps) == s.model.last_launches == 15 * nb + 4 + ER.n_upconvs(scale), (len(mine), len(taps), s.model.last_launches)
     assert [(t["kind"], t["name"]) for t in taps] == [(k, nm) for k, nm, _, _ in modules(s.cfg)]
     names = [k for _, k in mine]
@@ -139,12 +122,6 @@ def test_same_launches(side, name):
 
 # ------------------------------------------------------------------ B2
 
-def _differs(a, b):
-    d = (a != b)
-    idx = d.nonzero()[0].tolist()
-    return f"{int(d.sum())} of {d.numel()} elements differ, first at {idx}: executor {float(a[tuple(idx)])!r}, chain {float(b[tuple(idx)])!r}"
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_same_bits(side, name):
     from lightdiffusion_amd.upscale import MI355XUpscaler
@@ -152,42 +129,28 @@ def test_same_bits(side, name):
     s = side(tag)
     want, _ = s.chain_run(name)
     assert bool(torch.isfinite(want).all()), f"{name}: the chain read a channel nobody wrote"
-    got = s.executor_run(name)
-    assert got.shape == want.shape and torch.equal(got, want), f"{name}: {_differs(got, want)}"
-    for other in CASES:                                    # shape history A, B, A on the one handle
-        if other != name and CASES[other][0] == tag:
-            s.executor_run(other)
-            got = s.executor_run(name)
-            assert torch.equal(got, want), f"{name} after {other}: {_differs(got, want)}"
+    H.same_bits(name, want, s.executor_run, [o for o in CASES if o != name and CASES[o][0] == tag])      # shape history A, B, A on the one handle
     n, h, w = CASES[name][1]
     grown = MI355XUpscaler(s.cfg, _gen, device=DEV, max_batch=1, max_hw=(2, 2))       # a handle that has to grow its workspace for this case
     before = grown.workspace_bytes
     got = grown.forward_device(inputs(name))
     assert grown.workspace_bytes > before and grown.workspace_bytes == grown.plan_bytes(n, h, w)
-    assert torch.equal(got, want), f"{name} on a grown workspace: {_differs(got, want)}"
+    H.bits_held(got, want, f"{name} on a grown workspace")
 
 
 # ------------------------------------------------------------------ B3
-
-_PARITY = {}
-
-
-def _held(y, ref, bound, what, keep=None, **where):
-    extra = EB.rtn_noise(EB.independent_roundings(ref, keep)) if ref.numel() < 10 ** 4 else 0.0
-    return EB.check(y, ref, bound, what, bias_extra=extra, keep=keep, **where)
-
 
 def _bits(t):
     return t.contiguous().view(torch.int16)
 
 
 def _stage(tap, what):
-    """(error / bound, signed bias) of one tap's output against the fp64 reference of that stage; the stage's buffer contract bit for bit."""
+    """[(error / bound, signed bias)] of one tap's output against the fp64 reference of that stage; the stage's buffer contract bit for bit."""
     kind, i, p, out = tap["kind"], tap["inp"], tap["par"], tap["out"]
     if kind == "last":
         n, h, w, _ = i["x"].shape
         ref, bound = EB.esrgan_last_ref(i["x"], p["w"], p["b"])
-        return _held(out.reshape(-1, 3), ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool), image_rows=h * w, width=w)
+        return [H.held(out.reshape(-1, 3), ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool), image_rows=h * w, width=w)]
     c_off, cout = p["c_off"], p["cout"]
     before, after = tap["before"], tap["after"]
     n, h, w, ld = after.shape
@@ -204,37 +167,17 @@ def _stage(tap, what):
     else:
         res = [(s, r) for s, r in ((p["s1"], i["r1"]), (p["s2"], i["r2"])) if r is not None]
         ref, bound = dense_conv_ref(i["x"], p["w"], p["b"], p["slope"], res, up=p["up"])
-    return _held(out.reshape(-1, cout), ref, bound, what, image_rows=h * w, width=w)
-
-
-def _write_parity(fname, name, record):
-    if os.environ.get("LD_WRITE_PARITY") != "1":
-        return
-    path = os.path.join(ROOT, "profiles", fname)
-    have = json.load(open(path)) if os.path.exists(path) else {}
-    have.setdefault(name, {}).update(record)
-    with open(path, "w") as f:
-        json.dump(have, f, indent=1, sort_keys=True)
-        f.write("\n")
+    return [H.held(out.reshape(-1, cout), ref, bound, what, image_rows=h * w, width=w)]
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_every_stage_elementwise(side, name):
     s = side(CASES[name][0])
     _, taps = s.chain_run(name)
-    fails, worst = [], {}
-    for tap in taps:
-        what = f"{name} {tap['name']} [{tap['launches']}]"
-        try:
-            r, b = _stage(tap, what)
-            wk = worst.setdefault(tap["kind"], [0.0, 0.0])
-            wk[0], wk[1] = max(wk[0], r), (b if abs(b) > abs(wk[1]) else wk[1])
-        except AssertionError as e:
-            fails.append(str(e))
-    _PARITY[name] = {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / EB.BIAS_TOL, 4)} for k, v in sorted(worst.items())}
-    print(f"PARITY {name}: " + json.dumps(_PARITY[name]))
-    _write_parity("esrgan_chain_parity.json", name, _PARITY[name])
-    assert not fails, f"{len(fails)} of {len(taps)} stages outside their bound:\n" + "\n".join(fails[:12])
+    rec, fails = H.every_stage(name, taps, _stage)
+    print(f"PARITY {name}: " + json.dumps(rec))
+    H.record("esrgan_chain_parity.json", name, rec)
+    H.stages_held(fails, taps)
 
 
 # ------------------------------------------------------------------ B4
@@ -248,7 +191,7 @@ def test_chain_meets_the_goldens(side, fixture):
     assert y.shape == g["y"].shape
     err, allow = rel_l2(y, g["y"]), 2.0 * float(g["emul_rel_l2"])
     print(f"{fixture}: chain rel-L2 {err:.3e} (allowance {allow:.3e})")
-    _write_parity("esrgan_chain_parity.json", "fixture " + fixture, {"chain_rel_l2": round(err, 7), "allowance": round(allow, 7)})
+    H.record("esrgan_chain_parity.json", "fixture " + fixture, {"chain_rel_l2": round(err, 7), "allowance": round(allow, 7)})
     assert err <= allow, (err, allow)
 
 
@@ -266,5 +209,5 @@ def test_chain_meets_the_restatement_without_a_fixture(side, name):
     out, _ = s.chain_run(name)
     err, allow = rel_l2(out.cpu(), ref), 2.0 * emul
     print(f"{name}: chain rel-L2 {err:.3e}, emulation {emul:.3e} (allowance {allow:.3e})")
-    _write_parity("esrgan_chain_parity.json", name, {"vs_fp32_restatement": {"chain_rel_l2": round(err, 7), "emulation_rel_l2": round(emul, 7), "allowance": round(allow, 7)}})
+    H.record("esrgan_chain_parity.json", name, {"vs_fp32_restatement": {"chain_rel_l2": round(err, 7), "emulation_rel_l2": round(emul, 7), "allowance": round(allow, 7)}})
     assert out.shape == ref.shape and err <= allow, (err, emul, allow)

@@ -8,7 +8,7 @@ B2  same bits: torch.equal(executor, chain) on the fp32 decode AND on the uint8 
     LatentPreviewer(use_graph=True) captures and replays.  No tolerance.  Layers held under an exception instead: none.
 B3  every stage element-wise, on ALL rows: for each tap the fp64 reference of that one stage from the stage's own inputs and the bounds that
     exist — taesd_conv_ref (tests/test_taesd_conv_gpu.py), EB.taesd_first_ref, EB.taesd_last_ref — through EB.check with the signed-bias
-    statistic (EB.rtn_noise on top below 10^4 elements, as tests/test_vae_chain_gpu.py).  What only the executor reaches: three buffers
+    statistic (EB.rtn_noise on top below 10^4 elements: chain_harness.held).  What only the executor reaches: three buffers
     that rotate through four resolutions, a Block's third convolution writing over t1 with the Block's input as residual, the bias-free
     up-convolution from the old size into the next buffer at the new one.  The largest fp64 im2col is 136 x 264 x 576 (165 MB).
     With LD_WRITE_PARITY=1 the worst error / bound and signed bias per stage kind and case go to profiles/taesd_chain_parity.json (a record).
@@ -24,10 +24,10 @@ import math
 import pytest
 import torch
 
+import chain_harness as H
 import errbound as EB
 import taesd_ref as TR
 from conftest import load_golden, rel_l2
-from test_esrgan_chain_gpu import _differs, _write_parity
 from test_taesd_conv_gpu import taesd_conv_ref
 
 pytestmark = pytest.mark.gpu
@@ -69,7 +69,9 @@ class Side:
         return self._chain_runs[name]
 
     def executor_run(self, name, model=None):
-        return (model or self.model)._run(inputs(name), True)
+        got, img = (model or self.model)._run(inputs(name), True)
+        assert img.dtype == torch.uint8, img.dtype
+        return got, img
 
     def executor_table(self, name):
         return [r[4] for r in self.model.profile(inputs(name))]
@@ -89,13 +91,7 @@ def side():
 def test_same_launches(side, name):
     from taesd_chain import modules
     _, _, taps = side.chain_run(name)
-    mine = [(t["name"], k) for t in taps for k in t["launches"].split(";") if k]
-    theirs = side.executor_table(name)
-    for i, ((layer, a), b) in enumerate(zip(mine, theirs)):
-        assert a == b, f"{name}: launch {i} differs at {layer}: the chain ran {a}, the executor {b}"
-    assert len(mine) == len(theirs), (f"{name}: the chain has {len(mine)} launches, the executor {len(theirs)}; first unmatched: "
-                                      f"{mine[len(theirs)] if len(mine) > len(theirs) else theirs[len(mine)]}")
-    assert all(t["launches"] for t in taps), [t["name"] for t in taps if not t["launches"]]
+    mine = H.same_launches(name, taps, side.executor_table(name))
     assert len(mine) == len(taps) == side.model.last_launches == LAUNCHES
     assert [(t["kind"], t["name"]) for t in taps] == [(k, nm) for k, nm, _, _ in modules()]
     names = [k for _, k in mine]
@@ -114,22 +110,14 @@ def test_same_launches(side, name):
 def test_same_bits(side, name):
     want, want_img, _ = side.chain_run(name)
     assert bool(torch.isfinite(want).all()), f"{name}: the chain read an element nobody wrote"
-    got, img = side.executor_run(name)
-    assert got.shape == want.shape and torch.equal(got, want), f"{name}: {_differs(got, want)}"
-    assert img.dtype == torch.uint8 and torch.equal(img, want_img), f"{name}: image, {_differs(img, want_img)}"
     assert torch.equal(want_img, TR.to_image(want)), "the image is not the formula on the chain's own decode"
-    shape = CASES[name][0]
-    for other in CASES:                                    # shape history A, B, A on the one handle
-        if CASES[other][0] != shape:
-            side.executor_run(other)
-            got, img = side.executor_run(name)
-            assert torch.equal(got, want) and torch.equal(img, want_img), f"{name} after {other}: {_differs(got, want)}"
-    n, h, w = shape
+    n, h, w = shape = CASES[name][0]
+    H.same_bits(name, (want, want_img), side.executor_run, [o for o in CASES if CASES[o][0] != shape])      # the decode and the image; A, B, A on the one handle
     grown = _fresh()                                       # a handle that has to grow its workspace for this case
     before = grown.workspace_bytes
-    got, img = side.executor_run(name, grown)
+    got = side.executor_run(name, grown)
     assert grown.workspace_bytes > before and grown.workspace_bytes == grown.plan_bytes(n, h, w)
-    assert torch.equal(got, want) and torch.equal(img, want_img), f"{name} on a grown workspace: {_differs(got, want)}"
+    H.bits_held(got, (want, want_img), f"{name} on a grown workspace")
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -143,59 +131,41 @@ def test_same_bits_under_the_previewer_graph(side, name):
     for i in range(2):                                     # the capture's replay, and a second replay
         pv({"x": x, "i": i, "sigma": 1.0, "denoised": None})
         assert pv._graph is not None
-        assert torch.equal(pv._f32, want), f"{name} replay {i}: {_differs(pv._f32, want)}"
-        assert torch.equal(got[-1], want_img.cpu()), f"{name} replay {i}: image, {_differs(got[-1], want_img.cpu())}"
+        H.bits_held((pv._f32, got[-1]), (want, want_img.cpu()), f"{name} replay {i}")
 
 
 # ------------------------------------------------------------------ B3
 
-_PARITY = {}
-
-
-def _held(y, ref, bound, what, keep=None, **where):
-    extra = EB.rtn_noise(EB.independent_roundings(ref, keep)) if ref.numel() < 10 ** 4 else 0.0
-    return EB.check(y, ref, bound, what, bias_extra=extra, keep=keep, **where)
-
-
 def _stage(tap, what):
-    """(error / bound, signed bias) of one tap's output against the fp64 reference of that stage."""
+    """[(error / bound, signed bias)] of one tap's output against the fp64 reference of that stage."""
     kind, i, p, out = tap["kind"], tap["inp"], tap["par"], tap["out"]
     n, h, w, _ = out.shape
     where = dict(image_rows=h * w, width=w)
     if kind == "first":
         ref, bound = EB.taesd_first_ref(i["x"], p["w"], p["b"])
         assert float(out.min()) >= 0.0
-        return _held(out.reshape(-1, 64), ref, bound, what, keep=ref > 0, **where)
+        return [H.held(out.reshape(-1, 64), ref, bound, what, keep=ref > 0, **where)]
     if kind == "last":
         ref, bound, img_ref = EB.taesd_last_ref(i["x"], p["w"], p["b"])
         img = tap["image"]
         assert torch.equal(img, TR.to_image(out)), f"{what}: the image is not the formula on the device's own decode"
         off = (img.reshape(-1, 3).long() - img_ref.long()).abs()
         assert int(off.max()) <= 1, f"{what}: image byte {int(off.max())} counts from the fp64 reference's"
-        return _held(out.reshape(-1, 3), ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool), **where)
+        return [H.held(out.reshape(-1, 3), ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool), **where)]
     assert (kind == "up") == p["up"] and (p["b"] is None) == (kind == "up")
     ref, bound = taesd_conv_ref(i["x"], p["w"], p["b"], i["residual"], p["relu"], p["up"])
     if p["relu"]:
         assert float(out.min()) >= 0.0
-    return _held(out.reshape(-1, 64), ref, bound, what, **where)
+    return [H.held(out.reshape(-1, 64), ref, bound, what, **where)]
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_every_stage_elementwise(side, name):
     _, _, taps = side.chain_run(name)
-    fails, worst = [], {}
-    for tap in taps:
-        what = f"{name} {tap['name']} [{tap['launches']}]"
-        try:
-            r, b = _stage(tap, what)
-            wk = worst.setdefault(tap["kind"], [0.0, 0.0])
-            wk[0], wk[1] = max(wk[0], r), (b if abs(b) > abs(wk[1]) else wk[1])
-        except AssertionError as e:
-            fails.append(str(e))
-    _PARITY[name] = {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / EB.BIAS_TOL, 4)} for k, v in sorted(worst.items())}
-    print(f"PARITY {name}: " + json.dumps(_PARITY[name]))
-    _write_parity("taesd_chain_parity.json", name, _PARITY[name])
-    assert not fails, f"{len(fails)} of {len(taps)} stages outside their bound:\n" + "\n".join(fails[:12])
+    rec, fails = H.every_stage(name, taps, _stage)
+    print(f"PARITY {name}: " + json.dumps(rec))
+    H.record("taesd_chain_parity.json", name, rec)
+    H.stages_held(fails, taps)
 
 
 # ------------------------------------------------------------------ B4
@@ -211,6 +181,6 @@ def test_chain_meets_the_goldens(fixture):
     mx, mallow = float((d - g["y"]).abs().max()), 2.0 * float(g["emul_max_abs"])
     counts, callow = int((img.int() - g["image"].int()).abs().max()), math.ceil(255.0 * float(g["emul_max_abs"]))
     print(f"{fixture}: chain rel-L2 {err:.3e} (allowance {allow:.3e}), max-abs {mx:.3e} (allowance {mallow:.3e}), image {counts} counts (allowance {callow})")
-    _write_parity("taesd_chain_parity.json", "fixture " + fixture, {"chain_rel_l2": round(err, 7), "allowance": round(allow, 7), "chain_max_abs": round(mx, 6),
-                                                                     "max_abs_allowance": round(mallow, 6)})
+    H.record("taesd_chain_parity.json", "fixture " + fixture, {"chain_rel_l2": round(err, 7), "allowance": round(allow, 7), "chain_max_abs": round(mx, 6),
+                                                               "max_abs_allowance": round(mallow, 6)})
     assert err <= allow and mx <= mallow and counts <= callow, (err, allow, mx, mallow, counts, callow)

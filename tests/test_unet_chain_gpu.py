@@ -17,13 +17,13 @@ B4  the chain is the reference's network: its output on the unet_tiny goldens me
     oracle's apply_model on the same inputs.
 """
 import json
-import os
 
 import pytest
 import torch
 
+import chain_harness as H
 import errbound as EB
-from conftest import ROOT, load_golden, rel_l2
+from conftest import load_golden, rel_l2
 from lightdiffusion_amd import weights as W
 
 pytestmark = pytest.mark.gpu
@@ -99,18 +99,7 @@ class Side:
         return [r[4] for r in self.unet.profile_launches()]
 
 
-_SIDES = {}
-
-
-@pytest.fixture(scope="module")
-def side():
-    def get(tag):
-        if tag not in _SIDES:
-            _SIDES[tag] = Side(tag)
-        return _SIDES[tag]
-    yield get
-    _SIDES.clear()
-    torch.cuda.empty_cache()
+side = H.side_fixture(Side)
 
 
 # ------------------------------------------------------------------ B1
@@ -119,13 +108,7 @@ def side():
 def test_same_launches(side, name):
     s = side(CASES[name][0])
     _, taps = s.chain_run(name)
-    mine = [(t["name"], k) for t in taps for k in t["launches"].split(";") if k]
-    theirs = s.executor_table(name)
-    for i, ((layer, a), b) in enumerate(zip(mine, theirs)):
-        assert a == b, f"{name}: launch {i} differs at {layer}: the chain ran {a}, the executor {b}"
-    assert len(mine) == len(theirs), (f"{name}: the chain has {len(mine)} launches, the executor {len(theirs)}; first unmatched: "
-                                      f"{mine[len(theirs)] if len(mine) > len(theirs) else theirs[len(mine)]}")
-    assert all(t["launches"] for t in taps), [t["name"] for t in taps if not t["launches"]]
+    mine = H.same_launches(name, taps, s.executor_table(name))
     # what the case is in the table for (REACHES): a retuned threshold that moves it off that route must bring another shape
     names = {k for _, k in mine}
     layers = [t["name"] for t in taps]
@@ -152,24 +135,12 @@ REACHES = {
 
 # ------------------------------------------------------------------ B2
 
-def _differs(a, b):
-    d = (a != b)
-    idx = d.nonzero()[0].tolist()
-    return f"{int(d.sum())} of {d.numel()} elements differ, first at {idx}: executor {float(a[tuple(idx)])!r}, chain {float(b[tuple(idx)])!r}"
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_same_bits(side, name):
     tag, nb, (h, w), tokens, mode = CASES[name]
     s = side(tag)
     want, _ = s.chain_run(name)
-    got = s.executor_run(name)
-    assert torch.equal(got, want), f"{name}: {_differs(got, want)}"
-    for other in CASES:                                    # shape history A, B, A
-        if other != name and CASES[other][0] == tag:
-            s.executor_run(other)
-            got = s.executor_run(name)
-            assert torch.equal(got, want), f"{name} after {other}: {_differs(got, want)}"
+    H.same_bits(name, want, s.executor_run, [o for o in CASES if o != name and CASES[o][0] == tag])
     if mode == "eps":
         return                                             # (the wrapper's contract returns the denoised latent: no eps route behind it)
     # the captured graph the model_function_wrapper hook replays (LD.py:2558-2567), first contact and a replay
@@ -182,30 +153,11 @@ def test_same_bits(side, name):
         got = s.unet(None, params)
         run = s.unet._hook[(x.shape[0], h, w)]
         assert (run.pair if mode == "pair" else run.plain).graph is not None
-        assert torch.equal(got, want), f"{name} under the replayed graph, lap {lap}: {_differs(got, want)}"
+        H.bits_held(got, want, f"{name} under the replayed graph, lap {lap}")
     s.unet._hook.clear()
 
 
 # ------------------------------------------------------------------ B3
-
-_PARITY = {}
-
-
-def _held(y, ref, bound, what, bias_extra=0.0, keep=None, **where):
-    extra = EB.rtn_noise(EB.independent_roundings(ref, keep)) if ref.numel() < 10 ** 4 else 0.0
-    return EB.check(y, ref, bound, what, bias_extra=bias_extra + extra, keep=keep, **where)
-
-
-def _partials_held(part, y, what):
-    """A producer's GroupNorm partials against fp64 sums of the STORED fp16 outputs (tests/test_routes_gpu.py::test_conv_gn_partials_route)."""
-    n, cout = y.shape[0], y.shape[-1]
-    yg = y.double().reshape(n, -1, 32, cout // 32)
-    hw = yg.shape[1]
-    got = part.double().sum(1)
-    want = torch.stack([yg.sum((1, 3)), (yg * yg).sum((1, 3))], -1)
-    tol = torch.stack([yg.abs().sum((1, 3)), (yg * yg).sum((1, 3))], -1) * (EB.c_acc(hw * cout // 32) + 2.0 ** -22) + EB.TINY
-    assert bool(((got - want).abs() <= tol).all()), f"{what}: partial statistics, error / tolerance {float(((got - want).abs() / tol).max()):.3g}"
-
 
 def _stage(tap, chain, what):
     """[(error / bound, signed bias)] of one tap's output(s) against the fp64 reference of that stage."""
@@ -214,29 +166,29 @@ def _stage(tap, chain, what):
     if kind == "timestep":
         t, margin, emb, bound = EB.timestep_ref(i["sigma"], chain.log_sigmas, p["dim"], p["n"], p["sigma_mod"])
         assert float(margin.min()) > 1e-4, f"{what}: an ill-posed sigma (margin {float(margin.min()):.2e})"
-        return [_held(out, emb, bound, what, keep=torch.ones_like(emb, dtype=torch.bool))]
+        return [H.held(out, emb, bound, what, keep=torch.ones_like(emb, dtype=torch.bool))]
     if kind == "linear":
         ref, bound = EB.linear_ref(i["x"], p["w"], p["b"], None, 1.0, p["act"])
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "conv_in":
         ref, bound = EB.small_conv_in_ref(i["x"], p["w"], p["b"], scale_sigma=i["sigma"])
         nb = i["x"].shape[0]
         assert torch.equal(out[nb:], out[:nb].repeat(out.shape[0] // nb - 1, 1, 1, 1)), f"{what}: the pair's second copy differs"
-        return [_held(out[:nb].reshape(ref.shape), ref, bound, what)]
+        return [H.held(out[:nb].reshape(ref.shape), ref, bound, what)]
     if kind == "conv_out":
         ref, bound = EB.small_conv_out_ref(i["x"], p["w"], p["b"], p["mode"], i["x_in"], i["sigma"], p["in_mod"])
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "groupnorm":
         x = i["x"]
         ref, bound = EB.groupnorm_ref(x, None, p["gamma"], p["beta"], p["eps"], p["silu"])
-        return [_held(out.reshape(ref.shape), ref, bound, what)]
+        return [H.held(out.reshape(ref.shape), ref, bound, what)]
     if kind == "conv":
         x = i["x"]
         ref, bound, (ho, wo) = EB.conv_ref(x, p["w"], p["b"], i.get("residual"), i.get("stride", 1), None, i.get("x2"), None)
         cout = p["w"].shape[0]
         if tap.get("part") is not None:
-            _partials_held(tap["part"], out, what)
-        return [_held(out.reshape(-1, cout), ref, bound, what, image_rows=ho * wo, width=wo)]
+            H.partials_held(tap["part"], out, what)
+        return [H.held(out.reshape(-1, cout), ref, bound, what, image_rows=ho * wo, width=wo)]
     if kind == "upconv":
         x, (hv, wv) = i["x"], i["out_hw"]
         cout = p["w"].shape[0]
@@ -246,7 +198,7 @@ def _stage(tap, chain, what):
             ref, bound = ref.reshape(-1, cout), bound.reshape(-1, cout)
         else:
             ref, bound, _ = EB.conv_ref(x, p["w"], p["b"], None, 1, (hv, wv))
-        return [_held(out.reshape(-1, cout), ref, bound, what, image_rows=hv * wv, width=wv)]
+        return [H.held(out.reshape(-1, cout), ref, bound, what, image_rows=hv * wv, width=wv)]
     if kind == "gn_conv":
         x = i["x"]
         skip = (i["s1"], i["s2"], p["wskip"], p["bskip"]) if "wskip" in p else None
@@ -254,17 +206,17 @@ def _stage(tap, chain, what):
                                          residual=i.get("residual"), skip=skip)
         cout = p["w"].shape[0]
         if tap.get("part") is not None:
-            _partials_held(tap["part"], out, what)
-        return [_held(out.reshape(-1, cout), ref, bound, what, image_rows=x.shape[1] * x.shape[2], width=x.shape[2])]
+            H.partials_held(tap["part"], out, what)
+        return [H.held(out.reshape(-1, cout), ref, bound, what, image_rows=x.shape[1] * x.shape[2], width=x.shape[2])]
     if kind == "linear_ln":
         t, y = out
         tref, tb = EB.linear_ref(i["x"], p["w_prod"], p["b_prod"], i["residual"])
-        a = _held(t, tref, tb, what + " producer")
+        a = H.held(t, tref, tb, what + " producer")
         ref, bound = R._ln_ref(i["x"], p["w_prod"], p["b_prod"], p["gamma"], p["beta"], p["w"], p["b"], t, 1e-5, p["geglu"])
-        return [a, _held(y, ref, bound, what + " consumer", bias_extra=EB.GELU_FIT_BIAS if p["geglu"] else 0.0)]
+        return [a, H.held(y, ref, bound, what + " consumer", bias_extra=EB.GELU_FIT_BIAS if p["geglu"] else 0.0)]
     if kind == "attention":
         ref, bound = EB.attention_ref(i["q"].contiguous(), i["k"].contiguous(), i["v"].contiguous(), chain.heads)
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "dup":
         for full, half in zip(out, (i["t"], i["q2"], i["x"])):
             n = half.shape[0] if half.dim() == 4 else full.shape[0] // 2
@@ -278,25 +230,10 @@ def _stage(tap, chain, what):
 def test_every_stage_elementwise(side, name):
     s = side(CASES[name][0])
     _, taps = s.chain_run(name)
-    fails, worst = [], {}
-    for tap in taps:
-        what = f"{name} {tap['name']} [{tap['kernel'] or tap['launches']}]"
-        try:
-            for r, b in _stage(tap, s.chain, what):
-                w = worst.setdefault(tap["kind"], [0.0, 0.0])
-                w[0], w[1] = max(w[0], r), (b if abs(b) > abs(w[1]) else w[1])
-        except AssertionError as e:
-            fails.append(str(e))
-    _PARITY[name] = {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / EB.BIAS_TOL, 4)} for k, v in sorted(worst.items())}
-    print(f"PARITY {name}: " + json.dumps(_PARITY[name]))
-    if os.environ.get("LD_WRITE_PARITY") == "1":
-        path = os.path.join(ROOT, "profiles", "unet_chain_parity.json")
-        have = json.load(open(path)) if os.path.exists(path) else {}
-        have[name] = _PARITY[name]
-        with open(path, "w") as f:
-            json.dump(have, f, indent=1, sort_keys=True)
-            f.write("\n")
-    assert not fails, f"{len(fails)} of {len(taps)} stages outside their bound:\n" + "\n".join(fails[:12])
+    rec, fails = H.every_stage(name, taps, lambda tap, what: _stage(tap, s.chain, what))
+    print(f"PARITY {name}: " + json.dumps(rec))
+    H.record("unet_chain_parity.json", name, rec)
+    H.stages_held(fails, taps)
 
 
 # ------------------------------------------------------------------ B4

@@ -7,7 +7,7 @@ B2  same bits: torch.equal(executor, chain) on decode_device / encode_moments fo
     between on the same handle (decode, encode, decode: arena reuse, the decode plan cache that an encode drops, the padded output weights
     refilled per run).  No tolerance.  Layers held under an exception instead: none.
 B3  every stage element-wise: for each tap the fp64 reference of that one stage from the stage's own fp16 inputs, the bound of tests/errbound.py
-    and EB.check with the signed-bias statistic (EB.rtn_noise on top below 10^4 elements, as tests/test_unet_chain_gpu.py), producer partials
+    and EB.check with the signed-bias statistic (EB.rtn_noise on top below 10^4 elements: chain_harness.held), producer partials
     against fp64 sums of the stored outputs.  What only the VAE has: the statistics handed from a halo tile's epilogue to the next GroupNorm
     (tile partials; from 192 tiles on), the encoder's stride-2 convolution with zeros below and right of the image only, the three batched
     GEMMs around the row softmax with keys padded to a multiple of 8 (the pad columns of V^T and of the scores repeat the last valid column —
@@ -23,13 +23,13 @@ Cases (latent sizes; an encode case's image is 8x as large): the smallest that r
 reach what they are listed for (REACHES asserts it).
 """
 import json
-import os
 
 import pytest
 import torch
 
+import chain_harness as H
 import errbound as EB
-from conftest import ROOT, load_golden, rel_l2
+from conftest import load_golden, rel_l2
 from lightdiffusion_amd import weights as W
 
 pytestmark = pytest.mark.gpu
@@ -96,18 +96,7 @@ class Side:
         return [r[4] for r in rows]
 
 
-_SIDES = {}
-
-
-@pytest.fixture(scope="module")
-def side():
-    def get(tag):
-        if tag not in _SIDES:
-            _SIDES[tag] = Side(tag)
-        return _SIDES[tag]
-    yield get
-    _SIDES.clear()
-    torch.cuda.empty_cache()
+side = H.side_fixture(Side)
 
 
 # ------------------------------------------------------------------ B1
@@ -136,13 +125,7 @@ NEVER = {name: _HANDED + ("conv6_kernel",) for name in CASES if not name.startsw
 def test_same_launches(side, name):
     s = side(CASES[name][0])
     _, taps = s.chain_run(name)
-    mine = [(t["name"], k) for t in taps for k in t["launches"].split(";") if k]
-    theirs = s.executor_table(name)
-    for i, ((layer, a), b) in enumerate(zip(mine, theirs)):
-        assert a == b, f"{name}: launch {i} differs at {layer}: the chain ran {a}, the executor {b}"
-    assert len(mine) == len(theirs), (f"{name}: the chain has {len(mine)} launches, the executor {len(theirs)}; first unmatched: "
-                                      f"{mine[len(theirs)] if len(mine) > len(theirs) else theirs[len(mine)]}")
-    assert all(t["launches"] for t in taps), [t["name"] for t in taps if not t["launches"]]
+    mine = H.same_launches(name, taps, s.executor_table(name))
     names = {k for _, k in mine}
     layers = [t["name"] for t in taps]
     print(f"LAUNCHES {name}: {sorted(names)}")
@@ -165,47 +148,16 @@ def test_same_launches(side, name):
 
 # ------------------------------------------------------------------ B2
 
-def _differs(a, b):
-    d = (a != b)
-    idx = d.nonzero()[0].tolist()
-    return f"{int(d.sum())} of {d.numel()} elements differ, first at {idx}: executor {float(a[tuple(idx)])!r}, chain {float(b[tuple(idx)])!r}"
-
-
 @pytest.mark.parametrize("name", list(CASES))
 def test_same_bits(side, name):
     tag = CASES[name][0]
     s = side(tag)
     want, _ = s.chain_run(name)
-    got = s.executor_run(name)
-    assert got.shape == want.shape and torch.equal(got, want), f"{name}: {_differs(got, want)}"
-    for other in CASES:                                    # shape history A, B, A — decodes and encodes on the one handle
-        if other != name and CASES[other][0] == tag:
-            s.executor_run(other)
-            got = s.executor_run(name)
-            assert torch.equal(got, want), f"{name} after {other}: {_differs(got, want)}"
+    # shape history A, B, A — decodes and encodes on the one handle
+    H.same_bits(name, want, s.executor_run, [o for o in CASES if o != name and CASES[o][0] == tag])
 
 
 # ------------------------------------------------------------------ B3
-
-_PARITY = {}
-
-
-def _held(y, ref, bound, what, bias_extra=0.0, keep=None, **where):
-    extra = EB.rtn_noise(EB.independent_roundings(ref, keep)) if ref.numel() < 10 ** 4 else 0.0
-    return EB.check(y, ref, bound, what, bias_extra=bias_extra + extra, keep=keep, **where)
-
-
-def _partials_held(part, y, what):
-    """A producer's GroupNorm partials against fp64 sums of the STORED fp16 outputs (tests/test_routes_gpu.py::test_conv_gn_partials_route);
-    any chunking of an image's pixels: the VAE's are one chunk per tile."""
-    n, cout = y.shape[0], y.shape[-1]
-    yg = y.double().reshape(n, -1, 32, cout // 32)
-    hw = yg.shape[1]
-    got = part.double().sum(1)
-    want = torch.stack([yg.sum((1, 3)), (yg * yg).sum((1, 3))], -1)
-    tol = torch.stack([yg.abs().sum((1, 3)), (yg * yg).sum((1, 3))], -1) * (EB.c_acc(hw * cout // 32) + 2.0 ** -22) + EB.TINY
-    assert bool(((got - want).abs() <= tol).all()), f"{what}: partial statistics, error / tolerance {float(((got - want).abs() / tol).max()):.3g}"
-
 
 def _per_image(fn, n):
     """A stage reference image by image (the fp64 im2col of one 384 x 256 image is 0.9 GB): fn(i) -> (ref, bound) of image i, concatenated."""
@@ -218,13 +170,13 @@ def _stage(tap, what):
     kind, i, p, out = tap["kind"], tap["inp"], tap["par"], tap["out"]
     if kind == "conv_in":
         ref, bound = EB.small_conv_in_ref(i["x"], p["w"], p["b"], pre_w=p["pre_w"], pre_b=p["pre_b"])
-        return [_held(out.reshape(ref.shape), ref, bound, what)]
+        return [H.held(out.reshape(ref.shape), ref, bound, what)]
     if kind == "conv_out":
         ref, bound = EB.small_conv_out_ref(i["x"], p["w"], p["b"], p["mode"])
-        return [_held(out.reshape(ref.shape), ref, bound, what)]
+        return [H.held(out.reshape(ref.shape), ref, bound, what)]
     if kind == "groupnorm":
         ref, bound = EB.groupnorm_ref(i["x"], None, p["gamma"], p["beta"], p["eps"], p["silu"])
-        return [_held(out.reshape(ref.shape), ref, bound, what)]
+        return [H.held(out.reshape(ref.shape), ref, bound, what)]
     if kind in ("conv", "conv_pad"):
         x = i["x"]
         n, cout = x.shape[0], p["w"].shape[0]
@@ -238,13 +190,13 @@ def _stage(tap, what):
         ref, bound = _per_image(one, n)
         ho, wo = hw
         if tap.get("part") is not None:
-            _partials_held(tap["part"], out, what)
+            H.partials_held(tap["part"], out, what)
         got = out.reshape(-1, out.shape[-1])
         if kind == "conv_pad":                                  # 8 stored columns: the real ones, then exact zeros (zero weight rows, zero biases)
             assert bool((got[:, cout:] == 0).all()), f"{what}: the stored columns {cout} .. 7 are not zero"
             got = got[:, :cout]
         assert tuple(out.shape[1:3]) == (ho, wo), (what, out.shape, ho, wo)
-        return [_held(got, ref, bound, what, image_rows=ho * wo, width=wo)]
+        return [H.held(got, ref, bound, what, image_rows=ho * wo, width=wo)]
     if kind == "gn_conv":
         x = i["x"]
         n, h, w, _ = x.shape
@@ -252,35 +204,35 @@ def _stage(tap, what):
         res = i.get("residual")
         ref, bound = _per_image(lambda j: EB.gn_silu_conv_ref(x[j:j + 1], p["gamma"], p["beta"], p["eps"], p["w"], p["b"], residual=None if res is None else res[j:j + 1]), n)
         if tap.get("part") is not None:
-            _partials_held(tap["part"], out, what)
-        return [_held(out.reshape(-1, cout), ref, bound, what, image_rows=h * w, width=w)]
+            H.partials_held(tap["part"], out, what)
+        return [H.held(out.reshape(-1, cout), ref, bound, what, image_rows=h * w, width=w)]
     if kind == "linear":
         ref, bound = EB.linear_ref(i["x"], p["w"], p["b"], i.get("residual"), 1.0, p["act"])
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "attention":
         ref, bound = EB.attention_ref(i["q"].contiguous(), i["k"].contiguous(), i["v"].contiguous(), 1)
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "linear_batched":
         nv = p["n_valid"]
         ref, bound = EB.linear_batched_ref(i["x"], i["w"], bias_m=p["bias_m"], n_valid=nv, alpha=p["alpha"])
         EB.pad_columns_held(out, nv, what)
-        return [_held(out[..., :nv], ref, bound, what)]
+        return [H.held(out[..., :nv], ref, bound, what)]
     if kind == "softmax":
         lp = out.shape[-1]
         ref, bound = EB.softmax_ref(i["s"].reshape(-1, lp), p["valid"])
         got = out.reshape(-1, lp)
         assert bool((got[:, p["valid"]:] == 0).all()), f"{what}: pad columns must be exactly 0"
         keep = EB.top_half_per_row(ref)
-        return [_held(got, ref, bound, what, keep=keep, bias_extra=EB.subnormal_bias_allowance(ref, keep))]
+        return [H.held(got, ref, bound, what, keep=keep, bias_extra=EB.subnormal_bias_allowance(ref, keep))]
     if kind == "pv":
         ref, bound = EB.pv_ref(i["p"], i["vt"], p["valid"])
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     if kind == "out_finish":
         ref, bound = EB.vae_out_finish_ref(i["t8"], p["cout"])
-        return [_held(out, ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool))]
+        return [H.held(out, ref, bound, what, keep=torch.ones_like(ref, dtype=torch.bool))]
     if kind == "quant":
         ref, bound = EB.small_pointwise_ref(i["x"], p["w"], p["b"])
-        return [_held(out, ref, bound, what)]
+        return [H.held(out, ref, bound, what)]
     raise AssertionError(f"no reference for stage kind {kind}")
 
 
@@ -288,25 +240,10 @@ def _stage(tap, what):
 def test_every_stage_elementwise(side, name):
     s = side(CASES[name][0])
     _, taps = s.chain_run(name)
-    fails, worst = [], {}
-    for tap in taps:
-        what = f"{name} {tap['name']} [{tap['kernel'] or tap['launches']}]"
-        try:
-            for r, b in _stage(tap, what):
-                w = worst.setdefault(tap["kind"], [0.0, 0.0])
-                w[0], w[1] = max(w[0], r), (b if abs(b) > abs(w[1]) else w[1])
-        except AssertionError as e:
-            fails.append(str(e))
-    _PARITY[name] = {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / EB.BIAS_TOL, 4)} for k, v in sorted(worst.items())}
-    print(f"PARITY {name}: " + json.dumps(_PARITY[name]))
-    if os.environ.get("LD_WRITE_PARITY") == "1":
-        path = os.path.join(ROOT, "profiles", "vae_chain_parity.json")
-        have = json.load(open(path)) if os.path.exists(path) else {}
-        have[name] = _PARITY[name]
-        with open(path, "w") as f:
-            json.dump(have, f, indent=1, sort_keys=True)
-            f.write("\n")
-    assert not fails, f"{len(fails)} of {len(taps)} stages outside their bound:\n" + "\n".join(fails[:12])
+    rec, fails = H.every_stage(name, taps, _stage)
+    print(f"PARITY {name}: " + json.dumps(rec))
+    H.record("vae_chain_parity.json", name, rec)
+    H.stages_held(fails, taps)
 
 
 # ------------------------------------------------------------------ B4

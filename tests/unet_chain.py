@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import torch
 
+from chain_harness import ChainBase, Feat
 from lightdiffusion_amd import weights as W
 
 
@@ -69,23 +70,12 @@ def log_sigma_table() -> torch.Tensor:
 
 # ------------------------------------------------------------------ the chain
 
-class Feat:
-    """An activation [n][H][W][C] and, where its producer wrote them, the GroupNorm partial statistics of it."""
-
-    def __init__(self, t, part=None):
-        self.t, self.part = t, part
-
-
-class UNetChain:
+class UNetChain(ChainBase):
     def __init__(self, cfg: dict, device="cuda:0", seed: int = 0, source=None):
-        from lightdiffusion_amd import ops
-        self.ops, self.cfg, self.dev, self.seed = ops, dict(cfg), torch.device(device), seed
-        self.source = source                  # a WeightSource (name, shape -> fp32 master); None: the synthetic checkpoint of `seed`
-        self.shapes = W.unet_param_shapes(cfg)
+        super().__init__(W.unet_param_shapes(cfg), device, seed, source)
+        self.cfg = dict(cfg)
         self.blocks = modules(cfg)
         self.heads = cfg["num_heads"]
-        self._w = {}
-        self.taps = []
         self.ctx = None
         self.log_sigmas = log_sigma_table().to(self.dev)
         res = [l for _, layers in self.blocks for l in layers if l[0] == "res"]
@@ -97,36 +87,6 @@ class UNetChain:
         self.emb_total = off
         self.emb_w = torch.cat([self.mat(n + ".emb_layers.1.weight") for _, n, _, _ in res]).contiguous()
         self.emb_b = torch.cat([self.vec(n + ".emb_layers.1.bias") for _, n, _, _ in res]).contiguous()
-
-    # -- weights: the checkpoint's fp32 masters -> fp16, in the layouts the kernels read, by the seam's own operators
-    def master(self, name):
-        if self.source is not None:
-            return self.source(name, self.shapes[name])
-        return W.synth_tensor(name, self.shapes[name], self.seed)
-
-    def _cached(self, key, make):
-        if key not in self._w:
-            self._w[key] = make()
-        return self._w[key]
-
-    def vec(self, name):
-        return self._cached(name, lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def mat(self, name):
-        """[O][I] (a Linear, or a 1x1 convolution's [O][I][1][1])."""
-        return self._cached(name, lambda: self.master(name).half().reshape(self.shapes[name][0], -1).to(self.dev).contiguous())
-
-    def oihw(self, name):
-        """fp16 [O][I][k][k], the checkpoint's layout (what the fp64 references take)."""
-        return self._cached(("oihw", name), lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def conv3(self, name):
-        """[O][9 I] tap-major from the fp32 master, as a load repacks it."""
-        return self._cached(("c3", name), lambda: self.ops.repack_conv_weight(self.master(name).to(self.dev)))
-
-    def tap(self, kind, name, inp, par, out, **more):
-        self.taps.append(dict(kind=kind, name=name, inp=inp, par=par, out=out, kernel=self.ops.last_kernel(), launches=self.ops.last_launches(), **more))
-        return out
 
     # -- the context: K / V^T of every cross-attention, projected once (CrossAttention.forward's to_k / to_v, LD.py:4028-4036)
     def set_context(self, ctx: torch.Tensor):

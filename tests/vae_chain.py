@@ -20,6 +20,7 @@ import math
 
 import torch
 
+from chain_harness import ChainBase, Feat
 from lightdiffusion_amd import weights as W
 
 EPS = 1e-6            # Normalize(): GroupNorm(32, eps=1e-6) (LD.py:3931-3939)
@@ -61,54 +62,13 @@ def modules(cfg: dict, encoder: bool = False):
 
 # ------------------------------------------------------------------ the chain
 
-class Feat:
-    """An activation [n][H][W][C] and, where its producer wrote them, the GroupNorm partial statistics of it."""
-
-    def __init__(self, t, part=None):
-        self.t, self.part = t, part
-
-
-class VAEChain:
+class VAEChain(ChainBase):
     def __init__(self, cfg: dict, device="cuda:0", with_encoder: bool = False, seed: int = 0, source=None):
-        from lightdiffusion_amd import ops
-        self.ops, self.cfg, self.dev, self.seed = ops, dict(cfg), torch.device(device), seed
-        self.source = source                  # a WeightSource (name, shape -> fp32 master); None: the synthetic checkpoint of `seed`
-        self.with_encoder = with_encoder
-        self.shapes = dict(W.vae_decoder_param_shapes(cfg))
+        shapes = dict(W.vae_decoder_param_shapes(cfg))
         if with_encoder:
-            self.shapes.update(W.vae_encoder_param_shapes(cfg))
-        self._w = {}
-        self.taps = []
-
-    # -- weights: the checkpoint's fp32 masters -> fp16, in the layouts the kernels read, by the seam's own operators
-    def master(self, name):
-        if self.source is not None:
-            return self.source(name, self.shapes[name])
-        return W.synth_tensor(name, self.shapes[name], self.seed)
-
-    def _cached(self, key, make):
-        if key not in self._w:
-            self._w[key] = make()
-        return self._w[key]
-
-    def vec(self, name):
-        return self._cached(name, lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def mat(self, name):
-        """[O][I] (a 1x1 convolution's [O][I][1][1])."""
-        return self._cached(name, lambda: self.master(name).half().reshape(self.shapes[name][0], -1).to(self.dev).contiguous())
-
-    def oihw(self, name):
-        """fp16 [O][I][k][k], the checkpoint's layout (what the fp64 references take)."""
-        return self._cached(("oihw", name), lambda: self.master(name).half().to(self.dev).contiguous())
-
-    def conv3(self, name):
-        """[O][9 I] tap-major from the fp32 master, as a load repacks it."""
-        return self._cached(("c3", name), lambda: self.ops.repack_conv_weight(self.master(name).to(self.dev)))
-
-    def tap(self, kind, name, inp, par, out, **more):
-        self.taps.append(dict(kind=kind, name=name, inp=inp, par=par, out=out, kernel=self.ops.last_kernel(), launches=self.ops.last_launches(), **more))
-        return out
+            shapes.update(W.vae_encoder_param_shapes(cfg))
+        super().__init__(shapes, device, seed, source)
+        self.cfg, self.with_encoder = dict(cfg), with_encoder
 
     # -- ResnetBlock.forward (LD.py:3560-3576): norm1 + swish + conv1, [nin_shortcut], norm2 + swish + conv2 + the shortcut
     def resblock(self, name, f: Feat) -> Feat:
