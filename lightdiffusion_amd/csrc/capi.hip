@@ -161,10 +161,15 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
     p.R = (const half_t*)residual;
     if (g.n_valid > 0) p.n_valid = g.n_valid;
     if (g.ldc > 0) p.ldc = p.ldr = g.ldc;
+    // the close of every route below: the chunk count of the launch's plan to the caller, the executor's status back
+    const auto ran = [gn_chunks](const Op& o, const GemmPlan& pl) {
+        if (gn_chunks != nullptr) *gn_chunks = pl.gn_chunks;
+        return o.ex.status;
+    };
     if (g.form == LD_FORM_VAE) {
         // the VAE executor's launch (vae.hip VRun::conv): statistics from the kernels that sum what they store only, no chunk geometry; its scratch
         // is the split partials alone — no counters and no weight copy, so the row-resident kernel is never offered
-        if (gn_part != nullptr) want_gn_tile_partials(p, gn_part, gn_chunks);
+        if (gn_part != nullptr) want_gn_tile_partials(p, gn_part);
         Op op(ws, ws_bytes, stream);
         op.splitk(kCompositeSplitBytes);
         if (ws == nullptr || !op.fits()) return LD_ERR_ARG;
@@ -173,14 +178,12 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
             // at the pitch ldc (the executor asks the plan first, and so does this)
             const GemmPlan pl = op.ex.plan(p);
             if (!(pl.halo_tile && pl.bn == 32 && p.n_valid > 0 && p.n_valid <= p.ldc)) return LD_ERR_SHAPE;
-            op.ex.gemm(p, &pl);
-            return op.ex.status;
+            return ran(op, op.ex.gemm(p, &pl));
         }
-        op.ex.gemm(p);
-        return op.ex.status;
+        return ran(op, op.ex.gemm(p));
     }
     if (p.ldc < p.N) return LD_ERR_SHAPE;   // (the narrow store is the VAE output convolution's)
-    if (gn_part != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, gn_part, gn_chunks);   // (as the executors ask)
+    if (gn_part != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, gn_part);   // (as the executors ask)
     const size_t head = conv8_scratch_head(cout, c1 + c2);
     if (ws != nullptr && ksize == 3 && conv8_weight_eligible(cout, c1 + c2) && ws_bytes > head + ((size_t)8 << 20)) {
         // a roomy scratch buffer: the row-resident kernel where it takes the shape, by a carving of its own; the general kernels keep the
@@ -188,15 +191,11 @@ static int op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h,
         Op c8(ws, ws_bytes, stream);
         GemmParams q = p;
         c8.conv8_scratch(q, wt, ws_bytes - head);
-        if (const GemmPlan plan = c8.ex.plan(q); plan.route == GR_CONV8) {
-            c8.ex.gemm(q, &plan);
-            return c8.ex.status;
-        }
+        if (const GemmPlan plan = c8.ex.plan(q); plan.route == GR_CONV8) return ran(c8, c8.ex.gemm(q, &plan));
     }
     Op op(ws, ws_bytes, stream);
     op.splitk_rest();
-    op.ex.gemm(p);
-    return op.ex.status;
+    return ran(op, op.ex.gemm(p));
 }
 
 int ld_op_conv(const void* x1, int c1, const void* x2, int c2, int n, int h, int w, int hv, int wv, int stride, int ksize,
@@ -295,13 +294,14 @@ int ld_op_groupnorm_conv(const void* x1, int c1, const void* x2, int c2, int n, 
     p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
     p.R = (const half_t*)residual;
     if (form == LD_FORM_VAE) {   // vae.hip VRun::gn_conv: the tile epilogue's statistics or none, split partials as the only scratch
-        if (part != nullptr) want_gn_tile_partials(p, part, chunks);
+        if (part != nullptr) want_gn_tile_partials(p, part);
         op.splitk(kCompositeSplitBytes);
     } else {
-        if (part != nullptr) want_gn_partials(p, n, h * w, part, chunks);
+        if (part != nullptr) want_gn_partials(p, n, h * w, part);
         op.conv8_scratch(p, wt, kCompositeSplitBytes);
     }
-    op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g, in_part, in_chunks);
+    const GemmPlan pl = op.ex.gn_silu_conv(p, n, h * w, (const half_t*)gamma, (const half_t*)beta, eps, g, gn_stats(in_part, in_chunks));
+    if (chunks != nullptr) *chunks = pl.gn_chunks;
     return op.ex.status;
 }
 
@@ -326,15 +326,17 @@ static int op_conv_skip(const void* x, int c, int n, int h, int w, const void* w
     GemmParams p = conv_params((const half_t*)x, c, nullptr, 0, n, h, w, h, w, 1, 3, (const half_t*)wt, (const half_t*)bias, cout, (half_t*)y);
     add_skip_segment(p, (const half_t*)s1, sc1, (const half_t*)s2, sc2, wf, bf);
     p.rowvec = (const half_t*)rowvec; p.ldrv = cout;
-    if (part != nullptr) want_gn_partials(p, n, HW, part, chunks);
+    if (part != nullptr) want_gn_partials(p, n, HW, part);
+    GemmPlan pl;
     if (gamma == nullptr) {
         op.splitk(kCompositeSplitBytes);
-        op.ex.gemm(p);
+        pl = op.ex.gemm(p);
     } else {
         half_t* g = op.arena.halfs((size_t)n * HW * c);
         op.splitk(kCompositeSplitBytes);
-        op.ex.gn_silu_conv(p, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, g, in_part, in_chunks);
+        pl = op.ex.gn_silu_conv(p, n, HW, (const half_t*)gamma, (const half_t*)beta, eps, g, gn_stats(in_part, in_chunks));
     }
+    if (chunks != nullptr) *chunks = pl.gn_chunks;
     return op.ex.status;
 }
 
@@ -544,13 +546,15 @@ int ld_op_ctx_kv(const void* ctx16, const void* wk, const void* wv, int n, int t
     op_begin();
     // the two launches ld_unet_set_context makes per transformer, by the same builders: K = ctx Wk^T [n tp][c] and, per sample, V^T = Wv ctx^T [c][tp]
     if (ctx16 == nullptr || wk == nullptr || wv == nullptr || k_out == nullptr || vt_out == nullptr || n <= 0 || tp <= 0 || d <= 0 || c <= 0) return LD_ERR_ARG;
-    int st = gemm_launch(linear_params((const half_t*)ctx16, d, (const half_t*)wk, nullptr, n * tp, c, d, (half_t*)k_out), (hipStream_t)stream);
+    const GemmParams k = linear_params((const half_t*)ctx16, d, (const half_t*)wk, nullptr, n * tp, c, d, (half_t*)k_out);
+    const GemmPlan kp = gemm_plan(k);
+    const int st = gemm_run(k, kp, (hipStream_t)stream);
     if (st != LD_OK) return st;
-    note_kernel(&t_op_kernels, gemm_last_kernel_name());
+    note_kernel(&t_op_kernels, kp.kernel);
     GemmParams v = linear_params((const half_t*)wv, d, (const half_t*)ctx16, nullptr, c, tp, d, (half_t*)vt_out);
     v.batch = n; v.sW = (long long)tp * d; v.sC = (long long)c * tp;
-    st = gemm_launch(v, (hipStream_t)stream);
-    return noted(st, gemm_last_kernel_name());
+    const GemmPlan vp = gemm_plan(v);
+    return noted(gemm_run(v, vp, (hipStream_t)stream), vp.kernel);
 }
 
 int ld_op_mlp_out_fold(const void* wpo, const void* w2, const void* b2, const void* bpo, int c, void* w_out, void* b_out, void* stream) {
@@ -597,11 +601,10 @@ static int op_linear_ln(const void* x, const void* w_prod, const void* b_prod, c
     }
     if (st == LD_OK) st = ln_fold_launch(wr, N, C, (const half_t*)gamma, (const half_t*)beta, br, w2, b2, wsum, op.ex.stream);
     if (st != LD_OK) return st;
-    int parts = 0;
     GemmParams a = linear_params((const half_t*)x, C, (const half_t*)w_prod, (const half_t*)b_prod, M, C, C, (half_t*)t_out);
     a.R = (const half_t*)residual;   // (the residual stream itself in Run::transformer: t += ...)
-    ln_producer(a, stat, &parts);
-    op.ex.gemm(a);
+    ln_producer(a, stat);
+    const int parts = op.ex.gemm(a).stat_parts;
     GemmParams b = linear_params((const half_t*)t_out, C, w2, b2, M, N, C, (half_t*)y, geglu ? 2 : 0, bn);
     ln_consumer(b, stat, parts, M, C, eps, wsum);
     op.ex.gemm(b);   // (not launched when the producer failed)

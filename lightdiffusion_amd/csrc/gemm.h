@@ -55,8 +55,7 @@ struct GemmParams {
     size_t partial_bytes = 0;
     // ---- LayerNorm folded into the contractions around it (v3 / v4 kernels, no split-K; unet.hip "ln fold"):
     //   producer (the GEMM that writes the residual stream): per output row and N tile, (sum, sum of squares) of the fp16 outputs
-    float* stat_out = nullptr;       // [tiles_n][M][2] floats
-    int* stat_parts_out = nullptr;   // host int: gemm_run stores GemmPlan::stat_parts, the number of N tiles (parts) it used
+    float* stat_out = nullptr;       // [tiles_n][M][2] floats, tiles_n = GemmPlan::stat_parts
     //   consumer (a projection of LN(x), with gamma folded into W and beta into the bias at load time):
     //   out = rstd_row * (acc - mu_row * wsum[n]) + bias'[n]; with ln_swapped the LN rows are this GEMM's COLUMNS (V^T = Wv · x^T)
     const float* ln_stat = nullptr;  // the producer's stat_out
@@ -74,10 +73,9 @@ struct GemmParams {
     // ---- GroupNorm statistics of THIS contraction's output, emitted by its split-K second pass (the reduce kernel touches every output
     //   element anyway): per (image, pixel chunk, group) partial (sum, sum of squares) in exactly the layout, thread mapping and summation
     //   order of norm.hip's gn_stats_kernel, so the GroupNorm that follows skips its statistics launch and produces the same bits.
-    //   Honoured only when the launch splits over K (otherwise *gn_part_done stays 0 and the caller runs the statistics pass).
+    //   Honoured only when the launch splits over K (otherwise GemmPlan::gn_chunks is 0 and the caller runs the statistics pass).
     float* gn_part = nullptr;          // [n_img][gn_P][32][2] floats
     int gn_P = 0, gn_ppb = 0, gn_HW = 0;
-    int* gn_part_done = nullptr;       // host int, set to the number of pixel chunks per image of the partials that were written (0: none)
     // ---- row-resident small-M convolution (conv8.hip)
     const half_t* W8 = nullptr;  // the weights in conv8's own layout (conv8_repack_launch): required for that kernel
     //   its in-launch reduction of the channel-slab partial sums needs >= 4 * (N / 80) zeroed ints that it leaves zeroed (self-resetting)
@@ -109,21 +107,20 @@ struct GemmPlan {
     unsigned grid_x = 0, grid_z = 1;
     int reduce = GRD_NONE;
     // ---- what the callers need to know
-    int stat_parts = 0;          // LayerNorm-statistic parts per row the launch writes to stat_out (-> *stat_parts_out)
-    int gn_chunks = 0;           // pixel chunks per image of the GroupNorm partials it writes to gn_part (-> *gn_part_done); 0: none
+    int stat_parts = 0;          // LayerNorm-statistic parts per row the launch writes to stat_out
+    int gn_chunks = 0;           // pixel chunks per image of the GroupNorm partials it writes to gn_part; 0: none
     bool halo_tile = false;      // runs on the halo-tile kernel
     bool can_fuse_groupnorm = false;   // (asked with gn_offer) the halo-tile kernel takes gn_scale / gn_shift here, and the fusion pays
     bool takes_skip_segment = false;   // a 3x3 convolution on a tap-major kernel (128 x 160 / 256 x 320 implicit GEMM) or on the halo-tile kernel's
                                        // 256 x 320 tiles of whole <= 64-pixel rows: S1 / S2 can be appended
-    const char* kernel = "";     // profile name of what gemm_run dispatches, the reduce pass included
+    const char* kernel = "";     // profile name of what gemm_run dispatches, the reduce pass included ("" where status is not LD_OK: nothing is)
 };
 // gn_offer: the caller holds a GroupNorm (+SiLU) in front of this 3x3 convolution and sets gn_scale / gn_shift before gemm_run if
 // can_fuse_groupnorm comes back true.  The plan is that of p with both set; where the fusion is not available or does not pay, status is
 // LD_ERR_ARG (gemm_launch's answer to a gn_scale it cannot honour) and the caller plans the convolution of the normalised tensor instead.
 GemmPlan gemm_plan(const GemmParams& p, bool gn_offer = false);
-int gemm_run(const GemmParams& p, const GemmPlan& plan, hipStream_t stream);
+int gemm_run(const GemmParams& p, const GemmPlan& plan, hipStream_t stream);   // (launches only: writes no host memory)
 inline int gemm_launch(const GemmParams& p, hipStream_t stream) { return gemm_run(p, gemm_plan(p), stream); }
-const char* gemm_last_kernel_name();   // kernel instantiation the calling thread's last gemm_run dispatched ("" = none)
 
 // conv8.hip: row-resident 3x3 convolution for the two-image (batch-1 CFG pair) 16x16 / 8x8 levels.  conv8_plan: gemm_plan's question whether
 // this convolution runs there (p.W8, p.partial and p.sync set) and with which slab split; conv8_launch: gemm_run's launch with that split.

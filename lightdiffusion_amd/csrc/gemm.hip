@@ -11,6 +11,45 @@
 
 namespace {
 
+// the sum of a launch's split-K slabs for eight adjacent columns (`base`: the columns in slab 0; slabs `slab` floats apart): four slabs per
+// batch of loads, summed in slab order (a split of 16 read one slab after the other is 16 memory latencies in a row: the reduce launches of
+// the batch-1 step were latency-, not bandwidth-bound).  Returned by value: through a pointer to the caller's array the compiler keeps eight
+// scalar accumulators and pairs them into two-wide adds, where both second passes had one eight-wide accumulator
+struct F8 { float v[8]; };
+__device__ __forceinline__ F8 slab_sum8(const float* base, long long slab, int splitk) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    int s = 0;
+    for (; s + 4 <= splitk; s += 4) {
+        f32x4 x0[4], x1[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            x0[u] = *reinterpret_cast<const f32x4*>(base + (s + u) * slab);
+            x1[u] = *reinterpret_cast<const f32x4*>(base + (s + u) * slab + 4);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[j] += x0[u][j];
+                v[4 + j] += x1[u][j];
+            }
+    }
+    for (; s < splitk; ++s) {
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + s * slab), x1 = *reinterpret_cast<const f32x4*>(base + s * slab + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] += x0[j];
+            v[4 + j] += x1[j];
+        }
+    }
+    F8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r.v[j] = v[j];
+    return r;
+}
+
 // split-K second pass: sum the fp32 slabs and run the same epilogue
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, int bn) {
     const int out_n = p.act == 2 ? p.N / 2 : p.N;
@@ -41,36 +80,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p, 
             epilogue_store8(p, 0, m, no, 0, v);
         } else {
             const int n = cc * 8;
+            const F8 r = slab_sum8(p.partial + (long long)m * p.N + n, (long long)p.M * p.N, p.splitk);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = 0.f;
-            // four slabs per batch of loads, summed in slab order (a split of 16 read one slab after the other is 16 memory latencies in a
-            // row: the reduce launches of the batch-1 step were latency-, not bandwidth-bound)
-            const float* base = p.partial + (long long)m * p.N + n;
-            const long long slab = (long long)p.M * p.N;
-            int s = 0;
-            for (; s + 4 <= p.splitk; s += 4) {
-                f32x4 x0[4], x1[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    x0[u] = *reinterpret_cast<const f32x4*>(base + (s + u) * slab);
-                    x1[u] = *reinterpret_cast<const f32x4*>(base + (s + u) * slab + 4);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        v[j] += x0[u][j];
-                        v[4 + j] += x1[u][j];
-                    }
-            }
-            for (; s < p.splitk; ++s) {
-                const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + s * slab), x1 = *reinterpret_cast<const f32x4*>(base + s * slab + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[j] += x0[j];
-                    v[4 + j] += x1[j];
-                }
-            }
+            for (int j = 0; j < 8; ++j) v[j] = r.v[j];
             epilogue_store8(p, 0, m, n, n, v);
         }
     }
@@ -95,34 +107,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const GemmParams 
         for (int j = 0; j < 8; ++j) s[j] = ss[j] = 0.f;
         for (int pix = p_begin + prow; pix < p_end; pix += rows_par) {
             const int m = n * p.gn_HW + pix;
-            const float* base = p.partial + (long long)m * p.N + c0;
             float v[8];
+            const F8 r = slab_sum8(p.partial + (long long)m * p.N + c0, slab_stride, p.splitk);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = 0.f;
-            int sp = 0;
-            for (; sp + 4 <= p.splitk; sp += 4) {
-                f32x4 x0[4], x1[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    x0[u] = *reinterpret_cast<const f32x4*>(base + (sp + u) * slab_stride);
-                    x1[u] = *reinterpret_cast<const f32x4*>(base + (sp + u) * slab_stride + 4);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        v[j] += x0[u][j];
-                        v[4 + j] += x1[u][j];
-                    }
-            }
-            for (; sp < p.splitk; ++sp) {
-                const f32x4 x0 = *reinterpret_cast<const f32x4*>(base + sp * slab_stride), x1 = *reinterpret_cast<const f32x4*>(base + sp * slab_stride + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[j] += x0[j];
-                    v[4 + j] += x1[j];
-                }
-            }
+            for (int j = 0; j < 8; ++j) v[j] = r.v[j];
             epilogue_store8(p, 0, m, c0, c0, v);                       // (v comes back as the values before the fp16 rounding)
             float f[8];
             unpack8(pack8(v), f);                                      // statistics of what was stored: the fp16 values, as gn_stats_kernel reads them
@@ -160,9 +148,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_gn_kernel(const GemmParams 
         }
     }
 }
-
-// name of the kernel instantiation the last gemm_run on this thread dispatched (ld_unet_profile groups by it)
-thread_local const char* t_last_kernel = "";
 
 // the profile name of a plan: composed here and nowhere else, once per distinct plan and thread.  conv6's name says what differs from the
 // 256 x 320 tile: conv6_kernel<W64,halo+groupnorm>, conv6_kernel<W128,halo,128x512>, conv6_kernel<W64,halo,256,up>, ...
@@ -211,8 +196,6 @@ extern "C" void ld_debug_gemm_override(int bm, int splitk) {
     g_force_sk = splitk;
 }
 #endif
-
-const char* gemm_last_kernel_name() { return t_last_kernel; }
 
 // the split-K second pass of a launch: the plain reduce, or the one that also emits GroupNorm partials (GemmParams::gn_part)
 static void plan_reduce(const GemmParams& p, GemmPlan* pl) {
@@ -557,16 +540,12 @@ GemmPlan gemm_plan(const GemmParams& pin, bool gn_offer) {
 }
 
 int gemm_run(const GemmParams& pin, const GemmPlan& pl, hipStream_t stream) {
-    t_last_kernel = "";   // nothing dispatched until the route below launches
     if (pl.status != LD_OK) return pl.status;
     if (pl.gn != (pin.gn_scale != nullptr) || (pl.gn && pin.gn_shift == nullptr)) return LD_ERR_ARG;   // (a plan made with gn_offer, run without the operands — or the reverse)
     GemmParams p = pin;
-    if (p.stat_parts_out != nullptr) *p.stat_parts_out = pl.stat_parts;
-    if (p.gn_part_done != nullptr) *p.gn_part_done = pl.gn_chunks;
     if (p.conv && p.pad < 0) p.pad = p.ksize >> 1;
     if (p.n_valid <= 0 || p.n_valid > p.N) p.n_valid = p.N;
     const dim3 grid(pl.grid_x, 1, pl.grid_z);
-    t_last_kernel = pl.kernel;
     switch (pl.route) {
         case GR_CONV8:
             if (const int st = conv8_launch(p, pl.c8_S, stream); st != LD_OK) return st;

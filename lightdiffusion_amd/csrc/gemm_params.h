@@ -43,22 +43,18 @@ inline GemmParams linear_params(const half_t* x, int lda, const half_t* w, const
 }
 
 // GroupNorm partial statistics of p's output (gemm.h gn_part), n images of HW pixels, for the GroupNorm that reads the output next: where the
-// launch can emit them (its split-K second pass, the halo tile's epilogue, the row-resident kernel) *done receives the chunk count per
-// image and that GroupNorm skips its statistics launch; otherwise *done stays 0
-inline void want_gn_partials(GemmParams& p, int n, int HW, float* buf, int* done) {
+// launch can emit them (its split-K second pass, the halo tile's epilogue, the row-resident kernel) its plan's gn_chunks is the chunk count
+// per image and that GroupNorm skips its statistics launch; otherwise gn_chunks is 0
+inline void want_gn_partials(GemmParams& p, int n, int HW, float* buf) {
     p.gn_part = buf;
     p.gn_P = gn_num_chunks(n, HW);
     p.gn_HW = HW;
     p.gn_ppb = (HW + p.gn_P - 1) / p.gn_P;
-    p.gn_part_done = done;
 }
 // ... from the kernels that sum what they store (halo-tile epilogue, row-resident kernel) only: without the chunk geometry a split over K
 // keeps its plain second pass (gemm.hip plan_reduce asks for gn_P).  The VAE's form; not equivalent to the one above, which would move a
 // convolution of the VAE that splits over K onto the reduce pass that also writes statistics.
-inline void want_gn_tile_partials(GemmParams& p, float* buf, int* done) {
-    p.gn_part = buf;
-    p.gn_part_done = done;
-}
+inline void want_gn_tile_partials(GemmParams& p, float* buf) { p.gn_part = buf; }
 
 // A 1x1 convolution over the raw sources (s1, sc1) and (s2, sc2; may be null / 0) of the output's size, appended to the 3x3 convolution p
 // as a second K segment (gemm.h S1 / S2): wfold = [W | Wskip] ([N][K + sc1 + sc2]) and bfold = b + bskip (skip_fold_launch).  The sum
@@ -73,11 +69,8 @@ inline void add_skip_segment(GemmParams& p, const half_t* s1, int sc1, const hal
 }
 
 // LayerNorm fold (gemm.h stat_out / ln_stat).  Producer: the GEMM that writes the residual stream also writes per-row (sum, sum of squares)
-// partials of its fp16 outputs to `stat`, and the number of parts per row it used to *parts_out
-inline void ln_producer(GemmParams& p, float* stat, int* parts_out) {
-    p.stat_out = stat;
-    p.stat_parts_out = parts_out;
-}
+// partials of its fp16 outputs to `stat`, in as many parts per row as its plan's stat_parts says
+inline void ln_producer(GemmParams& p, float* stat) { p.stat_out = stat; }
 // Consumer: a projection of LayerNorm(x; eps) over C channels on the gamma / beta-folded weights (ln_fold_launch; wsum their fp32 row sums),
 // finished on the accumulators from the producer's `parts` partials per row of its `rows` rows
 inline void ln_consumer(GemmParams& p, const float* stat, int parts, int rows, int C, float eps, const float* wsum) {

@@ -183,6 +183,16 @@ inline void note_kernel(std::string* sink, const char* name) {
     *sink += name;
 }
 
+// GroupNorm partial statistics that a tensor's producer left for the GroupNorm that reads the tensor next (gemm.h gn_part: [n][chunks][32][2]
+// floats), or none.  The only way statistics travel: gn_stats makes one from the buffer a contraction was asked to fill (want_gn_partials /
+// want_gn_tile_partials) and the gn_chunks of the plan that Exec::gemm / Exec::gn_silu_conv returned, and it is empty where that is 0.
+struct GnStats {
+    float* part = nullptr;
+    int chunks = 0;   // pixel chunks per image
+    explicit operator bool() const { return chunks > 0; }
+};
+inline GnStats gn_stats(float* buf, int chunks) { return buf != nullptr && chunks > 0 ? GnStats{buf, chunks} : GnStats{}; }
+
 struct Exec {
     Timing* timing = nullptr;
     hipStream_t stream = nullptr;
@@ -240,7 +250,7 @@ struct Exec {
         }
         t_end(kernel_name);
     }
-    // ... under the name one of the launchers' last-kernel functions (gemm_last_kernel_name ...) gives after fn ran
+    // ... under the name one of the launchers' last-kernel functions (attention_last_kernel_name ...) gives after fn ran
     template <class F>
     void launch(int cls, double fl, const char* what, long long a, long long b, long long d, long long e, const char* (*last_kernel)(), F&& fn) {
         const bool run = open(cls, fl, 1, what, a, b, d, e);
@@ -267,63 +277,68 @@ struct Exec {
         with_scratch(p);
         return gemm_plan(p);
     }
-    // `planned`: gemm_plan of p with this executor's scratch, where the caller already asked for it
-    void gemm(GemmParams p, const GemmPlan* planned = nullptr) {
+    // `planned`: gemm_plan of p with this executor's scratch, where the caller already asked for it.  Returns the plan it ran, which says what
+    // the launch left behind (kernel, stat_parts, gn_chunks): a default plan — no kernel, no statistics — where it launched nothing (a dry
+    // run, or behind a launch that failed), so a dry run sizes the arena for a consumer that computes its own statistics
+    GemmPlan gemm(GemmParams p, const GemmPlan* planned = nullptr) {
         with_scratch(p);
-        launch(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, 2.0 * p.M * (double)p.N * p.K * p.batch,
-               p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"), p.M, p.N, p.K, p.batch, gemm_last_kernel_name, [&] {
-                   const GemmPlan pl = planned != nullptr ? *planned : gemm_plan(p);
-                   if (before_gemm != nullptr)
-                       if (const int st = before_gemm(p, pl, before_gemm_arg, stream); st != LD_OK) return st;
-                   const int st = gemm_run(p, pl, stream);
-                   note_kernel(names, gemm_last_kernel_name());
-                   return st;
-               });
+        GemmPlan pl;
+        if (open(p.conv && p.ksize == 3 ? KC_CONV3 : KC_GEMM, 2.0 * p.M * (double)p.N * p.K * p.batch, 1,
+                 p.conv ? (p.ksize == 3 ? "conv3" : "conv1") : (p.act == 2 ? "geglu" : "gemm"), p.M, p.N, p.K, p.batch)) {
+            pl = planned != nullptr ? *planned : gemm_plan(p);
+            int st = before_gemm != nullptr ? before_gemm(p, pl, before_gemm_arg, stream) : LD_OK;
+            if (st == LD_OK) st = gemm_run(p, pl, stream);
+            else pl = GemmPlan();
+            note(st);
+            note_kernel(names, pl.kernel);
+            note_kernel(all_names, pl.kernel);
+        }
+        t_end(pl.kernel);
+        return pl;
     }
     // would gemm() run this 3x3 convolution on a kernel that takes a second K segment (gemm.h S1 / S2)?
     bool conv_takes_skip_segment(const GemmParams& p) const { return plan(p).takes_skip_segment; }
-    // `ready` / `ready_P`: partial statistics the producer already wrote (gemm.h gn_part; ready_P pixel chunks per image): the statistics
-    // launch is skipped
+    // a buffer for the GroupNorm partial statistics of n images of HW pixels (gemm.h gn_part, norm.hip)
+    float* gn_buffer(int n, int HW) { return reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n, HW))); }
+    // `ready`: partial statistics the producer already wrote: the statistics launch is skipped
     void groupnorm(const half_t* x1, int C1, const half_t* x2, int C2, int n, int HW, const half_t* g, const half_t* b, float eps,
-                   int silu, half_t* y, float* ready = nullptr, int ready_P = 0) {
+                   int silu, half_t* y, GnStats ready = {}) {
         const size_t m = arena->mark();
-        if (ready_P <= 0) ready = nullptr;
-        float* ws = ready != nullptr ? ready : reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n, HW)));
-        launch(KC_GNORM, 0.0, "groupnorm", n, HW, C1 + C2, silu, ready != nullptr ? "gn_apply_kernel" : "gn_stats_kernel+gn_apply_kernel",
-               [&] { return groupnorm_launch(x1, C1, x2, C2, n, HW, g, b, eps, silu, y, ws, stream, ready != nullptr ? ready_P : 0); }, ready != nullptr ? 1 : 2);
+        float* ws = ready ? ready.part : gn_buffer(n, HW);
+        launch(KC_GNORM, 0.0, "groupnorm", n, HW, C1 + C2, silu, ready ? "gn_apply_kernel" : "gn_stats_kernel+gn_apply_kernel",
+               [&] { return groupnorm_launch(x1, C1, x2, C2, n, HW, g, b, eps, silu, y, ws, stream, ready.chunks); }, ready ? 1 : 2);
         arena->release(m);
     }
     // GroupNorm(32) + SiLU feeding a 3x3 convolution.  When the convolution runs on the halo-tile kernel the normalisation is fused
     // into its A operand: only the statistics pass + a tiny finalize run here (scale / shift per image and channel), the conv reads the
     // RAW tensor(s) — no normalised copy is written or read back.  Otherwise: the two-pass GroupNorm into `g` (caller-provided), then the conv.
-    // `p`: the convolution with A / A2 = the RAW sources; returns through p.C as usual.
-    // `ready` / `ready_P`: GroupNorm partial statistics of the input that its producer already wrote (see groupnorm)
-    void gn_silu_conv(GemmParams p, int n_img, int HW, const half_t* gamma, const half_t* beta, float eps, half_t* g, float* ready = nullptr, int ready_P = 0) {
+    // `p`: the convolution with A / A2 = the RAW sources; returns through p.C as usual, and the convolution's plan as gemm() does.
+    // `ready`: GroupNorm partial statistics of the input that its producer already wrote (see groupnorm)
+    GemmPlan gn_silu_conv(GemmParams p, int n_img, int HW, const half_t* gamma, const half_t* beta, float eps, half_t* g, GnStats ready = {}) {
         with_scratch(p);
-        if (ready_P <= 0) ready = nullptr;
         const GemmPlan fused = gemm_plan(p, /*gn_offer=*/true);
         if (fused.can_fuse_groupnorm) {
             const int C = p.C1 + p.C2;
             const size_t m = arena->mark();
-            float* ws = ready != nullptr ? ready : reinterpret_cast<float*>(arena->alloc(groupnorm_workspace_bytes(n_img, HW)));
+            float* ws = ready ? ready.part : gn_buffer(n_img, HW);
             float* scale = reinterpret_cast<float*>(arena->alloc((size_t)n_img * C * sizeof(float)));
             float* shift = reinterpret_cast<float*>(arena->alloc((size_t)n_img * C * sizeof(float)));
-            launch(KC_GNORM, 0.0, "gn_stats", n_img, HW, C, 1, ready != nullptr ? "gn_finalize_kernel" : "gn_stats_kernel+gn_finalize_kernel", [&] {
-                return groupnorm_scale_shift_launch(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, ws, scale, shift, stream, ready != nullptr ? ready_P : 0);
-            }, ready != nullptr ? 1 : 2);
+            launch(KC_GNORM, 0.0, "gn_stats", n_img, HW, C, 1, ready ? "gn_finalize_kernel" : "gn_stats_kernel+gn_finalize_kernel", [&] {
+                return groupnorm_scale_shift_launch(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, ws, scale, shift, stream, ready.chunks);
+            }, ready ? 1 : 2);
             p.gn_scale = scale;
             p.gn_shift = shift;
             p.gn_silu = 1;
-            gemm(p, &fused);
+            const GemmPlan ran = gemm(p, &fused);
             arena->release(m);
-            return;
+            return ran;
         }
-        groupnorm(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, 1, g, ready, ready_P);
+        groupnorm(p.A, p.C1, p.A2, p.C2, n_img, HW, gamma, beta, eps, 1, g, ready);
         p.A = g;
         p.A2 = nullptr;
         p.C1 = p.C1 + p.C2;
         p.C2 = 0;
-        gemm(p);
+        return gemm(p);
     }
     void attention(const AttnParams& p) {
         launch(KC_ATTN, 4.0 * p.B * p.H * (double)p.Lq * p.Lk * p.d, "attention", (long long)p.B * p.H, p.Lq, p.Lk, p.d, attention_last_kernel_name, [&] {

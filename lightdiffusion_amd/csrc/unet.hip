@@ -42,8 +42,7 @@ struct Layer {
 struct Feat {
     half_t* p;
     int C, H, W;
-    float* gn = nullptr;   // GroupNorm partial statistics of this tensor, written by its producer's epilogue ([n][gnP][32][2]; gemm.h gn_part), or null
-    int gnP = 0;
+    GnStats stats;         // GroupNorm partial statistics of this tensor, where its producer wrote them
 };
 
 }  // namespace
@@ -298,14 +297,13 @@ struct Run {
         return p;
     }
 
-    // stats / stats_done: GroupNorm partial statistics of the output, where the launch writes them (want_gn_partials)
-    half_t* conv3(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int wslot, int bslot,
-                  int cout, half_t* out, int ksize = 3, float* stats = nullptr, int* stats_done = nullptr, const half_t* wup = nullptr) {
+    // stats: a buffer for the GroupNorm partial statistics of the output (want_gn_partials); returns them where the launch wrote them
+    GnStats conv3(const half_t* x1, int C1, const half_t* x2, int C2, int Hs, int Ws, int Hv, int Wv, int stride, int wslot, int bslot,
+                  int cout, half_t* out, int ksize = 3, float* stats = nullptr, const half_t* wup = nullptr) {
         GemmParams p = conv_of(x1, C1, x2, C2, Hs, Ws, Hv, Wv, stride, ksize, wslot, bslot, cout, out);
         p.Wup = wup;
-        if (stats != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, stats, stats_done);
-        ex.gemm(p);
-        return out;
+        if (stats != nullptr) want_gn_partials(p, n, p.Ho * p.Wo, stats);
+        return gn_stats(stats, ex.gemm(p).gn_chunks);
     }
 
     void linear(const half_t* x, int lda, int wslot, int bslot, const half_t* R, half_t* y, int M, int N, int K, int act = 0, int bn = 0) {
@@ -315,14 +313,13 @@ struct Run {
     }
 
     // ResBlock1._forward, LD.py:5273-5287.  Input = channel concat of (x1,C1) and (x2,C2).
-    // in_stats / in_P: GroupNorm partial statistics of x1 from its producer (only usable when there is no second source)
-    Feat resblock(const ResW& r, const half_t* x1, int C1, const half_t* x2, int C2, int H, int W, float* in_stats = nullptr, int in_P = 0) {
+    // in_stats: GroupNorm partial statistics of x1 from its producer (only usable when there is no second source)
+    Feat resblock(const ResW& r, const half_t* x1, int C1, const half_t* x2, int C2, int H, int W, GnStats in_stats = {}) {
         Arena& ar = *ex.arena;
         const size_t M = (size_t)na() * H * W;                   // rows the tensors are sized for (the kernels run on n * H * W)
         half_t* out = ar.halfs(M * r.cout);
-        float* gno = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(na(), H * W)));   // statistics of `out` (for the next GroupNorm)
-        int gno_done = 0;
-        if (C2 != 0) in_stats = nullptr;
+        float* gno = ex.gn_buffer(na(), H * W);                  // statistics of `out` (for the next GroupNorm)
+        if (C2 != 0) in_stats = {};
         const size_t mk = ar.mark();
         // in_layers: GroupNorm + SiLU + conv3x3 (+ the time-embedding row vector); out_layers: GroupNorm + SiLU + conv3x3 (+ skip).
         // Each GroupNorm is fused into its convolution's A operand where that convolution runs on the halo-tile kernel
@@ -348,41 +345,35 @@ struct Run {
             }
         }
         // the GroupNorm statistics of h1 (out_layers' norm) come from conv1's split-K second pass where it has one (gemm.h gn_part)
-        float* gnp = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(na(), H * W)));
-        int gnp_done = 0;
-        {
-            GemmParams c1 = conv(x1, C1, x2, C2, r.c1_w, r.c1_b, h1);
-            c1.rowvec = emb_all + r.emb_off; c1.ldrv = u->emb_total;
-            want_gn_partials(c1, n, H * W, gnp, &gnp_done);
-            ex.gn_silu_conv(c1, n, H * W, P(r.gn1_g), P(r.gn1_b), 1e-5f, g1, in_stats, in_P);
-        }
+        float* gnp = ex.gn_buffer(na(), H * W);
+        GemmParams c1 = conv(x1, C1, x2, C2, r.c1_w, r.c1_b, h1);
+        c1.rowvec = emb_all + r.emb_off; c1.ldrv = u->emb_total;
+        want_gn_partials(c1, n, H * W, gnp);
+        const GnStats h1_stats = gn_stats(gnp, ex.gn_silu_conv(c1, n, H * W, P(r.gn1_g), P(r.gn1_b), 1e-5f, g1, in_stats).gn_chunks);
         half_t* g2 = g1;   // g1 is dead once conv1 has consumed it (stream order); reuse when it is large enough
         if (r.cout > r.cin) g2 = ar.halfs(M * r.cout);
-        {
-            GemmParams c2 = conv(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, out);
-            if (fold_skip)
-                add_skip_segment(c2, x1, C1, x2, C2, reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_w), reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_b));
-            else
-                c2.R = skip;
-            want_gn_partials(c2, n, H * W, gno, &gno_done);
-            ex.gn_silu_conv(c2, n, H * W, P(r.gn2_g), P(r.gn2_b), 1e-5f, g2, gnp_done ? gnp : nullptr, gnp_done);
-        }
+        GemmParams c2 = conv(h1, r.cout, nullptr, 0, r.c2_w, r.c2_b, out);
+        if (fold_skip)
+            add_skip_segment(c2, x1, C1, x2, C2, reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_w), reinterpret_cast<const half_t*>(u->fold_base + r.f_c2_b));
+        else
+            c2.R = skip;
+        want_gn_partials(c2, n, H * W, gno);
+        const GnStats out_stats = gn_stats(gno, ex.gn_silu_conv(c2, n, H * W, P(r.gn2_g), P(r.gn2_b), 1e-5f, g2, h1_stats).gn_chunks);
         ar.release(mk);
-        return {out, r.cout, H, W, gno_done ? gno : nullptr, gno_done};
+        return {out, r.cout, H, W, out_stats};
     }
 
     // SpatialTransformer.forward (LD.py:4239-4262) around BasicTransformerBlock._forward (LD.py:4117-4162)
-    Feat transformer(const StW& s, const half_t* x, int H, int W, float* in_stats = nullptr, int in_P = 0) {
+    Feat transformer(const StW& s, const half_t* x, int H, int W, GnStats in_stats = {}) {
         Arena& ar = *ex.arena;
         const int C = s.c, L = H * W, heads = u->cfg.num_heads, d = C / heads;
         int M = n * L;                                           // rows the kernels run on (doubles at the split of a CFG pair, below)
         const size_t Ma = (size_t)na() * L;                      // rows the tensors are sized for
         half_t* out = ar.halfs(Ma * C);
-        float* gno = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(na(), L)));   // statistics of `out` (for the next GroupNorm)
-        int gno_done = 0;
+        float* gno = ex.gn_buffer(na(), L);                      // statistics of `out` (for the next GroupNorm)
         const size_t mk = ar.mark();
         half_t* g = ar.halfs(Ma * C);
-        ex.groupnorm(x, C, nullptr, 0, n, L, P(s.gn_g), P(s.gn_b), 1e-6f, 0, g, in_stats, in_P);
+        ex.groupnorm(x, C, nullptr, 0, n, L, P(s.gn_g), P(s.gn_b), 1e-6f, 0, g, in_stats);
         half_t* t = ar.halfs(Ma * C);
         half_t* qkv = ar.halfs(Ma * 3 * C);
         half_t* ao = ar.halfs(Ma * C);
@@ -396,8 +387,8 @@ struct Run {
         auto producer = [&](const half_t* x_, int wslot, int bslot, const half_t* R) {   // t = x_ W^T + b (+ R), with row stats
             GemmParams p = linear_params(x_, C, P(wslot), P(bslot), M, C, C, t);
             p.R = R;
-            ln_producer(p, stat, &parts);
-            ex.gemm(p);
+            ln_producer(p, stat);
+            parts = ex.gemm(p).stat_parts;
         };
         // out = LN(t) W^T + b on the folded weights / bias / row sums at these offsets of the fold buffer
         auto consumer = [&](size_t w_off, size_t b_off, size_t wsum_off, int N, half_t* dst, int act = 0, int bn = 0) {
@@ -456,16 +447,14 @@ struct Run {
         // ---- GEGLU feed-forward: x = ff2(a * gelu(gate)) + x
         ff = ar.halfs(Ma * 4 * C);
         consumer(s.f_ff1_w, s.f_ff1_b, s.f_ff1_s, 8 * C, ff, 2, s.bn);
-        {
-            // out = x + proj_out(t + ff2(ff)) as one contraction over [ff | t] (K = 5C) against the folded [Wpo W2 | Wpo] (misc.hip)
-            GemmParams p = conv_params(ff, 4 * C, t, C, n, H, W, H, W, 1, 1, reinterpret_cast<const half_t*>(fb + s.f_mo_w),
-                                       reinterpret_cast<const half_t*>(fb + s.f_mo_b), C, out);
-            p.R = x;
-            want_gn_partials(p, n, L, gno, &gno_done);
-            ex.gemm(p);
-        }
+        // out = x + proj_out(t + ff2(ff)) as one contraction over [ff | t] (K = 5C) against the folded [Wpo W2 | Wpo] (misc.hip)
+        GemmParams p = conv_params(ff, 4 * C, t, C, n, H, W, H, W, 1, 1, reinterpret_cast<const half_t*>(fb + s.f_mo_w),
+                                   reinterpret_cast<const half_t*>(fb + s.f_mo_b), C, out);
+        p.R = x;
+        want_gn_partials(p, n, L, gno);
+        const GnStats out_stats = gn_stats(gno, ex.gemm(p).gn_chunks);
         ar.release(mk);
-        return {out, C, H, W, gno_done ? gno : nullptr, gno_done};
+        return {out, C, H, W, out_stats};
     }
 };
 
@@ -558,12 +547,12 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         for (const Layer& L : layers) {
             switch (L.kind) {
                 case L_RES: {
-                    f = R.resblock(u->res[L.idx], f.p, f.C, x2, C2, f.H, f.W, f.gn, f.gnP);
+                    f = R.resblock(u->res[L.idx], f.p, f.C, x2, C2, f.H, f.W, f.stats);
                     x2 = nullptr;
                     C2 = 0;
                     break;
                 }
-                case L_ST: f = R.transformer(u->st[L.idx], f.p, f.H, f.W, f.gn, f.gnP); break;
+                case L_ST: f = R.transformer(u->st[L.idx], f.p, f.H, f.W, f.stats); break;
                 case L_DOWN: {
                     const ConvW& cw = u->convs[L.idx];
                     const int Ho = (f.H - 1) / 2 + 1, Wo = (f.W - 1) / 2 + 1;
@@ -573,10 +562,8 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                         R.n = n;
                     }
                     half_t* o = ar.halfs((size_t)n * Ho * Wo * cw.cout);
-                    float* gno = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(n, Ho * Wo)));
-                    int gno_done = 0;
-                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 2, cw.w, cw.b, cw.cout, o, 3, gno, &gno_done);
-                    f = {o, cw.cout, Ho, Wo, gno_done ? gno : nullptr, gno_done};
+                    float* gno = ex.gn_buffer(n, Ho * Wo);
+                    f = {o, cw.cout, Ho, Wo, R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 2, cw.w, cw.b, cw.cout, o, 3, gno)};
                     break;
                 }
                 case L_UP: {   // Upsample1: nearest resize to the next skip's H x W, then conv (LD.py:5141-5152)
@@ -586,7 +573,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                     // (the folded weights are an offer: gemm_plan takes them for an exact 2x resize above the row-resident kernel's batch.  The launch is
                     // counted as the 3x3 convolution it implements — last_flops is algorithmic work — and executes 4/9 of it)
                     const half_t* wup = (u->fold_base != nullptr && cw.f_up >= 0) ? reinterpret_cast<const half_t*>(u->fold_base + cw.f_up) : nullptr;
-                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, o, 3, nullptr, nullptr, wup);
+                    R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, Hv, Wv, 1, cw.w, cw.b, cw.cout, o, 3, nullptr, wup);
                     f = {o, cw.cout, Hv, Wv};
                     break;
                 }
@@ -616,8 +603,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
             R.dup(const_cast<half_t*>(f.p), (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
             R.pair_pending = false;
             R.n = n;
-            f.gn = nullptr;                                      // (its statistics cover the first half of the batch only)
-            f.gnP = 0;
+            f.stats = {};                                        // (its statistics cover the first half of the batch only)
         }
         hs.push_back(f);
     }
@@ -635,7 +621,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     }
     {   // out: GroupNorm + SiLU, 3x3 conv to 4 channels fused with EPS.calculate_denoised, back to fp32 NCHW
         half_t* g = ar.halfs((size_t)n * f.H * f.W * f.C);
-        ex.groupnorm(f.p, f.C, nullptr, 0, n, f.H * f.W, u->pt.ptr(u->outn_g), u->pt.ptr(u->outn_b), 1e-5f, 1, g, f.gn, f.gnP);
+        ex.groupnorm(f.p, f.C, nullptr, 0, n, f.H * f.W, u->pt.ptr(u->outn_g), u->pt.ptr(u->outn_b), 1e-5f, 1, g, f.stats);
         SmallConvOutArgs a;
         a.x = g; a.w = u->pt.ptr(u->outc_w); a.b = u->pt.ptr(u->outc_b);
         a.N = n; a.H = f.H; a.W = f.W; a.Cin = f.C; a.Cout = c.out_channels;

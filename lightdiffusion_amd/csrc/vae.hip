@@ -148,83 +148,68 @@ int build(ld_vae* v) {
     return t.finalize();
 }
 
+// A tensor with the GroupNorm partial statistics its producer left (a convolution's epilogue sums what it stores: gemm.h gn_part), or
+// none: the GroupNorm that reads the tensor next skips its statistics pass over it
+struct VFeat {
+    half_t* p;
+    GnStats stats;
+};
+
 struct VRun {
     ld_vae* v;
     Exec ex;
     int n;
     half_t* P(int s) const { return v->pt.ptr(s); }
 
-    // GroupNorm partial statistics of the tensor a convolution just wrote (its epilogue sums what it stores: gemm.h gn_part), for the
-    // GroupNorm that reads that tensor next: the statistics pass over it is skipped
-    const half_t* st_of = nullptr;
-    float* st_buf = nullptr;
-    int st_P = 0;
-    void gn(const half_t* x, int C, int HW, int gslot, int bslot, int silu, half_t* y) {
-        const bool ready = x == st_of && st_P > 0;
-        ex.groupnorm(x, C, nullptr, 0, n, HW, P(gslot), P(bslot), 1e-6f, silu, y, ready ? st_buf : nullptr, ready ? st_P : 0);
+    void gn(const VFeat& x, int C, int HW, int gslot, int bslot, int silu, half_t* y) {
+        ex.groupnorm(x.p, C, nullptr, 0, n, HW, P(gslot), P(bslot), 1e-6f, silu, y, x.stats);
     }
 
-    // after a convolution wrote `out`: the statistics it left (done chunks per image), or none
-    void wrote(half_t* out, float* stats, int done) {
-        if (stats != nullptr) {
-            st_of = out;
-            st_buf = stats;
-            st_P = done;
-        } else if (out == st_of) {
-            st_of = nullptr;      // (the tensor the statistics described was overwritten)
-        }
-    }
-
-    // (a stride above 1 comes with its Ho, Wo: the encoder's downsampling)
-    void conv(const half_t* x, int cin, int Hs, int Ws, int Hv, int Wv, int ksize, int wslot, int bslot, int cout, const half_t* R, half_t* out,
-              int stride = 1, int pad = -1, int Ho = 0, int Wo = 0, float* stats = nullptr) {
+    // (a stride above 1 comes with its Ho, Wo: the encoder's downsampling).  stats: a buffer for the statistics of `out`, returned with it
+    VFeat conv(const half_t* x, int cin, int Hs, int Ws, int Hv, int Wv, int ksize, int wslot, int bslot, int cout, const half_t* R, half_t* out,
+               int stride = 1, int pad = -1, int Ho = 0, int Wo = 0, float* stats = nullptr) {
         GemmParams p = conv_params(x, cin, nullptr, 0, n, Hs, Ws, Hv, Wv, stride, ksize, P(wslot), P(bslot), cout, out, pad, Ho, Wo);
         p.R = R;
-        int done = 0;
-        if (stats != nullptr) want_gn_tile_partials(p, stats, &done);
-        ex.gemm(p);
-        wrote(out, stats, done);
+        if (stats != nullptr) want_gn_tile_partials(p, stats);
+        return {out, gn_stats(stats, ex.gemm(p).gn_chunks)};
     }
 
     // GroupNorm (eps 1e-6) + swish + 3x3 convolution (norm1 -> conv1, norm2 -> conv2 of a ResnetBlock): where the convolution's output is one
     // halo tile wide (N = 256 at 256-pixel rows, N = 128 at 512-pixel rows) the normalisation is applied inside its halo loader and only the
     // statistics are finalised here (Exec::gn_silu_conv); otherwise the two-pass GroupNorm into `g`, then the convolution, as before.
-    void gn_conv(const half_t* x, int cin, int H, int W, int gslot, int bslot, half_t* g, int wslot, int cbslot, int cout, const half_t* R, half_t* out,
-                 float* stats) {
-        GemmParams p = conv_params(x, cin, nullptr, 0, n, H, W, H, W, 1, 3, P(wslot), P(cbslot), cout, out);
+    VFeat gn_conv(const VFeat& x, int cin, int H, int W, int gslot, int bslot, half_t* g, int wslot, int cbslot, int cout, const half_t* R, half_t* out,
+                  float* stats) {
+        GemmParams p = conv_params(x.p, cin, nullptr, 0, n, H, W, H, W, 1, 3, P(wslot), P(cbslot), cout, out);
         p.R = R;
-        int done = 0;
-        if (stats != nullptr) want_gn_tile_partials(p, stats, &done);
-        const bool ready = x == st_of && st_P > 0;
-        ex.gn_silu_conv(p, n, H * W, P(gslot), P(bslot), 1e-6f, g, ready ? st_buf : nullptr, ready ? st_P : 0);
-        wrote(out, stats, done);
+        want_gn_tile_partials(p, stats);
+        return {out, gn_stats(stats, ex.gn_silu_conv(p, n, H * W, P(gslot), P(bslot), 1e-6f, g, x.stats).gn_chunks)};
     }
 
     // ResnetBlock.forward, LD.py:3560-3576 (GroupNorm eps 1e-6, swish)
-    half_t* resblock(const VResW& r, const half_t* x, int H, int W) {
+    VFeat resblock(const VResW& r, const VFeat& x, int H, int W) {
         Arena& ar = *ex.arena;
         const size_t M = (size_t)n * H * W;
         half_t* out = ar.halfs(M * r.cout);
-        float* so = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(n, H * W)));   // statistics of `out` (for the next GroupNorm)
+        float* so = ex.gn_buffer(n, H * W);   // statistics of `out` (for the next GroupNorm)
         const size_t mk = ar.mark();
         half_t* g1 = ar.halfs(M * r.cin);
         half_t* h1 = ar.halfs(M * r.cout);
-        float* s1 = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(n, H * W)));
-        gn_conv(x, r.cin, H, W, r.n1_g, r.n1_b, g1, r.c1_w, r.c1_b, r.cout, nullptr, h1, s1);
+        float* s1 = ex.gn_buffer(n, H * W);
+        const VFeat h = gn_conv(x, r.cin, H, W, r.n1_g, r.n1_b, g1, r.c1_w, r.c1_b, r.cout, nullptr, h1, s1);
         half_t* g2 = r.cout <= r.cin ? g1 : ar.halfs(M * r.cout);
-        const half_t* skip = x;
+        const half_t* skip = x.p;
         if (r.nin_w >= 0) {
             // (h1 stays live until conv2 has read it — the fused GroupNorm reads the raw tensor — so the shortcut gets its own buffer)
             half_t* sk = ar.halfs(M * r.cout);
-            conv(x, r.cin, H, W, H, W, 1, r.nin_w, r.nin_b, r.cout, nullptr, sk);   // (writes no statistics; h1's stay valid)
+            conv(x.p, r.cin, H, W, H, W, 1, r.nin_w, r.nin_b, r.cout, nullptr, sk);
             skip = sk;
         }
-        gn_conv(h1, r.cout, H, W, r.n2_g, r.n2_b, g2, r.c2_w, r.c2_b, r.cout, skip, out, so);
+        const VFeat o = gn_conv(h, r.cout, H, W, r.n2_g, r.n2_b, g2, r.c2_w, r.c2_b, r.cout, skip, out, so);
         ar.release(mk);
-        return out;
+        return o;
     }
 
-    // AttnBlock.forward, LD.py:3630-3642 (one head of C channels, pytorch_attention LD.py:3591-3602)
+    // AttnBlock.forward, LD.py:3630-3642 (one head of C channels, pytorch_attention LD.py:3591-3602); its output carries no statistics
     half_t* attn(const VAttnW& aw, const half_t* x, int H, int W) {
         Arena& ar = *ex.arena;
         const int C = aw.c, L = H * W;
@@ -295,17 +280,17 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
     const ld_vae_config& c = v->cfg;
     int H = h, W = w;
     int C = v->block_in0;
-    half_t* f = ar.halfs((size_t)b * H * W * C);
+    VFeat f{ar.halfs((size_t)b * H * W * C), {}};
     {
         SmallConvInArgs a;
         a.x = z; a.pre_w = v->pt.ptr(v->pq_w); a.pre_b = v->pt.ptr(v->pq_b);
-        a.w = v->pt.ptr(v->cin_w); a.b = v->pt.ptr(v->cin_b); a.y = f;
+        a.w = v->pt.ptr(v->cin_w); a.b = v->pt.ptr(v->cin_b); a.y = f.p;
         a.N = b; a.Cin = c.z_channels; a.H = H; a.W = W; a.Cout = C;
         ex.launch(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.z_channels, "conv_in", (long long)b * H * W, C, 9 * c.z_channels, 1, "small_conv_in_kernel",
                   [&] { return small_conv_in_launch(a, stream); });
     }
     f = R.resblock(v->mid1, f, H, W);
-    f = R.attn(v->mid_attn, f, H, W);
+    f = {R.attn(v->mid_attn, f.p, H, W), {}};
     f = R.resblock(v->mid2, f, H, W);
     for (int lvl = c.num_levels - 1; lvl >= 0; --lvl) {
         for (const VResW& r : v->up[lvl]) {
@@ -314,9 +299,8 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
         }
         if (lvl != 0) {   // Upsample: nearest 2x then conv (LD.py:3498-3511), fused into the conv's loader
             half_t* o = ar.halfs((size_t)b * 4 * H * W * C);
-            float* so = reinterpret_cast<float*>(ar.alloc(groupnorm_workspace_bytes(b, 4 * H * W)));
-            R.conv(f, C, H, W, 2 * H, 2 * W, 3, v->ups_w[lvl], v->ups_b[lvl], C, nullptr, o, 1, -1, 0, 0, so);
-            f = o;
+            float* so = ex.gn_buffer(b, 4 * H * W);
+            f = R.conv(f.p, C, H, W, 2 * H, 2 * W, 3, v->ups_w[lvl], v->ups_b[lvl], C, nullptr, o, 1, -1, 0, 0, so);
             H *= 2;
             W *= 2;
         }
@@ -340,7 +324,7 @@ int run_decode(ld_vae* v, bool dry, const float* z, float* out, int b, int h, in
                     hipMemcpyAsync(v->co_pad + (size_t)32 * 9 * C, v->pt.ptr(v->co_b), c.out_ch * sizeof(half_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
                     ex.note(LD_ERR_HIP);
             }
-            ex.launch(KC_CONV3, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1, gemm_last_kernel_name,
+            ex.launch(KC_CONV3, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_out", (long long)b * H * W, c.out_ch, 9 * C, 1, qp.kernel,
                       [&] { return gemm_run(q, qp, stream); });
             ex.launch(KC_MISC, 0.0, "out_finish", (long long)b * H * W, c.out_ch, 0, 1, "vae_out_finish_kernel",
                       [&] { return vae_out_finish_launch(t8, out, (long long)b * H * W, c.out_ch, stream); });
@@ -372,10 +356,10 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
         W *= 2;
     }
     int C = c.ch;
-    half_t* f = ar.halfs((size_t)b * H * W * C);
+    VFeat f{ar.halfs((size_t)b * H * W * C), {}};
     {
         SmallConvInArgs a;
-        a.x = px; a.w = v->pt.ptr(v->e_cin_w); a.b = v->pt.ptr(v->e_cin_b); a.y = f;
+        a.x = px; a.w = v->pt.ptr(v->e_cin_w); a.b = v->pt.ptr(v->e_cin_b); a.y = f.p;
         a.N = b; a.Cin = c.out_ch; a.H = H; a.W = W; a.Cout = C;
         ex.launch(KC_MISC, 2.0 * b * H * W * C * 9.0 * c.out_ch, "conv_in", (long long)b * H * W, C, 9 * c.out_ch, 1, "small_conv_in_kernel",
                   [&] { return small_conv_in_launch(a, stream); });
@@ -390,14 +374,13 @@ int run_encode(ld_vae* v, bool dry, const float* px, float* moments, int b, int 
             // bottom/right zeros supplied by the loader's bounds check
             const int Ho = (H + 1 - 3) / 2 + 1, Wo = (W + 1 - 3) / 2 + 1;
             half_t* o = ar.halfs((size_t)b * Ho * Wo * C);
-            R.conv(f, C, H, W, H, W, 3, v->dwn_w[lvl], v->dwn_b[lvl], C, nullptr, o, 2, 0, Ho, Wo);
-            f = o;
+            f = R.conv(f.p, C, H, W, H, W, 3, v->dwn_w[lvl], v->dwn_b[lvl], C, nullptr, o, 2, 0, Ho, Wo);
             H = Ho;
             W = Wo;
         }
     }
     f = R.resblock(v->e_mid1, f, H, W);
-    f = R.attn(v->e_attn, f, H, W);
+    f = {R.attn(v->e_attn, f.p, H, W), {}};
     f = R.resblock(v->e_mid2, f, H, W);
     {
         half_t* g = ar.halfs((size_t)b * H * W * C);
