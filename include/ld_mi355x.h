@@ -488,6 +488,19 @@ int ld_op_f32_gaussian_blur(const float* src, int src_pitch, float* dst, int dst
 int ld_op_f32_paste_u8(float* canvas, int canvas_pitch, int cw, int ch, int channels, const void* tile, int tile_pitch, const float* alpha, int alpha_pitch,
                        int tw, int th, int x0, int y0, void* stream);
 
+/* ---- the masked sampler step (inpainting): the two blends upstream's KSamplerX0Inpaint makes around the model call, on fp32 NCHW latents
+ * [B][C][HW] (HW = h * w, any positive value), contiguous.  The mask is fp32 [Bm][Cm][HW] with Bm in {1, B} and Cm in {1, C}, broadcast in the
+ * kernel.  Every fp32 operation is rounded on its own, in the order written (no FMA), so a result is the bits of the expression evaluated
+ * operation by operation.  Stream-ordered, no allocation, no host read: capturable.  LD_ERR_ARG: a NULL pointer; LD_ERR_SHAPE: B, C or HW < 1,
+ * Bm not in {1, B}, Cm not in {1, C}, B * C * HW >= 2^31 (the kernels index in 32 bits).  Nothing is launched then.
+ *
+ * out = x * m + (noise * sigma[b] + latent) * (1 - m): x * m, noise * sigma, + latent, 1 - m, the product, the sum.  sigma: DEVICE floats [B], one per
+ * sample.  out may be x; it may be neither the mask, the latent nor the noise. */
+int ld_op_inpaint_in(const float* x, const float* mask, const float* latent, const float* noise, const float* sigma, float* out, int B, int C, int HW, int Bm,
+                     int Cm, void* stream);
+/* den = den * m + latent * (1 - m) in place: den * m, 1 - m, latent * that, the sum. */
+int ld_op_inpaint_out(float* den, const float* mask, const float* latent, int B, int C, int HW, int Bm, int Cm, void* stream);
+
 /* ---- CLIP text model input stage with textual-inversion vectors (CLIPEmbeddings + SDClipModel.set_up_textual_embeddings, LD.py:4394-4410, 4642-4690).
  * out[b][l] = round_fp16(float(row(ids[b*L + l])) + float(pos[l])), fp16 [B, L, h].  `table` is the resident fp16 token table [V, h] (EOS = row V-1),
  * `extra` the prompt's E custom vectors, fp32 [E, h] (may be NULL when E == 0), `pos` the fp16 position table (at least L rows of h).

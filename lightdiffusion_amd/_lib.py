@@ -158,6 +158,8 @@ SIGNATURES = {
     "ld_op_f32_blur_tmp_bytes": (_Z, [_I, _I]),
     "ld_op_f32_gaussian_blur": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P]),
     "ld_op_f32_paste_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "ld_op_inpaint_in": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ld_op_inpaint_out": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_clip_embed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 

@@ -777,6 +777,17 @@ int ld_op_f32_paste_u8(float* canvas, int canvas_pitch, int cw, int ch, int chan
                                (hipStream_t)stream);
 }
 
+int ld_op_inpaint_in(const float* x, const float* mask, const float* latent, const float* noise, const float* sigma, float* out, int B, int C, int HW, int Bm,
+                     int Cm, void* stream) {
+    op_begin();
+    return inpaint_blend_in_launch(x, mask, latent, noise, sigma, out, B, C, HW, Bm, Cm, (hipStream_t)stream);
+}
+
+int ld_op_inpaint_out(float* den, const float* mask, const float* latent, int B, int C, int HW, int Bm, int Cm, void* stream) {
+    op_begin();
+    return inpaint_blend_out_launch(den, mask, latent, B, C, HW, Bm, Cm, (hipStream_t)stream);
+}
+
 int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
     op_begin();
     return launched(clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream),

@@ -216,6 +216,15 @@ int f32_gaussian_blur_launch(const float* src, int spitch, float* dst, int dpitc
 int f32_paste_u8_launch(float* canvas, int cpitch, int cw, int ch, int C, const uint8_t* tile, int tpitch, const float* alpha, int apitch, int tw, int th, int x0,
                         int y0, hipStream_t stream);
 
+// ---- inpaint/inpaint.hip: the masked sampler step's two blends on fp32 NCHW latents [B][C][HW]; mask [Bm][Cm][HW], Bm in {1, B}, Cm in {1, C}, broadcast
+// in the kernel; every fp32 operation rounded on its own, in the order written (see the file's header)
+constexpr long long INPAINT_MAX_FLOATS = 1LL << 31;      // B * C * HW stays below it (32-bit indices): LD_ERR_SHAPE otherwise
+// out = x * m + (noise * sigma[b] + latent) * (1 - m); sigma: device [B]; out may be x
+int inpaint_blend_in_launch(const float* x, const float* mask, const float* latent, const float* noise, const float* sigma, float* out, int B, int C,
+                            long long HW, int Bm, int Cm, hipStream_t stream);
+// den = den * m + latent * (1 - m), in place
+int inpaint_blend_out_launch(float* den, const float* mask, const float* latent, int B, int C, long long HW, int Bm, int Cm, hipStream_t stream);
+
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
 // (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout

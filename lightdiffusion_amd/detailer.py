@@ -29,7 +29,12 @@ Behaviours of the reference that are mirrored on purpose:
     DifferentialDiffusion.forward (LD.py:8951-8965), which do_detail installs when noise_mask_feather > 0 (LD.py:9451-9455), is never
     called and that blur feeds nothing.  The images of the reference are mirrored: the mask reaches the paste and nothing else.  The
     second blur is not computed; the model is still cloned and given the function, and the un-blurred mask rides along as
-    latent["noise_mask"] into sampling.sample's denoise_mask, where it is as inert as there;
+    latent["noise_mask"] into sampling.sample's denoise_mask, where it is as inert as there.
+    WITH apply_noise_mask=True (model_stages, do_detail, nodes.DetailerForEach; off by default, and nothing above changes while it is off) the
+    mask is honoured: the second blur is computed on the device (ops.f32_gaussian_blur(mask, noise_mask_feather, 10), when noise_mask_feather > 0),
+    that mask is the latent's noise_mask, the stage's sampler applies it (sampling.KSamplerX0Inpaint: two fp32 blend kernels around the model
+    call) and DifferentialDiffusion.forward is called once per model call.  The redraw is then held to the crop's latent where the mask is 0,
+    in the sampler and not only by the final paste.  These images are no longer the reference's, which cannot make them;
   * torchvision's GaussianBlur draws its sigma with torch.empty(1).uniform_(10, 10) on the host's global generator in every call, which moves
     the stream the VAE's posterior sample is drawn from next.  The draws are repeated here in the reference's places (one per segment before
     the empty-mask test, one per detailed segment for the inert noise-mask blur), so that a seeded run consumes the generator as it does;
@@ -155,24 +160,38 @@ class DifferentialDiffusion:
 
     def forward(self, sigma: torch.Tensor, denoise_mask: torch.Tensor, extra_options: dict):
         ms = extra_options["model"].inner_model.model_sampling
+        if sigma.is_cuda:
+            # the masked sampler step (sampling.KSamplerX0Inpaint) calls this once per model call with the step's sigma on the device: the same
+            # threshold and comparison there, so that no step waits for the host to read sigma.  The run's two constant timesteps come from host
+            # values and are looked up once per run (the run's `sigmas` tensor is one object from its first step to its last)
+            sigmas = extra_options["sigmas"]
+            run = self.__dict__.get("_run")
+            if run is None or run[0] is not sigmas or run[1] is not ms:
+                run = self._run = (sigmas, ms, int(ms.timestep(sigmas[0])), int(ms.timestep(ms.sigma_min)))
+            _, _, ts_from, ts_to = run
+            threshold = (ms.timestep_on_device(sigma[0]) - ts_to) / (ts_from - ts_to)
+            return (denoise_mask >= threshold).to(denoise_mask.dtype)
         ts_from, ts_to = ms.timestep(extra_options["sigmas"][0]), ms.timestep(ms.sigma_min)
         threshold = (ms.timestep(sigma[0]) - ts_to) / (ts_from - ts_to)
         return (denoise_mask >= threshold).to(denoise_mask.dtype)
 
 
 # ------------------------------------------------------------------ the run
-def model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops):
+def model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops, apply_noise_mask=False):
     """Stages on the resident VAE and sampler, for the op namespace `ops` (module docstring).  Pixels stay on the model's device; latents go
     through the host (the posterior sample and the sampler's noise are drawn on the host generator, as the reference does: VAE.encode's randn
     first, then prepare_noise's manual_seed(seed)).  sample(latent, seed) is ksampler_wrapper (LD.py:9160-9205): the tail of the longer
-    schedule, noise added; the latent's noise_mask goes to sampling.sample's denoise_mask, inert there as in the reference."""
+    schedule, noise added; the latent's noise_mask goes to sampling.sample's denoise_mask, inert there as in the reference — unless
+    apply_noise_mask: then the sampler honours it (module docstring), with the denoise-mask function of `model`, where it has one."""
     from . import sampling
+    inpaint_options = {"apply_denoise_mask": True} if apply_noise_mask else None
 
     def sample(latent, seed):
         x = latent["samples"]
         noise = sampling.prepare_noise(x, seed)
         sigmas = detail_sigmas(model.get_model_object("model_sampling"), scheduler, steps, denoise)
-        out = sampling.sample(model, noise, positive, negative, cfg, model.load_device, sampling.ksampler(sampler_name), sigmas, model.model_options,
+        sampler = sampling.ksampler(sampler_name, inpaint_options=inpaint_options)
+        out = sampling.sample(model, noise, positive, negative, cfg, model.load_device, sampler, sigmas, model.model_options,
                               latent_image=x, denoise_mask=latent.get("noise_mask"), seed=seed)
         return dict(latent, samples=out.to("cpu"))
 
@@ -194,14 +213,16 @@ def _refuse_out_of_scope(positive, negative, **given):
 def do_detail(image, segs, model, clip, vae, guide_size, guide_size_for_bbox, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative,
               denoise, feather, noise_mask, force_inpaint, wildcard_opt=None, detailer_hook=None, refiner_ratio=None, refiner_model=None,
               refiner_clip=None, refiner_positive=None, refiner_negative=None, cycle=1, inpaint_model=False, noise_mask_feather=0,
-              scheduler_func_opt=None, stages=None):
+              scheduler_func_opt=None, stages=None, apply_noise_mask=False):
     """DetailerForEach.do_detail (LD.py:9402-9590) with the reference's argument list: image [1, H, W, 3] fp32 in [0, 1], segs = ((H, W),
     [SEG...]) -> (image, cropped_list, enhanced_list, enhanced_alpha_list, cnet_pil_list, (segs[0], new_segs)), host fp32 tensors; the
     lists are sorted by shape, largest first, as there; enhanced_alpha is the enhanced crop with the blurred mask as a fourth channel;
     cnet_pil_list is empty.  See the module docstring for the work size, the inert noise mask and the other mirrored behaviours.
     `stages` (required): a namespace of stage callables and image ops — encode(pixels [1, h, w, 3]) -> latent dict, sample(latent, seed),
     decode(latent) -> [1, h, w, 3], ops, device, observe (or None, called after every paste).  Every detailed segment's crop, enhanced crop
-    and alpha stay on `device` until the one download at the end: memory grows with the number of segments, each of crop size."""
+    and alpha stay on `device` until the one download at the end: memory grows with the number of segments, each of crop size.
+    apply_noise_mask (not the reference's; off by default): with noise_mask_feather > 0 the second blur is computed and is the latent's noise_mask,
+    for stages whose sampler honours it (model_stages(..., apply_noise_mask=True) on a model that carries the denoise-mask function)."""
     if stages is None:
         raise ValueError("do_detail needs `stages` (model_stages(..., ops=lightdiffusion_amd.ops) for the device; nodes.DetailerForEach builds "
                          "them): there is no fall-back to the host (see the module docstring)")
@@ -236,7 +257,7 @@ def do_detail(image, segs, model, clip, vae, guide_size, guide_size_for_bbox, ma
             raise ValueError(f"segment {i}: control_net_wrapper is not supported (ControlNet is out of scope)")
 
     if model is not None and noise_mask_feather > 0 and "denoise_mask_function" not in model.model_options:
-        model = DifferentialDiffusion().apply(model)[0]                                  # LD.py:9451-9455; inert (module docstring)
+        model = DifferentialDiffusion().apply(model)[0]                                  # LD.py:9451-9455; inert: the stages sample with THEIR model
     st = stages
     ops, dev = st.ops, st.device
     sigma_draw = lambda: torch.empty(1).uniform_(BLUR_SIGMA, BLUR_SIGMA)                 # torchvision's GaussianBlur.get_params, for the generator only
@@ -253,12 +274,15 @@ def do_detail(image, segs, model, clip, vae, guide_size, guide_size_for_bbox, ma
         alpha = ops.f32_gaussian_blur(torch.from_numpy(mask).to(dev), feather, BLUR_SIGMA)
         seg_seed = seed + i
         new_w, new_h, W64, H64 = work_size(w, h, guide_size, max_size)
-        sigma_draw()                                                                     # the noise-mask blur of enhance_detail: drawn, not computed
+        sigma_draw()                                                                     # the noise-mask blur of enhance_detail: drawn, computed below if asked for
         crop_u8 = ops.u8_crop_from_f32(canvas, x1, y1, x2, y2)
         original = canvas[y1:y2, x1:x2].clone()
         tile = ops.u8_resample(crop_u8, (W64, H64), "lanczos")
         latent = st.encode(ops.f32_from_u8(tile)[None])
-        latent["noise_mask"] = torch.from_numpy(mask)[None]
+        if apply_noise_mask and noise_mask_feather > 0:
+            latent["noise_mask"] = ops.f32_gaussian_blur(torch.from_numpy(mask).to(dev), int(noise_mask_feather), BLUR_SIGMA)[None]
+        else:
+            latent["noise_mask"] = torch.from_numpy(mask)[None]
         for c in range(cycle):                                                           # the same latent again, at seed + c (LD.py:9286-9330)
             latent = st.sample(latent, seg_seed + c)
         decoded = st.decode(latent).to(dev, torch.float32)

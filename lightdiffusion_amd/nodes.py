@@ -159,12 +159,26 @@ class CLIPSetLastLayer:
 
 class KSampler2:
     def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
-               preview: Optional[LatentPreviewer] = None):
+               preview: Optional[LatentPreviewer] = None, apply_noise_mask: bool = False):
         """`preview`: a LatentPreviewer that shows the running latent through TAESD every step, where the reference's sampler loops call
-        taesd_preview (LD.py:937, 1105, 1237); its `every` counts from this call's first step."""
+        taesd_preview (LD.py:937, 1105, 1237); its `every` counts from this call's first step.  `apply_noise_mask`: honour
+        latent_image["noise_mask"] (SetLatentNoiseMask) — redraw where it is 1, keep the latent where it is 0; off, the mask is not looked at, as in
+        the reference."""
         if preview is not None:
             preview.reset()
-        return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=preview)
+        return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=preview,
+                               apply_noise_mask=apply_noise_mask)
+
+
+class SetLatentNoiseMask:
+    """set_mask(samples, mask) -> (latent,): a copy of the latent dict that carries `mask` (on the pixel grid or the latent grid, [H, W] or with
+    leading axes; 1 = redraw, 0 = keep) as noise_mask [-1, 1, H, W].  Upstream's node; the reference has none because its sampler drops the mask.
+    KSampler2().sample(..., apply_noise_mask=True) honours it (sampling.prepare_mask resizes it to the latent)."""
+
+    def set_mask(self, samples, mask):
+        s = samples.copy()
+        s["noise_mask"] = mask.reshape((-1, 1, mask.shape[-2], mask.shape[-1]))
+        return (s,)
 
 
 class LoraLoader:
@@ -304,13 +318,18 @@ class DetailerForEach:
 
     def doit(self, image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative,
              denoise, feather, noise_mask, force_inpaint, wildcard, detailer_hook=None, cycle=1, inpaint_model=False, noise_mask_feather=0,
-             scheduler_func_opt=None):
+             scheduler_func_opt=None, apply_noise_mask=False):
+        """apply_noise_mask (not the reference's; off by default): the sampler honours the segment's noise mask, blurred by noise_mask_feather
+        when that is > 0, and DifferentialDiffusion thresholds it per step (detailer.py, module docstring)."""
         from . import detailer, ops
-        stages = detailer.model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops=ops)
+        if apply_noise_mask and noise_mask_feather > 0 and "denoise_mask_function" not in model.model_options:
+            model = DifferentialDiffusion().apply(model)[0]          # what do_detail installs (LD.py:9451-9455), on the model the stages sample with
+        stages = detailer.model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops=ops,
+                                       apply_noise_mask=apply_noise_mask)
         enhanced, cropped, cropped_enhanced, cropped_enhanced_alpha, _, _ = detailer.do_detail(
             image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative, denoise,
             feather, noise_mask, force_inpaint, wildcard, detailer_hook, cycle=cycle, inpaint_model=inpaint_model, noise_mask_feather=noise_mask_feather,
-            scheduler_func_opt=scheduler_func_opt, stages=stages)
+            scheduler_func_opt=scheduler_func_opt, stages=stages, apply_noise_mask=apply_noise_mask)
         return enhanced, cropped, cropped_enhanced, cropped_enhanced_alpha, [torch.zeros(1, 64, 64, 3)]
 
 
@@ -451,6 +470,20 @@ def txt2img_sharded(model, clip, vae, prompt_tokens, negative_tokens, width=512,
         g = D.gather_images((images * 255.0).round().to(torch.uint8).to(model.load_device), dst=0)
         return None if g is None else g.cpu().float() / 255.0
     return D.gather_images(images, dst=0)
+
+
+def inpaint(model, clip, vae, image, mask, prompt_tokens, negative_tokens, seed=0, steps=20, cfg=7.0, sampler_name="dpmpp_2m_sde", scheduler="karras",
+            denoise=1.0):
+    """Masked redraw of an image: VAEEncode, SetLatentNoiseMask, KSampler2(apply_noise_mask=True), VAEDecode.  image: host fp32 [B, H, W, 3] in
+    [0, 1], H and W multiples of 64; mask [H, W] or [B, H, W] (or the latent grid's), 1 where the image is redrawn and 0 where its latent is kept
+    -> host fp32 [B, H, W, 3].  `*_tokens` as in txt2img.  The kept region goes through the VAE and back; nothing is composited in pixel space."""
+    enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
+    (pc, pp), (nc, npool) = enc(prompt_tokens), enc(negative_tokens)
+    pos, neg = [[pc, {"pooled_output": pp}]], [[nc, {"pooled_output": npool}]]
+    lat = VAEEncode().encode(vae, image)[0]
+    lat = SetLatentNoiseMask().set_mask(lat, torch.as_tensor(mask, dtype=torch.float32))[0]
+    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, denoise=denoise, apply_noise_mask=True)[0]
+    return VAEDecode().decode(vae, lat)[0]
 
 
 def img2img(model, clip, vae, upscale_model, image, prompt_tokens, negative_tokens, upscale_by=2, seed=0, steps=8, cfg=6, sampler_name="dpmpp_2m_sde",

@@ -906,6 +906,65 @@ def f32_paste_u8_(canvas: torch.Tensor, tile: torch.Tensor, alpha: torch.Tensor,
     return canvas
 
 
+# ------------------------------------------------------------------ the masked sampler step (inpaint/inpaint.hip)
+# The two blends sampling.KSamplerX0Inpaint makes around the model call, on contiguous fp32 latents [B, C, h, w]; the mask is [Bm, Cm, h, w] with
+# Bm in {1, B} and Cm in {1, C} and is broadcast in the kernel.  Every fp32 operation is rounded on its own, in the order of the expression.  A
+# bad argument is a ValueError on the host, before anything is launched.  For tensors on the host (the sampler's CPU tests run its loops on a
+# toy denoiser there) the same expression is evaluated with torch operations in the same order; a device tensor never takes that path.
+def _inpaint_args(what: str, x: torch.Tensor, mask: torch.Tensor, others: dict):
+    """-> (B, C, HW, Bm, Cm) after the shape / dtype / device checks of both blends."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{what}: a latent [B, C, h, w] with no empty side is needed, got {tuple(getattr(x, 'shape', ()))}")
+    b, c, h, w = x.shape
+    if x.numel() >= 1 << 31:
+        raise ValueError(f"{what}: a latent of {x.numel()} elements: the kernels index in 32 bits, fewer than 2^31 are needed")
+    if not isinstance(mask, torch.Tensor) or mask.dim() != 4 or tuple(mask.shape[2:]) != (h, w) or mask.shape[0] not in (1, b) or mask.shape[1] not in (1, c):
+        raise ValueError(f"{what}: mask of shape {tuple(getattr(mask, 'shape', ()))} for a latent of {tuple(x.shape)}: expected [1 or {b}, 1 or {c}, {h}, {w}]")
+    for name, t in others.items():
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(x.shape):
+            raise ValueError(f"{what}: {name} of shape {tuple(getattr(t, 'shape', ()))}, expected the latent's {tuple(x.shape)}")
+    for name, t in dict(others, latent=x, mask=mask).items():
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} has dtype {t.dtype}, expected torch.float32")
+        if t.device != x.device:
+            raise ValueError(f"{what}: {name} is on {t.device}, the latent on {x.device}: one device is needed")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} is not contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+    return b, c, h * w, mask.shape[0], mask.shape[1]
+
+
+def inpaint_in(x: torch.Tensor, mask: torch.Tensor, latent: torch.Tensor, noise: torch.Tensor, sigma: torch.Tensor,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = x * m + (noise * sigma[b] + latent) * (1 - m): what the model sees of a masked step — x where the mask is 1, the latent noised to this
+    step's sigma (EPS.noise_scaling, max_denoise = False, LD.py:1267-1274) where it is 0.  sigma: fp32 [B] on x's device, read there.  `out`: where
+    the result goes (a new tensor by default); it may be x."""
+    others = {"latent_image": latent, "noise": noise}
+    if out is not None:
+        others["out"] = out
+    b, c, hw, bm, cm = _inpaint_args("inpaint_in", x, mask, others)
+    if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or tuple(sigma.shape) != (b,) or sigma.device != x.device or not sigma.is_contiguous():
+        raise ValueError(f"inpaint_in: sigma must be a contiguous fp32 [{b}] on {x.device}, one value per sample, got "
+                         f"{tuple(getattr(sigma, 'shape', ()))} {getattr(sigma, 'dtype', type(sigma).__name__)} on {getattr(sigma, 'device', None)}")
+    if out is None:
+        out = torch.empty_like(x)
+    if not x.is_cuda:
+        return out.copy_(x * mask + (noise * sigma.view(b, 1, 1, 1) + latent) * (1.0 - mask))
+    with torch.cuda.device(x.device):
+        check(lib().ld_op_inpaint_in(x.data_ptr(), mask.data_ptr(), latent.data_ptr(), noise.data_ptr(), sigma.data_ptr(), out.data_ptr(), b, c, hw, bm, cm,
+                                     _stream()), "ld_op_inpaint_in")
+    return out
+
+
+def inpaint_out_(den: torch.Tensor, mask: torch.Tensor, latent: torch.Tensor) -> torch.Tensor:
+    """den = den * m + latent * (1 - m) in place: the model's answer where the mask is 1, the latent itself where it is 0.  -> den"""
+    b, c, hw, bm, cm = _inpaint_args("inpaint_out_", den, mask, {"latent_image": latent})
+    if not den.is_cuda:
+        return den.copy_(den * mask + latent * (1.0 - mask))
+    with torch.cuda.device(den.device):
+        check(lib().ld_op_inpaint_out(den.data_ptr(), mask.data_ptr(), latent.data_ptr(), b, c, hw, bm, cm, _stream()), "ld_op_inpaint_out")
+    return den
+
+
 # ------------------------------------------------------------------ the `operations=` namespace (secondary seam)
 # The reference builds every network from an injectable namespace (`operations=ops`: UNetModel1 LD.py:5338, ResBlock1
 # 5207, SpatialTransformer 4179, CrossAttention 4005, FeedForward 3908; BaseModel picks `manual_cast` or

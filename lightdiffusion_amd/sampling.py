@@ -51,6 +51,17 @@ class ModelSampling:
         d = sigma.detach().float().cpu().log() - self.log_sigmas[:, None]
         return d.abs().argmin(dim=0).view(sigma.shape)
 
+    def timestep_on_device(self, sigma: torch.Tensor) -> torch.Tensor:
+        """`timestep` for a sigma that lives on a device, without reading it on the host: the same log, difference and argmin as torch
+        operations on sigma's device (the table is uploaded once per device).  The host and the device round fp32 log alike up to its last bit,
+        so the index differs from `timestep`'s only for a sigma within that of the midpoint between two table entries."""
+        cache = self.__dict__.setdefault("_log_sigmas_on", {})
+        table = cache.get(sigma.device)
+        if table is None:
+            table = cache[sigma.device] = self.log_sigmas.to(sigma.device)
+        d = sigma.detach().float().log() - table[:, None]
+        return d.abs().argmin(dim=0).view(sigma.shape)
+
     def sigma(self, timestep: torch.Tensor) -> torch.Tensor:
         t = torch.clamp(timestep.float().cpu(), min=0, max=len(self.sigmas) - 1)
         lo, hi, w = t.floor().long(), t.ceil().long(), t.frac()
@@ -345,8 +356,54 @@ def sampling_function(model, x, timestep, uncond, cond, cond_scale, model_option
     return uncond_pred + (cond_pred - uncond_pred) * cond_scale
 
 
+def repeat_to_batch_size(tensor: torch.Tensor, batch_size: int) -> torch.Tensor:
+    """Upstream's helper (the reference's, LD.py:397, returns its argument): dim 0 cut to batch_size, or repeated up to it."""
+    if tensor.shape[0] > batch_size:
+        return tensor[:batch_size]
+    if tensor.shape[0] < batch_size:
+        return tensor.repeat([math.ceil(batch_size / tensor.shape[0])] + [1] * (tensor.dim() - 1))[:batch_size]
+    return tensor
+
+
+def prepare_mask(noise_mask: torch.Tensor, shape, device) -> torch.Tensor:
+    """Upstream's prepare_mask (the reference has none: its sampler drops the mask): a latent's noise_mask, on the pixel grid or the latent
+    grid, as the fp32 denoise mask [B, 1, h, w] of a latent of `shape` on `device` — bilinear resize, repeated to the batch.  ONE channel is kept
+    where upstream repeats it over the latent's channels: the blend kernels broadcast it (ops.inpaint_in)."""
+    m = noise_mask.reshape((-1, 1, noise_mask.shape[-2], noise_mask.shape[-1])).to(torch.float32)
+    m = torch.nn.functional.interpolate(m, size=(shape[2], shape[3]), mode="bilinear")
+    return repeat_to_batch_size(m, shape[0]).to(device).contiguous()
+
+
+class KSamplerX0Inpaint:
+    """Upstream's KSamplerX0Inpaint, of which the reference keeps the signature and drops the mask (LD.py:2629-2636): the denoiser of a masked
+    run.  Where the mask is 0 the model sees the latent noised to the step's sigma instead of the sampler's x, and its answer there is replaced
+    by the latent, so the sampler is led back to `latent_image` where the mask is 0 and draws freely where it is 1.  A "denoise_mask_function"
+    in model_options (detailer.DifferentialDiffusion.forward) is asked for the step's mask first.  Two launches beside the model call
+    (ops.inpaint_in, ops.inpaint_out_), sigma read on the device: no host read, and the guided step stays the replayed graph.
+    `noise` is the run's raw noise (before noise_scaling), `latent_image` the latent after process_latent_in, `denoise_mask` what prepare_mask
+    made; all fp32 on the latents' device."""
+
+    def __init__(self, model_wrap, sigmas, noise, latent_image, denoise_mask):
+        self.inner_model, self.sigmas = model_wrap, sigmas
+        self.noise = noise.to(torch.float32).contiguous()
+        self.latent_image = latent_image.to(torch.float32).contiguous()
+        self.denoise_mask = denoise_mask
+
+    def __call__(self, x, sigma, model_options=None, seed=None, **_unused):
+        model_options = {} if model_options is None else model_options
+        mask = self.denoise_mask
+        if "denoise_mask_function" in model_options:
+            mask = model_options["denoise_mask_function"](sigma, mask, extra_options={"model": self.inner_model, "sigmas": self.sigmas})
+        x_in = ops.inpaint_in(x, mask, self.latent_image, self.noise, sigma)
+        # the model's answer is the sampler's to keep (cfg_denoise hands out a copy of the captured graph's static buffer, the eager routes a
+        # new tensor), so the blend writes into it
+        out = self.inner_model(x_in, sigma, model_options=model_options, seed=seed)
+        return ops.inpaint_out_(out, mask, self.latent_image)
+
+
 class KSAMPLER:
-    """LD.py:2732-2773."""
+    """LD.py:2732-2773.  inpaint_options["apply_denoise_mask"]: honour `denoise_mask` (KSamplerX0Inpaint); without it the mask is dropped, as
+    the reference drops it."""
 
     def __init__(self, sampler_function, extra_options=None, inpaint_options=None):
         self.sampler_function = sampler_function
@@ -360,8 +417,12 @@ class KSAMPLER:
 
     def sample(self, model_wrap, sigmas, extra_args, callback, noise, latent_image=None, denoise_mask=None, disable_pbar=False):
         ms = model_wrap.inner_model.model_sampling
+        raw_noise = noise                                          # the masked route noises the latent per step from it (LD.py:2750-2756)
         noise = ms.noise_scaling(sigmas[0], noise, latent_image, self.max_denoise(model_wrap, sigmas))
-        model_k = lambda x, sigma, **kw: model_wrap(x, sigma, **{k: v for k, v in kw.items() if k in ("model_options", "seed")})
+        if self.inpaint_options.get("apply_denoise_mask") and denoise_mask is not None:
+            model_k = KSamplerX0Inpaint(model_wrap, sigmas, raw_noise, latent_image, denoise_mask)
+        else:
+            model_k = lambda x, sigma, **kw: model_wrap(x, sigma, **{k: v for k, v in kw.items() if k in ("model_options", "seed")})
         samples = self.sampler_function(model_k, noise, sigmas, extra_args=extra_args, callback=callback, disable=disable_pbar,
                                         **self.extra_options)
         return ms.inverse_noise_scaling(sigmas[-1], samples)
@@ -416,6 +477,8 @@ class CFGGuider:
         noise, latent_image = noise.to(device), latent_image.to(device)
         if torch.count_nonzero(latent_image) > 0:                 # don't shift the empty latent (LD.py:2938-2941)
             latent_image = self.inner_model.process_latent_in(latent_image)
+        if denoise_mask is not None and getattr(sampler, "inpaint_options", {}).get("apply_denoise_mask"):
+            denoise_mask = prepare_mask(denoise_mask, noise.shape, device)      # once per run; on the other route the mask is dropped as it is
         self.model_options = dict(self.model_options)
         self.model_options.pop("_ld_ctx_cache", None)
         extra_args = {"model_options": self.model_options, "seed": seed}
@@ -456,27 +519,33 @@ class KSampler1:
             self.sigmas = self.calculate_sigmas(int(steps / denoise))[-(steps + 1):]
 
     def sample(self, noise, positive, negative, cfg, latent_image=None, denoise_mask=None, sigmas=None, callback=None,
-               disable_pbar=False, seed=None, **_ignored):
+               disable_pbar=False, seed=None, apply_noise_mask: bool = False, **_ignored):
         sigmas = self.sigmas if sigmas is None else sigmas
-        return sample(self.model, noise, positive, negative, cfg, self.device, ksampler(self.sampler), sigmas, self.model_options,
+        sampler = ksampler(self.sampler, inpaint_options={"apply_denoise_mask": True}) if apply_noise_mask else ksampler(self.sampler)
+        return sample(self.model, noise, positive, negative, cfg, self.device, sampler, sigmas, self.model_options,
                       latent_image=latent_image, denoise_mask=denoise_mask, callback=callback, disable_pbar=disable_pbar, seed=seed)
 
 
 def sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0, noise_mask=None,
-            sigmas=None, callback=None, disable_pbar=False, seed=None, **_ignored):
-    """LD.py:3156-3203: returns the samples on the intermediate (CPU) device."""
+            sigmas=None, callback=None, disable_pbar=False, seed=None, apply_noise_mask: bool = False, **_ignored):
+    """LD.py:3156-3203: returns the samples on the intermediate (CPU) device.  apply_noise_mask: `noise_mask` is the sampler's denoise mask —
+    redrawn where it is 1, led back to `latent_image` where it is 0 (KSamplerX0Inpaint); by default it is dropped, as the reference drops it."""
     ks = KSampler1(model, steps=steps, device=model.load_device, sampler=sampler_name, scheduler=scheduler, denoise=denoise,
                    model_options=model.model_options)
     out = ks.sample(noise, positive, negative, cfg=cfg, latent_image=latent_image, denoise_mask=noise_mask, sigmas=sigmas,
-                    callback=callback, disable_pbar=disable_pbar, seed=seed)
+                    callback=callback, disable_pbar=disable_pbar, seed=seed, apply_noise_mask=apply_noise_mask)
     return out.to("cpu")
 
 
-def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, callback=None, **_ignored):
-    """LD.py:6657-6701.  `callback`: the sampler loop's per-step callback ({"x", "i", "sigma", "denoised"}), e.g. a preview.LatentPreviewer."""
+def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, callback=None,
+                    apply_noise_mask: bool = False, **_ignored):
+    """LD.py:6657-6701.  `callback`: the sampler loop's per-step callback ({"x", "i", "sigma", "denoised"}), e.g. a preview.LatentPreviewer.
+    apply_noise_mask: latent["noise_mask"], where there is one, is honoured by the sampler (sample1); by default it is not looked at."""
     latent_image = latent["samples"]
     noise = prepare_noise(latent_image, seed, latent.get("batch_index"))
-    samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=callback, seed=seed)
+    masked = {"noise_mask": latent.get("noise_mask"), "apply_noise_mask": True} if apply_noise_mask else {}
+    samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=callback, seed=seed,
+                      **masked)
     out = latent.copy()
     out["samples"] = samples
     return (out,)
