@@ -501,6 +501,33 @@ int ld_op_inpaint_in(const float* x, const float* mask, const float* latent, con
 /* den = den * m + latent * (1 - m) in place: den * m, 1 - m, latent * that, the sum. */
 int ld_op_inpaint_out(float* den, const float* mask, const float* latent, int B, int C, int HW, int Bm, int Cm, void* stream);
 
+/* ---- regional conditioning: conditioning entries that carry an area, a mask or a strength (upstream's get_area_and_mult and the accumulate / divide
+ * loops of calc_cond_batch; the reference keeps their skeleton with area = the whole latent and strength = 1, LD.py:2435-2458, 2492-2591), on fp32
+ * NCHW latents [B][C][H][W], contiguous.  Both calls copy their descriptor array (HOST memory, read before the call returns) into the kernel
+ * arguments; they are stream-ordered, allocate nothing and read nothing on the host afterwards: capturable.  Every fp32 operation is rounded on
+ * its own, in the order written (no FMA).  LD_ERR_ARG: a NULL pointer (an entry's `out` included; `mask` may be NULL).  LD_ERR_SHAPE: a size < 1,
+ * more than LD_REGIONAL_MAX_ENTRIES descriptors or none, a window or area that leaves the latent, list not in {0, 1}, mask_batch not in {1, B}
+ * where there is a mask, a tensor of 2^31 floats or more (the kernels index in 32 bits).  Nothing is launched then. */
+#define LD_REGIONAL_MAX_ENTRIES 16
+typedef struct { int y0, x0; } ld_regional_window;
+typedef struct {
+    const float* out;   /* DEVICE: this entry's model output [B][C][h][w] (its rows of the group's batch) */
+    const float* mask;  /* DEVICE: [mask_batch][H][W] on the latent's grid, or NULL */
+    int list;           /* 0: positive (cond), 1: negative (uncond) */
+    int mask_batch;     /* 1 or B; sample b reads plane b % mask_batch */
+    int y0, x0, h, w;   /* the entry's area on the latent */
+    float strength, mask_strength;
+} ld_regional_entry;
+/* out[(j * B + b)][c][y][x] = x[b][c][y0_j + y][x0_j + x] for the k windows, all h x w: the model input of one group of entries in one launch
+ * (k windows that are the whole latent: the latent k times).  out: [k * B][C][h][w]; it may not overlap x. */
+int ld_op_regional_gather(const float* x, float* out, int B, int C, int H, int W, int h, int w, const ld_regional_window* windows, int k, void* stream);
+/* result[b][c][Y][X] = u + (c - u) * cond_scale, where for each list pred = num / den (IEEE division) with num = 0, den = 1e-37f and, for the
+ * entries of the list that cover (Y, X), in array order: mult = (mask ? mask[b % mask_batch][Y][X] * mask_strength : 1) * strength; without a
+ * mask, for the area's edges top, bottom, left, right that are not edges of the latent and a pixel t < 8 rows / columns from that edge,
+ * mult = mult * (0.125f * (t + 1)); num += out * mult; den += mult.  A pixel no entry of a list covers gives 0 for that list.  result may not
+ * overlap an input. */
+int ld_op_regional_combine(const ld_regional_entry* entries, int n, float cond_scale, float* result, int B, int C, int H, int W, void* stream);
+
 /* ---- CLIP text model input stage with textual-inversion vectors (CLIPEmbeddings + SDClipModel.set_up_textual_embeddings, LD.py:4394-4410, 4642-4690).
  * out[b][l] = round_fp16(float(row(ids[b*L + l])) + float(pos[l])), fp16 [B, L, h].  `table` is the resident fp16 token table [V, h] (EOS = row V-1),
  * `extra` the prompt's E custom vectors, fp32 [E, h] (may be NULL when E == 0), `pos` the fp16 position table (at least L rows of h).

@@ -35,6 +35,18 @@ class LoraTerm(C.Structure):
     _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("dtype", C.c_int), ("rank", C.c_int), ("scale", C.c_float)]
 
 
+REGIONAL_MAX_ENTRIES = 16      # LD_REGIONAL_MAX_ENTRIES
+
+
+class RegionalWindow(C.Structure):
+    _fields_ = [("y0", C.c_int), ("x0", C.c_int)]
+
+
+class RegionalEntry(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("mask", C.c_void_p), ("list", C.c_int), ("mask_batch", C.c_int), ("y0", C.c_int), ("x0", C.c_int),
+                ("h", C.c_int), ("w", C.c_int), ("strength", C.c_float), ("mask_strength", C.c_float)]
+
+
 class LDError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -160,6 +172,8 @@ SIGNATURES = {
     "ld_op_f32_paste_u8": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_inpaint_in": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_inpaint_out": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ld_op_regional_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "ld_op_regional_combine": (_I, [_P, _I, _F, _P, _I, _I, _I, _I, _P]),
     "ld_op_clip_embed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 

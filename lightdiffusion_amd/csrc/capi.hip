@@ -788,6 +788,20 @@ int ld_op_inpaint_out(float* den, const float* mask, const float* latent, int B,
     return inpaint_blend_out_launch(den, mask, latent, B, C, HW, Bm, Cm, (hipStream_t)stream);
 }
 
+static_assert(sizeof(ld_regional_window) == sizeof(RegionalWindow) && sizeof(ld_regional_entry) == sizeof(RegionalEntry) &&
+                  offsetof(ld_regional_entry, mask_strength) == offsetof(RegionalEntry, mask_strength),
+              "the ABI's regional descriptors are the kernels' own");
+
+int ld_op_regional_gather(const float* x, float* out, int B, int C, int H, int W, int h, int w, const ld_regional_window* windows, int k, void* stream) {
+    op_begin();
+    return regional_gather_launch(x, out, B, C, H, W, h, w, reinterpret_cast<const RegionalWindow*>(windows), k, (hipStream_t)stream);
+}
+
+int ld_op_regional_combine(const ld_regional_entry* entries, int n, float cond_scale, float* result, int B, int C, int H, int W, void* stream) {
+    op_begin();
+    return regional_combine_launch(reinterpret_cast<const RegionalEntry*>(entries), n, cond_scale, result, B, C, H, W, (hipStream_t)stream);
+}
+
 int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
     op_begin();
     return launched(clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream),

@@ -225,6 +225,27 @@ int inpaint_blend_in_launch(const float* x, const float* mask, const float* late
 // den = den * m + latent * (1 - m), in place
 int inpaint_blend_out_launch(float* den, const float* mask, const float* latent, int B, int C, long long HW, int Bm, int Cm, hipStream_t stream);
 
+// ---- regional/regional.hip: regional conditioning on fp32 NCHW latents [B][C][H][W] — one launch that builds a group's UNet input from its
+// windows, one that reduces every group's output to the guided result; every fp32 operation rounded on its own, in the order written (see the
+// file's header).  The descriptors are copied into the kernel arguments: the host arrays are read before the call returns.
+constexpr int REGIONAL_MAX_ENTRIES = 16;                 // windows of one gather, entries of one combine: LD_ERR_SHAPE above it
+constexpr long long REGIONAL_MAX_FLOATS = 1LL << 31;     // every tensor stays below it (32-bit indices): LD_ERR_SHAPE otherwise
+struct RegionalWindow {                                  // (the layout of ld_regional_window)
+    int y0, x0;
+};
+struct RegionalEntry {                                   // (the layout of ld_regional_entry)
+    const float* out;                                    // the entry's UNet output [B][C][h][w]
+    const float* mask;                                   // [mask_batch][H][W] on the latent's grid, or nullptr
+    int list;                                            // 0: cond, 1: uncond
+    int mask_batch;                                      // 1 or B (not looked at without a mask)
+    int y0, x0, h, w;                                    // its area on the latent
+    float strength, mask_strength;
+};
+// out[(j * B + b)][c][y][x] = x[b][c][y0_j + y][x0_j + x], j < k, all windows h x w
+int regional_gather_launch(const float* x, float* out, int B, int C, int H, int W, int h, int w, const RegionalWindow* windows, int k, hipStream_t stream);
+// result = u + (c - u) * cond_scale with, per list, pred = sum(out * mult) / (1e-37f + sum(mult)) over the entries that cover the pixel, in table order
+int regional_combine_launch(const RegionalEntry* entries, int n, float cond_scale, float* result, int B, int C, int H, int W, hipStream_t stream);
+
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
 // (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout

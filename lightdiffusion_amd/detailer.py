@@ -177,14 +177,17 @@ class DifferentialDiffusion:
 
 
 # ------------------------------------------------------------------ the run
-def model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops, apply_noise_mask=False):
+def model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops, apply_noise_mask=False, apply_cond_areas=False):
     """Stages on the resident VAE and sampler, for the op namespace `ops` (module docstring).  Pixels stay on the model's device; latents go
     through the host (the posterior sample and the sampler's noise are drawn on the host generator, as the reference does: VAE.encode's randn
     first, then prepare_noise's manual_seed(seed)).  sample(latent, seed) is ksampler_wrapper (LD.py:9160-9205): the tail of the longer
     schedule, noise added; the latent's noise_mask goes to sampling.sample's denoise_mask, inert there as in the reference — unless
-    apply_noise_mask: then the sampler honours it (module docstring), with the denoise-mask function of `model`, where it has one."""
+    apply_noise_mask: then the sampler honours it (module docstring), with the denoise-mask function of `model`, where it has one.
+    apply_cond_areas: the sampler honours the conditioning entries' area / strength / mask / step range on the segment's latent
+    (sampling.sampling_function); off, they are inert as in the reference."""
     from . import sampling
     inpaint_options = {"apply_denoise_mask": True} if apply_noise_mask else None
+    cond_areas = {"apply_cond_areas": True} if apply_cond_areas else {}      # (off: the call is the one it has always been)
 
     def sample(latent, seed):
         x = latent["samples"]
@@ -192,7 +195,7 @@ def model_stages(model, vae, positive, negative, steps, cfg, sampler_name, sched
         sigmas = detail_sigmas(model.get_model_object("model_sampling"), scheduler, steps, denoise)
         sampler = sampling.ksampler(sampler_name, inpaint_options=inpaint_options)
         out = sampling.sample(model, noise, positive, negative, cfg, model.load_device, sampler, sigmas, model.model_options,
-                              latent_image=x, denoise_mask=latent.get("noise_mask"), seed=seed)
+                              latent_image=x, denoise_mask=latent.get("noise_mask"), seed=seed, **cond_areas)
         return dict(latent, samples=out.to("cpu"))
 
     return SimpleNamespace(ops=ops, device=torch.device(model.load_device), observe=None,

@@ -159,15 +159,70 @@ class CLIPSetLastLayer:
 
 class KSampler2:
     def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
-               preview: Optional[LatentPreviewer] = None, apply_noise_mask: bool = False):
+               preview: Optional[LatentPreviewer] = None, apply_noise_mask: bool = False, apply_cond_areas: bool = False):
         """`preview`: a LatentPreviewer that shows the running latent through TAESD every step, where the reference's sampler loops call
         taesd_preview (LD.py:937, 1105, 1237); its `every` counts from this call's first step.  `apply_noise_mask`: honour
         latent_image["noise_mask"] (SetLatentNoiseMask) — redraw where it is 1, keep the latent where it is 0; off, the mask is not looked at, as in
-        the reference."""
+        the reference.  `apply_cond_areas`: honour the conditioning entries' area, strength, mask and step range (ConditioningSetArea,
+        ConditioningSetMask, ConditioningSetTimestepRange; sampling.sampling_function); off, those keys are inert, as in the reference."""
         if preview is not None:
             preview.reset()
         return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=preview,
-                               apply_noise_mask=apply_noise_mask)
+                               apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas)
+
+
+def _conditioning_set_values(conditioning, values: dict):
+    """upstream's node_helpers.conditioning_set_values: a new list whose entries are [tensor, a copy of the dict with `values` set]"""
+    out = []
+    for t in conditioning:
+        d = t[1].copy()
+        d.update(values)
+        out.append([t[0], d])
+    return out
+
+
+class ConditioningCombine:
+    """combine(c1, c2) -> (c1 + c2,): both lists' entries in one list (upstream's node; the reference has none).  With apply_cond_areas every
+    entry is weighed by its own area / mask / strength; without it the sampler averages them over the whole latent."""
+
+    def combine(self, conditioning_1, conditioning_2):
+        return (conditioning_1 + conditioning_2,)
+
+
+class ConditioningSetArea:
+    """append(conditioning, width, height, x, y, strength) -> (conditioning,): the entries apply to a rectangle given in PIXELS (// 8 = latent
+    units), feathered over 8 latent pixels at its edges inside the latent (upstream's node)."""
+
+    def append(self, conditioning, width, height, x, y, strength):
+        return (_conditioning_set_values(conditioning, {"area": (height // 8, width // 8, y // 8, x // 8), "strength": strength,
+                                                        "set_area_to_bounds": False}),)
+
+
+class ConditioningSetAreaPercentage:
+    """append(conditioning, width, height, x, y, strength): the rectangle as fractions of the latent (upstream's node)."""
+
+    def append(self, conditioning, width, height, x, y, strength):
+        return (_conditioning_set_values(conditioning, {"area": ("percentage", height, width, y, x), "strength": strength,
+                                                        "set_area_to_bounds": False}),)
+
+
+class ConditioningSetMask:
+    """append(conditioning, mask, set_cond_area, strength): the entries are weighed by `mask` ([H, W] or [B, H, W], any resolution: resized to
+    the latent) times `strength`; set_cond_area "mask bounds" also restricts the model call to the mask's bounding box (upstream's node)."""
+
+    def append(self, conditioning, mask, set_cond_area, strength):
+        if set_cond_area not in ("default", "mask bounds"):
+            raise ValueError(f"set_cond_area must be 'default' or 'mask bounds', got {set_cond_area!r}")
+        if len(mask.shape) < 3:
+            mask = mask.unsqueeze(0)
+        return (_conditioning_set_values(conditioning, {"mask": mask, "set_area_to_bounds": set_cond_area != "default", "mask_strength": strength}),)
+
+
+class ConditioningSetTimestepRange:
+    """set_range(conditioning, start, end): the entries are active from fraction `start` to fraction `end` of the schedule (upstream's node)."""
+
+    def set_range(self, conditioning, start, end):
+        return (_conditioning_set_values(conditioning, {"start_percent": start, "end_percent": end}),)
 
 
 class SetLatentNoiseMask:
@@ -318,14 +373,15 @@ class DetailerForEach:
 
     def doit(self, image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative,
              denoise, feather, noise_mask, force_inpaint, wildcard, detailer_hook=None, cycle=1, inpaint_model=False, noise_mask_feather=0,
-             scheduler_func_opt=None, apply_noise_mask=False):
+             scheduler_func_opt=None, apply_noise_mask=False, apply_cond_areas=False):
         """apply_noise_mask (not the reference's; off by default): the sampler honours the segment's noise mask, blurred by noise_mask_feather
-        when that is > 0, and DifferentialDiffusion thresholds it per step (detailer.py, module docstring)."""
+        when that is > 0, and DifferentialDiffusion thresholds it per step (detailer.py, module docstring).  apply_cond_areas (likewise): every
+        segment's sampler honours the conditioning entries' area / strength / mask / step range, on the segment's latent."""
         from . import detailer, ops
         if apply_noise_mask and noise_mask_feather > 0 and "denoise_mask_function" not in model.model_options:
             model = DifferentialDiffusion().apply(model)[0]          # what do_detail installs (LD.py:9451-9455), on the model the stages sample with
         stages = detailer.model_stages(model, vae, positive, negative, steps, cfg, sampler_name, scheduler, denoise, ops=ops,
-                                       apply_noise_mask=apply_noise_mask)
+                                       apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas)
         enhanced, cropped, cropped_enhanced, cropped_enhanced_alpha, _, _ = detailer.do_detail(
             image, segs, model, clip, vae, guide_size, guide_size_for, max_size, seed, steps, cfg, sampler_name, scheduler, positive, negative, denoise,
             feather, noise_mask, force_inpaint, wildcard, detailer_hook, cycle=cycle, inpaint_model=inpaint_model, noise_mask_feather=noise_mask_feather,
@@ -399,20 +455,28 @@ class CheckpointLoaderSimple:
         return _attach(unet, self.device), clip, vae
 
 
+def _conditioning_of(clip, prompt):
+    """a prompt string or pre-tokenised chunks through the text model -> [[cond, {"pooled_output": ..}]]; a conditioning list as it is"""
+    if isinstance(prompt, (list, tuple)) and prompt and isinstance(prompt[0], (list, tuple)) and prompt[0] and isinstance(prompt[0][0], torch.Tensor):
+        return list(prompt)
+    cond, pooled = clip.encode_from_tokens(clip.tokenize(prompt) if isinstance(prompt, str) else prompt, return_pooled=True)
+    return [[cond, {"pooled_output": pooled}]]
+
+
 def txt2img(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=512, batch_size=1, seed=0, steps=20, cfg=7.0,
             sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False, upscale_model: Optional[MI355XUpscaler] = None,
-            preview: Optional[LatentPreviewer] = None):
+            preview: Optional[LatentPreviewer] = None, apply_cond_areas: bool = False):
     """The reference's headless `pipeline()` order (LD.py:10001-10086) with explicit arguments instead of hard-coded ones.
-    `*_tokens`: a prompt string (needs a tokenizer on `clip`) or pre-tokenised [[(id, weight), ...]] chunks.  `preview`: a LatentPreviewer
-    for the first sampler pass (the hires pass has another latent shape and runs without one)."""
-    enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
-    (pc, pp), (nc, npool) = enc(prompt_tokens), enc(negative_tokens)
-    pos, neg = [[pc, {"pooled_output": pp}]], [[nc, {"pooled_output": npool}]]
+    `*_tokens`: a prompt string (needs a tokenizer on `clip`), pre-tokenised [[(id, weight), ...]] chunks, or a conditioning list
+    [[tensor, {..}], ...] as the Conditioning* nodes build it.  `preview`: a LatentPreviewer for the first sampler pass (the hires pass has
+    another latent shape and runs without one).  `apply_cond_areas`: both sampler passes honour the entries' area / strength / mask / step
+    range (KSampler2)."""
+    pos, neg = _conditioning_of(clip, prompt_tokens), _conditioning_of(clip, negative_tokens)
     lat = EmptyLatentImage().generate(width, height, batch_size)[0]
-    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, preview=preview)[0]
+    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, preview=preview, apply_cond_areas=apply_cond_areas)[0]
     if hires:   # hires-fix (LD.py:10585-10603): bislerp x2, then 10 Euler-a steps at denoise 0.45, cfg 8
         lat = LatentUpscale(model.load_device).upscale(lat, "bislerp", width * 2, height * 2)[0]
-        lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45)[0]
+        lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45, apply_cond_areas=apply_cond_areas)[0]
     img = VAEDecode().decode(vae, lat)[0]
     if upscale_model is not None:   # the image-side upscale the reference builds next to the sampler nodes (LD.py:10014-10015)
         img = ImageUpscaleWithModel().upscale(upscale_model, img)[0]
@@ -473,16 +537,16 @@ def txt2img_sharded(model, clip, vae, prompt_tokens, negative_tokens, width=512,
 
 
 def inpaint(model, clip, vae, image, mask, prompt_tokens, negative_tokens, seed=0, steps=20, cfg=7.0, sampler_name="dpmpp_2m_sde", scheduler="karras",
-            denoise=1.0):
+            denoise=1.0, apply_cond_areas: bool = False):
     """Masked redraw of an image: VAEEncode, SetLatentNoiseMask, KSampler2(apply_noise_mask=True), VAEDecode.  image: host fp32 [B, H, W, 3] in
     [0, 1], H and W multiples of 64; mask [H, W] or [B, H, W] (or the latent grid's), 1 where the image is redrawn and 0 where its latent is kept
-    -> host fp32 [B, H, W, 3].  `*_tokens` as in txt2img.  The kept region goes through the VAE and back; nothing is composited in pixel space."""
-    enc = lambda t: clip.encode_from_tokens(clip.tokenize(t) if isinstance(t, str) else t, return_pooled=True)
-    (pc, pp), (nc, npool) = enc(prompt_tokens), enc(negative_tokens)
-    pos, neg = [[pc, {"pooled_output": pp}]], [[nc, {"pooled_output": npool}]]
+    -> host fp32 [B, H, W, 3].  `*_tokens` and `apply_cond_areas` as in txt2img.  The kept region goes through the VAE and back; nothing is
+    composited in pixel space."""
+    pos, neg = _conditioning_of(clip, prompt_tokens), _conditioning_of(clip, negative_tokens)
     lat = VAEEncode().encode(vae, image)[0]
     lat = SetLatentNoiseMask().set_mask(lat, torch.as_tensor(mask, dtype=torch.float32))[0]
-    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, denoise=denoise, apply_noise_mask=True)[0]
+    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, denoise=denoise, apply_noise_mask=True,
+                             apply_cond_areas=apply_cond_areas)[0]
     return VAEDecode().decode(vae, lat)[0]
 
 

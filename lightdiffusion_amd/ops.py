@@ -8,7 +8,7 @@ Tensors are torch CUDA tensors used as *device memory only*: fp16, channels-last
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -963,6 +963,169 @@ def inpaint_out_(den: torch.Tensor, mask: torch.Tensor, latent: torch.Tensor) ->
     with torch.cuda.device(den.device):
         check(lib().ld_op_inpaint_out(den.data_ptr(), mask.data_ptr(), latent.data_ptr(), b, c, hw, bm, cm, _stream()), "ld_op_inpaint_out")
     return den
+
+
+# ------------------------------------------------------------------ regional conditioning (regional/regional.hip)
+# The two launches sampling.sampling_function makes around the model calls of a step whose conditioning entries carry an area, a mask or a
+# strength, on contiguous fp32 latents [B, C, H, W]: `regional_gather` builds the model input of one group of entries (windows of one h x w),
+# `regional_combine` reduces every group's output to the guided result.  Every fp32 operation is rounded on its own, in the order of the
+# expression (ld_mi355x.h).  A bad argument is a ValueError on the host, before anything is launched.  For tensors on the host the same
+# expression is evaluated with torch operations in the same order; a device tensor never takes that path.
+REGIONAL_MAX_ENTRIES = 16
+
+
+class RegionalEntry(NamedTuple):
+    """One conditioning entry of a step, as regional_combine reads it: its `list` (0: cond, 1: uncond), where its output lies (rows
+    [slot * B, (slot + 1) * B) of outs[group]), its area (h, w, y0, x0) on the latent, its strength, and its mask ([Bm, H, W] on the latent's
+    grid, Bm in {1, B}, or None) with the mask's strength."""
+    list: int
+    group: int
+    slot: int
+    area: tuple
+    strength: float = 1.0
+    mask: Optional[torch.Tensor] = None
+    mask_strength: float = 1.0
+
+
+def _regional_latent(what: str, x, name: str = "the latent"):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or min(x.shape) < 1:
+        raise ValueError(f"{what}: {name} must be [B, C, H, W] with no empty side, got {tuple(getattr(x, 'shape', ()))}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} has dtype {x.dtype}, expected torch.float32")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: {name} is not contiguous (shape {tuple(x.shape)}, strides {x.stride()})")
+    if x.numel() >= 1 << 31:
+        raise ValueError(f"{what}: {name} has {x.numel()} elements: the kernels index in 32 bits, fewer than 2^31 are needed")
+
+
+def _regional_area(what: str, area, H: int, W: int):
+    if len(area) != 4 or not all(isinstance(v, int) and not isinstance(v, bool) for v in area):
+        raise ValueError(f"{what}: an area is four ints (h, w, y0, x0), got {area!r}")
+    h, w, y0, x0 = area
+    if h < 1 or w < 1:
+        raise ValueError(f"{what}: area {tuple(area)} has a side < 1")
+    if y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+        raise ValueError(f"{what}: area {tuple(area)} leaves the {H} x {W} latent")
+    return h, w, y0, x0
+
+
+def regional_gather(x: torch.Tensor, windows, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[(j * B + b), c, y, x] = x[b, c, y0_j + y, x0_j + x]: the k windows (h, w, y0, x0) of one group, all of one h x w, as ONE batch
+    [k * B, C, h, w] — the model input of the group (k windows that are the whole latent: the latent k times)."""
+    what = "regional_gather"
+    _regional_latent(what, x)
+    b, c, H, W = x.shape
+    windows = [tuple(v) for v in windows]
+    if not 1 <= len(windows) <= REGIONAL_MAX_ENTRIES:
+        raise ValueError(f"{what}: {len(windows)} windows; 1 to {REGIONAL_MAX_ENTRIES} are needed")
+    areas = [_regional_area(what, v, H, W) for v in windows]
+    h, w = areas[0][:2]
+    if any(a[:2] != (h, w) for a in areas):
+        raise ValueError(f"{what}: the windows of one group have one shape, got {sorted({a[:2] for a in areas})}")
+    k = len(areas)
+    if k * b * c * h * w >= 1 << 31:
+        raise ValueError(f"{what}: a batch of {k * b * c * h * w} elements: the kernels index in 32 bits, fewer than 2^31 are needed")
+    if out is None:
+        out = torch.empty((k * b, c, h, w), dtype=torch.float32, device=x.device)
+    else:
+        _regional_latent(what, out, "out")
+        if tuple(out.shape) != (k * b, c, h, w) or out.device != x.device:
+            raise ValueError(f"{what}: out of shape {tuple(out.shape)} on {out.device}, expected {(k * b, c, h, w)} on {x.device}")
+    if not x.is_cuda:
+        return out.copy_(torch.cat([x[:, :, y0:y0 + h, x0:x0 + w] for _, _, y0, x0 in areas]))
+    from ._lib import RegionalWindow
+    tab = (RegionalWindow * k)(*[RegionalWindow(y0, x0) for _, _, y0, x0 in areas])
+    with torch.cuda.device(x.device):
+        check(lib().ld_op_regional_gather(x.data_ptr(), out.data_ptr(), b, c, H, W, h, w, tab, k, _stream()), "ld_op_regional_gather")
+    return out
+
+
+def _regional_ramp(h: int, from_end: bool) -> torch.Tensor:
+    """the factors of one feathered edge along an axis of h pixels: 0.125 * (t + 1) for the pixel t < 8 from the edge, 1 beyond"""
+    r = torch.ones(h)
+    n = min(8, h)
+    r[:n] = 0.125 * (torch.arange(n, dtype=torch.float32) + 1.0)
+    return r.flip(0) if from_end else r
+
+
+def regional_combine(outs, entries, cond_scale: float, shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The guided result [B, C, H, W] (`shape`) of one step: u + (c - u) * cond_scale, where each list's prediction is
+    sum(out_e * mult_e) / (1e-37 + sum(mult_e)) over its entries e that cover the pixel, accumulated in the order of `entries`:
+    mult = (mask ? mask[b % Bm] * mask_strength : 1) * strength, and without a mask the eight-pixel ramps 0.125 * (t + 1) at the area's top,
+    bottom, left and right edges that are not edges of the latent, multiplied in in that order.  A pixel that no entry of a list covers gives 0
+    for that list.  outs: the groups' model outputs [k_g * B, C, h_g, w_g]; entries: RegionalEntry rows."""
+    what = "regional_combine"
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f"{what}: shape must be (B, C, H, W) with no empty side, got {tuple(shape)}")
+    b, c, H, W = (int(v) for v in shape)
+    if b * c * H * W >= 1 << 31:
+        raise ValueError(f"{what}: a latent of {b * c * H * W} elements: the kernels index in 32 bits, fewer than 2^31 are needed")
+    outs, entries = list(outs), [RegionalEntry(*e) for e in entries]
+    if not outs or not 1 <= len(entries) <= REGIONAL_MAX_ENTRIES:
+        raise ValueError(f"{what}: {len(outs)} group outputs and {len(entries)} entries; at least one group and 1 to {REGIONAL_MAX_ENTRIES} entries are needed")
+    for g, o in enumerate(outs):
+        _regional_latent(what, o, f"outs[{g}]")
+        if o.shape[0] % b or o.shape[1] != c or o.device != outs[0].device:
+            raise ValueError(f"{what}: outs[{g}] of shape {tuple(o.shape)} on {o.device}: rows in multiples of {b}, {c} channels, on {outs[0].device}")
+    dev = outs[0].device
+    seen = set()
+    for i, e in enumerate(entries):
+        h, w, y0, x0 = _regional_area(f"{what}: entry {i}", e.area, H, W)
+        if e.list not in (0, 1):
+            raise ValueError(f"{what}: entry {i}: list {e.list!r}, expected 0 (cond) or 1 (uncond)")
+        if not isinstance(e.group, int) or not 0 <= e.group < len(outs):
+            raise ValueError(f"{what}: entry {i}: group {e.group!r} of {len(outs)}")
+        o = outs[e.group]
+        if tuple(o.shape[2:]) != (h, w) or not isinstance(e.slot, int) or not 0 <= e.slot < o.shape[0] // b or (e.group, e.slot) in seen:
+            raise ValueError(f"{what}: entry {i}: area {tuple(e.area)}, slot {e.slot!r} do not fit outs[{e.group}] of shape {tuple(o.shape)} (or the slot is taken)")
+        seen.add((e.group, e.slot))
+        if e.mask is not None:
+            m = e.mask
+            if not isinstance(m, torch.Tensor) or m.dim() != 3 or tuple(m.shape[1:]) != (H, W) or m.shape[0] not in (1, b):
+                raise ValueError(f"{what}: entry {i}: mask of shape {tuple(getattr(m, 'shape', ()))}, expected [1 or {b}, {H}, {W}]")
+            if m.dtype != torch.float32 or m.device != dev or not m.is_contiguous():
+                raise ValueError(f"{what}: entry {i}: the mask must be contiguous fp32 on {dev}, got {m.dtype} on {m.device}, strides {m.stride()}")
+    if out is None:
+        out = torch.empty((b, c, H, W), dtype=torch.float32, device=dev)
+    else:
+        _regional_latent(what, out, "out")
+        if tuple(out.shape) != (b, c, H, W) or out.device != dev:
+            raise ValueError(f"{what}: out of shape {tuple(out.shape)} on {out.device}, expected {(b, c, H, W)} on {dev}")
+    if not dev.type == "cuda":
+        num = [torch.zeros((b, c, H, W)), torch.zeros((b, c, H, W))]
+        den = [torch.full((b, c, H, W), 1e-37), torch.full((b, c, H, W), 1e-37)]
+        for e in entries:
+            h, w, y0, x0 = e.area
+            o = outs[e.group][e.slot * b:(e.slot + 1) * b]
+            if e.mask is not None:
+                mult = ((e.mask[:, y0:y0 + h, x0:x0 + w] * e.mask_strength) * e.strength)[:, None]
+            else:
+                mult = torch.ones((1, 1, h, w)) * e.strength
+                if y0 != 0:
+                    mult = mult * _regional_ramp(h, False).view(1, 1, h, 1)
+                if y0 + h < H:
+                    mult = mult * _regional_ramp(h, True).view(1, 1, h, 1)
+                if x0 != 0:
+                    mult = mult * _regional_ramp(w, False).view(1, 1, 1, w)
+                if x0 + w < W:
+                    mult = mult * _regional_ramp(w, True).view(1, 1, 1, w)
+            num[e.list][:, :, y0:y0 + h, x0:x0 + w] += o * mult
+            den[e.list][:, :, y0:y0 + h, x0:x0 + w] += mult
+        cond, uncond = num[0] / den[0], num[1] / den[1]
+        return out.copy_(uncond + (cond - uncond) * cond_scale)
+    from ._lib import RegionalEntry as _Entry
+    tab = (_Entry * len(entries))()
+    for t, e in zip(tab, entries):
+        h, w, y0, x0 = e.area
+        o = outs[e.group]
+        t.out = o.data_ptr() + e.slot * b * c * h * w * 4
+        t.mask = None if e.mask is None else e.mask.data_ptr()
+        t.list, t.mask_batch = e.list, 1 if e.mask is None else e.mask.shape[0]
+        t.y0, t.x0, t.h, t.w = y0, x0, h, w
+        t.strength, t.mask_strength = e.strength, e.mask_strength
+    with torch.cuda.device(dev):
+        check(lib().ld_op_regional_combine(tab, len(entries), float(cond_scale), out.data_ptr(), b, c, H, W, _stream()), "ld_op_regional_combine")
+    return out
 
 
 # ------------------------------------------------------------------ the `operations=` namespace (secondary seam)

@@ -67,6 +67,15 @@ class ModelSampling:
         lo, hi, w = t.floor().long(), t.ceil().long(), t.frac()
         return ((1 - w) * self.log_sigmas[lo] + w * self.log_sigmas[hi]).exp()
 
+    def percent_to_sigma(self, percent: float) -> float:
+        """Upstream's ModelSamplingDiscrete.percent_to_sigma (the reference has none): the sigma at a fraction of the run, for the
+        start_percent / end_percent of a conditioning entry — beyond every sigma at 0 and before, 0 at 1 and after."""
+        if percent <= 0.0:
+            return 999999999.9
+        if percent >= 1.0:
+            return 0.0
+        return float(self.sigma(torch.tensor((1.0 - percent) * 999.0)))
+
     # EPS
     def noise_scaling(self, sigma, noise, latent_image, max_denoise=False):
         scale = math.sqrt(1.0 + float(sigma) ** 2.0) if max_denoise else float(sigma)
@@ -302,27 +311,248 @@ def _cat_ctx(ctx_list: List[torch.Tensor]) -> torch.Tensor:
     return torch.cat([c if c.shape[1] == tgt else c.repeat(1, tgt // c.shape[1], 1) for c in ctx_list])
 
 
+def _ctx_rows(c: dict, b: int) -> torch.Tensor:
+    """an entry's context for a latent batch of b: its own rows, or its one row b times"""
+    t = c["cross_attn"]
+    if t.shape[0] != b:
+        if t.shape[0] != 1:
+            raise RuntimeError(f"conditioning batch {t.shape[0]} does not match latent batch {b}")
+        t = t.expand(b, -1, -1)
+    return t
+
+
+# ------------------------------------------------------------------ regional conditioning (model_options["ld_cond_areas"])
+REGIONAL_MAX_ENTRIES = ops.REGIONAL_MAX_ENTRIES     # entries active in one step: the combine kernel's table travels in its arguments
+_NO_START, _NO_END = float("inf"), float("-inf")
+
+
+def _fp32(v: float) -> float:
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _cond_is_keyed(c: dict) -> bool:
+    """does the entry ask for anything but the whole latent at weight 1?  (strength 1 counts as none; a step range does not matter to an
+    entry that is active)"""
+    return c.get("area") is not None or c.get("mask") is not None or c.get("strength", 1.0) != 1.0
+
+
+def _host_sigma(timestep: torch.Tensor) -> float:
+    """THE host read of a regional step: sigma[0], which upstream compares with an entry's timestep range on the host (get_area_and_mult).
+    Called once per step, and only in a run in which some entry carries a range; a skipped entry then costs no UNet work."""
+    return float(timestep[0])
+
+
+def resolve_areas_and_cond_masks(conds: List[dict], b: int, h: int, w: int, device) -> List[dict]:
+    """Upstream's resolve_areas_and_cond_masks (the reference's, LD.py:2654-2667, has an empty body), on copies: percentage areas become
+    latent units, a mask becomes a contiguous fp32 [Bm, h, w] on `device` with Bm in {1, b} (bilinear resize, align_corners=False, where it has
+    another size), and with set_area_to_bounds the area becomes the bounding box of max_b |mask| > 0, its sides raised to at least 8 and cut
+    at the latent's edge ((8, 8, 0, 0) for a mask of zeros)."""
+    out = []
+    for c in conds:
+        c = c.copy()
+        area = c.get("area")
+        if area is not None:
+            if len(area) == 5 and area[0] == "percentage":
+                area = (max(1, round(area[1] * h)), max(1, round(area[2] * w)), round(area[3] * h), round(area[4] * w))
+            if len(area) != 4:
+                raise ValueError(f"a conditioning area is (h, w, y, x) or ('percentage', h, w, y, x), got {tuple(area)!r}")
+            c["area"] = tuple(int(v) for v in area)
+        if c.get("mask") is not None:
+            mask = c["mask"].to(device=device, dtype=torch.float32)
+            if mask.dim() == 2:
+                mask = mask.unsqueeze(0)
+            if mask.dim() != 3:
+                raise ValueError(f"a conditioning mask is [Bm, Hm, Wm] or [Hm, Wm], got {tuple(mask.shape)}")
+            if tuple(mask.shape[1:]) != (h, w):
+                mask = torch.nn.functional.interpolate(mask.unsqueeze(1), size=(h, w), mode="bilinear", align_corners=False).squeeze(1)
+            if mask.shape[0] not in (1, b):
+                mask = repeat_to_batch_size(mask, b)
+            mask = mask.contiguous()
+            if c.get("set_area_to_bounds", False):
+                lit = mask.abs().amax(dim=0) > 0
+                ys, xs = torch.nonzero(lit.any(dim=1)).flatten().tolist(), torch.nonzero(lit.any(dim=0)).flatten().tolist()
+                if not ys:
+                    c["area"] = (8, 8, 0, 0)
+                else:
+                    y0, x0 = ys[0], xs[0]
+                    c["area"] = (min(max(8, ys[-1] - y0 + 1), h - y0), min(max(8, xs[-1] - x0 + 1), w - x0), y0, x0)
+            c["mask"] = mask
+        out.append(c)
+    return out
+
+
+def calculate_start_end_timesteps(model_sampling: ModelSampling, conds: List[dict]) -> None:
+    """Upstream's (LD.py:2654-2667: an empty body): start_percent / end_percent -> timestep_start / timestep_end, as sigmas.  In place: the dicts
+    are process_conds' copies."""
+    for c in conds:
+        if "start_percent" in c:
+            c["timestep_start"] = model_sampling.percent_to_sigma(c["start_percent"])
+        if "end_percent" in c:
+            c["timestep_end"] = model_sampling.percent_to_sigma(c["end_percent"])
+
+
+def create_cond_with_same_area_if_none(conds: List[dict], c: dict) -> None:
+    """Upstream's rule (LD.py:2654-2667: an empty body): an entry `c` with an area needs an entry of the same area in the OTHER list `conds`.
+    Candidates are its entries whose area contains c's (one without an area contains everything and loses to any that has one); the one with the
+    smallest h * w wins, the earlier one on a tie; unless it has exactly c's area, a copy of it with c's area is appended."""
+    if c.get("area") is None:
+        return
+    ca = c["area"]
+    smallest = None
+    for x in conds:
+        a = x.get("area")
+        if a is not None:
+            if ca[2] >= a[2] and ca[3] >= a[3] and a[0] + a[2] >= ca[0] + ca[2] and a[1] + a[3] >= ca[1] + ca[3]:
+                if smallest is None or smallest.get("area") is None or smallest["area"][0] * smallest["area"][1] > a[0] * a[1]:
+                    smallest = x
+        elif smallest is None:
+            smallest = x
+    if smallest is None or smallest.get("area") == ca:
+        return
+    out = smallest.copy()
+    out["area"] = ca
+    conds.append(out)
+
+
+def _max_active(conds: List[dict]) -> int:
+    """the largest number of entries one step can have active: ranges are closed sigma intervals, so the maximum is met at an interval's end"""
+    spans = [(_fp32(c.get("timestep_end", _NO_END)), _fp32(c.get("timestep_start", _NO_START))) for c in conds]
+    return max((sum(1 for lo, hi in spans if lo <= s <= hi) for s in {v for span in spans for v in span}), default=0)
+
+
+def process_conds(positive: List[dict], negative: List[dict], shape, device, model_sampling: ModelSampling):
+    """Upstream's process_conds for the keys this stack honours, once per run (CFGGuider.sample, when model_options["ld_cond_areas"]) ->
+    (positive, negative): new lists of new dicts — the caller's are not modified.  Areas and masks are resolved on the latent of `shape`
+    ([B, C, H, W]), percent ranges become sigmas, and every entry with an area gets a partner of that area in the other list (positive ->
+    negative first, then negative -> positive).  ValueError, before anything is launched: an area that leaves the latent or has a side < 1;
+    an unmasked area narrower than 8 on an axis where it has an edge inside the latent (upstream's feather slices wrap around there, which is
+    not reproduced); more than REGIONAL_MAX_ENTRIES entries active in one step."""
+    b, _, h, w = shape
+    positive = resolve_areas_and_cond_masks(positive, b, h, w, device)
+    negative = resolve_areas_and_cond_masks(negative, b, h, w, device)
+    calculate_start_end_timesteps(model_sampling, positive)
+    calculate_start_end_timesteps(model_sampling, negative)
+    for c in list(positive):
+        create_cond_with_same_area_if_none(negative, c)
+    for c in list(negative):
+        create_cond_with_same_area_if_none(positive, c)
+    for name, conds in (("positive", positive), ("negative", negative)):
+        for i, c in enumerate(conds):
+            if c.get("area") is None:
+                continue
+            ah, aw, y, x = c["area"]
+            where = f"{name} conditioning entry {i}: area (h, w, y, x) = {c['area']}"
+            if ah < 1 or aw < 1:
+                raise ValueError(f"{where} has a side < 1")
+            if y < 0 or x < 0 or y + ah > h or x + aw > w:
+                raise ValueError(f"{where} leaves the {h} x {w} latent")
+            if c.get("mask") is None and ((ah < 8 and (y != 0 or y + ah < h)) or (aw < 8 and (x != 0 or x + aw < w))):
+                raise ValueError(f"{where} is narrower than 8 on an axis where it has an edge inside the {h} x {w} latent: the 8-pixel feather "
+                                 f"does not fit (upstream's slices wrap around there; that is not reproduced)")
+    n = _max_active(positive + negative)
+    if n > REGIONAL_MAX_ENTRIES:
+        raise ValueError(f"{n} conditioning entries are active in one step; at most {REGIONAL_MAX_ENTRIES} are supported")
+    return positive, negative
+
+
+class _RegionalGroup:
+    """the entries of one area shape that are active together: one eager UNet call on k * B rows"""
+
+    def __init__(self, windows, ctx, token, cond_or_uncond):
+        self.windows, self.ctx, self.token, self.cond_or_uncond = windows, ctx, token, cond_or_uncond
+
+
+def _regional_plan(active, b: int, H: int, W: int):
+    """What a step does for one set of active entries [(list, entry)...] in the order [cond.., uncond..] (upstream's to-run list, LD.py:2505):
+    ("plain", uncond, cond) when the existing route serves it — one unkeyed entry per list — else ("regional", groups, table): the entries
+    grouped by area shape in the order a shape first appears, batched in reverse inside a group (LD.py:2507-2516 when everything fits one batch),
+    and the combine's table in the order the entries were batched.  Each group's context is concatenated once and tagged with a token of its
+    own, so the resident K / V are re-projected only when the group on the device changes."""
+    if sum(1 for l, _ in active if l == 0) == 1 and sum(1 for l, _ in active if l == 1) == 1 and not any(_cond_is_keyed(c) for _, c in active):
+        return ("plain", [c for l, c in active if l == 1], [c for l, c in active if l == 0])
+    if len(active) > REGIONAL_MAX_ENTRIES:
+        raise ValueError(f"{len(active)} conditioning entries are active in one step; at most {REGIONAL_MAX_ENTRIES} are supported")
+    by_shape = {}
+    for l, c in active:
+        area = tuple(c["area"]) if c.get("area") is not None else (H, W, 0, 0)
+        by_shape.setdefault(area[:2], []).append((l, c, area))
+    groups, table = [], []
+    for g, members in enumerate(by_shape.values()):
+        members = members[::-1]
+        ctx = _cat_ctx([_ctx_rows(c, b) for _, c, _ in members]).contiguous()
+        groups.append(_RegionalGroup([area for _, _, area in members], ctx, next(_CTX_TOKENS), [l for l, _, _ in members]))
+        for slot, (l, c, area) in enumerate(members):
+            table.append(ops.RegionalEntry(l, g, slot, area, float(c.get("strength", 1.0)), c.get("mask"), float(c.get("mask_strength", 1.0))))
+    return ("regional", groups, table)
+
+
+def _regional_step(model, x, timestep, uncond, cond, cond_scale, model_options):
+    """One guided step with regional conditioning -> the guided result, or (uncond, cond) single unkeyed lists for the existing route.  The
+    plans are kept per run (the guider's per-run model_options) and per set of active entries."""
+    b, _, H, W = x.shape
+    state = model_options.setdefault("_ld_regional", {})
+    key = (b, H, W, id(uncond), id(cond))
+    if state.get("key") != key:
+        state.clear()
+        entries = [(0, c) for c in cond] + [(1, c) for c in uncond]
+        spans = [(_fp32(c.get("timestep_end", _NO_END)), _fp32(c.get("timestep_start", _NO_START))) for _, c in entries]
+        state.update(key=key, entries=entries, spans=spans, plans={},
+                     ranged=any("timestep_start" in c or "timestep_end" in c for _, c in entries), keep=(uncond, cond))
+    entries = state["entries"]
+    if state["ranged"]:
+        s = _host_sigma(timestep)                 # upstream: skipped when sigma[0] > timestep_start or sigma[0] < timestep_end (fp32 values)
+        active = tuple(i for i, (lo, hi) in enumerate(state["spans"]) if lo <= s <= hi)
+    else:
+        active = tuple(range(len(entries)))
+    plan = state["plans"].get(active)
+    if plan is None:
+        plan = state["plans"][active] = _regional_plan([entries[i] for i in active], b, H, W)
+    if plan[0] == "plain":
+        return plan[1], plan[2]
+    _, groups, table = plan
+    if not table:                                 # no entry is active: both lists give 0 / 1e-37 (upstream)
+        return torch.zeros_like(x)
+    wrapper = model_options.get("model_function_wrapper")
+    x = x.to(torch.float32).contiguous()
+    outs = []
+    for grp in groups:
+        k = len(grp.windows)
+        xs = ops.regional_gather(x, grp.windows)
+        ss = torch.cat([timestep] * k)
+        c = {"c_crossattn": grp.ctx, "transformer_options": {"cond_or_uncond": grp.cond_or_uncond, "sigmas": timestep, "ld_ctx_token": grp.token}}
+        if wrapper is not None:
+            out = wrapper(model.apply_model, {"input": xs, "timestep": ss, "c": c, "cond_or_uncond": grp.cond_or_uncond})
+        else:
+            out = model.apply_model(xs, ss, **c)
+        outs.append(out.to(torch.float32).contiguous())
+    return ops.regional_combine(outs, table, cond_scale, x.shape)
+
+
 def sampling_function(model, x, timestep, uncond, cond, cond_scale, model_options=None, seed=None):
     """sampling_function / calc_cond_batch / cfg_function (LD.py:2492-2626): ONE batched UNet call in the order
     [uncond, cond] (the reference reverses its to-run list, LD.py:2515), then uncond + (cond - uncond) * scale.
 
     Several entries in a conditioning list: the reference runs every entry over the WHOLE latent with weight 1 and averages
     them per list — its `get_area_and_mult` (LD.py:2435-2458) hard-codes area = the full latent and strength = 1.0 and never
-    looks at "area", "strength", "mask" or timestep-range keys, so neither does this mirror (same images as the reference;
-    those keys are inert there).  That case takes one eager UNet call on (len(uncond) + len(cond)) * B samples; the single-entry
-    case — every call the reference's own pipelines make — replays the captured hipGraph."""
+    looks at "area", "strength", "mask" or timestep-range keys, so by default neither does this mirror (same images as the
+    reference; those keys are inert there).  That case takes one eager UNet call on (len(uncond) + len(cond)) * B samples; the
+    single-entry case — every call the reference's own pipelines make — replays the captured hipGraph.
+
+    model_options["ld_cond_areas"] (apply_cond_areas=True on the sampler nodes; off by default) gives the keys upstream's meaning
+    (`_regional_step`; the entries are those CFGGuider.sample resolved with `process_conds`): per step the active entries — those whose
+    timestep range holds sigma[0] — are grouped by area shape, each group is one eager UNet call on its windows of the latent
+    (ops.regional_gather), and ops.regional_combine weighs the outputs by strength, mask and the 8-pixel feather of area edges, normalises per
+    list and applies the guidance.  A step whose active entries are one per list and carry no key takes the route above unchanged."""
     model_options = model_options or {}
     b = x.shape[0]
+    if model_options.get("ld_cond_areas"):
+        routed = _regional_step(model, x, timestep, uncond or [], cond or [], cond_scale, model_options)
+        if isinstance(routed, torch.Tensor):
+            return routed
+        uncond, cond = routed
     if not cond or not uncond:
         raise ValueError("sampling_function needs at least one positive and one negative conditioning entry")
-
-    def ctx_of(c):
-        t = c["cross_attn"]
-        if t.shape[0] != b:
-            if t.shape[0] != 1:
-                raise RuntimeError(f"conditioning batch {t.shape[0]} does not match latent batch {b}")
-            t = t.expand(b, -1, -1)
-        return t
+    ctx_of = lambda c: _ctx_rows(c, b)
 
     # the batched context is step-invariant: build it once per run (cache lives in the guider's per-run model_options) and
     # tag it with a token that is never reused, so the UNet wrapper re-projects K / V^T exactly once per run.
@@ -481,6 +711,10 @@ class CFGGuider:
             denoise_mask = prepare_mask(denoise_mask, noise.shape, device)      # once per run; on the other route the mask is dropped as it is
         self.model_options = dict(self.model_options)
         self.model_options.pop("_ld_ctx_cache", None)
+        self.model_options.pop("_ld_regional", None)
+        if self.model_options.get("ld_cond_areas"):               # once per run, on copies: areas, masks, ranges, the same-area partners
+            self.conds["positive"], self.conds["negative"] = process_conds(self.conds["positive"], self.conds["negative"], noise.shape, device,
+                                                                           self.inner_model.model_sampling)
         extra_args = {"model_options": self.model_options, "seed": seed}
         samples = sampler.sample(self, sigmas, extra_args, callback, noise, latent_image, denoise_mask, disable_pbar)
         out = self.inner_model.process_latent_out(samples.to(torch.float32))
@@ -489,9 +723,12 @@ class CFGGuider:
 
 
 def sample(model, noise, positive, negative, cfg, device, sampler, sigmas, model_options=None, latent_image=None, denoise_mask=None,
-           callback=None, disable_pbar=False, seed=None):
-    """LD.py:3010-3031."""
+           callback=None, disable_pbar=False, seed=None, apply_cond_areas: bool = False):
+    """LD.py:3010-3031.  apply_cond_areas: this run honours the conditioning entries' "area", "strength", "mask" and step-range keys
+    (model_options["ld_cond_areas"] on the guider's own copy of the options; sampling_function)."""
     g = CFGGuider(model)
+    if apply_cond_areas:
+        g.model_options = dict(g.model_options, ld_cond_areas=True)
     g.set_conds(positive, negative)
     g.set_cfg(cfg)
     return g.sample(noise, latent_image, sampler, sigmas, denoise_mask, callback, disable_pbar, seed)
@@ -519,31 +756,37 @@ class KSampler1:
             self.sigmas = self.calculate_sigmas(int(steps / denoise))[-(steps + 1):]
 
     def sample(self, noise, positive, negative, cfg, latent_image=None, denoise_mask=None, sigmas=None, callback=None,
-               disable_pbar=False, seed=None, apply_noise_mask: bool = False, **_ignored):
+               disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
         sigmas = self.sigmas if sigmas is None else sigmas
         sampler = ksampler(self.sampler, inpaint_options={"apply_denoise_mask": True}) if apply_noise_mask else ksampler(self.sampler)
         return sample(self.model, noise, positive, negative, cfg, self.device, sampler, sigmas, self.model_options,
-                      latent_image=latent_image, denoise_mask=denoise_mask, callback=callback, disable_pbar=disable_pbar, seed=seed)
+                      latent_image=latent_image, denoise_mask=denoise_mask, callback=callback, disable_pbar=disable_pbar, seed=seed,
+                      apply_cond_areas=apply_cond_areas)
 
 
 def sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0, noise_mask=None,
-            sigmas=None, callback=None, disable_pbar=False, seed=None, apply_noise_mask: bool = False, **_ignored):
+            sigmas=None, callback=None, disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
     """LD.py:3156-3203: returns the samples on the intermediate (CPU) device.  apply_noise_mask: `noise_mask` is the sampler's denoise mask —
-    redrawn where it is 1, led back to `latent_image` where it is 0 (KSamplerX0Inpaint); by default it is dropped, as the reference drops it."""
+    redrawn where it is 1, led back to `latent_image` where it is 0 (KSamplerX0Inpaint); by default it is dropped, as the reference drops it.
+    apply_cond_areas: the conditioning entries' area, strength, mask and step-range keys are honoured (sampling_function); by default they are
+    inert, as in the reference."""
     ks = KSampler1(model, steps=steps, device=model.load_device, sampler=sampler_name, scheduler=scheduler, denoise=denoise,
                    model_options=model.model_options)
     out = ks.sample(noise, positive, negative, cfg=cfg, latent_image=latent_image, denoise_mask=noise_mask, sigmas=sigmas,
-                    callback=callback, disable_pbar=disable_pbar, seed=seed, apply_noise_mask=apply_noise_mask)
+                    callback=callback, disable_pbar=disable_pbar, seed=seed, apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas)
     return out.to("cpu")
 
 
 def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, callback=None,
-                    apply_noise_mask: bool = False, **_ignored):
+                    apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
     """LD.py:6657-6701.  `callback`: the sampler loop's per-step callback ({"x", "i", "sigma", "denoised"}), e.g. a preview.LatentPreviewer.
-    apply_noise_mask: latent["noise_mask"], where there is one, is honoured by the sampler (sample1); by default it is not looked at."""
+    apply_noise_mask: latent["noise_mask"], where there is one, is honoured by the sampler (sample1); by default it is not looked at.
+    apply_cond_areas: the conditioning entries' area / strength / mask / step-range keys are honoured (sample1); by default they are inert."""
     latent_image = latent["samples"]
     noise = prepare_noise(latent_image, seed, latent.get("batch_index"))
     masked = {"noise_mask": latent.get("noise_mask"), "apply_noise_mask": True} if apply_noise_mask else {}
+    if apply_cond_areas:
+        masked["apply_cond_areas"] = True
     samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=callback, seed=seed,
                       **masked)
     out = latent.copy()
