@@ -272,10 +272,14 @@ __global__ __launch_bounds__(64 * NW, WPS) void flash_attn2_kernel(const AttnPar
             for (int e = 0; e < 16; e += 2) {
                 const float p0 = __builtin_amdgcn_exp2f(s[e]);
                 const float p1 = __builtin_amdgcn_exp2f(s[e + 1]);
-                if (!ONES) psum += p0 + p1;
-                // round to NEAREST (v_cvt_pk_f16_f32): without the ones column the denominator sums the unrounded p, and truncated
-                // weights against it shrank every output by their mean truncation error (-3.4e-4, V == 1 gave 0.99951)
+                // round to NEAREST (v_cvt_pk_f16_f32): truncated weights against an unrounded denominator shrank every output by their
+                // mean truncation error (-3.4e-4, V == 1 gave 0.99951)
                 const half2v h2 = __builtin_bit_cast(half2v, pk2h(p0, p1));
+                // without the ones column the denominator sums the ROUNDED weights, the ones the MFMA multiplies: numerator and
+                // denominator are one set of weights, so a constant V comes back exactly.  (Summing the unrounded p left the mean
+                // rounding error of P in every output: inside 2^-12 while many keys share the weight, but a row that two or three
+                // keys dominate — one in 1e5 randn rows of 77 keys — lost an fp16 ulp: V == 1 gave 0.99951 there.)
+                if (!ONES) psum += (float)h2[0] + (float)h2[1];
                 pf[e >> 3][e & 7] = h2[0];
                 pf[e >> 3][(e & 7) + 1] = h2[1];
             }
@@ -496,8 +500,8 @@ __global__ __launch_bounds__(512, 2) void flash_attn512_kernel(const AttnParams 
         for (int e = 0; e < 16; e += 2) {
             const float p0 = __builtin_amdgcn_exp2f(s[e] - m_ref);
             const float p1 = __builtin_amdgcn_exp2f(s[e + 1] - m_ref);
-            psum += p0 + p1;
-            const half2v h2 = __builtin_bit_cast(half2v, pk2h(p0, p1));   // round to nearest: see flash_attn2_kernel
+            const half2v h2 = __builtin_bit_cast(half2v, pk2h(p0, p1));   // round to nearest, and the denominator sums what the MFMA multiplies: see flash_attn2_kernel
+            psum += (float)h2[0] + (float)h2[1];
             pf[e >> 3][e & 7] = h2[0];
             pf[e >> 3][(e & 7) + 1] = h2[1];
         }

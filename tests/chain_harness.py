@@ -5,7 +5,8 @@ The chain side: `ChainBase`, the weight plumbing and the tap list of tests/unet_
 
   B1  `same_launches`   the chain's launch list against the executor's profile table, entry by entry;
   B2  `differs`, `bits_held`, `same_bits`   torch.equal with the shape history A, B, A; no tolerance;
-  B3  `held`, `partials_held`, `every_stage`, `stages_held`   EB.check per tap, the worst figures per stage kind;
+  B3  `held`, `partials_held`, `every_stage`, `stages_held`   EB.check per tap, the worst figures per stage kind; `tap_images`: a tap cut to
+      a fixed subset of its images (a full-width case evaluates its fp64 references on two images, one at a time);
   `record`, `stage_record`   the one LD_WRITE_PARITY=1 writer into profiles/; `side_fixture`   the module-scoped cache of a module's Side.
 
 pytest rewrites no assertion of a helper module: every assert here carries its message.
@@ -139,17 +140,60 @@ def stage_record(worst: dict, tol: float = 1.0) -> dict:
     return {k: {"worst_error_over_bound": round(v[0], 4), "signed_bias_over_tolerance": round(v[1] / tol, 4)} for k, v in sorted(worst.items())}
 
 
-def every_stage(name, taps, stage_fn):
-    """stage_fn(tap, what) -> [(error / bound, signed bias)] on every tap.  -> (the record per stage kind, the failed stages' messages)."""
+EVERY_IMAGE = "every image"     # as the `images` of every_stage: all images of a tap, one at a time
+
+
+def image_indices(images, n):
+    """The image subset of a case table (negative: counted from the end; EVERY_IMAGE: all) as sorted indices into a tap of n images."""
+    if images == EVERY_IMAGE:
+        return list(range(n))
+    assert all(-n <= i < n for i in images), f"image subset {tuple(images)} of a tap of {n} images"
+    return sorted({i % n for i in images})
+
+
+def tap_images(tap, images):
+    """The tap restricted to `images` of the tap['n'] images it ran on: every tensor of its inputs, output(s) and partial statistics cut to
+    those images — [n][...] by index, the rows [n L][C] of a linear as L rows per image.  Parameters (tap['par']) are shared by the images.
+    Only for stages that are separable per image (a convolution, GroupNorm's statistics, attention, the rows of a linear)."""
+    n = tap["n"]
+    idx = image_indices(images, n)
+
+    def cut(t):
+        if isinstance(t, (tuple, list)):
+            return type(t)(cut(e) for e in t)
+        if not isinstance(t, torch.Tensor):
+            return t
+        at = torch.as_tensor(idx, device=t.device)
+        if t.shape[0] == n:
+            return t.index_select(0, at)
+        assert t.dim() == 2 and t.shape[0] % n == 0, f"{tap['name']}: a tensor of shape {tuple(t.shape)} in a tap of {n} images"
+        return t.reshape(n, t.shape[0] // n, t.shape[1]).index_select(0, at).reshape(-1, t.shape[1])
+
+    cutd = dict(tap, n=len(idx), inp={k: cut(v) for k, v in tap["inp"].items()}, out=cut(tap["out"]))
+    if tap.get("part") is not None:
+        cutd["part"] = cut(tap["part"])
+    return cutd
+
+
+def every_stage(name, taps, stage_fn, images=None):
+    """stage_fn(tap, what) -> [(error / bound, signed bias)] on every tap.  -> (the record per stage kind, the failed stages' messages).
+    images: a fixed subset of images (negative: from the end).  A tap that carries its image count (tap['n']: a stage separable per image)
+    is then evaluated on those images only, one image at a time (`tap_images`; the failure names the image) — the other images of such a
+    tap are NOT looked at; a tap without 'n' is evaluated whole."""
     fails, worst = [], {}
     for tap in taps:
         what = f"{name} {tap['name']} [{tap.get('kernel') or tap['launches']}]"
-        try:
-            for r, b in stage_fn(tap, what):
-                w = worst.setdefault(tap["kind"], [0.0, 0.0])
-                w[0], w[1] = max(w[0], r), (b if abs(b) > abs(w[1]) else w[1])
-        except AssertionError as e:
-            fails.append(str(e))
+        if images is None or "n" not in tap:
+            views = [(tap, what)]
+        else:
+            views = ((tap_images(tap, [j]), f"{what} image {j}") for j in image_indices(images, tap["n"]))
+        for view, where in views:
+            try:
+                for r, b in stage_fn(view, where):
+                    w = worst.setdefault(tap["kind"], [0.0, 0.0])
+                    w[0], w[1] = max(w[0], r), (b if abs(b) > abs(w[1]) else w[1])
+            except AssertionError as e:
+                fails.append(str(e))
     return stage_record(worst, EB.BIAS_TOL), fails
 
 

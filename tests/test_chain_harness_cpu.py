@@ -98,6 +98,67 @@ def test_every_stage_reports_the_failed_stage_and_keeps_the_others():
                                  "last": {"worst_error_over_bound": 0.75, "signed_bias_over_tolerance": round(-1e-5 / EB.BIAS_TOL, 4)}}
 
 
+def _image_tap(n=5, rows=3, c=8, bad=None):
+    """A tap of n images in the three layouts a chain hands over — [n][h][w][C], the rows [n L][C] of a linear, [n][C] — with an output pair;
+    bad: (image, factor) scales that image's first output."""
+    ref, bound = _operands(3, (n, rows, 1, c))[1:]
+    y = ref.half()
+    if bad is not None:
+        y[bad[0]] *= bad[1]
+    return dict(kind="conv", name="block.0", launches="k_conv", kernel="k_conv", n=n, par=dict(w=torch.arange(n)),
+                inp=dict(x=ref, rows=ref.reshape(n * rows, c), rowvec=ref[:, 0, 0], stride=1, out_hw=(rows, 1), none=None),
+                out=(y, y.reshape(n * rows, c)), part=torch.arange(n * 4.0).reshape(n, 2, 2))
+
+
+def test_tap_images_cuts_every_layout_by_image():
+    tap = _image_tap()
+    cut = H.tap_images(tap, (0, -1))
+    assert cut["n"] == 2 and cut["kind"] == "conv" and cut["par"] is tap["par"]                 # (parameters are shared: 5 weights stay 5)
+    for k, full in (("x", tap["inp"]["x"]), ("rowvec", tap["inp"]["rowvec"])):
+        assert torch.equal(cut["inp"][k], full[[0, 4]])
+    assert torch.equal(cut["inp"]["rows"], tap["inp"]["x"][[0, 4]].reshape(6, 8))
+    assert cut["inp"]["stride"] == 1 and cut["inp"]["out_hw"] == (3, 1) and cut["inp"]["none"] is None
+    assert torch.equal(cut["out"][0], tap["out"][0][[0, 4]]) and torch.equal(cut["out"][1], tap["out"][1].reshape(5, 3, 8)[[0, 4]].reshape(6, 8))
+    assert torch.equal(cut["part"], tap["part"][[0, 4]])
+    assert H.image_indices((0, -1), 5) == [0, 4] and H.image_indices((0, -1), 1) == [0] and H.image_indices(H.EVERY_IMAGE, 3) == [0, 1, 2]
+    with pytest.raises(AssertionError, match=r"image subset \(0, 7\) of a tap of 5 images"):
+        H.tap_images(tap, (0, 7))
+    with pytest.raises(AssertionError, match=r"block\.0: a tensor of shape \(7, 8\) in a tap of 5 images"):
+        H.tap_images(dict(tap, inp=dict(x=torch.zeros(7, 8))), (0,))
+
+
+def test_every_stage_on_an_image_subset():
+    """The subset is a condition of the case table, not coverage: a defect in an image inside it is rejected by name, one in an image
+    outside it is NOT SEEN by B3 (B2 still compares every image's bits with the chain's) — by construction."""
+    whole = dict(kind="first", name="conv_in", launches="k_in", inp=dict(x=torch.zeros(5, 2)), par={}, out=torch.zeros(5, 2))
+    seen = []
+
+    def stage(tap, what):
+        seen.append((what, tap.get("n"), tuple(tap["out"][0].shape) if "n" in tap else tuple(tap["out"].shape)))
+        if "n" not in tap:
+            return [(0.0, 0.0)]
+        ref, bound = _operands(3, (5, 3, 1, 8))[1:]
+        if " image " in what:                                            # (the reference of that one image, from the image the message names)
+            j = int(what.rsplit(" ", 1)[1])
+            ref, bound = ref[j:j + 1], bound[j:j + 1]
+        return [H.held(tap["out"][0], ref, bound, what)]
+    tap0 = _image_tap()
+    rec, fails = H.every_stage("case", [whole, tap0], stage, images=(0, -1))
+    assert not fails and sorted(rec) == ["conv", "first"]
+    assert seen == [("case conv_in [k_in]", None, (5, 2)), ("case block.0 [k_conv] image 0", 1, (1, 3, 1, 8)), ("case block.0 [k_conv] image 4", 1, (1, 3, 1, 8))]
+    tap0 = _image_tap(bad=(4, 1.01))                                     # inside the subset
+    rec, fails = H.every_stage("case", [whole, tap0], stage, images=(0, -1))
+    assert len(fails) == 1 and fails[0].startswith("case block.0 [k_conv] image 4: element bound: "), fails
+    tap0 = _image_tap(bad=(2, 1.01))                                     # outside the subset: not seen ...
+    rec, fails = H.every_stage("case", [whole, tap0], stage, images=(0, -1))
+    assert not fails
+    rec, fails = H.every_stage("case", [whole, tap0], stage, images=H.EVERY_IMAGE)            # ... seen with every image, one at a time
+    assert len(fails) == 1 and fails[0].startswith("case block.0 [k_conv] image 2: element bound: "), fails
+    seen.clear()
+    H.every_stage("case", [whole, _image_tap()], stage)                  # no subset: the tap whole, as it was
+    assert seen[1] == ("case block.0 [k_conv]", 5, (5, 3, 1, 8))
+
+
 def test_partials_held():
     y = torch.randn(1, 2, 2, 64, generator=torch.Generator().manual_seed(1)).half()          # 4 pixels, 32 groups of 2 channels
     yg = y.double().reshape(1, 4, 32, 2)

@@ -76,7 +76,9 @@ def test_rtn_bias_statistic_is_noise():
 
 def _simulated_attention(q, k, v, heads, rtz):
     """The flash kernels' arithmetic without the ones column: fp32 scores from the fp16-rounded q * scale * log2(e), exp2 weights, P
-    converted to fp16 (round to nearest or toward zero), numerator from the fp16 P, denominator from the unrounded fp32 weights."""
+    converted to fp16 (round to nearest or toward zero), numerator from the fp16 P, denominator from the unrounded fp32 weights — the
+    arithmetic whose rounding mode the bias statistic has to tell apart.  (The kernels' denominator has since summed the ROUNDED weights
+    without the ones column too — attention.hip — which only shrinks the error this models: _simulated_lazy_attention follows them.)"""
     b, lq, c = q.shape
     d = c // heads
     c2 = (1.0 / math.sqrt(d)) * 1.4426950408889634
@@ -108,8 +110,8 @@ def _simulated_lazy_attention(q, k, v, heads, ones, causal, defect=None):
     """The flash kernels' lazy-reference recursion in torch fp32 (attention.hip): Q * scale * log2(e) rounded to fp16 once; per 32-key
     subtile the scores relative to the reference m_ref; the first subtile sets m_ref to its maximum, a later one moves it (per row) by
     delta = its maximum where that exceeds TAU and by 0 elsewhere; a move scales O and l by alpha = 2^-delta and shifts the scores; P is
-    rounded to fp16 to nearest, the numerator sums the rounded P, the denominator the rounded P (`ones`: the spare V column of 1.0, part
-    of O) or the unrounded weights (l_run).  defect: 'o' O not rescaled, 'l' l_run not rescaled (the unrounded denominator only), 'shift'
+    rounded to fp16 to nearest, numerator and denominator both sum the rounded P: the denominator as the spare V column of 1.0, part of O
+    (`ones`), or in a register of its own (l_run).  defect: 'o' O not rescaled, 'l' l_run not rescaled (the register only), 'shift'
     scores not shifted after a move, 'wave' every row of a 32-row wave rescaled by the wave's largest delta (scores by their own)."""
     import attn_patterns as AP
     b, lq, c = q.shape
@@ -145,7 +147,7 @@ def _simulated_lazy_attention(q, k, v, heads, ones, causal, defect=None):
         p = torch.exp2(s)
         ph = p.half().float()
         o = o + ph @ vf[:, :, keys]
-        l = l + (ph if ones else p).sum(-1, keepdim=True)
+        l = l + ph.sum(-1, keepdim=True)
     return (o * (1.0 / l)).half().transpose(1, 2).reshape(b, lq, c)
 
 
@@ -236,8 +238,14 @@ def test_peaked_inputs_hold_their_margins_for_every_route_row():
     ATTN_PEAKED here, and hold each case's facts to what its pattern is for."""
     import attn_patterns as AP
     import test_routes_gpu as R
+    built = {}                                             # (the V layouts of one shape take the same inputs: built once; the last two kept)
     for seam, b, heads, lq, lk, d, causal, route, pattern in R.ATTN_PEAKED_CASES:
-        facts = AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)[3]
+        key = (pattern, b, heads, lq, lk, d, causal)
+        if key not in built:
+            if len(built) == 2:
+                built.pop(next(iter(built)))
+            built[key] = AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)[3]
+        facts = built[key]
         moves, pl, jumps = facts["moves"], facts["planted"], facts["jumps"]
         nsub, what = moves.shape[-1], (route, pattern, b, heads, lq, lk, d)
         if pattern in ("spike", "stairs", "onehot"):
@@ -460,6 +468,36 @@ def test_small_conv_out_ref_and_bound(n, h, w, cin, cout):
         EB.check(x_in - _rtz(v32.double()).float() * sg, ref, bound, "RTZ eps")
     ref2, _ = EB.small_conv_out_ref(torch.cat([x, x]), wt, b, 0, x_in, sigma, in_mod=n)
     assert torch.equal(ref2[:n], ref) and torch.equal(ref2[n:], ref)
+
+
+def test_small_conv_out_mode0_accepts_what_mode2_accepts_near_zero():
+    """Mode 0 rounds v to fp16 before x_in - eps sigma.  Near v = 0 the fp16 grid (2^-24 below 2^-14) is finer than the accumulation error
+    e_v that mode 2 allows, so a device v inside e_v may round SEVERAL fp16 numbers away from the mirror's eps: a bound of one step there
+    rejected a right kernel (2 to 5 outputs of a full-width UNet step).  Every v that mode 2 accepts must give an output mode 0 accepts;
+    a v outside e_v by a few fp16 steps is still rejected, and away from zero the bound is the one step it was."""
+    n, h, w, cin, cout = 1, 24, 24, 320, 4
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(n, h, w, cin, generator=g).half()
+    wt = (torch.randn(cout, 9 * cin, generator=g) / math.sqrt(9 * cin)).half()
+    b = torch.zeros(cout).half()
+    x_in, sigma = torch.randn(n, cout, h, w, generator=g) * 3.0, torch.tensor([7.0])
+    v64, e_v = EB.small_conv_out_ref(x, wt, b, 2)
+    ref, bound = EB.small_conv_out_ref(x, wt, b, 0, x_in, sigma)
+    ulp = EB._fp16_ulp(v64)
+    fine = e_v >= 0.5 * ulp                                              # where the grid is finer than the accumulation error
+    assert int(fine.sum()) >= 10 and int((~fine).sum()) >= 1000, (int(fine.sum()), int((~fine).sum()))
+    out = lambda v: x_in.double() - v.half().double() * 7.0
+    for sign in (1.0, -1.0):
+        v_dev = v64 + sign * 0.95 * e_v
+        EB.check(v_dev, v64, e_v, "mode 2 accepts")
+        EB.check(out(v_dev), ref, bound, "mode 0 on the same v")
+        moved = ((v_dev.half().double() - v64.half().double()).abs() / ulp)[fine]
+        assert float(moved.max()) >= 2.0, "no eps moved more than one fp16 step: the case does not show the flaw"
+    one_step = 7.0 * ulp + 2.0 ** -23 * (x_in.double().abs() + 2.0 * (v64.half().double() * 7.0).abs()) + 1e-30
+    assert bool((bound[~fine] <= one_step[~fine]).all()), "away from zero the bound is one fp16 step at the most"
+    far = v64 + 2.5 * e_v + 3.0 * ulp
+    with pytest.raises(AssertionError, match="element bound"):
+        EB.check(out(far), ref, bound, "v outside e_v")
 
 
 def test_fold_refs_and_bounds():

@@ -18,6 +18,7 @@ fp64 run of the recursion records and whose margins keep them independent of rou
 descend (all weight in the first subtile, the rest underflows in P), offset (every score of a row +-35 units away from zero), onehot (one key
 40 units above all others: the output row is that key's v row bit for bit).  Same route assertion, same element bound.
 """
+import functools
 import math
 
 import pytest
@@ -50,7 +51,7 @@ def _fa2(dk, rowv, masked, nw):
 
 # (V layout, b, heads, Lq, Lk, d, causal, expected route).  Lq = 100 / 200 end inside a 128-query workgroup; Lk % 64 in {0, 1, 63};
 # d = 24 / 56 / 72 / 88 / 120 / 152 leave a tail inside their k-step class; even DK (d in 17-32, 49-64, 81-96, 113-128, 145-160) have no
-# spare V column for the ones trick: their softmax denominator is summed from the unrounded weights.
+# spare V column for the ones trick: their softmax denominator is summed in a register, from the rounded weights the MFMA multiplies.
 ATTN_ROUTES = []
 for _d, _dk in [(8, 1), (16, 1), (24, 2), (32, 2), (40, 3), (48, 3), (56, 4), (64, 4), (72, 5), (80, 5), (88, 6), (96, 6),
                 (120, 8), (128, 8), (152, 10), (160, 10)]:
@@ -64,6 +65,12 @@ for _d, _dk in [(40, 3), (64, 4)]:
         ATTN_ROUTES.append((_rowv, 8, 8, 2048, 63, _d, False, _fa2(_dk, _rowv, True, 8)))
         # one block short of the 8-wave rule: 4 waves
         ATTN_ROUTES.append((_rowv, 8, 8, 1920, 64, _d, False, _fa2(_dk, _rowv, False, 4)))
+for _d, _dk in [(40, 3), (64, 4)]:
+    for _rowv in (False, True):
+        # 8-wave workgroups that END inside their 256 queries: Lq = 2112 is 8 blocks and 64 queries, six of the last block's eight waves hold no
+        # query; 33 full key tiles (self-attention), and the 77 keys of a prompt
+        ATTN_ROUTES.append((_rowv, 8, 8, 2112, 2112, _d, False, _fa2(_dk, _rowv, False, 8)))
+        ATTN_ROUTES.append((_rowv, 8, 8, 2112, 77, _d, False, _fa2(_dk, _rowv, True, 8)))
 for _d, _dk in [(64, 4), (160, 10)]:
     ATTN_ROUTES.append((False, 1, 2, 77, 77, _d, True, _fa2(_dk, False, True, 4)))        # causal (CLIP: d = 64, L = 77)
     ATTN_ROUTES.append((True, 1, 2, 128, 128, _d, True, _fa2(_dk, True, True, 4)))
@@ -90,9 +97,11 @@ def test_attention_route(ops, rowv, b, heads, lq, lk, d, causal, route):
 
 @pytest.mark.parametrize("rowv,b,heads,lq,lk,d,causal,route", ATTN_ROUTES, ids=lambda v: str(v))
 def test_attention_constant_v_is_exact(ops, rowv, b, heads, lq, lk, d, causal, route):
-    """V == 1: every output is a weighted mean of ones.  With P rounded to nearest the relative error of the denominator is a weighted mean of
-    +-2^-11 errors, far inside the half ulp (2^-12) below 1.0: every instantiation returns exactly 1.0 from 64 keys on.  Below 64 keys (a
-    causal row sees fewer) a handful of weights can move it one fp16 ulp.  Truncated P against an unrounded denominator returned 0.99951."""
+    """V == 1: every output is a weighted mean of ones.  Numerator and denominator sum the same fp16-rounded weights (the ones column, or
+    l_run), so every instantiation returns exactly 1.0 from 64 keys on.  Below 64 keys (a causal row sees fewer) a handful of weights can move
+    it one fp16 ulp.  Truncated P against an unrounded denominator returned 0.99951 in every row; P rounded to nearest against an unrounded
+    denominator (the weighted mean of +-2^-11 errors: inside the half ulp 2^-12 below 1.0 while many keys share the weight) still did in the
+    ONE row of 135168 that two keys dominate — d = 64, 2112 queries, 77 keys, effective key count 2.3 — until l_run summed the rounded weights."""
     q, k = r16((b, lq, heads * d), 4), r16((b, lk, heads * d), 5)
     v = torch.ones(b, lk, heads * d, dtype=torch.float16, device=DEV)
     o = _attn_call(ops, rowv, q, k, v, heads, causal).float()
@@ -146,7 +155,20 @@ for _d, _dk in [(40, 3), (64, 4)]:
 for _d, _dk in [(40, 3), (80, 5), (160, 10)]:
     ATTN_PEAKED.append(("qkv", 2, 8, 192, 192, _d, False, _fa2(_dk, True, False, 4), ("spike", "stairs")))       # the executors' own layout
 ATTN_PEAKED.append(("qkv", 2, 1, 256, 256, 512, False, "flash_attn512_kernel<512,plain>", ("spike", "stairs")))
+for _d, _dk in [(40, 3), (64, 4)]:
+    for _lk, _masked in ((2112, False), (77, True)):
+        for _rowv in (False, True):
+            # the 8-wave workgroup that ends inside its 256 queries (ATTN_ROUTES); the two V layouts of a shape side by side: they share inputs
+            ATTN_PEAKED.append(("rowv" if _rowv else "vt", 8, 8, 2112, _lk, _d, False, _fa2(_dk, _rowv, _masked, 8), ("spike", "onehot")))
 ATTN_PEAKED_CASES = [row[:8] + (pat,) for row in ATTN_PEAKED for pat in row[8]]
+
+
+@functools.lru_cache(maxsize=2)
+def _peaked_inputs(pattern, b, heads, lq, lk, d, causal):
+    """attn_patterns.make on the CPU (never changed by a test); the last two kept: the V layouts of one shape run on the same inputs, and the
+    fp64 recursion of a 2112 x 2112 case takes longer than its kernel and reference together."""
+    import attn_patterns as AP
+    return AP.make(pattern, b, heads, lq, lk, d, causal, seed=d)
 
 
 @pytest.mark.parametrize("seam,b,heads,lq,lk,d,causal,route,pattern", ATTN_PEAKED_CASES, ids=lambda v: str(v))
@@ -154,7 +176,7 @@ def test_attention_route_peaked(ops, seam, b, heads, lq, lk, d, causal, route, p
     """The same route, element bound and bias statistic as test_attention_route on inputs whose softmax reference moves after the first subtile
     (tests/attn_patterns.py), and the onehot rows bit for bit."""
     import attn_patterns as AP
-    q, k, v, facts = (t.to(DEV) if isinstance(t, torch.Tensor) else t for t in AP.make(pattern, b, heads, lq, lk, d, causal, seed=d))
+    q, k, v, facts = (t.to(DEV) if isinstance(t, torch.Tensor) else t for t in _peaked_inputs(pattern, b, heads, lq, lk, d, causal))
     if seam == "qkv":
         o = ops.attention_qkv(torch.cat([q, k, v], -1).contiguous(), heads, causal=causal)
     else:
@@ -348,6 +370,20 @@ CONV_ROUTES = [
     (2, 40, 40, 640, 640, 640, 1, None, 1, False, True, "gemm4_kernel<64,64,conv,2wg>"),              # 1x1 over two sources
     (2, 32, 32, 128, 64, 256, 1, None, 3, False, False, "gemm3_kernel<64,128,conv>+splitk_reduce_kernel"),
     (4, 64, 64, 512, 0, 512, 1, None, 3, False, True, "gemm3_kernel<128,128,conv>"),
+    # H != W, the levels of a 512 x 768 request (latent 96 x 64): the halo tile with 24 / 12 four- and eight-row tiles per image, the smallest
+    # image counts that keep 192 tiles
+    (8, 96, 64, 320, 0, 320, 1, None, 3, True, True, "conv6_kernel<W64,halo>"),
+    (8, 48, 32, 320, 0, 320, 1, (96, 64), 3, False, False, "conv6_kernel<W64,halo,up>"),
+    (32, 48, 32, 320, 0, 320, 1, None, 3, False, True, "conv6_kernel<W32,halo>"),
+    (32, 24, 16, 320, 0, 320, 1, (48, 32), 3, False, False, "conv6_kernel<W32,halo,up>"),
+    (128, 24, 16, 320, 0, 320, 1, None, 3, False, False, "gemm5_kernel<256,320,conv>"),            # 24 rows are no whole 16-row W16 tiles: declined
+    # the declines at full width: two portrait images per level (the row-resident kernel takes Ho == Wo only, the halo tile has too few tiles)
+    # and a landscape level (a 96-pixel row is no tile width of either)
+    (2, 12, 8, 1280, 0, 1280, 1, None, 3, False, True, "gemm3_kernel<64,160,conv,deep>+splitk_reduce_kernel"),
+    (2, 24, 16, 640, 0, 640, 1, None, 3, True, False, "gemm3_kernel<64,160,conv>+splitk_reduce_kernel"),
+    (2, 48, 32, 320, 0, 640, 1, None, 3, False, False, "gemm3_kernel<64,160,conv>+splitk_reduce_kernel"),
+    (2, 64, 96, 320, 0, 320, 1, None, 3, True, True, "gemm3_kernel<64,160,conv,deep>"),
+    (2, 96, 64, 320, 0, 320, 1, None, 3, False, False, "gemm3_kernel<64,160,conv,deep>"),
 ]
 
 
@@ -383,6 +419,10 @@ GN_CONV_ROUTES = [
     (3, 128, 128, 256, 0, 256, "conv6_kernel<W128,halo+groupnorm,256>"),
     (2, 256, 256, 128, 0, 128, "conv6_kernel<W128,halo+groupnorm,128x512>"),
     (3, 128, 128, 320, 0, 320, "conv6_kernel<W128,halo+groupnorm>"),
+    # H != W: level 0 of a 512 x 768 request, 24 four-row tiles per image, 192 in all
+    (8, 96, 64, 320, 0, 320, "conv6_kernel<W64,halo+groupnorm>"),
+    (8, 96, 64, 128, 192, 320, "conv6_kernel<W64,halo+groupnorm>"),
+    (2, 64, 96, 320, 0, 320, "gemm3_kernel<64,160,conv,deep>"),           # landscape: the two-pass GroupNorm in front of the general tiles
 ]
 
 
@@ -410,11 +450,14 @@ GN_PART_ROUTES = [
     (8, 16, 16, 1280, 1280, "gemm3_kernel<128,160,conv>+splitk_reduce_gn_kernel"),
     (8, 32, 32, 1280, 640, "conv6_kernel<W32,halo>+splitk_reduce_gn_kernel"),
     (16, 16, 16, 1280, 1280, "conv6_kernel<W16,halo>+splitk_reduce_gn_kernel"),
+    (8, 48, 32, 1280, 640, "conv6_kernel<W32,halo>+splitk_reduce_gn_kernel"),          # H != W: level 1 of a 512 x 768 request
+    (8, 24, 16, 1280, 1280, "gemm3_kernel<128,160,conv>+splitk_reduce_gn_kernel"),     # its level 2: no whole W16 tiles
 ]
 
 
 SKIP_ROUTES = [
     (12, 64, 64, 320, 320, 320, 320, "gemm5_kernel<256,320,conv>"),        # 192 tiles of 256 x 320, K = 9 c + skip channels
+    (8, 96, 64, 320, 320, 320, 320, "gemm5_kernel<256,320,conv>"),         # H != W: 192 tiles of four image rows
 ]
 
 
@@ -470,20 +513,39 @@ def _contraction(name):
     return any(name.startswith(b) for b in ("gemm", "conv6_kernel", "conv8_kernel", "flash_attn", "splitk_reduce"))
 
 
-@pytest.mark.parametrize("batch,hw,pair", [(8, 64, True), (1, 64, True), (4, 128, True)])
+def halo_routes_off_square():
+    """The routes of the convolution tables' rows with H != W (the size the kernel runs at: out_hw where the row resizes)."""
+    routes = set()
+    for table, hw_of in ((CONV_ROUTES, lambda r: r[7] or (r[1], r[2])), (GN_CONV_ROUTES, lambda r: (r[1], r[2])), (GN_PART_ROUTES, lambda r: (r[1], r[2])),
+                         (SKIP_ROUTES, lambda r: (r[1], r[2]))):
+        routes.update(row[-1] for row in table if hw_of(row)[0] != hw_of(row)[1])
+    return routes
+
+
+@pytest.mark.parametrize("batch,hw,pair", [(8, (64, 64), True), (1, (64, 64), True), (4, (128, 128), True), (4, (96, 64), True), (1, (64, 96), True)],
+                         ids=lambda v: (str(v[0]) if v[0] == v[1] else f"{v[0]}x{v[1]}") if isinstance(v, tuple) else None)
 def test_unet_forward_routes_are_pinned(batch, hw, pair):
-    """Every contraction instantiation the profiled SD1.5 UNet forward (CFG pair) dispatches at batch 8 / 1 at 64^2 and at the hires step
-    (b = 4 at 128^2) has a row above, with its epilogue / split suffix."""
+    """Every contraction instantiation the profiled SD1.5 UNet forward (CFG pair) dispatches at batch 8 / 1 at 64^2, at the hires step
+    (b = 4 at 128^2) and at the non-square requests (b = 4 at 96 x 64, b = 1 at 64 x 96) has a row above, with its epilogue / split suffix.
+    The name alone does not say at which geometry a row runs: every halo-tile route a NON-SQUARE forward dispatches also has a row with
+    H != W (tiles of whole image rows: the tile count per image and the band edges follow H, the tile width W)."""
     from lightdiffusion_amd import weights as W
     from lightdiffusion_amd.unet import synthetic_unet
-    u = synthetic_unet(W.sd15_unet_config(), max_batch=2 * batch, max_hw=(hw, hw))
+    h, w = hw
+    u = synthetic_unet(W.sd15_unet_config(), max_batch=2 * batch, max_hw=(h, w))
     u.set_context(torch.randn(2 * batch, 77, 768))
-    x = torch.randn(batch, 4, hw, hw, device=DEV)
+    x = torch.randn(batch, 4, h, w, device=DEV)
     u.profile_pair(x, torch.full((batch,), 3.0, device=DEV))
     seen = {k for k in u.profile_kernels() if _contraction(k)}
     assert seen, "no contraction kernels profiled"
     missing = sorted(seen - route_names())
     assert not missing, f"dispatched but not pinned by a route row: {missing}"
+    if h != w:
+        halo = {k for k in seen if k.startswith("conv6_kernel<") and "halo" in k}
+        # (portrait: 64-, 32- and 16-pixel rows are tile widths; landscape: 96-, 48- and 24-pixel rows are not)
+        assert bool(halo) == (w == 64), f"{batch} x {h} x {w}: halo-tile routes {sorted(halo)}"
+        square_only = sorted(halo - halo_routes_off_square())
+        assert not square_only, f"halo-tile routes of a non-square forward whose rows are all square: {square_only}"
 
 
 def test_vae_decode_routes_are_pinned():

@@ -60,9 +60,11 @@ def inputs(name):
 
 class Side:
     """One config and weight source: the executor's handle, the chain, and per case the chain's output and taps (computed once, never changed).
-    source: a WeightSource for both (None: the synthetic checkpoint); cases / inputs_of: another case table and its inputs (None: CASES / inputs)."""
+    source: a WeightSource for both (None: the synthetic checkpoint); cases / inputs_of: another case table and its inputs (None: CASES / inputs).
+    one_case_taps: keep the taps of ONE case at a time (a full-width case's are gigabytes): asking for another case's taps drops them and
+    runs that case's chain again, which must return the bits it returned before; every case's output stays (`chain_out`)."""
 
-    def __init__(self, tag, source=None, cases=None, inputs_of=None):
+    def __init__(self, tag, source=None, cases=None, inputs_of=None, one_case_taps=False):
         from lightdiffusion_amd.unet import MI355XUNet, synthetic_unet
         from unet_chain import UNetChain
         self.tag, self.cfg = tag, config(tag)
@@ -72,16 +74,26 @@ class Side:
                   max_tokens=max(c[3] for c in mine))
         self.unet = synthetic_unet(self.cfg, **kw) if source is None else MI355XUNet(self.cfg, source, **kw)
         self.chain = UNetChain(self.cfg, DEV, source=source)
+        self.one_case_taps = one_case_taps
         self._chain_runs = {}
 
     def chain_run(self, name):
-        if name not in self._chain_runs:
+        if name not in self._chain_runs or self._chain_runs[name][1] is None:
             _, _, _, _, mode = self.cases[name]
+            if self.one_case_taps:
+                self._chain_runs = {k: (o, None) for k, (o, _) in self._chain_runs.items()}
+                self.chain.taps = []
             x, sigma, ctx = self.inputs(name)
             self.chain.set_context(ctx)
             out = self.chain.forward(x, sigma, eps_only=mode == "eps", pair=mode == "pair")
+            if name in self._chain_runs:
+                H.bits_held(out, self._chain_runs[name][0], f"{name}: the chain, run again for its taps,")
             self._chain_runs[name] = (out, self.chain.taps)
         return self._chain_runs[name]
+
+    def chain_out(self, name):
+        """The chain's output of the case alone (no taps asked for: none evicted)."""
+        return self._chain_runs[name][0] if name in self._chain_runs else self.chain_run(name)[0]
 
     def executor_run(self, name):
         _, _, _, _, mode = self.cases[name]
@@ -215,7 +227,13 @@ def _stage(tap, chain, what):
         ref, bound = R._ln_ref(i["x"], p["w_prod"], p["b_prod"], p["gamma"], p["beta"], p["w"], p["b"], t, 1e-5, p["geglu"])
         return [a, H.held(y, ref, bound, what + " consumer", bias_extra=EB.GELU_FIT_BIAS if p["geglu"] else 0.0)]
     if kind == "attention":
-        ref, bound = EB.attention_ref(i["q"].contiguous(), i["k"].contiguous(), i["v"].contiguous(), chain.heads)
+        q, k, v, heads = i["q"], i["k"], i["v"], chain.heads
+        if 8 * q.shape[0] * heads * q.shape[1] * k.shape[1] <= 1 << 31:
+            ref, bound = EB.attention_ref(q.contiguous(), k.contiguous(), v.contiguous(), heads)
+        else:                                              # the same reference head by head (the heads' columns are independent): fp64 score matrices of 2 GB at the most
+            d = q.shape[-1] // heads
+            per = [EB.attention_ref(*(t[..., j * d:(j + 1) * d].contiguous() for t in (q, k, v)), 1) for j in range(heads)]
+            ref, bound = torch.cat([r for r, _ in per], -1), torch.cat([b for _, b in per], -1)
         return [H.held(out, ref, bound, what)]
     if kind == "dup":
         for full, half in zip(out, (i["t"], i["q2"], i["x"])):

@@ -6,7 +6,8 @@ Downsample1 / Upsample1 (LD.py:5141-5186), EPS.calculate_input / calculate_denoi
 CFG pair of calc_cond_batch (LD.py:2515-2547) — every step ONE call of the operator seam (lightdiffusion_amd/ops.py), on weights taken from
 the synthetic checkpoint and brought into the resident layouts by the seam's own repack / fold operators.  Nothing here reads the executor:
 the chain is what tests/test_unet_chain_gpu.py diffs the executor against, launch by launch and bit by bit, and every call leaves a tap
-(stage kind, layer name, inputs, parameters, output, launches) from which the test recomputes that one stage in fp64.
+(stage kind, layer name, inputs, parameters, output, launches; `n`, the images it ran on, where the stage is separable per image — what
+chain_harness.tap_images cuts by) from which the test recomputes that one stage in fp64.
 
 `modules(cfg)` is the host-only walk of the constructor: the list of (kind, name, ...) the forward runs over.
 """
@@ -124,18 +125,18 @@ class UNetChain(ChainBase):
             wsk, bsk = self.mat(name + ".skip_connection.weight"), self.vec(name + ".skip_connection.bias")
             if not fold:
                 res = ops.conv2d(x1, wsk, bsk, ksize=1, x2=x2)
-                self.tap("conv", name + ".skip_connection", dict(x=x1, x2=x2), dict(w=self.oihw(name + ".skip_connection.weight"), b=bsk), res)
+                self.tap("conv", name + ".skip_connection", dict(x=x1, x2=x2), dict(w=self.oihw(name + ".skip_connection.weight"), b=bsk), res, n=n)
         h1, p1 = ops.group_norm_silu_conv2d(x1, g1, b1, 1e-5, w1, bias1, x2=x2, rowvec=rv, partials=True, in_part=in_part)
         self.tap("gn_conv", name + ".in_layers", dict(x=x1, x2=x2, rowvec=rv, in_part=in_part),
-                 dict(gamma=g1, beta=b1, eps=1e-5, w=self.oihw(name + ".in_layers.2.weight"), b=bias1), h1, part=p1)
+                 dict(gamma=g1, beta=b1, eps=1e-5, w=self.oihw(name + ".in_layers.2.weight"), b=bias1), h1, part=p1, n=n)
         if fold:
             out, po = ops.group_norm_silu_conv2d_skip(h1, g2, b2, 1e-5, w2, bias2, x1, x2, wsk, bsk, partials=True, in_part=p1)
             self.tap("gn_conv", name + ".out_layers+skip", dict(x=h1, x2=None, rowvec=None, in_part=p1, s1=x1, s2=x2),
-                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2, wskip=wsk, bskip=bsk), out, part=po)
+                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2, wskip=wsk, bskip=bsk), out, part=po, n=n)
         else:
             out, po = ops.group_norm_silu_conv2d(h1, g2, b2, 1e-5, w2, bias2, residual=res, partials=True, in_part=p1)
             self.tap("gn_conv", name + ".out_layers", dict(x=h1, x2=None, rowvec=None, in_part=p1, residual=res),
-                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2), out, part=po)
+                     dict(gamma=g2, beta=b2, eps=1e-5, w=self.oihw(name + ".out_layers.3.weight"), b=bias2), out, part=po, n=n)
         return out, po
 
     # -- SpatialTransformer.forward (LD.py:4239-4262) around BasicTransformerBlock._forward (LD.py:4117-4162)
@@ -152,7 +153,7 @@ class UNetChain(ChainBase):
             g = ops.group_norm_from_partials(x, f.part, gng, gnb, 1e-6)
         else:
             g = ops.group_norm(x, gng, gnb, 1e-6)
-        self.tap("groupnorm", name + ".norm", dict(x=x, in_part=f.part), dict(gamma=gng, beta=gnb, eps=1e-6, silu=False), g)
+        self.tap("groupnorm", name + ".norm", dict(x=x, in_part=f.part), dict(gamma=gng, beta=gnb, eps=1e-6, silu=False), g, n=n)
         # proj_in, then [q | k | v] of attn1 on LayerNorm1 of it
         wqkv = self._cached(("qkv", b), lambda: torch.cat([self.mat(b + ".attn1.to_q.weight"), self.mat(b + ".attn1.to_k.weight"),
                                                            self.mat(b + ".attn1.to_v.weight")]).contiguous())
@@ -161,15 +162,15 @@ class UNetChain(ChainBase):
         g2d = g.reshape(n * L, C)
         t, qkv = ops.linear_ln(g2d, pin_w, pin_b, *ln(1), wqkv, None)
         self.tap("linear_ln", name + ".proj_in>attn1.qkv", dict(x=g2d, residual=None), dict(w_prod=pin_w, b_prod=pin_b, gamma=ln(1)[0], beta=ln(1)[1], w=wqkv, b=None,
-                                                                                         geglu=False), (t, qkv))
+                                                                                         geglu=False), (t, qkv), n=n)
         ao = ops.attention_qkv(qkv.view(n, L, 3 * C), heads)
-        self.tap("attention", b + ".attn1", dict(q=qkv.view(n, L, 3 * C)[..., :C], k=qkv.view(n, L, 3 * C)[..., C:2 * C], v=qkv.view(n, L, 3 * C)[..., 2 * C:]), {}, ao)
+        self.tap("attention", b + ".attn1", dict(q=qkv.view(n, L, 3 * C)[..., :C], k=qkv.view(n, L, 3 * C)[..., C:2 * C], v=qkv.view(n, L, 3 * C)[..., 2 * C:]), {}, ao, n=n)
         o1w, o1b, q2w = self.mat(b + ".attn1.to_out.0.weight"), self.vec(b + ".attn1.to_out.0.bias"), self.mat(b + ".attn2.to_q.weight")
         ao2d = ao.reshape(n * L, C)
         t_in = t
         t, q2 = ops.linear_ln(ao2d, o1w, o1b, *ln(2), q2w, None, residual=t_in)
         self.tap("linear_ln", b + ".attn1.to_out>attn2.to_q", dict(x=ao2d, residual=t_in), dict(w_prod=o1w, b_prod=o1b, gamma=ln(2)[0], beta=ln(2)[1], w=q2w, b=None,
-                                                                                                geglu=False), (t, q2))
+                                                                                                geglu=False), (t, q2), n=n)
         if pending:
             full = lambda *shape: torch.empty((n_all,) + shape, dtype=torch.float16, device=self.dev)
             tf, qf, xf = full(L, C), full(L, C), full(H, Wd, C)
@@ -181,20 +182,20 @@ class UNetChain(ChainBase):
             t, q2, x, n = tf.view(n_all * L, C), qf.view(n_all * L, C), xf, n_all
         k, vt, _ = self.ctx[name]
         ao = ops.attention_vt(q2.view(n, L, C), k, vt, heads)
-        self.tap("attention", b + ".attn2", dict(q=q2.view(n, L, C), k=k, v=vt[:, :, :k.shape[1]].transpose(1, 2)), {}, ao)
+        self.tap("attention", b + ".attn2", dict(q=q2.view(n, L, C), k=k, v=vt[:, :, :k.shape[1]].transpose(1, 2)), {}, ao, n=n)
         o2w, o2b = self.mat(b + ".attn2.to_out.0.weight"), self.vec(b + ".attn2.to_out.0.bias")
         f1w, f1b = self.mat(b + ".ff.net.0.proj.weight"), self.vec(b + ".ff.net.0.proj.bias")
         ao2d = ao.reshape(n * L, C)
         t_in = t
         t, ff = ops.linear_ln_geglu(ao2d, o2w, o2b, *ln(3), f1w, f1b, residual=t_in)
         self.tap("linear_ln", b + ".attn2.to_out>ff.net.0", dict(x=ao2d, residual=t_in), dict(w_prod=o2w, b_prod=o2b, gamma=ln(3)[0], beta=ln(3)[1], w=f1w, b=f1b,
-                                                                                              geglu=True), (t, ff))
+                                                                                              geglu=True), (t, ff), n=n)
         # ff.net.2, the block's residual, proj_out and the transformer's residual: one contraction over [ff | t] on [Wpo W2 | Wpo]
         wmo, bmo = self._cached(("mo", name), lambda: ops.mlp_out_fold(self.mat(name + ".proj_out.weight"), self.mat(b + ".ff.net.2.weight"),
                                                                        self.vec(b + ".ff.net.2.bias"), self.vec(name + ".proj_out.bias")))
         ff4, t4 = ff.view(n, H, Wd, 4 * C), t.view(n, H, Wd, C)
         out, po = ops.conv2d_gn_partials(ff4, wmo, bmo, residual=x, ksize=1, x2=t4)
-        self.tap("conv", name + ".ff.net.2>proj_out", dict(x=ff4, x2=t4, residual=x), dict(w=wmo.view(C, 5 * C, 1, 1), b=bmo), out, part=po)
+        self.tap("conv", name + ".ff.net.2>proj_out", dict(x=ff4, x2=t4, residual=x), dict(w=wmo.view(C, 5 * C, 1, 1), b=bmo), out, part=po, n=n)
         return out, po, n
 
     # -- apply_model: calculate_input, UNetModel1.forward, calculate_denoised
@@ -244,14 +245,14 @@ class UNetChain(ChainBase):
                     assert not pending, "a CFG pair is split at the first cross-attention, in front of every resampling of the supported layouts"
                     wd, bd = self.conv3(name + ".weight"), self.vec(name + ".bias")
                     out, po = ops.conv2d_gn_partials(f.t, wd, bd, stride=2)
-                    self.tap("conv", name, dict(x=f.t, stride=2), dict(w=self.oihw(name + ".weight"), b=bd), out, part=po)
+                    self.tap("conv", name, dict(x=f.t, stride=2), dict(w=self.oihw(name + ".weight"), b=bd), out, part=po, n=f.t.shape[0])
                     f = Feat(out, po)
                 elif kind == "up":
                     hv, wv = (hs[-1].shape[1], hs[-1].shape[2]) if hs else (2 * f.t.shape[1], 2 * f.t.shape[2])
                     wu, bu = self.conv3(name + ".weight"), self.vec(name + ".bias")
                     wf = self._cached(("up", name), lambda: ops.upconv2x_fold(wu))
                     out = ops.upconv2x(f.t, wu, wf, bu, out_hw=(hv, wv))
-                    self.tap("upconv", name, dict(x=f.t, out_hw=(hv, wv)), dict(w=self.oihw(name + ".weight"), b=bu), out)
+                    self.tap("upconv", name, dict(x=f.t, out_hw=(hv, wv)), dict(w=self.oihw(name + ".weight"), b=bu), out, n=f.t.shape[0])
                     f = Feat(out)
             if where == "input":
                 assert not (pending and bi >= 1), "first input block without a transformer: not a layout of this chain"
@@ -262,7 +263,7 @@ class UNetChain(ChainBase):
             g = ops.group_norm_from_partials(f.t, f.part, og, ob, 1e-5, silu=True)
         else:
             g = ops.group_norm(f.t, og, ob, 1e-5, silu=True)
-        self.tap("groupnorm", "out.0", dict(x=f.t, in_part=f.part), dict(gamma=og, beta=ob, eps=1e-5, silu=True), g)
+        self.tap("groupnorm", "out.0", dict(x=f.t, in_part=f.part), dict(gamma=og, beta=ob, eps=1e-5, silu=True), g, n=f.t.shape[0])
         wo, bo = self.conv3("out.2.weight"), self.vec("out.2.bias")
         mode = 2 if eps_only else 0
         out = ops.small_conv_out(g, wo, bo, mode, x_in=x, sigma=sigma, in_mod=in_mod)
