@@ -122,6 +122,55 @@ size_t ld_unet_patch_bytes(const ld_unet* u);
 int ld_unet_last_launches(const ld_unet* u);
 double ld_unet_last_flops(const ld_unet* u);
 
+/* ------------------------------------------------------------------ ControlNet (upstream ComfyUI's cldm.ControlNet; the reference keeps the seams —
+ * apply_control1 at LD.py:5290, called at "middle" and "output" in UNetModel1.forward, LD.py:5742, 5747 — and fills none of them)
+ * The control branch is an ld_unet in control mode: time_embed, input_blocks and middle_block of the UNet (same names, same routes), no output
+ * blocks and no out.*, plus input_hint_block.{0,2,..,14} (the hint encoder: eight 3x3 convolutions hint_channels -> 16 -> 16 -> 32 -> 32 -> 96 -> 96 ->
+ * 256 -> model_channels, stride 2 at the third, fifth and seventh, SiLU behind all but the last), zero_convs.{i}.0 (1x1, one per input block) and
+ * middle_block_out.0.  Every ld_unet_* call that is not a forward or a profile works on it unchanged: param_count / param_info / load_param /
+ * read_param / reserve / set_context / weight_bytes / last_launches / last_flops / destroy.  LD_ERR_ARG: a UNet forward on a control handle, a
+ * control call on a UNet handle. */
+int ld_controlnet_create(const ld_unet_config* cfg, int hint_channels, ld_unet** out);
+/* Encode the control image once per run: image_nchw fp32 [hb][hint_channels][H][W] (device), H = 8 h and W = 8 w of the latents that follow; hb is 1 or
+ * divides the batch of the forwards (sample s reads hint s % hb).  The encoded hint [hb][h][w][model_channels] fp16 stays resident in the handle
+ * until the next reserve.  Uses the handle's activation workspace: stream-ordered with the forwards.  LD_ERR_SHAPE: hb, H / 8 or W / 8 beyond the
+ * reserved plan, H or W not a multiple of 8. */
+int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, int W, void* stream);
+/* The control branch on x [n][in_channels][h][w] / sigma [n] as ld_unet_forward reads them, against the handle's own resident context (n rows):
+ * h = conv_in(x / sqrt(sigma^2 + 1)) + hint, the input blocks, the middle block; residual i = zero_convs.i.0 of input block i's output, the last one
+ * middle_block_out.0 of the middle block's — raw fp16 NHWC, in buffers that persist in the handle (allocated by ld_unet_reserve for the reserved
+ * maximum), valid until the next forward.  Only enqueues on `stream`; capturable.  LD_ERR_STATE: no hint set; LD_ERR_SHAPE: (h, w) is not the hint's. */
+int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream);
+/* ... for a classifier-free-guidance pair: x / sigma hold nb samples, the context 2 nb rows; the residuals are those of ld_controlnet_forward on
+ * cat([x, x]) (conv_in runs once per latent, everything else on all 2 nb samples) */
+int ld_controlnet_forward_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream);
+/* residuals of the last forward: their number without the middle one (= input blocks), their batch, and residual i (i = count: the middle one) as a
+ * device pointer to [batch][H][W][C] fp16 */
+int ld_controlnet_residual_count(const ld_unet* cn);
+int ld_controlnet_residual_batch(const ld_unet* cn);
+int ld_controlnet_residual(const ld_unet* cn, int i, const void** ptr, int* C, int* H, int* W);
+/* a copy of residual i into dst_f16 (device), ordered on `stream` */
+int ld_controlnet_read_residual(const ld_unet* cn, int i, void* dst_f16, void* stream);
+/* What a UNet forward adds where upstream calls apply_control: residual[i] ([r_n][h[i]][w[i]][c[i]] fp16 NHWC, device) to skip tensor i — the output
+ * of input block i; upstream pops control["output"] from the back in step with hs.pop() — and `middle` (shape entry `count`) to the middle block's
+ * output, each as t = fp16(float(t) + strength * float(r)); sample s of the forward reads residual sample s % r_n. */
+typedef struct {
+    const void* residual[16];
+    int count;
+    const void* middle;
+    int r_n;
+    float strength;
+    int c[16], h[16], w[16];   /* of residual i; entry `count`: of the middle one */
+} ld_control;
+/* the descriptor of a control handle's last forward (r_n <= 0: its batch) */
+int ld_controlnet_fill_control(const ld_unet* cn, int r_n, float strength, ld_control* out);
+/* ld_unet_forward / ld_unet_forward_pair with the residuals of `ctl` added in ONE launch behind the middle block, when every skip tensor is complete
+ * and the encoder reads none of them again.  ctl == NULL: the plain forward, launch for launch; strength == 0 launches nothing more either.
+ * LD_ERR_SHAPE, before anything is launched: count is not the number of skip tensors, a shape is not its skip tensor's (the middle block's output),
+ * r_n does not divide the batch.  LD_ERR_ARG: a NULL residual. */
+int ld_unet_forward_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, const ld_control* ctl, void* stream);
+int ld_unet_forward_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream);
+
 /* ------------------------------------------------------------------ VAE decoder (Decoder ctor arguments, LD.py:6312-6323) */
 typedef struct {
     int z_channels, ch, num_levels;
@@ -527,6 +576,20 @@ int ld_op_regional_gather(const float* x, float* out, int B, int C, int H, int W
  * mult = mult * (0.125f * (t + 1)); num += out * mult; den += mult.  A pixel no entry of a list covers gives 0 for that list.  result may not
  * overlap an input. */
 int ld_op_regional_combine(const ld_regional_entry* entries, int n, float cond_scale, float* result, int B, int C, int H, int W, void* stream);
+
+/* ---- ControlNet's two kernels (csrc/control/control.hip), for parity tests.
+ * control add: for each of `count` (1 .. 16) segments, t[i] [n][per[i]] fp16 in place: t = fp16(float(t) + strength * float(r)), r[i] [r_n][per[i]] fp16,
+ * sample s reads residual sample s % r_n (r_n divides n).  One fp32 product, one fp32 sum, each rounded on its own (no FMA), one rounding to fp16:
+ * the bits of (t.float() + strength * r.float()).half().  t, r, per: HOST arrays of device pointers / halves per sample, read before the call
+ * returns.  16-byte accesses where every per[i] is a multiple of 8 and every pointer 16-byte aligned, single halves otherwise: the same bits.
+ * LD_ERR_SHAPE: count, n, r_n out of range, n * per[i] >= 2^31.  LD_ERR_ARG: a NULL pointer. */
+int ld_op_control_add(void* const* t, const void* const* r, const long long* per, int count, int n, int r_n, float strength, void* stream);
+/* one layer of the hint encoder: y [n][ho][wo][cout] fp16 = silu?(conv3x3, pad 1, stride 1 | 2, + bias), ho = (h - 1) / stride + 1; the input is
+ * x_f16_nhwc [n][h][w][cin] (cin a multiple of 8) or x_f32_nchw [n][cin][h][w] (cin <= 4; every sample rounded to fp16 once) — exactly one of them;
+ * wt [cout][ky][kx][cin] fp16 (what ld_op_repack_conv writes), cout a multiple of 8.  fp32 accumulation in the order (ky, kx, ci), + bias, SiLU in
+ * fp32, one rounding at the store. */
+int ld_op_hint_conv(const void* x_f16_nhwc, const float* x_f32_nchw, int n, int h, int w, int cin, const void* wt, const void* bias, int cout, int stride,
+                    int silu, void* y, void* stream);
 
 /* ---- CLIP text model input stage with textual-inversion vectors (CLIPEmbeddings + SDClipModel.set_up_textual_embeddings, LD.py:4394-4410, 4642-4690).
  * out[b][l] = round_fp16(float(row(ids[b*L + l])) + float(pos[l])), fp16 [B, L, h].  `table` is the resident fp16 token table [V, h] (EOS = row V-1),

@@ -47,6 +47,15 @@ class RegionalEntry(C.Structure):
                 ("h", C.c_int), ("w", C.c_int), ("strength", C.c_float), ("mask_strength", C.c_float)]
 
 
+CONTROL_MAX_SEGMENTS = 16      # residual slots of ld_control, segments of one ld_op_control_add
+
+
+class Control(C.Structure):
+    """ld_control"""
+    _fields_ = [("residual", C.c_void_p * 16), ("count", C.c_int), ("middle", C.c_void_p), ("r_n", C.c_int), ("strength", C.c_float),
+                ("c", C.c_int * 16), ("h", C.c_int * 16), ("w", C.c_int * 16)]
+
+
 class LDError(RuntimeError):
     def __init__(self, status: int, where: str):
         self.status = status
@@ -90,6 +99,17 @@ SIGNATURES = {
     "ld_unet_read_param": (_I, [_P, C.c_char_p, _P, _P]),
     "ld_unet_refresh_derived": (_I, [_P, _P]),
     "ld_unet_patch_bytes": (_Z, [_P]),
+    "ld_controlnet_create": (_I, [C.POINTER(UNetConfig), _I, C.POINTER(_P)]),
+    "ld_controlnet_set_hint": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_forward_pair": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_residual_count": (_I, [_P]),
+    "ld_controlnet_residual_batch": (_I, [_P]),
+    "ld_controlnet_residual": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "ld_controlnet_read_residual": (_I, [_P, _I, _P, _P]),
+    "ld_controlnet_fill_control": (_I, [_P, _I, _F, C.POINTER(Control)]),
+    "ld_unet_forward_control": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Control), _P]),
+    "ld_unet_forward_pair_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P]),
     "ld_vae_create": (_I, [C.POINTER(VAEConfig), C.POINTER(_P)]),
     "ld_vae_decode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
@@ -174,6 +194,8 @@ SIGNATURES = {
     "ld_op_inpaint_out": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ld_op_regional_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "ld_op_regional_combine": (_I, [_P, _I, _F, _P, _I, _I, _I, _I, _P]),
+    "ld_op_control_add": (_I, [C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_longlong), _I, _I, _I, _F, _P]),
+    "ld_op_hint_conv": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
     "ld_op_clip_embed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
 }
 

@@ -28,7 +28,8 @@ def _count(keys, pattern: str) -> int:
     return max(idx) + 1 if idx else 0
 
 
-def detect_unet_config(sd: Dict[str, torch.Tensor], prefix: str = UNET_PREFIX, num_heads: int = 8) -> dict:
+def detect_unet_config(sd: Dict[str, torch.Tensor], prefix: str = UNET_PREFIX, num_heads: int = 8, encoder_only: bool = False) -> dict:
+    """`encoder_only`: the keys are a ControlNet's (detect_controlnet_config) — no output blocks and no out.*; out_channels = in_channels."""
     keys = [k[len(prefix):] for k in sd if k.startswith(prefix)]
     ks = set(keys)
     if "input_blocks.0.0.weight" not in ks:
@@ -57,9 +58,35 @@ def detect_unet_config(sd: Dict[str, torch.Tensor], prefix: str = UNET_PREFIX, n
     td_out = [depth_of(f"output_blocks.{j}.1") for j in reversed(range(n_out))]
     if max(td_in + td_out + [0]) > 1:
         raise ValueError("transformer depth > 1 is not an SD1.x UNet")
-    return dict(in_channels=int(cin), out_channels=int(get("out.2.weight").shape[0]), model_channels=int(mc), channel_mult=channel_mult,
+    return dict(in_channels=int(cin), out_channels=int(cin if encoder_only else get("out.2.weight").shape[0]), model_channels=int(mc), channel_mult=channel_mult,
                 num_res_blocks=num_res, transformer_depth=td_in, transformer_depth_output=td_out,
                 transformer_depth_middle=depth_of("middle_block.1"), context_dim=int(context_dim), num_heads=num_heads)
+
+
+CONTROL_PREFIX = "control_model."
+
+
+def controlnet_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """A ControlNet file's tensors under bare cldm names (time_embed.*, input_blocks.*, middle_block.*, input_hint_block.*, zero_convs.*,
+    middle_block_out.*), with or without the `control_model.` prefix.  ValueError for what is not that layout: a diffusers-layout ControlNet
+    (controlnet_cond_embedding.*), a T2I-Adapter (adapter.* / body.*), a ControlLoRA (lora_controlnet)."""
+    keys = list(sd)
+    if any(k.startswith("controlnet_cond_embedding.") or ".controlnet_cond_embedding." in k for k in keys):
+        raise ValueError("a diffusers-layout ControlNet is not supported: convert it to the cldm layout (control_model.* keys)")
+    if "lora_controlnet" in sd:
+        raise ValueError("a ControlLoRA is not supported")
+    if any(k.startswith(("adapter.", "body.")) for k in keys):
+        raise ValueError("a T2I-Adapter is not supported")
+    out = {(k[len(CONTROL_PREFIX):] if k.startswith(CONTROL_PREFIX) else k): v for k, v in sd.items()}
+    if "input_hint_block.0.weight" not in out or "zero_convs.0.0.weight" not in out:
+        raise ValueError("not a cldm-layout ControlNet: no input_hint_block / zero_convs keys")
+    return out
+
+
+def detect_controlnet_config(sd: Dict[str, torch.Tensor], num_heads: int = 8) -> Tuple[dict, int]:
+    """(the UNet config the ControlNet was built on, hint_channels), read from the shapes of bare-named tensors (controlnet_state_dict)."""
+    cfg = detect_unet_config(sd, prefix="", num_heads=num_heads, encoder_only=True)
+    return cfg, int(sd["input_hint_block.0.weight"].shape[1])
 
 
 def detect_vae_config(sd: Dict[str, torch.Tensor], prefix: str = VAE_PREFIX) -> Tuple[dict, bool]:

@@ -802,6 +802,22 @@ int ld_op_regional_combine(const ld_regional_entry* entries, int n, float cond_s
     return regional_combine_launch(reinterpret_cast<const RegionalEntry*>(entries), n, cond_scale, result, B, C, H, W, (hipStream_t)stream);
 }
 
+int ld_op_control_add(void* const* t, const void* const* r, const long long* per, int count, int n, int r_n, float strength, void* stream) {
+    op_begin();
+    if (t == nullptr || r == nullptr || per == nullptr) return LD_ERR_ARG;
+    if (count < 1 || count > CONTROL_MAX_SEGMENTS) return LD_ERR_SHAPE;
+    ControlSegment segs[CONTROL_MAX_SEGMENTS];
+    for (int i = 0; i < count; ++i) segs[i] = {(half_t*)t[i], (const half_t*)r[i], per[i]};
+    return launched(control_add_launch(segs, count, n, r_n, strength, (hipStream_t)stream), "control_add_kernel");
+}
+
+int ld_op_hint_conv(const void* x_f16_nhwc, const float* x_f32_nchw, int n, int h, int w, int cin, const void* wt, const void* bias, int cout, int stride, int silu,
+                    void* y, void* stream) {
+    op_begin();
+    return launched(hint_conv_launch((const half_t*)x_f16_nhwc, x_f32_nchw, n, h, w, cin, (const half_t*)wt, (const half_t*)bias, cout, stride, silu, (half_t*)y,
+                                     (hipStream_t)stream), "hint_conv_kernel");
+}
+
 int ld_op_clip_embed(const int* ids, const void* table, const float* extra, const void* pos, void* out, int B, int L, int V, int E, int h, void* stream) {
     op_begin();
     return launched(clip_embed_launch(ids, (const half_t*)table, extra, (const half_t*)pos, (half_t*)out, B, L, V, E, h, (hipStream_t)stream),

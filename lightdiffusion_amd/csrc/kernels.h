@@ -246,6 +246,21 @@ int regional_gather_launch(const float* x, float* out, int B, int C, int H, int 
 // result = u + (c - u) * cond_scale with, per list, pred = sum(out * mult) / (1e-37f + sum(mult)) over the entries that cover the pixel, in table order
 int regional_combine_launch(const RegionalEntry* entries, int n, float cond_scale, float* result, int B, int C, int H, int W, hipStream_t stream);
 
+// ---- control/control.hip: what ControlNet adds around the UNet executor's routes (see the file's header)
+constexpr int CONTROL_MAX_SEGMENTS = 16;                 // segments of one control add: LD_ERR_SHAPE above it
+constexpr long long CONTROL_MAX_HALFS = 1LL << 31;       // every tensor stays below it (32-bit indices): LD_ERR_SHAPE otherwise
+struct ControlSegment {
+    half_t* t;            // [n][per] fp16, updated in place
+    const half_t* r;      // [r_n][per] fp16
+    long long per;        // halves per sample
+};
+// t[s][e] = fp16(float(t[s][e]) + strength * float(r[s % r_n][e])) for every segment, one launch; r_n divides n.  The host array is read before the call returns.
+int control_add_launch(const ControlSegment* segs, int count, int n, int r_n, float strength, hipStream_t stream);
+// y [n][ho][wo][cout] = silu?(conv3x3 pad 1 at `stride` (1 | 2) of the input + bias), ho = (h - 1) / stride + 1; the input is x [n][h][w][cin] fp16 (cin a
+// multiple of 8) or x_nchw_f32 [n][cin][h][w] fp32 (cin <= 4, rounded to fp16 once) — exactly one of the two; wt [cout][ky][kx][cin], cout a multiple of 8
+int hint_conv_launch(const half_t* x, const float* x_nchw_f32, int n, int h, int w, int cin, const half_t* wt, const half_t* bias, int cout, int stride, int silu,
+                     half_t* y, hipStream_t stream);
+
 // LoRA merge into a resident weight slot (lora.hip; load-class, never on the per-step path):
 //   dst = round_fp16( float(base) + sum_j scale_j * up_j[rows][rank_j] * down_j[rank_j][cols] ), fp32 products and sum, ONE rounding for all terms.
 // (rows, cols) are the LOGICAL checkpoint matrix (a conv: cols = Cin * 9 in (i, ky, kx) order); base and dst are in the slot's RESIDENT layout

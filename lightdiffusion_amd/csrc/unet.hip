@@ -84,6 +84,20 @@ struct ld_unet : Model {
     // further resident copy, held only while the slot is patched.  Every merge reads the snapshot, ld_unet_unpatch copies it back.
     std::unordered_map<int, half_t*> backups;
     size_t patch_bytes = 0;
+    // "control" mode (ld_controlnet_create; upstream's cldm.ControlNet): time_embed, input_blocks and middle_block as above, no output blocks and
+    // no out.*; instead the hint encoder (input_hint_block), one 1x1 zero convolution per input block and middle_block_out.  A forward writes
+    // the zero convolutions' raw outputs — the residuals — into buffers that persist in the handle (carved from the workspace by ld_unet_reserve).
+    bool control = false;
+    int hint_channels = 0;
+    struct HintW { int w, b, cin, cout, stride; };
+    std::vector<HintW> hint_convs;
+    std::vector<int> zc_w, zc_b;                    // zero_convs.{i}.0 of input block i; the last pair is middle_block_out.0
+    half_t* hint = nullptr;                         // the encoded hint [hint_b][hint_h][hint_w][model_channels]
+    int hint_b = 0, hint_h = 0, hint_w = 0;         // 0: none set since the last reserve
+    std::vector<half_t*> res_buf;                   // one per zero convolution, each for the reserved maximum
+    struct ResShape { int C = 0, H = 0, W = 0; };
+    std::vector<ResShape> res_shape;                // of the last forward; its batch: res_n
+    int res_n = 0;
     void drop_backup(int slot) {
         auto it = backups.find(slot);
         if (it == backups.end()) return;
@@ -232,6 +246,31 @@ int build(ld_unet* u) {
     u->mid_block.push_back({L_RES, add_res(u, "middle_block.0", ch, ch)});
     if (c.transformer_depth_middle > 0) u->mid_block.push_back({L_ST, add_st(u, "middle_block.1", ch)});
     u->mid_block.push_back({L_RES, add_res(u, "middle_block.2", ch, ch)});
+    if (u->control) {   // upstream's cldm.ControlNet: the encoder half above, then
+        if (u->hint_channels < 1 || u->hint_channels > 4 || u->in_blocks.size() + 1 > (size_t)CONTROL_MAX_SEGMENTS) return LD_ERR_ARG;
+        const int hc[9] = {u->hint_channels, 16, 16, 32, 32, 96, 96, 256, mc};
+        for (int i = 0; i < 8; ++i) {   // input_hint_block: conv, SiLU, conv, SiLU, ... conv — the convolutions at the even indices
+            ld_unet::HintW hw;
+            hw.cin = hc[i];
+            hw.cout = hc[i + 1];
+            hw.stride = (i == 2 || i == 4 || i == 6) ? 2 : 1;
+            hw.w = t.add(S("input_hint_block.%d.weight", 2 * i), PK_CONV3, {hw.cout, hw.cin, 3, 3});
+            hw.b = t.add(S("input_hint_block.%d.bias", 2 * i), PK_VEC, {hw.cout});
+            u->hint_convs.push_back(hw);
+        }
+        for (size_t i = 0; i < chans.size(); ++i) {
+            u->zc_w.push_back(t.add(S("zero_convs.%d.0.weight", (int)i), PK_MAT, {chans[i], chans[i], 1, 1}));
+            u->zc_b.push_back(t.add(S("zero_convs.%d.0.bias", (int)i), PK_VEC, {chans[i]}));
+        }
+        u->zc_w.push_back(t.add("middle_block_out.0.weight", PK_MAT, {ch, ch, 1, 1}));
+        u->zc_b.push_back(t.add("middle_block_out.0.bias", PK_VEC, {ch}));
+        for (size_t i = 0; i < u->res.size(); ++i)
+            u->res[i].emb_w = t.add(u->res[i].prefix + ".emb_layers.1.weight", PK_MAT, {u->res[i].cout, u->ted}, i == 0 ? 256 : 16);
+        for (size_t i = 0; i < u->res.size(); ++i)
+            u->res[i].emb_b = t.add(u->res[i].prefix + ".emb_layers.1.bias", PK_VEC, {u->res[i].cout}, i == 0 ? 256 : 16);
+        u->outn_g = u->outn_b = u->outc_w = u->outc_b = -1;
+        return t.finalize();
+    }
     // the reference pops transformer_depth_output from the END of the list (LD.py:5621)
     int n_out = 0;
     for (int lvl = 0; lvl < c.num_levels; ++lvl) n_out += c.num_res_blocks[lvl] + 1;
@@ -513,8 +552,40 @@ int refresh_derived(ld_unet* u, hipStream_t stream) {
 // `pair`: classifier-free-guidance pair (ld_unet_forward_pair).  x / sigma hold n / 2 samples; the batch is [uncond x n/2 ; cond x n/2] of the SAME latents
 // (what calc_cond_batch feeds the model: cat([x, x]), LD.py:2515-2547); the resident context has n rows.  The layers in front of the first
 // cross-attention run once on n / 2 samples (Run::pair_pending), everything else on n.  out: n samples.
+// (C, H, W) of the skip tensors of an h x w latent, one per input block, as the walk below produces them
+std::vector<ld_unet::ResShape> skip_shapes(const ld_unet* u, int h, int w) {
+    std::vector<ld_unet::ResShape> s;
+    int C = u->cfg.model_channels, H = h, W = w;
+    for (const auto& block : u->in_blocks) {
+        for (const Layer& L : block) {
+            if (L.kind == L_RES) C = u->res[L.idx].cout;
+            else if (L.kind == L_DOWN) {
+                C = u->convs[L.idx].cout;
+                H = (H - 1) / 2 + 1;
+                W = (W - 1) / 2 + 1;
+            }
+        }
+        s.push_back({C, H, W});
+    }
+    return s;
+}
+
+// does `ctl` fit the skip tensors and the middle tensor of an n x h x w forward of this UNet?
+int check_control(const ld_unet* u, const ld_control* ctl, int n, int h, int w) {
+    if (ctl == nullptr) return LD_OK;
+    const std::vector<ld_unet::ResShape> s = skip_shapes(u, h, w);
+    if (ctl->count != (int)s.size() || ctl->count + 1 > CONTROL_MAX_SEGMENTS || ctl->r_n < 1 || n % ctl->r_n != 0) return LD_ERR_SHAPE;
+    for (int i = 0; i <= ctl->count; ++i) {
+        const ld_unet::ResShape& want = s[i < ctl->count ? i : ctl->count - 1];   // (the middle block keeps the last skip's shape)
+        if (ctl->c[i] != want.C || ctl->h[i] != want.H || ctl->w[i] != want.W) return LD_ERR_SHAPE;
+        if ((i < ctl->count ? ctl->residual[i] : ctl->middle) == nullptr) return LD_ERR_ARG;
+    }
+    return LD_OK;
+}
+
+// `ctl` (a UNet, may be null): ControlNet residuals added to every skip tensor and to the middle block's output, once the encoder is done with them.
 int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, hipStream_t stream,
-                size_t* dry_peak = nullptr, bool pair = false) {
+                size_t* dry_peak = nullptr, bool pair = false, const ld_control* ctl = nullptr) {
     if (!dry) {
         const int st = refresh_derived(u, stream);
         if (st != LD_OK) return st;
@@ -530,7 +601,19 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     const ld_unet_config& c = u->cfg;
     const int mc = c.model_channels, ted = u->ted;
     const int in_mod = pair ? n / 2 : 0;   // CFG pair: x / sigma hold n / 2 samples; the kernels that read them per sample index n % in_mod
-    if (pair) R.pair_pending = true;
+    // (the control branch shares no prefix: its pair form reads x / sigma per sample % (n / 2), duplicates conv_in's output and runs all n samples)
+    if (pair && !u->control) R.pair_pending = true;
+    // one launch of the control add over `count` segments of n samples each
+    auto control_add = [&](const ControlSegment* segs, int count, int r_n, float strength) {
+        long long bytes = 0;
+        for (int i = 0; i < count; ++i) bytes += (long long)n * segs[i].per * (long long)sizeof(half_t);
+        ex.launch(KC_MISC, 0.0, "ctl_add", bytes, count, r_n, 1, "control_add_kernel", [&] { return control_add_launch(segs, count, n, r_n, strength, stream); });
+    };
+    // control mode: residual i = zero convolution i (1x1) of the block's output, into the handle's persistent buffer
+    auto zero_conv = [&](size_t i, const Feat& f) {
+        R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 1, u->zc_w[i], u->zc_b[i], f.C, dry ? nullptr : u->res_buf[i], 1);
+        if (!dry) u->res_shape[i] = {f.C, f.H, f.W};
+    };
 
     // timestep embedding -> time_embed MLP -> all ResBlock emb_layers at once (every consumer applies SiLU first)
     half_t* temb = ar.halfs((size_t)n * mc);
@@ -593,12 +676,22 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         a.x = x; a.scale_sigma = sigma; a.w = u->pt.ptr(cw.w); a.b = u->pt.ptr(cw.b); a.y = o;
         a.N = R.n; a.Cin = c.in_channels; a.H = h; a.W = w; a.Cout = mc;
         if (R.pair_pending) a.dup_off = (long long)R.n * h * w * mc;   // a skip connection: read by the last output block on all n samples
-        ex.launch(KC_MISC, 2.0 * R.n * h * w * mc * 9.0 * c.in_channels, "", 0, 0, 0, 0, "small_conv_in_kernel", [&] { return small_conv_in_launch(a, stream); });
+        if (u->control && pair) {                                 // the control branch's pair form: conv_in once per latent, stored for both halves
+            a.N = n / 2;
+            a.dup_off = (long long)a.N * h * w * mc;
+        }
+        ex.launch(KC_MISC, 2.0 * a.N * h * w * mc * 9.0 * c.in_channels, "", 0, 0, 0, 0, "small_conv_in_kernel", [&] { return small_conv_in_launch(a, stream); });
         f = {o, mc, h, w};
         hs.push_back(f);
+        if (u->control) {                                         // h = conv_in(x) + hint (cldm.ControlNet.forward: guided_hint joins the first block's output)
+            const ControlSegment seg{o, u->hint, (long long)h * w * mc};
+            control_add(&seg, 1, dry ? 1 : u->hint_b, 1.0f);
+            zero_conv(0, f);
+        }
     }
     for (size_t b = 1; b < u->in_blocks.size(); ++b) {
         f = run_layers(u->in_blocks[b], f, nullptr, 0, 0, 0);
+        if (u->control) zero_conv(b, f);
         if (R.pair_pending && b == 1) {                          // no transformer in the first block: its output is the last shared tensor
             R.dup(const_cast<half_t*>(f.p), (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
             R.pair_pending = false;
@@ -612,6 +705,23 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         R.n = n;
     }
     f = run_layers(u->mid_block, f, nullptr, 0, 0, 0);
+    if (u->control) {                                            // middle_block_out; a control branch ends here
+        zero_conv(u->in_blocks.size(), f);
+        if (!dry) u->res_n = n;
+        return u->end(ex, dry_peak, true);
+    }
+    if (ctl != nullptr && ctl->strength != 0.0f) {
+        // apply_control1 at "output" and "middle" (LD.py:5290, 5742, 5747), all of it in one launch: every skip tensor is complete (on the pair
+        // route the second halves of the first two were filled by the hand-over above) and the encoder reads none of them again.  Residual i
+        // belongs to hs[i]: upstream pops control["output"] from the back in step with hs.pop().  A strength of 0 adds nothing and launches nothing.
+        ControlSegment segs[CONTROL_MAX_SEGMENTS];
+        int k = 0;
+        for (; k < (int)hs.size() && k < ctl->count && k < CONTROL_MAX_SEGMENTS - 1; ++k)
+            segs[k] = {hs[k].p, static_cast<const half_t*>(ctl->residual[k]), (long long)hs[k].H * hs[k].W * hs[k].C};
+        segs[k++] = {f.p, static_cast<const half_t*>(ctl->middle), (long long)f.H * f.W * f.C};
+        control_add(segs, k, ctl->r_n, ctl->strength);
+        f.stats = {};                                            // (they describe the middle tensor as it was before the add)
+    }
     for (size_t b = 0; b < u->out_blocks.size(); ++b) {
         const Feat skip = hs.back();
         hs.pop_back();
@@ -658,10 +768,17 @@ bool capturing(hipStream_t stream) {
 
 extern "C" {
 
-int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) {
+static int create_handle(const ld_unet_config* cfg, bool control, int hint_channels, ld_unet** out);
+
+int ld_unet_create(const ld_unet_config* cfg, ld_unet** out) { return create_handle(cfg, false, 0, out); }
+int ld_controlnet_create(const ld_unet_config* cfg, int hint_channels, ld_unet** out) { return create_handle(cfg, true, hint_channels, out); }
+
+static int create_handle(const ld_unet_config* cfg, bool control, int hint_channels, ld_unet** out) {
     if (cfg == nullptr || out == nullptr) return LD_ERR_ARG;
     ld_unet* u = new ld_unet();
     u->cfg = *cfg;
+    u->control = control;
+    u->hint_channels = hint_channels;
     const int st = build(u);
     if (st != LD_OK) {
         ld_unet_destroy(u);
@@ -820,8 +937,24 @@ int ld_unet_reserve(ld_unet* u, int max_n, int max_h, int max_w, int max_tok) {
     const size_t tpad = (size_t)u->ctx_tpad;
     size_t ctxb = ((size_t)max_n * tpad * u->cfg.context_dim * sizeof(half_t) + 255) / 256 * 256;
     for (const StW& s : u->st) ctxb += 2 * (((size_t)max_n * tpad * s.c * sizeof(half_t) + 255) / 256 * 256);
+    // control mode: behind the context, the encoded hint and one residual buffer per zero convolution, each for the reserved maximum; the hint
+    // encoder's two ping-pong buffers (its widest layer: 16 channels at 8h x 8w) share the activations' arena — it never runs beside a forward
+    auto pad256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    std::vector<ld_unet::ResShape> rs;
+    size_t ctlb = 0;
+    if (u->control) {
+        rs = skip_shapes(u, max_h, max_w);
+        rs.push_back(rs.back());
+        ctlb = pad256((size_t)max_n * max_h * max_w * u->cfg.model_channels * sizeof(half_t));
+        for (const auto& r : rs) ctlb += pad256((size_t)max_n * r.H * r.W * r.C * sizeof(half_t));
+        const size_t hint_ws = 2 * pad256((size_t)max_n * 64 * max_h * max_w * 16 * sizeof(half_t));
+        if (hint_ws > peak) peak = hint_ws;
+    }
+    u->hint = nullptr;
+    u->hint_b = u->hint_h = u->hint_w = u->res_n = 0;
+    u->res_buf.clear();
     u->splitk_bytes = SPLITK_BYTES;
-    const size_t bytes = Model::padded(peak, SPLITK_BYTES + ctxb), act = bytes - SPLITK_BYTES - ctxb - 4096;
+    const size_t bytes = Model::padded(peak, SPLITK_BYTES + ctxb + ctlb), act = bytes - SPLITK_BYTES - ctxb - ctlb - 4096;
     st = u->set_workspace(bytes, act);
     if (st != LD_OK) return st;
     char* p = u->ws_base + act;   // behind the activations: the contractions' scratch, then the context and its projections
@@ -835,6 +968,15 @@ int ld_unet_reserve(ld_unet* u, int max_n, int max_h, int max_w, int max_tok) {
         p += b;
         u->ctx_vt[i] = reinterpret_cast<half_t*>(p);
         p += b;
+    }
+    if (u->control) {
+        u->hint = reinterpret_cast<half_t*>(p);
+        p += pad256((size_t)max_n * max_h * max_w * u->cfg.model_channels * sizeof(half_t));
+        for (const auto& r : rs) {
+            u->res_buf.push_back(reinterpret_cast<half_t*>(p));
+            p += pad256((size_t)max_n * r.H * r.W * r.C * sizeof(half_t));
+        }
+        u->res_shape.assign(rs.size(), ld_unet::ResShape());
     }
     if (getenv("LD_PROFILE_DUMP") != nullptr)   // (where the allocations landed: tools/alloc_probe.py)
         fprintf(stderr, "[ld_reserve] workspace %p (%zu MiB)  weights %p  folds %p  conv8 weights %p\n", (void*)u->ws_base, u->ws_bytes >> 20, (void*)u->pt.base,
@@ -871,12 +1013,115 @@ int ld_unet_set_context(ld_unet* u, const void* ctx, int dtype, int n, int token
     return LD_OK;
 }
 
-static int forward_checked(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream, bool pair) {
-    if (u == nullptr || x == nullptr || sigma == nullptr || out == nullptr) return LD_ERR_ARG;
+static int forward_checked(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream, bool pair,
+                           const ld_control* ctl = nullptr) {
+    if (u == nullptr || x == nullptr || sigma == nullptr || out == nullptr || u->control) return LD_ERR_ARG;
+    if (ctl != nullptr && h >= 1 && w >= 1 && n >= 1) {
+        const int st = check_control(u, ctl, n, h, w);
+        if (st != LD_OK) return st;
+    }
     return abi_checked_run(*u, u->ctx_n != 0, n == u->ctx_n && n <= u->max_n && h >= 1 && w >= 1,
                            [&](size_t* peak) { return run_forward(u, true, nullptr, nullptr, nullptr, n, h, w, eps_only, nullptr, peak, pair); },
-                           [&] { return run_forward(u, false, x, sigma, out, n, h, w, eps_only, (hipStream_t)stream, nullptr, pair); },
+                           [&] { return run_forward(u, false, x, sigma, out, n, h, w, eps_only, (hipStream_t)stream, nullptr, pair, ctl); },
                            &u->planned, PlanKey{{n, h, w, (int)pair}});
+}
+
+// ---------------------------------------------------------------------------------------------------- ControlNet
+int ld_unet_forward_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, const ld_control* ctl, void* stream) {
+    return forward_checked(u, x, sigma, out, n, h, w, eps_only, stream, false, ctl);
+}
+
+int ld_unet_forward_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream) {
+    if (nb < 1) return LD_ERR_SHAPE;
+    return forward_checked(u, x, sigma, out, 2 * nb, h, w, 0, stream, true, ctl);
+}
+
+int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, int W, void* stream_) {
+    if (cn == nullptr || image_nchw == nullptr || !cn->control) return LD_ERR_ARG;
+    if (cn->ws_base == nullptr || !cn->pt.all_loaded()) return LD_ERR_STATE;
+    if (hb < 1 || hb > cn->max_n || H < 8 || W < 8 || H % 8 != 0 || W % 8 != 0 || H / 8 > cn->max_h || W / 8 > cn->max_w) return LD_ERR_SHAPE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t half_ws = ((size_t)hb * H * W * 16 * sizeof(half_t) + 255) / 256 * 256;   // the widest layer's output
+    if (2 * half_ws > cn->arena.cap) return LD_ERR_SHAPE;
+    half_t* buf[2] = {reinterpret_cast<half_t*>(cn->ws_base), reinterpret_cast<half_t*>(cn->ws_base + half_ws)};
+    cn->hint_b = 0;
+    const half_t* src = nullptr;
+    int h = H, w = W;
+    for (size_t i = 0; i < cn->hint_convs.size(); ++i) {
+        const ld_unet::HintW& L = cn->hint_convs[i];
+        const bool last = i + 1 == cn->hint_convs.size();
+        half_t* dst = last ? cn->hint : buf[i & 1];
+        const int st = hint_conv_launch(src, i == 0 ? image_nchw : nullptr, hb, h, w, L.cin, cn->pt.ptr(L.w), cn->pt.ptr(L.b), L.cout, L.stride, !last, dst, stream);
+        if (st != LD_OK) return st;
+        h = (h - 1) / L.stride + 1;
+        w = (w - 1) / L.stride + 1;
+        src = dst;
+    }
+    cn->hint_b = hb;
+    cn->hint_h = h;
+    cn->hint_w = w;
+    return LD_OK;
+}
+
+static int control_forward_checked(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream, bool pair) {
+    if (cn == nullptr || x == nullptr || sigma == nullptr || !cn->control) return LD_ERR_ARG;
+    if (cn->hint_b == 0) return LD_ERR_STATE;
+    const bool shape_ok = n == cn->ctx_n && n <= cn->max_n && h >= 1 && w >= 1 && h <= cn->max_h && w <= cn->max_w && h == cn->hint_h && w == cn->hint_w &&
+                          n % cn->hint_b == 0;
+    return abi_checked_run(*cn, cn->ctx_n != 0, shape_ok,
+                           [&](size_t* peak) { return run_forward(cn, true, nullptr, nullptr, nullptr, n, h, w, 0, nullptr, peak, pair); },
+                           [&] { return run_forward(cn, false, x, sigma, nullptr, n, h, w, 0, (hipStream_t)stream, nullptr, pair); },
+                           &cn->planned, PlanKey{{n, h, w, (int)pair}});
+}
+
+int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream) {
+    return control_forward_checked(cn, x, sigma, n, h, w, stream, false);
+}
+
+int ld_controlnet_forward_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream) {
+    if (nb < 1) return LD_ERR_SHAPE;
+    return control_forward_checked(cn, x, sigma, 2 * nb, h, w, stream, true);
+}
+
+int ld_controlnet_residual_count(const ld_unet* cn) { return cn != nullptr && cn->control ? (int)cn->in_blocks.size() : 0; }
+
+int ld_controlnet_residual_batch(const ld_unet* cn) { return cn != nullptr && cn->control ? cn->res_n : 0; }
+
+int ld_controlnet_residual(const ld_unet* cn, int i, const void** ptr, int* C, int* H, int* W) {
+    if (cn == nullptr || !cn->control || i < 0 || i > (int)cn->in_blocks.size()) return LD_ERR_ARG;
+    if (cn->res_n == 0 || cn->res_buf.size() <= (size_t)i) return LD_ERR_STATE;
+    if (ptr) *ptr = cn->res_buf[i];
+    if (C) *C = cn->res_shape[i].C;
+    if (H) *H = cn->res_shape[i].H;
+    if (W) *W = cn->res_shape[i].W;
+    return LD_OK;
+}
+
+int ld_controlnet_read_residual(const ld_unet* cn, int i, void* dst_f16, void* stream) {
+    const void* p = nullptr;
+    int C = 0, H = 0, W = 0;
+    if (dst_f16 == nullptr) return LD_ERR_ARG;
+    const int st = ld_controlnet_residual(cn, i, &p, &C, &H, &W);
+    if (st != LD_OK) return st;
+    return hipMemcpyAsync(dst_f16, p, (size_t)cn->res_n * C * H * W * sizeof(half_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? LD_OK : LD_ERR_HIP;
+}
+
+int ld_controlnet_fill_control(const ld_unet* cn, int r_n, float strength, ld_control* out) {
+    if (out == nullptr) return LD_ERR_ARG;
+    const int count = ld_controlnet_residual_count(cn);
+    if (count < 1 || count + 1 > CONTROL_MAX_SEGMENTS) return LD_ERR_ARG;
+    memset(out, 0, sizeof *out);
+    for (int i = 0; i <= count; ++i) {
+        const void* p = nullptr;
+        const int st = ld_controlnet_residual(cn, i, &p, &out->c[i], &out->h[i], &out->w[i]);
+        if (st != LD_OK) return st;
+        if (i < count) out->residual[i] = p;
+        else out->middle = p;
+    }
+    out->count = count;
+    out->r_n = r_n > 0 ? r_n : cn->res_n;
+    out->strength = strength;
+    return LD_OK;
 }
 
 int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream) {

@@ -159,16 +159,19 @@ class CLIPSetLastLayer:
 
 class KSampler2:
     def sample(self, model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0,
-               preview: Optional[LatentPreviewer] = None, apply_noise_mask: bool = False, apply_cond_areas: bool = False):
+               preview: Optional[LatentPreviewer] = None, apply_noise_mask: bool = False, apply_cond_areas: bool = False,
+               apply_control: bool = False):
         """`preview`: a LatentPreviewer that shows the running latent through TAESD every step, where the reference's sampler loops call
         taesd_preview (LD.py:937, 1105, 1237); its `every` counts from this call's first step.  `apply_noise_mask`: honour
         latent_image["noise_mask"] (SetLatentNoiseMask) — redraw where it is 1, keep the latent where it is 0; off, the mask is not looked at, as in
         the reference.  `apply_cond_areas`: honour the conditioning entries' area, strength, mask and step range (ConditioningSetArea,
-        ConditioningSetMask, ConditioningSetTimestepRange; sampling.sampling_function); off, those keys are inert, as in the reference."""
+        ConditioningSetMask, ConditioningSetTimestepRange; sampling.sampling_function); off, those keys are inert, as in the reference.  `apply_control`: honour the
+        entries' "control" key (ControlNetApply / ControlNetApplyAdvanced): the ControlNet's branch runs in every step inside its range; off, the
+        key is inert, as in the reference."""
         if preview is not None:
             preview.reset()
         return common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=preview,
-                               apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas)
+                               apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas, apply_control=apply_control)
 
 
 def _conditioning_set_values(conditioning, values: dict):
@@ -223,6 +226,84 @@ class ConditioningSetTimestepRange:
 
     def set_range(self, conditioning, start, end):
         return (_conditioning_set_values(conditioning, {"start_percent": start, "end_percent": end}),)
+
+
+class ControlNetLoader:
+    """load_controlnet(state_dict_or_path) -> (control_net,): a ControlNet in upstream's cldm key layout (time_embed.*, input_blocks.*,
+    middle_block.*, input_hint_block.*, zero_convs.*, middle_block_out.*), with or without the `control_model.` prefix; the configuration is
+    read from the shapes, as the checkpoint loader reads the UNet's.  Diffusers-layout files, T2I-Adapters and ControlLoRAs are refused
+    (ValueError).  The workspace is sized on first use."""
+
+    def __init__(self, device="cuda:0", unet_heads: int = 8, max_batch: int = 1, max_hw=(64, 64), max_tokens: int = 77):
+        self.device, self.unet_heads, self.max_batch, self.max_hw, self.max_tokens = device, unet_heads, max_batch, max_hw, max_tokens
+
+    def load_controlnet(self, control_net_name):
+        from . import checkpoint as CK
+        from .controlnet import ControlNet, MI355XControlNet
+        sd = CK.load_state_dict(os.fspath(control_net_name)) if isinstance(control_net_name, (str, os.PathLike)) else dict(control_net_name)
+        sd = CK.controlnet_state_dict(sd)
+        cfg, hint_channels = CK.detect_controlnet_config(sd, num_heads=self.unet_heads)
+        cm = MI355XControlNet(cfg, sd, hint_channels=hint_channels, device=self.device, max_batch=2 * self.max_batch, max_hw=self.max_hw,
+                              max_tokens=self.max_tokens)
+        return (ControlNet(cm),)
+
+
+def load_synthetic_controlnet(device="cuda:0", max_batch: int = 1, max_hw=(64, 64), tiny: bool = False, seed: int = 0, max_tokens: int = 77,
+                              hint_channels: int = 3):
+    """A ControlNet with deterministic random-init weights on the synthetic UNet's configuration — the offline stand-in for a downloaded one.
+    Its zero convolutions are NOT zero (weights.synth_controlnet_tensor): it visibly steers the synthetic UNet."""
+    from .controlnet import ControlNet, synthetic_controlnet
+    cfg = W.tiny_unet_config() if tiny else W.sd15_unet_config()
+    return ControlNet(synthetic_controlnet(cfg, seed, hint_channels, device=device, max_batch=2 * max_batch, max_hw=max_hw, max_tokens=max_tokens))
+
+
+class ControlNetApply:
+    """apply_controlnet(conditioning, control_net, image, strength) -> (conditioning,) (upstream's node): every entry carries a copy of
+    `control_net` with `image` ([B, H, W, 3] in [0, 1]) as its hint, and control_apply_to_uncond = True, so the sampler gives the negative list
+    the same control.  KSampler2().sample(..., apply_control=True) honours it."""
+
+    def apply_controlnet(self, conditioning, control_net, image, strength):
+        if strength == 0:
+            return (conditioning,)
+        hint = image.movedim(-1, 1)
+        c = []
+        for t in conditioning:
+            n = [t[0], t[1].copy()]
+            cn = control_net.copy().set_cond_hint(hint, strength)
+            if "control" in t[1]:
+                cn.set_previous_controlnet(t[1]["control"])
+            n[1]["control"] = cn
+            n[1]["control_apply_to_uncond"] = True
+            c.append(n)
+        return (c,)
+
+
+class ControlNetApplyAdvanced:
+    """apply_controlnet(positive, negative, control_net, image, strength, start_percent, end_percent) -> (positive, negative) (upstream's node):
+    both lists carry ONE copy of `control_net`, active from fraction start_percent to end_percent of the schedule; control_apply_to_uncond = False."""
+
+    def apply_controlnet(self, positive, negative, control_net, image, strength, start_percent, end_percent):
+        if strength == 0:
+            return (positive, negative)
+        hint = image.movedim(-1, 1)
+        cnets = {}
+        out = []
+        for conditioning in (positive, negative):
+            c = []
+            for t in conditioning:
+                d = t[1].copy()
+                prev = d.get("control")
+                if prev in cnets:
+                    cn = cnets[prev]
+                else:
+                    cn = control_net.copy().set_cond_hint(hint, strength, (start_percent, end_percent))
+                    cn.set_previous_controlnet(prev)
+                    cnets[prev] = cn
+                d["control"] = cn
+                d["control_apply_to_uncond"] = False
+                c.append([t[0], d])
+            out.append(c)
+        return (out[0], out[1])
 
 
 class SetLatentNoiseMask:
@@ -465,18 +546,20 @@ def _conditioning_of(clip, prompt):
 
 def txt2img(model, clip, vae, prompt_tokens, negative_tokens, width=512, height=512, batch_size=1, seed=0, steps=20, cfg=7.0,
             sampler_name="dpmpp_2m_sde", scheduler="karras", hires: bool = False, upscale_model: Optional[MI355XUpscaler] = None,
-            preview: Optional[LatentPreviewer] = None, apply_cond_areas: bool = False):
+            preview: Optional[LatentPreviewer] = None, apply_cond_areas: bool = False, apply_control: bool = False):
     """The reference's headless `pipeline()` order (LD.py:10001-10086) with explicit arguments instead of hard-coded ones.
     `*_tokens`: a prompt string (needs a tokenizer on `clip`), pre-tokenised [[(id, weight), ...]] chunks, or a conditioning list
     [[tensor, {..}], ...] as the Conditioning* nodes build it.  `preview`: a LatentPreviewer for the first sampler pass (the hires pass has
     another latent shape and runs without one).  `apply_cond_areas`: both sampler passes honour the entries' area / strength / mask / step
-    range (KSampler2)."""
+    range (KSampler2).  `apply_control`: both passes honour the entries' ControlNet (the hint is resized and encoded again for the hires latent)."""
     pos, neg = _conditioning_of(clip, prompt_tokens), _conditioning_of(clip, negative_tokens)
     lat = EmptyLatentImage().generate(width, height, batch_size)[0]
-    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, preview=preview, apply_cond_areas=apply_cond_areas)[0]
+    lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, preview=preview, apply_cond_areas=apply_cond_areas,
+                             apply_control=apply_control)[0]
     if hires:   # hires-fix (LD.py:10585-10603): bislerp x2, then 10 Euler-a steps at denoise 0.45, cfg 8
         lat = LatentUpscale(model.load_device).upscale(lat, "bislerp", width * 2, height * 2)[0]
-        lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45, apply_cond_areas=apply_cond_areas)[0]
+        lat = KSampler2().sample(model, seed, 10, 8, "euler_ancestral", "normal", pos, neg, lat, denoise=0.45, apply_cond_areas=apply_cond_areas,
+                                 apply_control=apply_control)[0]
     img = VAEDecode().decode(vae, lat)[0]
     if upscale_model is not None:   # the image-side upscale the reference builds next to the sampler nodes (LD.py:10014-10015)
         img = ImageUpscaleWithModel().upscale(upscale_model, img)[0]
@@ -537,16 +620,16 @@ def txt2img_sharded(model, clip, vae, prompt_tokens, negative_tokens, width=512,
 
 
 def inpaint(model, clip, vae, image, mask, prompt_tokens, negative_tokens, seed=0, steps=20, cfg=7.0, sampler_name="dpmpp_2m_sde", scheduler="karras",
-            denoise=1.0, apply_cond_areas: bool = False):
+            denoise=1.0, apply_cond_areas: bool = False, apply_control: bool = False):
     """Masked redraw of an image: VAEEncode, SetLatentNoiseMask, KSampler2(apply_noise_mask=True), VAEDecode.  image: host fp32 [B, H, W, 3] in
     [0, 1], H and W multiples of 64; mask [H, W] or [B, H, W] (or the latent grid's), 1 where the image is redrawn and 0 where its latent is kept
-    -> host fp32 [B, H, W, 3].  `*_tokens` and `apply_cond_areas` as in txt2img.  The kept region goes through the VAE and back; nothing is
+    -> host fp32 [B, H, W, 3].  `*_tokens`, `apply_cond_areas` and `apply_control` as in txt2img.  The kept region goes through the VAE and back; nothing is
     composited in pixel space."""
     pos, neg = _conditioning_of(clip, prompt_tokens), _conditioning_of(clip, negative_tokens)
     lat = VAEEncode().encode(vae, image)[0]
     lat = SetLatentNoiseMask().set_mask(lat, torch.as_tensor(mask, dtype=torch.float32))[0]
     lat = KSampler2().sample(model, seed, steps, cfg, sampler_name, scheduler, pos, neg, lat, denoise=denoise, apply_noise_mask=True,
-                             apply_cond_areas=apply_cond_areas)[0]
+                             apply_cond_areas=apply_cond_areas, apply_control=apply_control)[0]
     return VAEDecode().decode(vae, lat)[0]
 
 

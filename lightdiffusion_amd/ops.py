@@ -12,7 +12,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import ERR_SHAPE, F16, F32, LDError, check, lib
+from ._lib import CONTROL_MAX_SEGMENTS, ERR_SHAPE, F16, F32, LDError, check, lib
 
 
 def _stream() -> int:
@@ -1126,6 +1126,40 @@ def regional_combine(outs, entries, cond_scale: float, shape, out: Optional[torc
     with torch.cuda.device(dev):
         check(lib().ld_op_regional_combine(tab, len(entries), float(cond_scale), out.data_ptr(), b, c, H, W, _stream()), "ld_op_regional_combine")
     return out
+
+
+# ------------------------------------------------------------------ ControlNet's kernels (control/control.hip)
+def control_add_(ts, rs, strength: float, n: Optional[int] = None, r_n: Optional[int] = None):
+    """In place, ONE launch over up to 16 (t, r) pairs: t = fp16(float(t) + strength * float(r)); t [n, ...] and r [r_n, ...] fp16 on one
+    device, r_n dividing n: sample s reads residual sample s % r_n.  The bits of (t.float() + strength * r.float()).half()."""
+    import ctypes as C
+    if len(ts) != len(rs) or not 1 <= len(ts) <= CONTROL_MAX_SEGMENTS:
+        raise LDError(ERR_SHAPE, f"control_add: {len(ts)} segments, {len(rs)} residuals (1 .. {CONTROL_MAX_SEGMENTS})")
+    n = ts[0].shape[0] if n is None else n
+    r_n = rs[0].shape[0] if r_n is None else r_n
+    for t, r in zip(ts, rs):
+        assert t.dtype == torch.float16 and r.dtype == torch.float16 and t.is_cuda and r.is_cuda
+        if t.numel() % n or r.numel() * n != t.numel() * r_n:
+            raise LDError(ERR_SHAPE, f"control_add: segment {tuple(t.shape)} against residual {tuple(r.shape)} with n = {n}, r_n = {r_n}")
+    tp = (C.c_void_p * len(ts))(*[_p(t) for t in ts])
+    rp = (C.c_void_p * len(ts))(*[_p(r) for r in rs])
+    per = (C.c_longlong * len(ts))(*[t.numel() // n for t in ts])
+    with torch.cuda.device(ts[0].device):
+        check(lib().ld_op_control_add(tp, rp, per, len(ts), n, r_n, float(strength), _stream()), "ld_op_control_add")
+    return ts
+
+
+def hint_conv(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, stride: int = 1, silu: bool = True) -> torch.Tensor:
+    """One layer of ControlNet's hint encoder: x fp16 NHWC [n, h, w, cin] or — the first layer — fp32 NCHW [n, cin, h, w] -> fp16 NHWC
+    [n, ho, wo, cout]; wt fp16 [cout, 9 cin] tap-major (repack_conv_weight), bias fp16 [cout]."""
+    first = x.dtype == torch.float32
+    n, cin, h, w = x.shape if first else (x.shape[0], x.shape[3], x.shape[1], x.shape[2])
+    cout = wt.shape[0]
+    y = torch.empty(n, (h - 1) // stride + 1, (w - 1) // stride + 1, cout, dtype=torch.float16, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().ld_op_hint_conv(None if first else _p(x), _p(x) if first else None, n, h, w, cin, _p(wt), _p(bias), cout, stride, int(silu), _p(y),
+                                    _stream()), "ld_op_hint_conv")
+    return y
 
 
 # ------------------------------------------------------------------ the `operations=` namespace (secondary seam)

@@ -25,13 +25,16 @@ class GraphedBody:
     Capture runs in `thread_local` error mode: the reference calls its wrapper from a worker thread (LD.py:10453), and a live
     RCCL process group's watchdog thread issues event queries that must not invalidate a capture in progress."""
 
-    def __init__(self, unet: MI355XUNet, body, use_graph: bool = True):
-        self.unet, self.body, self.use_graph = unet, body, use_graph
+    def __init__(self, unet: MI355XUNet, body, use_graph: bool = True, extra_state=None):
+        """`extra_state`: a callable whose value joins the state key — what else the body's launches bake in (a ControlNet's workspace, context
+        shape and hint batch)."""
+        self.unet, self.body, self.use_graph, self.extra_state = unet, body, use_graph, extra_state
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._key = None
 
     def _state_key(self):
-        return (self.unet.reserve_epoch, self.unet.ctx_shape)
+        key = (self.unet.reserve_epoch, self.unet.ctx_shape)
+        return key if self.extra_state is None else key + (self.extra_state(),)
 
     def _capture(self) -> None:
         dev = self.unet.device
@@ -57,8 +60,11 @@ class GraphedBody:
 
 
 class CFGDenoiser:
-    def __init__(self, unet: MI355XUNet, batch: int, h: int, w: int, cfg_scale: float, use_graph: bool = True):
+    def __init__(self, unet: MI355XUNet, batch: int, h: int, w: int, cfg_scale: float, use_graph: bool = True, control=None):
+        """`control`: (MI355XControlNet, strength) — the step is then the control branch on the [uncond, cond] batch (its own context and hint
+        already resident), the UNet pair forward with its residuals, the guidance mix: still one captured graph, sigma on the device."""
         self.unet, self.batch, self.cfg_scale = unet, batch, float(cfg_scale)
+        self.control = control
         dev = unet.device
         c = unet.cfg["in_channels"]
         with torch.inference_mode(False):      # static buffers are plain tensors whatever mode the first call came in (the reference calls
@@ -67,7 +73,9 @@ class CFGDenoiser:
             self.den2 = torch.zeros(2 * batch, c, h, w, dtype=torch.float32, device=dev)    # later call outside it)
             self.den = torch.zeros(batch, c, h, w, dtype=torch.float32, device=dev)
         self.use_graph = use_graph
-        self._run = GraphedBody(unet, self._body, use_graph)
+        cn = None if control is None else control[0]
+        self._run = GraphedBody(unet, self._body, use_graph,
+                                None if cn is None else (lambda: (cn.reserve_epoch, cn.ctx_shape, cn.hint_shape)))
 
     @property
     def _graph(self):
@@ -79,8 +87,13 @@ class CFGDenoiser:
         self.unet.set_context(torch.cat([rep(uncond), rep(cond)]).contiguous())
 
     def _body(self) -> None:
-        self.unet.forward_pair(self.x1, self.sigma1, out=self.den2)
         from ._lib import check, lib
+        if self.control is not None:
+            cn, strength = self.control
+            cn.forward_pair(self.x1, self.sigma1)
+            self.unet.forward_pair_control(self.x1, self.sigma1, cn.control(strength), out=self.den2)
+        else:
+            self.unet.forward_pair(self.x1, self.sigma1, out=self.den2)
         check(lib().ld_op_cfg_combine(self.den2.data_ptr(), self.den.data_ptr(), self.cfg_scale, self.den.numel(),
                                       torch.cuda.current_stream().cuda_stream), "ld_op_cfg_combine")
 

@@ -528,6 +528,61 @@ def _regional_step(model, x, timestep, uncond, cond, cond_scale, model_options):
     return ops.regional_combine(outs, table, cond_scale, x.shape)
 
 
+# ------------------------------------------------------------------ ControlNet (model_options["ld_control"])
+def _fill_control_to_uncond(positive: List[dict], negative: List[dict]) -> None:
+    """Upstream's apply_empty_x_to_equal_area(filter(control_apply_to_uncond, positive), negative, "control", ...) (the reference's call:
+    LD.py:2872-2886): unless a negative entry without an area already carries a control, the controls of the positive entries that ask for it go
+    to the negative entries without one, round robin.  In place, on process_control's copies."""
+    cond_cnets = [c["control"] for c in positive if c.get("control_apply_to_uncond", False) is True and "area" not in c and c.get("control") is not None]
+    if any(c.get("control") is not None for c in negative if "area" not in c):
+        return
+    others = [i for i, c in enumerate(negative) if "area" not in c]
+    if not others:
+        return
+    for ix, cn in enumerate(cond_cnets):
+        i = others[ix % len(others)]
+        if negative[i].get("control") is not None:
+            negative.append(dict(negative[i], control=cn))
+        else:
+            negative[i] = dict(negative[i], control=cn)
+
+
+def control_step_active(timestep_range, sigma0: float) -> bool:
+    """upstream's ControlBase.get_control: skipped when t[0] > timestep_range[0] or t[0] < timestep_range[1]; both boundary sigmas are inside"""
+    return timestep_range is None or not (sigma0 > timestep_range[0] or sigma0 < timestep_range[1])
+
+
+def process_control(positive: List[dict], negative: List[dict], model, model_options: dict):
+    """Once per run with model_options["ld_control"] (CFGGuider.sample) -> (positive, negative, control): copies of the lists with the
+    control_apply_to_uncond fill, and the one ControlNet the run applies (None: no entry carries one), after its pre_run.  What this stack does
+    not run is refused here, before anything is launched (NotImplementedError): chained ControlNets, a control on only one of the lists or
+    different controls on the entries, control beside regional conditioning (ld_cond_areas), a model that is not driven through the captured
+    guided step (the bare model_function_wrapper hook seam, ld_eager_unbatched)."""
+    positive, negative = [c.copy() for c in positive], [c.copy() for c in negative]
+    _fill_control_to_uncond(positive, negative)
+    controls = [c.get("control") for c in positive + negative]
+    if all(cn is None for cn in controls):
+        return positive, negative, None
+    cn = next(c for c in controls if c is not None)
+    if any(c is not cn for c in controls):
+        raise NotImplementedError("apply_control: every entry of both conditioning lists must carry the SAME ControlNet (ControlNetApply sets "
+                                  "control_apply_to_uncond; ControlNetApplyAdvanced takes both lists): a control on one list only, or different "
+                                  "controls on different entries, is not supported")
+    if getattr(cn, "previous_controlnet", None) is not None:
+        raise NotImplementedError("apply_control: chained ControlNets (previous_controlnet) are not supported")
+    if model_options.get("ld_cond_areas"):
+        raise NotImplementedError("apply_control cannot be combined with apply_cond_areas: control on regional conditioning groups is not supported")
+    if len(positive) != 1 or len(negative) != 1:
+        raise NotImplementedError("apply_control: one positive and one negative conditioning entry are supported")
+    wrapper = model_options.get("model_function_wrapper")
+    if not hasattr(wrapper, "cfg_denoise") or model_options.get("ld_eager_unbatched", False):
+        raise NotImplementedError("apply_control needs the resident UNet's guided step (cfg_denoise): control on the bare model_function_wrapper "
+                                  "hook seam, or with ld_eager_unbatched, is not supported")
+    # (a patcher's LoRA patches go to the UNet only: the control branch keeps its loaded weights)
+    cn.pre_run(model, model.model_sampling.percent_to_sigma)
+    return positive, negative, cn
+
+
 def sampling_function(model, x, timestep, uncond, cond, cond_scale, model_options=None, seed=None):
     """sampling_function / calc_cond_batch / cfg_function (LD.py:2492-2626): ONE batched UNet call in the order
     [uncond, cond] (the reference reverses its to-run list, LD.py:2515), then uncond + (cond - uncond) * scale.
@@ -568,6 +623,15 @@ def sampling_function(model, x, timestep, uncond, cond, cond_scale, model_option
     single = n_u == 1 and n_c == 1
     if single and hasattr(wrapper, "cfg_denoise") and not model_options.get("ld_eager_unbatched", False):
         # MI355X fast path: the whole guided step (cat, UNet on 2B samples, CFG mix) is one replayed hipGraph
+        control = model_options.get("_ld_control") if model_options.get("ld_control") else None
+        if control is not None:
+            # ControlNet (process_control resolved it for this run): inside its step range the step is the control branch on the same
+            # [uncond, cond] batch and context, the UNet pair forward with its residuals and the mix — one replayed graph of its own; outside,
+            # the ordinary step.  Only a run whose range excludes some step reads sigma[0] on the host (upstream compares it there).
+            if control.ranged and not control_step_active(control.timestep_range, _host_sigma(timestep)):
+                control = None
+        if control is not None:
+            return wrapper.cfg_denoise(x, timestep, ctx, cond_scale, token=token, use_graph=model_options.get("ld_use_graph", True), control=control)
         return wrapper.cfg_denoise(x, timestep, ctx, cond_scale, token=token, use_graph=model_options.get("ld_use_graph", True))
     chunks = n_u + n_c
     xs = torch.cat([x] * chunks)
@@ -712,23 +776,36 @@ class CFGGuider:
         self.model_options = dict(self.model_options)
         self.model_options.pop("_ld_ctx_cache", None)
         self.model_options.pop("_ld_regional", None)
+        self.model_options.pop("_ld_control", None)
+        control = None
+        if self.model_options.get("ld_control"):                  # once per run, on copies: the uncond fill, what is refused, pre_run
+            self.conds["positive"], self.conds["negative"], control = process_control(self.conds["positive"], self.conds["negative"],
+                                                                                     self.inner_model, self.model_options)
+            if control is not None:
+                self.model_options["_ld_control"] = control
         if self.model_options.get("ld_cond_areas"):               # once per run, on copies: areas, masks, ranges, the same-area partners
             self.conds["positive"], self.conds["negative"] = process_conds(self.conds["positive"], self.conds["negative"], noise.shape, device,
                                                                            self.inner_model.model_sampling)
         extra_args = {"model_options": self.model_options, "seed": seed}
         samples = sampler.sample(self, sigmas, extra_args, callback, noise, latent_image, denoise_mask, disable_pbar)
         out = self.inner_model.process_latent_out(samples.to(torch.float32))
+        if control is not None:
+            control.cleanup()                                     # cleanup_models' place (LD.py:2300-2340)
         del self.inner_model, self.conds
         return out
 
 
 def sample(model, noise, positive, negative, cfg, device, sampler, sigmas, model_options=None, latent_image=None, denoise_mask=None,
-           callback=None, disable_pbar=False, seed=None, apply_cond_areas: bool = False):
+           callback=None, disable_pbar=False, seed=None, apply_cond_areas: bool = False, apply_control: bool = False):
     """LD.py:3010-3031.  apply_cond_areas: this run honours the conditioning entries' "area", "strength", "mask" and step-range keys
-    (model_options["ld_cond_areas"] on the guider's own copy of the options; sampling_function)."""
+    (model_options["ld_cond_areas"] on the guider's own copy of the options; sampling_function).  apply_control: this run honours their
+    "control" key — a controlnet.ControlNet, as ControlNetApply sets it (model_options["ld_control"]; process_control, sampling_function);
+    without it the key is inert, as in the reference."""
     g = CFGGuider(model)
     if apply_cond_areas:
         g.model_options = dict(g.model_options, ld_cond_areas=True)
+    if apply_control:
+        g.model_options = dict(g.model_options, ld_control=True)
     g.set_conds(positive, negative)
     g.set_cfg(cfg)
     return g.sample(noise, latent_image, sampler, sigmas, denoise_mask, callback, disable_pbar, seed)
@@ -756,29 +833,32 @@ class KSampler1:
             self.sigmas = self.calculate_sigmas(int(steps / denoise))[-(steps + 1):]
 
     def sample(self, noise, positive, negative, cfg, latent_image=None, denoise_mask=None, sigmas=None, callback=None,
-               disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
+               disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False, apply_control: bool = False, **_ignored):
         sigmas = self.sigmas if sigmas is None else sigmas
         sampler = ksampler(self.sampler, inpaint_options={"apply_denoise_mask": True}) if apply_noise_mask else ksampler(self.sampler)
         return sample(self.model, noise, positive, negative, cfg, self.device, sampler, sigmas, self.model_options,
                       latent_image=latent_image, denoise_mask=denoise_mask, callback=callback, disable_pbar=disable_pbar, seed=seed,
-                      apply_cond_areas=apply_cond_areas)
+                      apply_cond_areas=apply_cond_areas, apply_control=apply_control)
 
 
 def sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=1.0, noise_mask=None,
-            sigmas=None, callback=None, disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
+            sigmas=None, callback=None, disable_pbar=False, seed=None, apply_noise_mask: bool = False, apply_cond_areas: bool = False,
+            apply_control: bool = False, **_ignored):
     """LD.py:3156-3203: returns the samples on the intermediate (CPU) device.  apply_noise_mask: `noise_mask` is the sampler's denoise mask —
     redrawn where it is 1, led back to `latent_image` where it is 0 (KSamplerX0Inpaint); by default it is dropped, as the reference drops it.
     apply_cond_areas: the conditioning entries' area, strength, mask and step-range keys are honoured (sampling_function); by default they are
-    inert, as in the reference."""
+    inert, as in the reference.  apply_control: the entries' "control" key (a ControlNet) is honoured (sampling_function); by default it is
+    inert too."""
     ks = KSampler1(model, steps=steps, device=model.load_device, sampler=sampler_name, scheduler=scheduler, denoise=denoise,
                    model_options=model.model_options)
     out = ks.sample(noise, positive, negative, cfg=cfg, latent_image=latent_image, denoise_mask=noise_mask, sigmas=sigmas,
-                    callback=callback, disable_pbar=disable_pbar, seed=seed, apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas)
+                    callback=callback, disable_pbar=disable_pbar, seed=seed, apply_noise_mask=apply_noise_mask, apply_cond_areas=apply_cond_areas,
+                    apply_control=apply_control)
     return out.to("cpu")
 
 
 def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, negative, latent, denoise=1.0, callback=None,
-                    apply_noise_mask: bool = False, apply_cond_areas: bool = False, **_ignored):
+                    apply_noise_mask: bool = False, apply_cond_areas: bool = False, apply_control: bool = False, **_ignored):
     """LD.py:6657-6701.  `callback`: the sampler loop's per-step callback ({"x", "i", "sigma", "denoised"}), e.g. a preview.LatentPreviewer.
     apply_noise_mask: latent["noise_mask"], where there is one, is honoured by the sampler (sample1); by default it is not looked at.
     apply_cond_areas: the conditioning entries' area / strength / mask / step-range keys are honoured (sample1); by default they are inert."""
@@ -787,6 +867,8 @@ def common_ksampler(model, seed, steps, cfg, sampler_name, scheduler, positive, 
     masked = {"noise_mask": latent.get("noise_mask"), "apply_noise_mask": True} if apply_noise_mask else {}
     if apply_cond_areas:
         masked["apply_cond_areas"] = True
+    if apply_control:                                             # the entries' "control" key is honoured (sample1); by default it is inert
+        masked["apply_control"] = True
     samples = sample1(model, noise, steps, cfg, sampler_name, scheduler, positive, negative, latent_image, denoise=denoise, callback=callback, seed=seed,
                       **masked)
     out = latent.copy()

@@ -206,6 +206,37 @@ class MI355XUNet(ResidentModel):
             check(lib().ld_unet_forward_pair(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), b, h, w, _stream()), "ld_unet_forward_pair")
         return out
 
+    def forward_control(self, x: torch.Tensor, sigma: torch.Tensor, control, out: Optional[torch.Tensor] = None, eps_only: bool = False) -> torch.Tensor:
+        """`forward` with ControlNet residuals (`control`: an `_lib.Control`, e.g. MI355XControlNet.control(); None: `forward`) added to the skip
+        tensors and the middle block's output in one launch behind the middle block (`ld_unet_forward_control`)."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert sigma.is_cuda and sigma.dtype == torch.float32 and sigma.is_contiguous()
+        if out is None:
+            out = torch.empty_like(x)
+        n, _, h, w = x.shape
+        mn, mh, mw, _ = self._reserved
+        if n > mn or h > mh or w > mw:
+            raise LDError(ERR_SHAPE, f"ld_unet_forward_control: input {n}x{h}x{w} exceeds the reserved plan {mn}x{mh}x{mw} (reserve(), then set_context)")
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_forward_control(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), n, h, w, int(eps_only),
+                                                None if control is None else C.byref(control), _stream()), "ld_unet_forward_control")
+        return out
+
+    def forward_pair_control(self, x: torch.Tensor, sigma: torch.Tensor, control, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`forward_pair` with ControlNet residuals for the 2B-sample batch (`ld_unet_forward_pair_control`)."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        assert sigma.is_cuda and sigma.dtype == torch.float32 and sigma.is_contiguous()
+        b, c, h, w = x.shape
+        if out is None:
+            out = torch.empty(2 * b, c, h, w, dtype=torch.float32, device=x.device)
+        mn, mh, mw, _ = self._reserved
+        if 2 * b > mn or h > mh or w > mw:
+            raise LDError(ERR_SHAPE, f"ld_unet_forward_pair_control: input 2x{b}x{h}x{w} exceeds the reserved plan {mn}x{mh}x{mw} (reserve(), then set_context)")
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_forward_pair_control(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), b, h, w,
+                                                     None if control is None else C.byref(control), _stream()), "ld_unet_forward_pair_control")
+        return out
+
     KERNEL_CLASSES = ("conv3x3", "gemm", "attention", "groupnorm", "layernorm", "misc")
 
     def profile(self, x: torch.Tensor, sigma: torch.Tensor) -> dict:
@@ -328,21 +359,27 @@ class MI355XUNet(ResidentModel):
         return run.out.clone()
 
     def cfg_denoise(self, x: torch.Tensor, timestep: torch.Tensor, ctx: torch.Tensor, cond_scale: float, token=None,
-                    use_graph: bool = True) -> torch.Tensor:
+                    use_graph: bool = True, control=None) -> torch.Tensor:
         """One classifier-free-guided step (sampling_function, LD.py:2609-2626) through a cached, hipGraph-captured
         `pipeline.CFGDenoiser`: ctx is the [uncond.., cond..] batch (2B rows), x [B,4,h,w], timestep [B] (sigma) on the device.
         This is what `KSampler2.sample` reaches through `sampling.sampling_function`; the reference's counterpart is the
-        CUDA-graph option of its stable-fast patch (LD.py:9902-9946)."""
+        CUDA-graph option of its stable-fast patch (LD.py:9902-9946).
+        `control`: a controlnet.ControlNet whose branch runs on the same [uncond, cond] batch and context in front of the UNet, inside the
+        same captured step; the denoiser is keyed by the resident control model and the strength as well."""
         from .pipeline import CFGDenoiser
         b, _, h, w = x.shape
         x = x.to(self.device, torch.float32)
         self._sync_context(ctx, 2 * b, h, w, token)
         key = (b, h, w, float(cond_scale), bool(use_graph))
+        if control is not None:
+            control.prepare(ctx, token, b, h, w)
+            key += (id(control.control_model), float(control.strength))
         d = self._denoisers.get(key)
         if d is None:
             if len(self._denoisers) >= 4:                      # a few shapes per session (txt2img + hires pass); drop the oldest
                 self._denoisers.pop(next(iter(self._denoisers)))
-            d = self._denoisers[key] = CFGDenoiser(self, b, h, w, cond_scale, use_graph=use_graph)
+            d = self._denoisers[key] = CFGDenoiser(self, b, h, w, cond_scale, use_graph=use_graph,
+                                                   control=None if control is None else (control.control_model, float(control.strength)))
         return d.run(x, timestep.to(self.device, torch.float32)).clone()   # samplers keep `denoised` across steps (old_denoised)
 
     def to(self, device):

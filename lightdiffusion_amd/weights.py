@@ -137,6 +137,46 @@ def unet_param_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
     return shp
 
 
+HINT_CHANNELS = (16, 16, 32, 32, 96, 96, 256)      # cldm.ControlNet.input_hint_block's widths between hint_channels and model_channels
+HINT_STRIDES = (1, 1, 2, 1, 2, 1, 2, 1)
+
+
+def controlnet_param_shapes(cfg: dict, hint_channels: int = 3) -> Dict[str, Tuple[int, ...]]:
+    """name -> shape for upstream's cldm.ControlNet built on the UNet config `cfg` (keys as under `control_model.`): the UNet's time_embed,
+    input_blocks and middle_block, plus input_hint_block.{0,2,..,14} (eight 3x3 convolutions), zero_convs.{i}.0 (1x1, one per input block) and
+    middle_block_out.0."""
+    n_out = sum(cfg["num_res_blocks"]) + len(cfg["channel_mult"])      # (a detected ControlNet config has no output blocks: none are kept below)
+    unet = unet_param_shapes(dict(cfg, transformer_depth_output=[0] * n_out, out_channels=cfg.get("out_channels", cfg["in_channels"])))
+    shp = {k: v for k, v in unet.items() if k.startswith(("time_embed.", "input_blocks.", "middle_block."))}
+    mc = cfg["model_channels"]
+    chain = (hint_channels,) + HINT_CHANNELS + (mc,)
+    for i in range(8):
+        shp[f"input_hint_block.{2 * i}.weight"] = (chain[i + 1], chain[i], 3, 3)
+        shp[f"input_hint_block.{2 * i}.bias"] = (chain[i + 1],)
+    chans = [mc]
+    for level, mult in enumerate(cfg["channel_mult"]):
+        chans += [mult * mc] * cfg["num_res_blocks"][level]
+        if level != len(cfg["channel_mult"]) - 1:
+            chans.append(mult * mc)
+    for i, c in enumerate(chans):
+        shp[f"zero_convs.{i}.0.weight"] = (c, c, 1, 1)
+        shp[f"zero_convs.{i}.0.bias"] = (c,)
+    shp["middle_block_out.0.weight"] = (chans[-1], chans[-1], 1, 1)
+    shp["middle_block_out.0.bias"] = (chans[-1],)
+    return shp
+
+
+CONTROL_NAME_PREFIX = "control_model."
+
+
+def synth_controlnet_tensor(name: str, shape: Tuple[int, ...], seed: int = 0) -> torch.Tensor:
+    """A synthetic ControlNet's parameter by the name-and-seed rule, under the checkpoint's `control_model.` prefix so that no tensor repeats the
+    synthetic UNet's of the same name.  A trained ControlNet's zero convolutions start at zero and stay small; these are N(0, 1 / fan_in) like
+    every other matrix, which puts a residual at the scale of the skip tensor it joins: control at strength 1 moves the UNet's output far beyond
+    the parity bound (tests/test_controlnet_cpu.py holds rel-L2 >= 0.05 on the fp32 reference)."""
+    return synth_tensor(CONTROL_NAME_PREFIX + name, shape, seed)
+
+
 def vae_decoder_param_shapes(cfg: dict) -> Dict[str, Tuple[int, ...]]:
     """name -> shape for `post_quant_conv` + `decoder.*` (LD.py:3461-3473, 3761-3882)."""
     ch, cm, nrb = cfg["ch"], cfg["ch_mult"], cfg["num_res_blocks"]
