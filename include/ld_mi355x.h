@@ -151,6 +151,13 @@ int ld_controlnet_residual_batch(const ld_unet* cn);
 int ld_controlnet_residual(const ld_unet* cn, int i, const void** ptr, int* C, int* H, int* W);
 /* a copy of residual i into dst_f16 (device), ordered on `stream` */
 int ld_controlnet_read_residual(const ld_unet* cn, int i, void* dst_f16, void* stream);
+/* the encoded hint of the last ld_controlnet_set_hint: its shape [*hb][*h][*w][*C] (each pointer may be NULL) and, unless dst_f16 is NULL, a copy of
+ * it into dst_f16 (device, fp16 NHWC), ordered on `stream`.  LD_ERR_STATE: no hint set since the last reserve. */
+int ld_controlnet_read_hint(const ld_unet* cn, void* dst_f16, int* hb, int* h, int* w, int* C, void* stream);
+/* ld_controlnet_forward / ld_controlnet_forward_pair with HIP events around every launch: ld_unet_profile_launches / ld_unet_profile_kernels then
+ * describe the control branch's launches.  (ld_controlnet_set_hint counts its eight launches as a forward does: ld_unet_last_launches is 8 behind it.) */
+int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream);
+int ld_controlnet_profile_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream);
 /* What a UNet forward adds where upstream calls apply_control: residual[i] ([r_n][h[i]][w[i]][c[i]] fp16 NHWC, device) to skip tensor i — the output
  * of input block i; upstream pops control["output"] from the back in step with hs.pop() — and `middle` (shape entry `count`) to the middle block's
  * output, each as t = fp16(float(t) + strength * float(r)); sample s of the forward reads residual sample s % r_n. */
@@ -170,6 +177,12 @@ int ld_controlnet_fill_control(const ld_unet* cn, int r_n, float strength, ld_co
  * r_n does not divide the batch.  LD_ERR_ARG: a NULL residual. */
 int ld_unet_forward_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, const ld_control* ctl, void* stream);
 int ld_unet_forward_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream);
+/* ld_unet_profile / ld_unet_profile_pair of those two: the launch table of the controlled forward (the plain table with one control_add_kernel
+ * entry behind the middle block's last launch; ctl == NULL or strength == 0: the plain table) */
+int ld_unet_profile_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, const ld_control* ctl, void* stream,
+                            double ms[6], double flops[6], int launches[6]);
+int ld_unet_profile_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream,
+                                 double ms[6], double flops[6], int launches[6]);
 
 /* ------------------------------------------------------------------ VAE decoder (Decoder ctor arguments, LD.py:6312-6323) */
 typedef struct {

@@ -107,9 +107,14 @@ SIGNATURES = {
     "ld_controlnet_residual_batch": (_I, [_P]),
     "ld_controlnet_residual": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ld_controlnet_read_residual": (_I, [_P, _I, _P, _P]),
+    "ld_controlnet_read_hint": (_I, [_P, _P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
+    "ld_controlnet_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_profile_pair": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_controlnet_fill_control": (_I, [_P, _I, _F, C.POINTER(Control)]),
     "ld_unet_forward_control": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Control), _P]),
     "ld_unet_forward_pair_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P]),
+    "ld_unet_profile_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
+    "ld_unet_profile_pair_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_vae_create": (_I, [C.POINTER(VAEConfig), C.POINTER(_P)]),
     "ld_vae_decode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),

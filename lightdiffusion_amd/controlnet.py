@@ -152,6 +152,29 @@ class MI355XControlNet(ResidentModel):
         with torch.cuda.device(self.device):
             check(lib().ld_controlnet_forward_pair(self._h, x.data_ptr(), sigma.data_ptr(), b, h, w, _stream()), "ld_controlnet_forward_pair")
 
+    def profile(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
+        """`forward` with HIP events around every launch: `profile_launches()` is then the control branch's launch table."""
+        n, _, h, w = x.shape
+        self._check(n, h, w, "ld_controlnet_profile")
+        with torch.cuda.device(self.device):
+            check(lib().ld_controlnet_profile(self._h, x.data_ptr(), sigma.data_ptr(), n, h, w, _stream()), "ld_controlnet_profile")
+
+    def profile_pair(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
+        """`profile` of `forward_pair`: x [B,..], sigma [B]."""
+        b, _, h, w = x.shape
+        self._check(2 * b, h, w, "ld_controlnet_profile_pair")
+        with torch.cuda.device(self.device):
+            check(lib().ld_controlnet_profile_pair(self._h, x.data_ptr(), sigma.data_ptr(), b, h, w, _stream()), "ld_controlnet_profile_pair")
+
+    def hint(self) -> torch.Tensor:
+        """A copy of the resident encoded hint, fp16 [hb, h, w, model_channels]."""
+        hb, h, w, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(lib().ld_controlnet_read_hint(self._h, None, C.byref(hb), C.byref(h), C.byref(w), C.byref(c), None), "ld_controlnet_read_hint")
+        t = torch.empty(hb.value, h.value, w.value, c.value, dtype=torch.float16, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().ld_controlnet_read_hint(self._h, t.data_ptr(), None, None, None, None, _stream()), "ld_controlnet_read_hint")
+        return t
+
     def control(self, strength: float, r_n: int = 0) -> Control:
         """The `ld_control` of the last forward's residuals (they live at fixed addresses until the workspace moves)."""
         ctl = Control()

@@ -1047,16 +1047,22 @@ int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, 
     cn->hint_b = 0;
     const half_t* src = nullptr;
     int h = H, w = W;
+    Arena none;
+    Exec ex = cn->begin(false, stream, none);   // counted and named as a forward's launches are: last_launches is 8 behind a set_hint
     for (size_t i = 0; i < cn->hint_convs.size(); ++i) {
         const ld_unet::HintW& L = cn->hint_convs[i];
         const bool last = i + 1 == cn->hint_convs.size();
         half_t* dst = last ? cn->hint : buf[i & 1];
-        const int st = hint_conv_launch(src, i == 0 ? image_nchw : nullptr, hb, h, w, L.cin, cn->pt.ptr(L.w), cn->pt.ptr(L.b), L.cout, L.stride, !last, dst, stream);
-        if (st != LD_OK) return st;
-        h = (h - 1) / L.stride + 1;
-        w = (w - 1) / L.stride + 1;
+        const int ho = (h - 1) / L.stride + 1, wo = (w - 1) / L.stride + 1;
+        ex.launch(KC_MISC, 2.0 * hb * ho * wo * L.cout * 9.0 * L.cin, "hint_conv", (long long)hb * ho * wo, L.cout, 9 * L.cin, L.stride, "hint_conv_kernel", [&] {
+            return hint_conv_launch(src, i == 0 ? image_nchw : nullptr, hb, h, w, L.cin, cn->pt.ptr(L.w), cn->pt.ptr(L.b), L.cout, L.stride, !last, dst, stream);
+        });
+        h = ho;
+        w = wo;
         src = dst;
     }
+    const int st = cn->end(ex, nullptr, true);
+    if (st != LD_OK) return st;
     cn->hint_b = hb;
     cn->hint_h = h;
     cn->hint_w = w;
@@ -1081,6 +1087,27 @@ int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n
 int ld_controlnet_forward_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream) {
     if (nb < 1) return LD_ERR_SHAPE;
     return control_forward_checked(cn, x, sigma, 2 * nb, h, w, stream, true);
+}
+
+int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream) {
+    return abi_profile(cn, stream, [&] { return control_forward_checked(cn, x, sigma, n, h, w, stream, false); });
+}
+
+int ld_controlnet_profile_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream) {
+    if (nb < 1) return LD_ERR_SHAPE;
+    return abi_profile(cn, stream, [&] { return control_forward_checked(cn, x, sigma, 2 * nb, h, w, stream, true); });
+}
+
+int ld_controlnet_read_hint(const ld_unet* cn, void* dst_f16, int* hb, int* h, int* w, int* C, void* stream) {
+    if (cn == nullptr || !cn->control) return LD_ERR_ARG;
+    if (cn->hint_b == 0 || cn->hint == nullptr) return LD_ERR_STATE;
+    if (hb) *hb = cn->hint_b;
+    if (h) *h = cn->hint_h;
+    if (w) *w = cn->hint_w;
+    if (C) *C = cn->cfg.model_channels;
+    if (dst_f16 == nullptr) return LD_OK;
+    const size_t bytes = (size_t)cn->hint_b * cn->hint_h * cn->hint_w * cn->cfg.model_channels * sizeof(half_t);
+    return hipMemcpyAsync(dst_f16, cn->hint, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? LD_OK : LD_ERR_HIP;
 }
 
 int ld_controlnet_residual_count(const ld_unet* cn) { return cn != nullptr && cn->control ? (int)cn->in_blocks.size() : 0; }
@@ -1134,7 +1161,7 @@ int ld_unet_forward_pair(ld_unet* u, const float* x, const float* sigma, float* 
 }
 
 static int profile_any(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6], double flops[6],
-                       int launches[6], bool pair);
+                       int launches[6], bool pair, const ld_control* ctl = nullptr);
 
 int ld_unet_profile(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6],
                     double flops[6], int launches[6]) {
@@ -1146,10 +1173,20 @@ int ld_unet_profile_pair(ld_unet* u, const float* x, const float* sigma, float* 
     return profile_any(u, x, sigma, out, 2 * nb, h, w, stream, ms, flops, launches, true);
 }
 
+int ld_unet_profile_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, const ld_control* ctl, void* stream,
+                            double ms[6], double flops[6], int launches[6]) {
+    return profile_any(u, x, sigma, out, n, h, w, stream, ms, flops, launches, false, ctl);
+}
+
+int ld_unet_profile_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream,
+                                 double ms[6], double flops[6], int launches[6]) {
+    return profile_any(u, x, sigma, out, 2 * nb, h, w, stream, ms, flops, launches, true, ctl);
+}
+
 static int profile_any(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6], double flops[6],
-                       int launches[6], bool pair) {
+                       int launches[6], bool pair, const ld_control* ctl) {
     if (u == nullptr || ms == nullptr || flops == nullptr || launches == nullptr) return LD_ERR_ARG;
-    const int st = abi_profile(u, stream, [&] { return forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair); });
+    const int st = abi_profile(u, stream, [&] { return forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair, ctl); });
     if (st != LD_OK) return st;
     for (int i = 0; i < KC_COUNT; ++i) {
         ms[i] = u->timing.ms[i];

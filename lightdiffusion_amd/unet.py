@@ -259,6 +259,26 @@ class MI355XUNet(ResidentModel):
                   "ld_unet_profile_pair")
         return {k: (ms[i], fl[i], nl[i]) for i, k in enumerate(self.KERNEL_CLASSES)}
 
+    def profile_control(self, x: torch.Tensor, sigma: torch.Tensor, control) -> dict:
+        """`profile` of `forward_control` (`control`: an `_lib.Control` or None)."""
+        out = torch.empty_like(x)
+        ms, fl, nl = (C.c_double * 6)(), (C.c_double * 6)(), (C.c_int * 6)()
+        n, _, h, w = x.shape
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_profile_control(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), n, h, w,
+                                                None if control is None else C.byref(control), _stream(), ms, fl, nl), "ld_unet_profile_control")
+        return {k: (ms[i], fl[i], nl[i]) for i, k in enumerate(self.KERNEL_CLASSES)}
+
+    def profile_pair_control(self, x: torch.Tensor, sigma: torch.Tensor, control) -> dict:
+        """`profile_pair` of `forward_pair_control`: x [B,..], sigma [B]."""
+        b, c, h, w = x.shape
+        out = torch.empty(2 * b, c, h, w, dtype=torch.float32, device=x.device)
+        ms, fl, nl = (C.c_double * 6)(), (C.c_double * 6)(), (C.c_int * 6)()
+        with torch.cuda.device(self.device):
+            check(lib().ld_unet_profile_pair_control(self._h, x.data_ptr(), sigma.data_ptr(), out.data_ptr(), b, h, w,
+                                                     None if control is None else C.byref(control), _stream(), ms, fl, nl), "ld_unet_profile_pair_control")
+        return {k: (ms[i], fl[i], nl[i]) for i, k in enumerate(self.KERNEL_CLASSES)}
+
     def profile_kernels(self) -> dict:
         """Per kernel instantiation of the last `profile()` call: {name: (ms, flops, launches)}."""
         buf = C.create_string_buffer(1 << 16)

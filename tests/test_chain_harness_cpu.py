@@ -195,3 +195,28 @@ def test_record(monkeypatch, tmp_path):
     H.record("x_parity.json", "case", {"b": 2})
     H.record("x_parity.json", "new", {"c": 3})
     assert (tmp_path / "x_parity.json").read_text() == '{\n "case": {\n  "a": 1,\n  "b": 2\n },\n "new": {\n  "c": 3\n },\n "other": {\n  "z": 0\n }\n}\n'
+
+
+# ------------------------------------------------------------------ the ControlNet chain tests' own stages and launch cost record
+
+def test_control_add_stage_rejects_the_wrong_residual_sample():
+    """tests/test_controlnet_chain_gpu.py `_stage`, kind control_add: sample s reads residual s % r_n — a residual read as s // r_n, the strength
+    left out, or a sum rounded twice is named by its segment."""
+    import test_controlnet_chain_gpu as T
+    g = torch.Generator().manual_seed(3)
+    t0, t1 = torch.randn(4, 2, 3, 8, generator=g).half(), torch.randn(4, 5, generator=g).half()
+    r0, r1 = torch.randn(2, 2, 3, 8, generator=g).half(), torch.randn(2, 5, generator=g).half()
+    good = lambda t, r, s=0.6: (t.float() + s * r.float().repeat((2,) + (1,) * (r.dim() - 1))).half()
+    tap = dict(kind="control_add", name="control", inp=dict(t=[t0, t1], r=[r0, r1]), par=dict(strength=0.6, r_n=2), out=(good(t0, r0), good(t1, r1)))
+    assert T._stage(tap, None, "case") == [(0.0, 0.0)]
+    wrong_sample = (t1.float() + 0.6 * r1.float().repeat_interleave(2, 0)).half()
+    for bad, segment in (((good(t0, r0), wrong_sample), 1), ((good(t0, r0, 1.0), good(t1, r1)), 0),
+                         (((t0 + (0.6 * r0.float()).half().repeat(2, 1, 1, 1)), good(t1, r1)), 0)):
+        with pytest.raises(AssertionError, match=rf"^case: segment {segment}: \d+ of \d+ elements differ"):
+            T._stage(dict(tap, out=bad), None, "case")
+
+
+def test_cost_of_sums_a_launch_table():
+    import test_controlnet_chain_gpu as T
+    rows = [("conv1", (8, 320, 320, 1), 0.0, 10.0, "a"), ("conv1", (8, 320, 320, 1), 0.0, 2.5, "b"), ("", (0, 0, 0, 0), 0.0, 1.25, "a")]
+    assert T.cost_of(rows) == {"launches": 3, "us": 13.8, "per_kernel": {"a": [2, 11.2], "b": [1, 2.5]}}

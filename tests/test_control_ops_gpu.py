@@ -143,7 +143,7 @@ def weights_of(g, cin, cout):
 
 def held(y, ref, bound, what, width):
     n_eff = EB.independent_roundings(ref)
-    EB.check(y.reshape(ref.shape), ref, bound, what, image_rows=ref.shape[0] // y.shape[0], width=width, bias_extra=EB.rtn_noise(n_eff))
+    return EB.check(y.reshape(ref.shape), ref, bound, what, image_rows=ref.shape[0] // y.shape[0], width=width, bias_extra=EB.rtn_noise(n_eff))
 
 
 @pytest.mark.parametrize("hw", [(16, 24), (8, 8)])

@@ -416,6 +416,41 @@ def test_unet_workspace_history(L, make):
     _history("unet", handles, large, small)
 
 
+def test_controlnet_workspace_history():
+    """The control branch: batch 4 at 16x16 with 154 context tokens and a hint batch of 2 on adverse inputs, then batch 1 at 7x9 with 77 tokens
+    and its own hint, and the CFG pair on it — the residual buffers, the encoded hint and the arena the hint encoder shares all hold the large
+    call's rows by then.  The small calls' hint and 13 residuals are the bits of a handle that never saw the large one.  (Every call stays
+    inside the reserved plan: nothing re-reserves, and the hint is set anew for each latent size, as the branch demands.)"""
+    from lightdiffusion_amd import weights as W
+    from lightdiffusion_amd.controlnet import synthetic_controlnet
+    cfg = W.tiny_unet_config()
+    handles = [synthetic_controlnet(cfg, max_batch=4, max_hw=(16, 16), max_tokens=154) for _ in range(2)]
+    epochs = [hd.reserve_epoch for hd in handles]
+    xl, cl, sl = A.big((4, 4, 16, 16), 1).float(), A.outlier((4, 154, 64), 2).float() * 16.0, torch.full((4,), 10.0, device=DEV)
+    hl = torch.ones(2, 3, 128, 128, device=DEV)
+    xs, ss, c1, c2 = _rand((1, 4, 7, 9), 3), torch.ones(1, device=DEV), _rand((1, 77, 64), 4), _rand((2, 77, 64), 5)
+    hs = torch.rand(1, 3, 56, 72, generator=torch.Generator().manual_seed(6)).to(DEV)
+
+    def large(hd):
+        hd.set_context(cl)
+        hd.set_hint(hl)
+        hd.forward(xl, sl)
+
+    def small(hd):
+        hd.set_context(c1)
+        hd.set_hint(hs)
+        enc = hd.hint()
+        hd.forward(xs, ss)
+        r1 = hd.residuals()
+        hd.set_context(c2)
+        hd.forward_pair(xs, ss)
+        r2 = hd.residuals()
+        assert all(r.shape[0] == 1 for r in r1) and all(r.shape[0] == 2 for r in r2) and len(r1) == len(r2) == hd.residual_count + 1
+        return [enc] + r1 + r2
+    _history("controlnet", handles, large, small)
+    assert [hd.reserve_epoch for hd in handles] == epochs, "a call inside the reserved plan moved the workspace"
+
+
 def _sized_history(L, make, name, entry, big_shape, small_shape, ins, outs):
     """A family whose run is entry(handle, inputs..., outputs..., b, h, w, stream): ins / outs(b, h, w, adverse) -> tensors."""
     from lightdiffusion_amd._lib import OK

@@ -384,6 +384,16 @@ CONV_ROUTES = [
     (2, 48, 32, 320, 0, 640, 1, None, 3, False, False, "gemm3_kernel<64,160,conv>+splitk_reduce_kernel"),
     (2, 64, 96, 320, 0, 320, 1, None, 3, True, True, "gemm3_kernel<64,160,conv,deep>"),
     (2, 96, 64, 320, 0, 320, 1, None, 3, False, False, "gemm3_kernel<64,160,conv,deep>"),
+    # ControlNet's zero convolutions: ONE source, 1x1, C -> C, no residual, no row vector — every kernel the launch tables of
+    # tests/test_controlnet_chain_gpu.py / _full_gpu.py show for them, each at the smallest problem gemm_plan still gives that kernel
+    # (gemm.hip: the v3 / v4 tail; tiles = ceil(M / bm) * ceil(N / 160)):
+    (2, 2, 2, 1280, 0, 1280, 1, None, 1, False, False, "gemm3_kernel<64,160,conv,deep>+splitk_reduce_kernel"),   # the 2 x 2 level of a 16 x 16 latent: 8 rows; K / 640 = 2 slices
+    (1, 1, 1, 320, 0, 320, 1, None, 1, False, False, "gemm3_kernel<64,160,conv,deep>"),              # <= 32 tiles, K < 1280: no split; one row
+    (1, 45, 45, 1280, 0, 1280, 1, None, 1, False, False, "gemm3_kernel<64,160,conv,deep>"),          # 32 panels x 8 = 256 tiles: the low edge of deep's one round (2025 rows, a ragged last panel; 26 panels up: past skinny_conv1)
+    (1, 19, 27, 640, 0, 640, 1, None, 1, False, False, "gemm3_kernel<64,160,conv>"),                 # 513 rows: 9 panels x 4 = 36 tiles, the first count above deep's 32
+    (1, 89, 91, 1280, 0, 1280, 1, None, 1, False, False, "gemm3_kernel<128,160,conv>"),              # 8099 rows: 64 panels of 128 x 8 = 512 tiles, where bm turns 128 (8064 rows: still 63)
+    (1, 5, 77, 1280, 0, 1280, 1, None, 1, False, False, "gemm4_kernel<64,64,conv,2wg>"),             # skinny_conv1: 385 rows = 7 x 20 = 140 tiles of 64 x 64 > 128, 1280 <= K <= 3200
+    (1, 1, 2, 256, 0, 256, 1, None, 1, False, False, "gemm3_kernel<64,128,conv>"),                   # the tiny configuration's (N = 64 / 128 / 256 takes 128 columns): its 1 x 2 level
 ]
 
 

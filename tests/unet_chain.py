@@ -72,10 +72,13 @@ def log_sigma_table() -> torch.Tensor:
 # ------------------------------------------------------------------ the chain
 
 class UNetChain(ChainBase):
-    def __init__(self, cfg: dict, device="cuda:0", seed: int = 0, source=None):
-        super().__init__(W.unet_param_shapes(cfg), device, seed, source)
+    shares_prefix = True      # a CFG pair runs the layers in front of the first cross-attention once for both halves
+
+    def __init__(self, cfg: dict, device="cuda:0", seed: int = 0, source=None, shapes=None, prefix: str = ""):
+        """shapes / prefix: the parameter shapes and what the synthetic checkpoint's keys carry in front of the names (None: the UNet's own)."""
+        super().__init__(W.unet_param_shapes(cfg) if shapes is None else shapes, device, seed, source, prefix)
         self.cfg = dict(cfg)
-        self.blocks = modules(cfg)
+        self.blocks = self.block_list(cfg)
         self.heads = cfg["num_heads"]
         self.ctx = None
         self.log_sigmas = log_sigma_table().to(self.dev)
@@ -88,6 +91,24 @@ class UNetChain(ChainBase):
         self.emb_total = off
         self.emb_w = torch.cat([self.mat(n + ".emb_layers.1.weight") for _, n, _, _ in res]).contiguous()
         self.emb_b = torch.cat([self.vec(n + ".emb_layers.1.bias") for _, n, _, _ in res]).contiguous()
+
+    def block_list(self, cfg):
+        return modules(cfg)
+
+    # -- what a subclass runs behind a block (the control branch: the hint and the zero convolutions); the UNet: nothing
+    def block_done(self, where, bi, f: Feat) -> Feat:
+        return f
+
+    # -- apply_control1 at "output" and "middle" (LD.py:5290, 5742, 5747) as upstream fills it: residual i joins hs[i], the last one the middle
+    # block's output; ONE call over all of them.  The sums go into copies: the taps of the producers keep the tensors they wrote.
+    def apply_control(self, hs, f: Feat, control):
+        residuals, r_n, strength = control
+        assert len(residuals) == len(hs) + 1, f"{len(residuals)} residuals for {len(hs)} skip tensors and the middle block"
+        before = hs + [f.t]
+        after = [t.clone() for t in before]
+        self.ops.control_add_(after, list(residuals), strength, r_n=r_n)
+        self.tap("control_add", "control (skips + middle)", dict(t=before, r=list(residuals)), dict(strength=float(strength), r_n=r_n), tuple(after))
+        return after[:-1], Feat(after[-1])           # (the middle tensor's partial statistics describe it as it was before the add)
 
     # -- the context: K / V^T of every cross-attention, projected once (CrossAttention.forward's to_k / to_v, LD.py:4028-4036)
     def set_context(self, ctx: torch.Tensor):
@@ -199,8 +220,10 @@ class UNetChain(ChainBase):
         return out, po, n
 
     # -- apply_model: calculate_input, UNetModel1.forward, calculate_denoised
-    def forward(self, x: torch.Tensor, sigma: torch.Tensor, eps_only: bool = False, pair: bool = False):
-        """x [n][4][h][w] fp32, sigma [n] (pair: both hold n / 2 samples, run against the 2 x (n / 2)-row context) -> denoised (eps) [n or 2 (n / 2)] fp32."""
+    def forward(self, x: torch.Tensor, sigma: torch.Tensor, eps_only: bool = False, pair: bool = False, control=None):
+        """x [n][4][h][w] fp32, sigma [n] (pair: both hold n / 2 samples, run against the 2 x (n / 2)-row context) -> denoised (eps) [n or 2 (n / 2)] fp32.
+        control: (residuals, r_n, strength) — 13 tensors [r_n][H][W][C] fp16 as the control branch leaves them, added behind the middle block;
+        None or strength 0: the plain forward, call for call."""
         ops, cfg = self.ops, self.cfg
         self.taps = []
         mc = cfg["model_channels"]
@@ -208,8 +231,8 @@ class UNetChain(ChainBase):
         n_all = 2 * nb if pair else nb
         assert self.ctx is not None and self.ctx_n == n_all
         in_mod = nb if pair else 0
-        n = nb                                       # samples the layers run on: all of them, or the first half of a pair up to the first cross-attention
-        pending = pair
+        pending = pair and self.shares_prefix
+        n = nb if pending else n_all                 # samples the layers run on: all of them, or the first half of a pair up to the first cross-attention
         # time embedding (timestep_embedding LD.py:803-812, time_embed, every ResBlock's emb_layers)
         temb, _ = ops.timestep_embed_mod(sigma, self.log_sigmas, mc, n_all, in_mod)
         self.tap("timestep", "timestep_embedding", dict(sigma=sigma), dict(dim=mc, n=n_all, sigma_mod=in_mod), temb)
@@ -254,9 +277,16 @@ class UNetChain(ChainBase):
                     out = ops.upconv2x(f.t, wu, wf, bu, out_hw=(hv, wv))
                     self.tap("upconv", name, dict(x=f.t, out_hw=(hv, wv)), dict(w=self.oihw(name + ".weight"), b=bu), out, n=f.t.shape[0])
                     f = Feat(out)
+            f = self.block_done(where, bi, f)
             if where == "input":
                 assert not (pending and bi >= 1), "first input block without a transformer: not a layout of this chain"
                 hs.append(f.t)
+            elif where == "middle" and control is not None and control[2] != 0.0:
+                hs, f = self.apply_control(hs, f, control)
+        return self.finish(f, x, sigma, eps_only, in_mod)
+
+    def finish(self, f: Feat, x, sigma, eps_only, in_mod):
+        ops = self.ops
         # out: GroupNorm + SiLU, the 3x3 convolution to the latent's channels, calculate_denoised
         og, ob = self.vec("out.0.weight"), self.vec("out.0.bias")
         if f.part is not None:
