@@ -74,22 +74,28 @@ size_t ld_unet_workspace_bytes(const ld_unet* u);
 size_t ld_unet_weight_bytes(const ld_unet* u);
 /* ctx: [n][tokens][context_dim] (LD_F16 / LD_F32), batch order as the reference builds it: [uncond..., cond...] */
 int ld_unet_set_context(ld_unet* u, const void* ctx, int dtype, int n, int tokens, void* stream);
+/* ld_control: what a UNet forward adds where upstream calls apply_control — see the ControlNet section below */
+typedef struct ld_control ld_control;
+#define LD_FWD_EPS_ONLY 1   /* out = the raw UNet output (fp32 of the fp16 eps), not denoised */
+#define LD_FWD_PAIR     2   /* CFG pair: x / sigma hold n samples, the batch run and written is 2n: [uncond.. ; cond..] */
 /* x, out: [n][in_channels][h][w] fp32 NCHW; sigma: [n] fp32 (sigma, not t).  out = denoised = x - eps * sigma.
- * eps_only != 0 writes the raw UNet output (fp32 of the fp16 eps) instead. */
-int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream);
-/* Classifier-free-guidance pair — what the reference's calc_cond_batch feeds the model every step: cat([x, x]) against cat([uncond, cond]) (LD.py:2515-2547).
- * x: [nb][in_channels][h][w], sigma: [nb]; the resident context has 2 nb rows ([uncond x nb ; cond x nb]); out: [2 nb][..] denoised, same order.
- * Same result as ld_unet_forward on the duplicated inputs; the layers in front of the first cross-attention (conv_in, the first ResBlock, the first
- * transformer's GroupNorm / proj_in / self-attention) see identical inputs in both halves and are evaluated ONCE, their outputs copied (exact; per sample
- * the bits can differ from ld_unet_forward where a contraction's tile / split choice follows the row count). */
-int ld_unet_forward_pair(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, void* stream);
-/* one forward with a HIP-event pair around every launch (recorded on `stream`), summed per kernel class:
- * 0 conv3x3 (implicit GEMM)  1 linear / 1x1 GEMM  2 attention  3 GroupNorm  4 LayerNorm  5 misc.  Synchronises the stream. */
-int ld_unet_profile(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6],
-                    double flops[6], int launches[6]);
-/* the same for ld_unet_forward_pair (x, sigma: nb samples; out: 2 nb) */
-int ld_unet_profile_pair(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, void* stream, double ms[6],
-                         double flops[6], int launches[6]);
+ * flags: LD_FWD_* bits.  LD_ERR_ARG, before anything is launched: a bit that is not a flag, LD_FWD_PAIR | LD_FWD_EPS_ONLY.
+ * LD_FWD_PAIR is the classifier-free-guidance pair — what the reference's calc_cond_batch feeds the model every step: cat([x, x]) against
+ * cat([uncond, cond]) (LD.py:2515-2547).  x: [n][in_channels][h][w], sigma: [n]; the resident context has 2 n rows ([uncond x n ; cond x n]);
+ * out: [2 n][..] denoised, same order (n < 1: LD_ERR_SHAPE).  Same result as the plain forward on the duplicated inputs; the layers in front of the
+ * first cross-attention (conv_in, the first ResBlock, the first transformer's GroupNorm / proj_in / self-attention) see identical inputs in both
+ * halves and are evaluated ONCE, their outputs copied (exact; per sample the bits can differ from the plain forward where a contraction's tile /
+ * split choice follows the row count).
+ * ctl (may be NULL): the residuals of a control branch, added in ONE launch behind the middle block, when every skip tensor is complete and the
+ * encoder reads none of them again.  ctl == NULL: the plain forward, launch for launch; strength == 0 launches nothing more either.
+ * LD_ERR_SHAPE, before anything is launched: count is not the number of skip tensors, a shape is not its skip tensor's (the middle block's output),
+ * r_n does not divide the batch.  LD_ERR_ARG: a NULL residual. */
+int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int flags, const ld_control* ctl, void* stream);
+/* the same forward with a HIP-event pair around every launch (recorded on `stream`), summed per kernel class:
+ * 0 conv3x3 (implicit GEMM)  1 linear / 1x1 GEMM  2 attention  3 GroupNorm  4 LayerNorm  5 misc.  Synchronises the stream.  With ctl the launch
+ * table is the plain one with one control_add_kernel entry behind the middle block's last launch (ctl == NULL or strength == 0: the plain table). */
+int ld_unet_profile(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int flags, const ld_control* ctl, void* stream,
+                    double ms[6], double flops[6], int launches[6]);
 /* per kernel INSTANTIATION (the names rocprofv3 --kernel-trace lists, abbreviated) of the last ld_unet_profile call:
  * one text line "name<TAB>launches<TAB>total ms<TAB>algorithmic FLOPs" each, NUL-terminated.  LD_ERR_ARG if buf is too small. */
 int ld_unet_profile_kernels(const ld_unet* u, char* buf, size_t buf_bytes);
@@ -140,10 +146,9 @@ int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, 
  * h = conv_in(x / sqrt(sigma^2 + 1)) + hint, the input blocks, the middle block; residual i = zero_convs.i.0 of input block i's output, the last one
  * middle_block_out.0 of the middle block's — raw fp16 NHWC, in buffers that persist in the handle (allocated by ld_unet_reserve for the reserved
  * maximum), valid until the next forward.  Only enqueues on `stream`; capturable.  LD_ERR_STATE: no hint set; LD_ERR_SHAPE: (h, w) is not the hint's. */
-int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream);
-/* ... for a classifier-free-guidance pair: x / sigma hold nb samples, the context 2 nb rows; the residuals are those of ld_controlnet_forward on
- * cat([x, x]) (conv_in runs once per latent, everything else on all 2 nb samples) */
-int ld_controlnet_forward_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream);
+/* flags: LD_FWD_PAIR or 0 (LD_FWD_EPS_ONLY, a branch writes no output: LD_ERR_ARG).  LD_FWD_PAIR: x / sigma hold n samples, the context 2 n rows; the
+ * residuals are those of the plain forward on cat([x, x]) (conv_in runs once per latent, everything else on all 2 n samples) */
+int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, int flags, void* stream);
 /* residuals of the last forward: their number without the middle one (= input blocks), their batch, and residual i (i = count: the middle one) as a
  * device pointer to [batch][H][W][C] fp16 */
 int ld_controlnet_residual_count(const ld_unet* cn);
@@ -154,35 +159,22 @@ int ld_controlnet_read_residual(const ld_unet* cn, int i, void* dst_f16, void* s
 /* the encoded hint of the last ld_controlnet_set_hint: its shape [*hb][*h][*w][*C] (each pointer may be NULL) and, unless dst_f16 is NULL, a copy of
  * it into dst_f16 (device, fp16 NHWC), ordered on `stream`.  LD_ERR_STATE: no hint set since the last reserve. */
 int ld_controlnet_read_hint(const ld_unet* cn, void* dst_f16, int* hb, int* h, int* w, int* C, void* stream);
-/* ld_controlnet_forward / ld_controlnet_forward_pair with HIP events around every launch: ld_unet_profile_launches / ld_unet_profile_kernels then
- * describe the control branch's launches.  (ld_controlnet_set_hint counts its eight launches as a forward does: ld_unet_last_launches is 8 behind it.) */
-int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream);
-int ld_controlnet_profile_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream);
+/* ld_controlnet_forward with HIP events around every launch: ld_unet_profile_launches / ld_unet_profile_kernels then describe the control branch's
+ * launches.  (ld_controlnet_set_hint counts its eight launches as a forward does: ld_unet_last_launches is 8 behind it.) */
+int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, int flags, void* stream);
 /* What a UNet forward adds where upstream calls apply_control: residual[i] ([r_n][h[i]][w[i]][c[i]] fp16 NHWC, device) to skip tensor i — the output
  * of input block i; upstream pops control["output"] from the back in step with hs.pop() — and `middle` (shape entry `count`) to the middle block's
  * output, each as t = fp16(float(t) + strength * float(r)); sample s of the forward reads residual sample s % r_n. */
-typedef struct {
+struct ld_control {
     const void* residual[16];
     int count;
     const void* middle;
     int r_n;
     float strength;
     int c[16], h[16], w[16];   /* of residual i; entry `count`: of the middle one */
-} ld_control;
+};
 /* the descriptor of a control handle's last forward (r_n <= 0: its batch) */
 int ld_controlnet_fill_control(const ld_unet* cn, int r_n, float strength, ld_control* out);
-/* ld_unet_forward / ld_unet_forward_pair with the residuals of `ctl` added in ONE launch behind the middle block, when every skip tensor is complete
- * and the encoder reads none of them again.  ctl == NULL: the plain forward, launch for launch; strength == 0 launches nothing more either.
- * LD_ERR_SHAPE, before anything is launched: count is not the number of skip tensors, a shape is not its skip tensor's (the middle block's output),
- * r_n does not divide the batch.  LD_ERR_ARG: a NULL residual. */
-int ld_unet_forward_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, const ld_control* ctl, void* stream);
-int ld_unet_forward_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream);
-/* ld_unet_profile / ld_unet_profile_pair of those two: the launch table of the controlled forward (the plain table with one control_add_kernel
- * entry behind the middle block's last launch; ctl == NULL or strength == 0: the plain table) */
-int ld_unet_profile_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, const ld_control* ctl, void* stream,
-                            double ms[6], double flops[6], int launches[6]);
-int ld_unet_profile_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream,
-                                 double ms[6], double flops[6], int launches[6]);
 
 /* ------------------------------------------------------------------ VAE decoder (Decoder ctor arguments, LD.py:6312-6323) */
 typedef struct {

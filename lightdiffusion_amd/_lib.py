@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LD_MI355X_LIB") or os.path.join(_HERE, "libld_mi355x.
 
 OK, ERR_ARG, ERR_SHAPE, ERR_HIP, ERR_STATE = 0, 1, 2, 3, 4
 F16, F32 = 0, 1
+FWD_EPS_ONLY, FWD_PAIR = 1, 2      # LD_FWD_*: the flags of ld_unet_forward / ld_controlnet_forward and their profiles
 
 
 class UNetConfig(C.Structure):
@@ -89,10 +90,8 @@ SIGNATURES = {
     "ld_unet_reserve": (_I, [_P, _I, _I, _I, _I]),
     "ld_unet_weight_bytes": (_Z, [_P]),
     "ld_unet_set_context": (_I, [_P, _P, _I, _I, _I, _P]),
-    "ld_unet_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "ld_unet_forward_pair": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
-    "ld_unet_profile_pair": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
-    "ld_unet_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
+    "ld_unet_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Control), _P]),
+    "ld_unet_profile": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Control), _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_unet_profile_kernels": (_I, [_P, C.c_char_p, _Z]),
     "ld_unet_patch_param": (_I, [_P, C.c_char_p, C.POINTER(LoraTerm), _I, _P]),
     "ld_unet_unpatch": (_I, [_P, C.c_char_p, _P]),
@@ -101,20 +100,14 @@ SIGNATURES = {
     "ld_unet_patch_bytes": (_Z, [_P]),
     "ld_controlnet_create": (_I, [C.POINTER(UNetConfig), _I, C.POINTER(_P)]),
     "ld_controlnet_set_hint": (_I, [_P, _P, _I, _I, _I, _P]),
-    "ld_controlnet_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ld_controlnet_forward_pair": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ld_controlnet_residual_count": (_I, [_P]),
     "ld_controlnet_residual_batch": (_I, [_P]),
     "ld_controlnet_residual": (_I, [_P, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ld_controlnet_read_residual": (_I, [_P, _I, _P, _P]),
     "ld_controlnet_read_hint": (_I, [_P, _P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _P]),
-    "ld_controlnet_profile": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "ld_controlnet_profile_pair": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ld_controlnet_profile": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ld_controlnet_fill_control": (_I, [_P, _I, _F, C.POINTER(Control)]),
-    "ld_unet_forward_control": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(Control), _P]),
-    "ld_unet_forward_pair_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P]),
-    "ld_unet_profile_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
-    "ld_unet_profile_pair_control": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(Control), _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_I)]),
     "ld_vae_create": (_I, [C.POINTER(VAEConfig), C.POINTER(_P)]),
     "ld_vae_decode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ld_vae_encode": (_I, [_P, _P, _P, _I, _I, _I, _P]),
@@ -227,7 +220,8 @@ def lib() -> C.CDLL:
                 if not os.environ.get("LD_MI355X_LIB"):
                     raise AttributeError(f"{LIB_PATH} does not export {name}: header and library out of sync — rebuild it")
                 # an older commit's library named for a same-box comparison (tools/build_ref_lib.sh) has fewer entry points: a call of a
-                # missing one fails with a clear message instead of an AttributeError deep inside ctypes
+                # missing one fails with a clear message instead of an AttributeError deep inside ctypes.  (Not older than the flag form of
+                # ld_unet_forward / ld_controlnet_forward: a symbol that is there is called with the signature above.)
                 missing.append(name)
                 setattr(l, name, _missing_symbol(name))
                 continue

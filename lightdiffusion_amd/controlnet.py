@@ -22,8 +22,9 @@ from typing import Optional
 import torch
 
 from . import weights as W
-from ._lib import ERR_SHAPE, F16, F32, Control, LDError, UNetConfig, check, lib
-from ._model import ResidentModel, WeightSource, _stream
+from ._lib import ERR_SHAPE, FWD_PAIR, Control, LDError, check, lib
+from ._model import WeightSource, _stream
+from .unet import UNetHandle
 
 
 def common_upscale(samples: torch.Tensor, width: int, height: int, upscale_method: str = "nearest-exact", crop: str = "center") -> torch.Tensor:
@@ -43,27 +44,17 @@ def common_upscale(samples: torch.Tensor, width: int, height: int, upscale_metho
     return torch.nn.functional.interpolate(samples, size=(height, width), mode=upscale_method)
 
 
-class MI355XControlNet(ResidentModel):
+class MI355XControlNet(UNetHandle):
     """The control branch of an SD1.x ControlNet resident on one MI355X.  `cfg`: the UNet config it was built on."""
 
-    family, key_prefixes, reserve_rank = "unet", ("", "control_model."), 4
+    key_prefixes = ("", "control_model.")
 
     def __init__(self, cfg: dict, weights: WeightSource, hint_channels: int = 3, device="cuda:0", max_batch: int = 2, max_hw=(64, 64),
                  max_tokens: int = 77):
         self.cfg = dict(cfg)
         self.hint_channels = int(hint_channels)
         self.device = torch.device(device)
-        c = UNetConfig()
-        c.in_channels, c.out_channels, c.model_channels = cfg["in_channels"], cfg["out_channels"], cfg["model_channels"]
-        c.num_levels = len(cfg["channel_mult"])
-        for i, v in enumerate(cfg["channel_mult"]):
-            c.channel_mult[i] = v
-        for i, v in enumerate(cfg["num_res_blocks"]):
-            c.num_res_blocks[i] = v
-        for i, v in enumerate(cfg["transformer_depth"]):
-            c.transformer_depth[i] = v
-        c.transformer_depth_middle = cfg["transformer_depth_middle"]
-        c.context_dim, c.num_heads = cfg["context_dim"], cfg["num_heads"]
+        c = self._config(cfg)
         self._ctx_token = None
         self.ctx_shape = None
         self.hint_shape = None           # (hb, h, w) of the resident encoded hint, latent units
@@ -78,45 +69,9 @@ class MI355XControlNet(ResidentModel):
         self._ctx_token = self.ctx_shape = self.hint_shape = None
 
     @property
-    def weight_bytes(self) -> int:
-        return lib().ld_unet_weight_bytes(self._h)
-
-    @property
     def residual_count(self) -> int:
         """residuals of a forward without the middle one: one per input block"""
         return lib().ld_controlnet_residual_count(self._h)
-
-    def read_param(self, name: str) -> torch.Tensor:
-        shapes = self.param_shapes()
-        if name not in shapes:
-            raise KeyError(name)
-        out = torch.empty(shapes[name], dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            check(lib().ld_unet_read_param(self._h, name.encode(), out.data_ptr(), _stream()), f"ld_unet_read_param({name})")
-        return out
-
-    def set_context(self, ctx: torch.Tensor) -> None:
-        """ctx [N, T, context_dim], in the batch order of the forwards that follow ([uncond.., cond..] under CFG)."""
-        ctx = ctx.to(self.device)
-        if ctx.dtype not in (torch.float16, torch.float32):
-            ctx = ctx.float()
-        ctx = ctx.contiguous()
-        _, mh, mw, _ = self._reserved
-        self._ensure(ctx.shape[0], mh, mw, ctx.shape[1])
-        with torch.cuda.device(self.device):
-            check(lib().ld_unet_set_context(self._h, ctx.data_ptr(), F32 if ctx.dtype == torch.float32 else F16, ctx.shape[0], ctx.shape[1],
-                                            _stream()), "ld_unet_set_context")
-        self._ctx_token = None
-        self.ctx_shape = (ctx.shape[0], ctx.shape[1])
-
-    def sync_context(self, ctx: torch.Tensor, n: int, h: int, w: int, token) -> None:
-        """The context of a run, by the sampling stack's per-run token (sampling.sampling_function): projected once per run.  Call it before
-        `set_hint`: growing the workspace drops the hint."""
-        self._ensure(n, h, w, ctx.shape[1])
-        if token is not None and token == self._ctx_token and self.ctx_shape == (ctx.shape[0], ctx.shape[1]):
-            return
-        self.set_context(ctx)
-        self._ctx_token = token
 
     def set_hint(self, image_nchw: torch.Tensor) -> None:
         """image_nchw [hb, hint_channels, 8 h, 8 w] in [0, 1]: encoded once (eight launches), resident until the workspace moves."""
@@ -131,40 +86,34 @@ class MI355XControlNet(ResidentModel):
         self.hint_shape = (hb, H // 8, W // 8)
         self.hint_epoch += 1
 
-    def _check(self, n, h, w, what):
+    def _run(self, x: torch.Tensor, sigma: torch.Tensor, *, pair: bool, profile: bool = False) -> None:
+        """`ld_controlnet_forward` / `ld_controlnet_profile` behind the checks every public form shares: x [B,4,h,w] fp32, sigma [B] fp32 on the
+        device, against the resident hint and the resident N-row context, N = 2B for a `pair`, else B.  The residuals stay in the handle."""
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.is_contiguous()
+        b, _, h, w = x.shape
+        n = 2 * b if pair else b
+        entry = "ld_controlnet_profile" if profile else "ld_controlnet_forward"
         mn, mh, mw, _ = self._reserved
         if n > mn or h > mh or w > mw:
-            raise LDError(ERR_SHAPE, f"{what}: input {n}x{h}x{w} exceeds the reserved plan {mn}x{mh}x{mw}")
+            raise LDError(ERR_SHAPE, f"{entry}: input {n}x{h}x{w} exceeds the reserved plan {mn}x{mh}x{mw}")
+        with torch.cuda.device(self.device):
+            check(getattr(lib(), entry)(self._h, x.data_ptr(), sigma.data_ptr(), b, h, w, FWD_PAIR if pair else 0, _stream()), entry)
 
     def forward(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
         """x [N,4,h,w] fp32, sigma [N] fp32 on the device, against the resident N-row context and hint: the residuals stay in the handle."""
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.is_contiguous()
-        n, _, h, w = x.shape
-        self._check(n, h, w, "ld_controlnet_forward")
-        with torch.cuda.device(self.device):
-            check(lib().ld_controlnet_forward(self._h, x.data_ptr(), sigma.data_ptr(), n, h, w, _stream()), "ld_controlnet_forward")
+        self._run(x, sigma, pair=False)
 
     def forward_pair(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
         """The CFG pair of one step: x [B,4,h,w], sigma [B] against the 2B-row context: the residuals of `forward` on cat([x, x])."""
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and sigma.is_cuda and sigma.dtype == torch.float32 and sigma.is_contiguous()
-        b, _, h, w = x.shape
-        self._check(2 * b, h, w, "ld_controlnet_forward_pair")
-        with torch.cuda.device(self.device):
-            check(lib().ld_controlnet_forward_pair(self._h, x.data_ptr(), sigma.data_ptr(), b, h, w, _stream()), "ld_controlnet_forward_pair")
+        self._run(x, sigma, pair=True)
 
     def profile(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
         """`forward` with HIP events around every launch: `profile_launches()` is then the control branch's launch table."""
-        n, _, h, w = x.shape
-        self._check(n, h, w, "ld_controlnet_profile")
-        with torch.cuda.device(self.device):
-            check(lib().ld_controlnet_profile(self._h, x.data_ptr(), sigma.data_ptr(), n, h, w, _stream()), "ld_controlnet_profile")
+        self._run(x, sigma, pair=False, profile=True)
 
     def profile_pair(self, x: torch.Tensor, sigma: torch.Tensor) -> None:
         """`profile` of `forward_pair`: x [B,..], sigma [B]."""
-        b, _, h, w = x.shape
-        self._check(2 * b, h, w, "ld_controlnet_profile_pair")
-        with torch.cuda.device(self.device):
-            check(lib().ld_controlnet_profile_pair(self._h, x.data_ptr(), sigma.data_ptr(), b, h, w, _stream()), "ld_controlnet_profile_pair")
+        self._run(x, sigma, pair=True, profile=True)
 
     def hint(self) -> torch.Tensor:
         """A copy of the resident encoded hint, fp16 [hb, h, w, model_channels]."""

@@ -45,6 +45,9 @@ struct Feat {
     GnStats stats;         // GroupNorm partial statistics of this tensor, where its producer wrote them
 };
 
+// every piece of the resident layouts (derived weight copies, the hint encoder's buffers) takes a multiple of 256 bytes
+constexpr size_t pad256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
 }  // namespace
 
 struct ld_unet : Model {
@@ -75,10 +78,16 @@ struct ld_unet : Model {
     void want_w8(int slot, int N, int Cin) {
         if (!conv8_weight_eligible(N, Cin)) return;
         w8_list.push_back({slot, N, Cin, w8_bytes});
-        w8_bytes += (conv8_weight_bytes(N, Cin) + 255) / 256 * 256;
+        w8_bytes += pad256(conv8_weight_bytes(N, Cin));
     }
     char* fold_base = nullptr;     // LN-folded copies of the LN-consuming projections (see StW)
     size_t fold_bytes = 0;
+    // the next piece of the fold buffer: its byte offset into fold_base.  The order of the takes IS the resident layout.
+    size_t take_fold(size_t bytes) {
+        const size_t off = fold_bytes;
+        fold_bytes += pad256(bytes);
+        return off;
+    }
     bool fold_dirty = true;        // set by every ld_unet_load_param / patch / unpatch; cleared when the fold kernels have run
     // LoRA patches (ld_unet_patch_param): per patched slot a device snapshot of its resident bytes as they were before the first patch — a
     // further resident copy, held only while the slot is patched.  Every merge reads the snapshot, ld_unet_unpatch copies it back.
@@ -134,11 +143,8 @@ int add_res(ld_unet* u, const std::string& p, int cin, int cout) {
     if (cin != cout) {
         r.sk_w = t.add(p + ".skip_connection.weight", PK_MAT, {cout, cin, 1, 1});
         r.sk_b = t.add(p + ".skip_connection.bias", PK_VEC, {cout});
-        size_t& fb = u->fold_bytes;
-        r.f_c2_w = fb;
-        fb += ((size_t)cout * (9 * cout + cin) * sizeof(half_t) + 255) / 256 * 256;
-        r.f_c2_b = fb;
-        fb += ((size_t)cout * sizeof(half_t) + 255) / 256 * 256;
+        r.f_c2_w = u->take_fold((size_t)cout * (9 * cout + cin) * sizeof(half_t));
+        r.f_c2_b = u->take_fold((size_t)cout * sizeof(half_t));
     }
     r.emb_off = u->emb_total;
     u->emb_total += cout;
@@ -181,24 +187,18 @@ int add_st(ld_unet* u, const std::string& p, int c) {
     s.pout_w = t.add(p + ".proj_out.weight", PK_MAT, {c, c, 1, 1});
     s.pout_b = t.add(p + ".proj_out.bias", PK_VEC, {c});
     {   // LN-fold buffer layout (256-byte aligned pieces)
-        size_t& fb = u->fold_bytes;
-        auto take = [&](size_t bytes) {
-            const size_t o = fb;
-            fb += (bytes + 255) / 256 * 256;
-            return o;
-        };
         const size_t C = (size_t)c;
-        s.f_qk_w = take(3 * C * C * sizeof(half_t));   // [Wq ; Wk ; Wv] of attn1
-        s.f_q2_w = take(C * C * sizeof(half_t));
-        s.f_ff1_w = take(8 * C * C * sizeof(half_t));
-        s.f_qk_b = take(3 * C * sizeof(half_t));
-        s.f_q2_b = take(C * sizeof(half_t));
-        s.f_ff1_b = take(8 * C * sizeof(half_t));
-        s.f_qk_s = take(3 * C * sizeof(float));
-        s.f_q2_s = take(C * sizeof(float));
-        s.f_ff1_s = take(8 * C * sizeof(float));
-        s.f_mo_w = take(5 * C * C * sizeof(half_t));
-        s.f_mo_b = take(C * sizeof(half_t));
+        s.f_qk_w = u->take_fold(3 * C * C * sizeof(half_t));   // [Wq ; Wk ; Wv] of attn1
+        s.f_q2_w = u->take_fold(C * C * sizeof(half_t));
+        s.f_ff1_w = u->take_fold(8 * C * C * sizeof(half_t));
+        s.f_qk_b = u->take_fold(3 * C * sizeof(half_t));
+        s.f_q2_b = u->take_fold(C * sizeof(half_t));
+        s.f_ff1_b = u->take_fold(8 * C * sizeof(half_t));
+        s.f_qk_s = u->take_fold(3 * C * sizeof(float));
+        s.f_q2_s = u->take_fold(C * sizeof(float));
+        s.f_ff1_s = u->take_fold(8 * C * sizeof(float));
+        s.f_mo_w = u->take_fold(5 * C * C * sizeof(half_t));
+        s.f_mo_b = u->take_fold(C * sizeof(half_t));
     }
     u->st.push_back(s);
     return (int)u->st.size() - 1;
@@ -291,8 +291,7 @@ int build(ld_unet* u) {
             if (lvl && i == c.num_res_blocks[lvl]) {
                 L.push_back({L_UP, add_conv(u, S("output_blocks.%d.%d.conv", idx, j), ch, ch)});
                 u->want_w8(u->convs.back().w, ch, ch);
-                u->convs.back().f_up = (long long)u->fold_bytes;
-                u->fold_bytes += (16 * (size_t)ch * ch * sizeof(half_t) + 255) / 256 * 256;
+                u->convs.back().f_up = (long long)u->take_fold(16 * (size_t)ch * ch * sizeof(half_t));
             }
             u->out_blocks.push_back(L);
             ++idx;
@@ -315,17 +314,36 @@ struct Run {
     ld_unet* u;
     Exec ex;
     int n;                   // samples the kernels run on
-    int n_alloc = 0;         // samples every tensor is SIZED for (= n, except in front of the first cross-attention of a CFG pair)
-    bool pair_pending = false;   // CFG pair (ld_unet_forward_pair): the layers in front of the first cross-attention see the same input in the uncond and
+    int n_alloc;             // samples every tensor is SIZED for (= n, except in front of the first cross-attention of a CFG pair)
+    bool pair_pending = false;   // CFG pair (LD_FWD_PAIR): the layers in front of the first cross-attention see the same input in the uncond and
                                  // the cond half of the batch, so they run ONCE on n = n_alloc / 2 samples and their results are copied into the second half
     const half_t* emb_all;   // [n_alloc][emb_total]
+    Run(ld_unet* u_, int n_) : u(u_), n(n_), n_alloc(n_) {}
     half_t* P(int slot) const { return u->pt.ptr(slot); }
-    int na() const { return n_alloc > 0 ? n_alloc : n; }
-    // first half of a [2 * half_bytes] tensor -> its second half (a memcpy node of the step's hipGraph; layouts other than SD1.5's, whose hand-over is one dup_halves launch)
-    void dup(void* base, size_t half_bytes) {
-        ex.launch(KC_MISC, 0.0, "dup", (long long)half_bytes, 0, 0, 1, "hipMemcpyAsync(pair)", [&] {
-            return hipMemcpyAsync(static_cast<char*>(base) + half_bytes, base, half_bytes, hipMemcpyDeviceToDevice, ex.stream) == hipSuccess ? LD_OK : LD_ERR_HIP;
-        });
+    // The two ends of a CFG pair's shared prefix, and the only writers of n and pair_pending.  begin_pair: the kernels run on the first half of the
+    // batch.  hand_over: the first halves (half_bytes each) of the tensors that are read again become their second halves too, and the kernels run on
+    // all n_alloc samples.  SD1.5's hand-over, inside its first transformer, copies three tensors in one dup_halves launch; a layout whose shared
+    // prefix ends elsewhere copies one, as a memcpy node of the step's hipGraph; with nothing left to share nothing is launched.
+    void begin_pair() {
+        n = n_alloc / 2;
+        pair_pending = true;
+    }
+    void hand_over(std::initializer_list<const half_t*> firsts = {}, size_t half_bytes = 0) {
+        if (firsts.size() == 1) {
+            char* base = reinterpret_cast<char*>(const_cast<half_t*>(*firsts.begin()));
+            ex.launch(KC_MISC, 0.0, "dup", (long long)half_bytes, 0, 0, 1, "hipMemcpyAsync(pair)", [&] {
+                return hipMemcpyAsync(base + half_bytes, base, half_bytes, hipMemcpyDeviceToDevice, ex.stream) == hipSuccess ? LD_OK : LD_ERR_HIP;
+            });
+        } else if (firsts.size() > 1) {
+            DupArgs da;
+            for (const half_t* t : firsts) {
+                da.base[da.count] = reinterpret_cast<char*>(const_cast<half_t*>(t));
+                da.bytes[da.count++] = half_bytes;
+            }
+            ex.launch(KC_MISC, 0.0, "dup3", (long long)half_bytes, 0, 0, 1, "dup_halves_kernel", [&] { return dup_halves_launch(da, ex.stream); });
+        }
+        n = n_alloc;
+        pair_pending = false;
     }
 
     // a convolution of this run's n images on resident weights, with the row-resident kernel's copy of them where there is one
@@ -355,9 +373,9 @@ struct Run {
     // in_stats: GroupNorm partial statistics of x1 from its producer (only usable when there is no second source)
     Feat resblock(const ResW& r, const half_t* x1, int C1, const half_t* x2, int C2, int H, int W, GnStats in_stats = {}) {
         Arena& ar = *ex.arena;
-        const size_t M = (size_t)na() * H * W;                   // rows the tensors are sized for (the kernels run on n * H * W)
+        const size_t M = (size_t)n_alloc * H * W;                   // rows the tensors are sized for (the kernels run on n * H * W)
         half_t* out = ar.halfs(M * r.cout);
-        float* gno = ex.gn_buffer(na(), H * W);                  // statistics of `out` (for the next GroupNorm)
+        float* gno = ex.gn_buffer(n_alloc, H * W);                  // statistics of `out` (for the next GroupNorm)
         if (C2 != 0) in_stats = {};
         const size_t mk = ar.mark();
         // in_layers: GroupNorm + SiLU + conv3x3 (+ the time-embedding row vector); out_layers: GroupNorm + SiLU + conv3x3 (+ skip).
@@ -384,7 +402,7 @@ struct Run {
             }
         }
         // the GroupNorm statistics of h1 (out_layers' norm) come from conv1's split-K second pass where it has one (gemm.h gn_part)
-        float* gnp = ex.gn_buffer(na(), H * W);
+        float* gnp = ex.gn_buffer(n_alloc, H * W);
         GemmParams c1 = conv(x1, C1, x2, C2, r.c1_w, r.c1_b, h1);
         c1.rowvec = emb_all + r.emb_off; c1.ldrv = u->emb_total;
         want_gn_partials(c1, n, H * W, gnp);
@@ -407,9 +425,9 @@ struct Run {
         Arena& ar = *ex.arena;
         const int C = s.c, L = H * W, heads = u->cfg.num_heads, d = C / heads;
         int M = n * L;                                           // rows the kernels run on (doubles at the split of a CFG pair, below)
-        const size_t Ma = (size_t)na() * L;                      // rows the tensors are sized for
+        const size_t Ma = (size_t)n_alloc * L;                      // rows the tensors are sized for
         half_t* out = ar.halfs(Ma * C);
-        float* gno = ex.gn_buffer(na(), L);                      // statistics of `out` (for the next GroupNorm)
+        float* gno = ex.gn_buffer(n_alloc, L);                      // statistics of `out` (for the next GroupNorm)
         const size_t mk = ar.mark();
         half_t* g = ar.halfs(Ma * C);
         ex.groupnorm(x, C, nullptr, 0, n, L, P(s.gn_g), P(s.gn_b), 1e-6f, 0, g, in_stats);
@@ -455,20 +473,12 @@ struct Run {
         // conditioning).  Then the residual stream t, q2 and the block's input (its residual at the end) are copied into the second half and
         // everything else runs on all n_alloc samples (the statistics of the first half are not needed again: the out-projection of attn2
         // rewrites them for all rows).
-        const bool split_here = pair_pending;
         producer(ao, s.o1_w, s.o1_b, t);
         // ---- cross attention against the hoisted context K / V^T
         half_t* q2 = qkv;   // reuse
         consumer(s.f_q2_w, s.f_q2_b, s.f_q2_s, C, q2);
-        if (split_here) {
-            const size_t hb = (size_t)M * C * sizeof(half_t);
-            DupArgs da;
-            da.count = 3;
-            da.base[0] = reinterpret_cast<char*>(t); da.base[1] = reinterpret_cast<char*>(q2); da.base[2] = reinterpret_cast<char*>(const_cast<half_t*>(x));
-            da.bytes[0] = da.bytes[1] = da.bytes[2] = hb;
-            ex.launch(KC_MISC, 0.0, "dup3", (long long)hb, 0, 0, 1, "dup_halves_kernel", [&] { return dup_halves_launch(da, ex.stream); });
-            pair_pending = false;
-            n = n_alloc;
+        if (pair_pending) {
+            hand_over({t, q2, x}, (size_t)M * C * sizeof(half_t));
             M = n * L;
         }
         {
@@ -549,9 +559,6 @@ int refresh_derived(ld_unet* u, hipStream_t stream) {
     return LD_OK;
 }
 
-// `pair`: classifier-free-guidance pair (ld_unet_forward_pair).  x / sigma hold n / 2 samples; the batch is [uncond x n/2 ; cond x n/2] of the SAME latents
-// (what calc_cond_batch feeds the model: cat([x, x]), LD.py:2515-2547); the resident context has n rows.  The layers in front of the first
-// cross-attention run once on n / 2 samples (Run::pair_pending), everything else on n.  out: n samples.
 // (C, H, W) of the skip tensors of an h x w latent, one per input block, as the walk below produces them
 std::vector<ld_unet::ResShape> skip_shapes(const ld_unet* u, int h, int w) {
     std::vector<ld_unet::ResShape> s;
@@ -583,6 +590,9 @@ int check_control(const ld_unet* u, const ld_control* ctl, int n, int h, int w) 
     return LD_OK;
 }
 
+// `pair`: classifier-free-guidance pair (LD_FWD_PAIR).  x / sigma hold n / 2 samples; the batch is [uncond x n/2 ; cond x n/2] of the SAME latents
+// (what calc_cond_batch feeds the model: cat([x, x]), LD.py:2515-2547); the resident context has n rows.  The layers in front of the first
+// cross-attention run once on n / 2 samples (Run::pair_pending), everything else on n.  out: n samples.
 // `ctl` (a UNet, may be null): ControlNet residuals added to every skip tensor and to the middle block's output, once the encoder is done with them.
 int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, hipStream_t stream,
                 size_t* dry_peak = nullptr, bool pair = false, const ld_control* ctl = nullptr) {
@@ -591,10 +601,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         if (st != LD_OK) return st;
     }
     if (pair && (n & 1)) return LD_ERR_SHAPE;
-    Run R;
-    R.u = u;
-    R.n = n;
-    R.n_alloc = n;
+    Run R(u, n);
     Arena plan;
     Exec& ex = R.ex = u->begin(dry, stream, plan);
     Arena& ar = *ex.arena;
@@ -602,7 +609,7 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     const int mc = c.model_channels, ted = u->ted;
     const int in_mod = pair ? n / 2 : 0;   // CFG pair: x / sigma hold n / 2 samples; the kernels that read them per sample index n % in_mod
     // (the control branch shares no prefix: its pair form reads x / sigma per sample % (n / 2), duplicates conv_in's output and runs all n samples)
-    if (pair && !u->control) R.pair_pending = true;
+    if (pair && !u->control) R.begin_pair();
     // one launch of the control add over `count` segments of n samples each
     auto control_add = [&](const ControlSegment* segs, int count, int r_n, float strength) {
         long long bytes = 0;
@@ -639,11 +646,8 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
                 case L_DOWN: {
                     const ConvW& cw = u->convs[L.idx];
                     const int Ho = (f.H - 1) / 2 + 1, Wo = (f.W - 1) / 2 + 1;
-                    if (R.pair_pending) {                         // (not in front of the first transformer of any supported layout; be safe)
-                        R.dup(const_cast<half_t*>(f.p), (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
-                        R.pair_pending = false;
-                        R.n = n;
-                    }
+                    if (R.pair_pending)                           // (not in front of the first transformer of any supported layout; be safe)
+                        R.hand_over({f.p}, (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
                     half_t* o = ar.halfs((size_t)n * Ho * Wo * cw.cout);
                     float* gno = ex.gn_buffer(n, Ho * Wo);
                     f = {o, cw.cout, Ho, Wo, R.conv3(f.p, f.C, nullptr, 0, f.H, f.W, f.H, f.W, 2, cw.w, cw.b, cw.cout, o, 3, gno)};
@@ -671,7 +675,6 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
     {   // input_blocks[0]: conv_in fused with EPS.calculate_input and the fp32 NCHW -> fp16 NHWC layout change
         const ConvW& cw = u->convs[u->in_blocks[0][0].idx];
         half_t* o = ar.halfs((size_t)n * h * w * mc);
-        if (R.pair_pending) R.n = n / 2;                          // the shared prefix runs on the first half (see Run::pair_pending)
         SmallConvInArgs a;
         a.x = x; a.scale_sigma = sigma; a.w = u->pt.ptr(cw.w); a.b = u->pt.ptr(cw.b); a.y = o;
         a.N = R.n; a.Cin = c.in_channels; a.H = h; a.W = w; a.Cout = mc;
@@ -693,17 +696,12 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         f = run_layers(u->in_blocks[b], f, nullptr, 0, 0, 0);
         if (u->control) zero_conv(b, f);
         if (R.pair_pending && b == 1) {                          // no transformer in the first block: its output is the last shared tensor
-            R.dup(const_cast<half_t*>(f.p), (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
-            R.pair_pending = false;
-            R.n = n;
+            R.hand_over({f.p}, (size_t)R.n * f.H * f.W * f.C * sizeof(half_t));
             f.stats = {};                                        // (its statistics cover the first half of the batch only)
         }
         hs.push_back(f);
     }
-    if (R.pair_pending) {                                        // (a UNet without input blocks: nothing left to share)
-        R.pair_pending = false;
-        R.n = n;
-    }
+    if (R.pair_pending) R.hand_over();                           // (a UNet without input blocks: nothing left to share)
     f = run_layers(u->mid_block, f, nullptr, 0, 0, 0);
     if (u->control) {                                            // middle_block_out; a control branch ends here
         zero_conv(u->in_blocks.size(), f);
@@ -740,6 +738,30 @@ int run_forward(ld_unet* u, bool dry, const float* x, const float* sigma, float*
         ex.launch(KC_MISC, 2.0 * n * f.H * f.W * f.C * 9.0 * c.out_channels, "", 0, 0, 0, 0, "small_conv_out_kernel", [&] { return small_conv_out_launch(a, stream); });
     }
     return u->end(ex, dry_peak, true);
+}
+
+// The regions that stay resident behind the activations and the contractions' scratch, each for the reserved maximum and starting on a multiple
+// of 256 bytes: the padded context, every transformer's cross-attention K and V^T and, in control mode, the encoded hint and one residual buffer per
+// zero convolution.  Stores the pointers in the handle and returns the bytes taken.  ld_unet_reserve carves twice: an arena without a base gives the
+// byte count that sizes the workspace, the arena behind the scratch the addresses.
+size_t carve_resident(ld_unet* u, Arena& ar, int max_n, int max_h, int max_w) {
+    const size_t rows = (size_t)max_n * u->ctx_tpad;
+    u->ctx16 = ar.halfs(rows * u->cfg.context_dim);
+    for (size_t i = 0; i < u->st.size(); ++i) {
+        u->ctx_k[i] = ar.halfs(rows * u->st[i].c);
+        u->ctx_vt[i] = ar.halfs(rows * u->st[i].c);
+    }
+    u->hint = nullptr;
+    u->res_buf.clear();
+    if (u->control) {
+        std::vector<ld_unet::ResShape> rs = skip_shapes(u, max_h, max_w);
+        rs.push_back(rs.back());       // (middle_block_out: the middle block keeps the last skip's shape)
+        u->hint = ar.halfs((size_t)max_n * max_h * max_w * u->cfg.model_channels);
+        for (const auto& r : rs) u->res_buf.push_back(ar.halfs((size_t)max_n * r.H * r.W * r.C));
+        u->res_shape.assign(rs.size(), ld_unet::ResShape());
+    }
+    ar.alloc(0);                       // (the last region takes its padded size too)
+    return ar.off;
 }
 
 }  // namespace
@@ -928,56 +950,29 @@ int ld_unet_reserve(ld_unet* u, int max_n, int max_h, int max_w, int max_tok) {
     size_t peak = 0;
     int st = run_forward(u, true, nullptr, nullptr, nullptr, max_n, max_h, max_w, 0, nullptr, &peak);
     if (st != LD_OK) return st;
-    if (!(max_n & 1)) {   // the CFG-pair route (ld_unet_forward_pair) keeps the duplicated inputs in the arena as well
+    if (!(max_n & 1)) {   // the CFG-pair route (LD_FWD_PAIR) keeps the duplicated inputs in the arena as well
         size_t peak2 = 0;
         st = run_forward(u, true, nullptr, nullptr, nullptr, max_n, max_h, max_w, 0, nullptr, &peak2, true);
         if (st != LD_OK) return st;
         if (peak2 > peak) peak = peak2;
     }
-    const size_t tpad = (size_t)u->ctx_tpad;
-    size_t ctxb = ((size_t)max_n * tpad * u->cfg.context_dim * sizeof(half_t) + 255) / 256 * 256;
-    for (const StW& s : u->st) ctxb += 2 * (((size_t)max_n * tpad * s.c * sizeof(half_t) + 255) / 256 * 256);
-    // control mode: behind the context, the encoded hint and one residual buffer per zero convolution, each for the reserved maximum; the hint
-    // encoder's two ping-pong buffers (its widest layer: 16 channels at 8h x 8w) share the activations' arena — it never runs beside a forward
-    auto pad256 = [](size_t b) { return (b + 255) / 256 * 256; };
-    std::vector<ld_unet::ResShape> rs;
-    size_t ctlb = 0;
+    // control mode: the hint encoder's two ping-pong buffers (its widest layer: 16 channels at 8h x 8w) share the activations' arena — it never
+    // runs beside a forward
     if (u->control) {
-        rs = skip_shapes(u, max_h, max_w);
-        rs.push_back(rs.back());
-        ctlb = pad256((size_t)max_n * max_h * max_w * u->cfg.model_channels * sizeof(half_t));
-        for (const auto& r : rs) ctlb += pad256((size_t)max_n * r.H * r.W * r.C * sizeof(half_t));
         const size_t hint_ws = 2 * pad256((size_t)max_n * 64 * max_h * max_w * 16 * sizeof(half_t));
         if (hint_ws > peak) peak = hint_ws;
     }
-    u->hint = nullptr;
     u->hint_b = u->hint_h = u->hint_w = u->res_n = 0;
-    u->res_buf.clear();
     u->splitk_bytes = SPLITK_BYTES;
-    const size_t bytes = Model::padded(peak, SPLITK_BYTES + ctxb + ctlb), act = bytes - SPLITK_BYTES - ctxb - ctlb - 4096;
+    Arena sizes;                       // (no base: the regions' byte count)
+    const size_t resident = carve_resident(u, sizes, max_n, max_h, max_w);
+    const size_t bytes = Model::padded(peak, SPLITK_BYTES + resident), act = bytes - SPLITK_BYTES - resident - 4096;
     st = u->set_workspace(bytes, act);
     if (st != LD_OK) return st;
-    char* p = u->ws_base + act;   // behind the activations: the contractions' scratch, then the context and its projections
-    u->splitk_ws = reinterpret_cast<float*>(p);
-    p += u->splitk_bytes;
-    u->ctx16 = reinterpret_cast<half_t*>(p);
-    p += ((size_t)max_n * tpad * u->cfg.context_dim * sizeof(half_t) + 255) / 256 * 256;
-    for (size_t i = 0; i < u->st.size(); ++i) {
-        const size_t b = ((size_t)max_n * tpad * u->st[i].c * sizeof(half_t) + 255) / 256 * 256;
-        u->ctx_k[i] = reinterpret_cast<half_t*>(p);
-        p += b;
-        u->ctx_vt[i] = reinterpret_cast<half_t*>(p);
-        p += b;
-    }
-    if (u->control) {
-        u->hint = reinterpret_cast<half_t*>(p);
-        p += pad256((size_t)max_n * max_h * max_w * u->cfg.model_channels * sizeof(half_t));
-        for (const auto& r : rs) {
-            u->res_buf.push_back(reinterpret_cast<half_t*>(p));
-            p += pad256((size_t)max_n * r.H * r.W * r.C * sizeof(half_t));
-        }
-        u->res_shape.assign(rs.size(), ld_unet::ResShape());
-    }
+    u->splitk_ws = reinterpret_cast<float*>(u->ws_base + act);   // behind the activations: the contractions' scratch, then the resident regions
+    Arena behind;
+    behind.base = u->ws_base + act + u->splitk_bytes;
+    carve_resident(u, behind, max_n, max_h, max_w);
     if (getenv("LD_PROFILE_DUMP") != nullptr)   // (where the allocations landed: tools/alloc_probe.py)
         fprintf(stderr, "[ld_reserve] workspace %p (%zu MiB)  weights %p  folds %p  conv8 weights %p\n", (void*)u->ws_base, u->ws_bytes >> 20, (void*)u->pt.base,
                 (void*)u->fold_base, (void*)u->w8_base);
@@ -1013,13 +1008,27 @@ int ld_unet_set_context(ld_unet* u, const void* ctx, int dtype, int n, int token
     return LD_OK;
 }
 
-static int forward_checked(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream, bool pair,
-                           const ld_control* ctl = nullptr) {
+// What both forwards ask of their flags, on the host: LD_ERR_ARG for a bit that is not a flag, for eps of a pair (no kernel writes it) and for eps
+// of a control branch (it writes no output); LD_ERR_SHAPE for a pair of no samples.  *n: the samples x / sigma hold -> the batch that runs.
+static int check_flags(int flags, bool control, int* n) {
+    if ((flags & ~(LD_FWD_EPS_ONLY | LD_FWD_PAIR)) != 0 || flags == (LD_FWD_EPS_ONLY | LD_FWD_PAIR) || (control && (flags & LD_FWD_EPS_ONLY))) return LD_ERR_ARG;
+    if (flags & LD_FWD_PAIR) {
+        if (*n < 1) return LD_ERR_SHAPE;
+        *n *= 2;
+    }
+    return LD_OK;
+}
+
+static int forward_checked(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int flags, const ld_control* ctl, void* stream) {
+    int st = check_flags(flags, false, &n);
+    if (st != LD_OK) return st;
     if (u == nullptr || x == nullptr || sigma == nullptr || out == nullptr || u->control) return LD_ERR_ARG;
     if (ctl != nullptr && h >= 1 && w >= 1 && n >= 1) {
-        const int st = check_control(u, ctl, n, h, w);
+        st = check_control(u, ctl, n, h, w);
         if (st != LD_OK) return st;
     }
+    const bool pair = flags & LD_FWD_PAIR;
+    const int eps_only = flags & LD_FWD_EPS_ONLY;
     return abi_checked_run(*u, u->ctx_n != 0, n == u->ctx_n && n <= u->max_n && h >= 1 && w >= 1,
                            [&](size_t* peak) { return run_forward(u, true, nullptr, nullptr, nullptr, n, h, w, eps_only, nullptr, peak, pair); },
                            [&] { return run_forward(u, false, x, sigma, out, n, h, w, eps_only, (hipStream_t)stream, nullptr, pair, ctl); },
@@ -1027,21 +1036,12 @@ static int forward_checked(ld_unet* u, const float* x, const float* sigma, float
 }
 
 // ---------------------------------------------------------------------------------------------------- ControlNet
-int ld_unet_forward_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, const ld_control* ctl, void* stream) {
-    return forward_checked(u, x, sigma, out, n, h, w, eps_only, stream, false, ctl);
-}
-
-int ld_unet_forward_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream) {
-    if (nb < 1) return LD_ERR_SHAPE;
-    return forward_checked(u, x, sigma, out, 2 * nb, h, w, 0, stream, true, ctl);
-}
-
 int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, int W, void* stream_) {
     if (cn == nullptr || image_nchw == nullptr || !cn->control) return LD_ERR_ARG;
     if (cn->ws_base == nullptr || !cn->pt.all_loaded()) return LD_ERR_STATE;
     if (hb < 1 || hb > cn->max_n || H < 8 || W < 8 || H % 8 != 0 || W % 8 != 0 || H / 8 > cn->max_h || W / 8 > cn->max_w) return LD_ERR_SHAPE;
     hipStream_t stream = (hipStream_t)stream_;
-    const size_t half_ws = ((size_t)hb * H * W * 16 * sizeof(half_t) + 255) / 256 * 256;   // the widest layer's output
+    const size_t half_ws = pad256((size_t)hb * H * W * 16 * sizeof(half_t));   // the widest layer's output
     if (2 * half_ws > cn->arena.cap) return LD_ERR_SHAPE;
     half_t* buf[2] = {reinterpret_cast<half_t*>(cn->ws_base), reinterpret_cast<half_t*>(cn->ws_base + half_ws)};
     cn->hint_b = 0;
@@ -1069,9 +1069,12 @@ int ld_controlnet_set_hint(ld_unet* cn, const float* image_nchw, int hb, int H, 
     return LD_OK;
 }
 
-static int control_forward_checked(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream, bool pair) {
+static int control_forward_checked(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, int flags, void* stream) {
+    const int st = check_flags(flags, true, &n);
+    if (st != LD_OK) return st;
     if (cn == nullptr || x == nullptr || sigma == nullptr || !cn->control) return LD_ERR_ARG;
     if (cn->hint_b == 0) return LD_ERR_STATE;
+    const bool pair = flags & LD_FWD_PAIR;
     const bool shape_ok = n == cn->ctx_n && n <= cn->max_n && h >= 1 && w >= 1 && h <= cn->max_h && w <= cn->max_w && h == cn->hint_h && w == cn->hint_w &&
                           n % cn->hint_b == 0;
     return abi_checked_run(*cn, cn->ctx_n != 0, shape_ok,
@@ -1080,22 +1083,12 @@ static int control_forward_checked(ld_unet* cn, const float* x, const float* sig
                            &cn->planned, PlanKey{{n, h, w, (int)pair}});
 }
 
-int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream) {
-    return control_forward_checked(cn, x, sigma, n, h, w, stream, false);
+int ld_controlnet_forward(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, int flags, void* stream) {
+    return control_forward_checked(cn, x, sigma, n, h, w, flags, stream);
 }
 
-int ld_controlnet_forward_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream) {
-    if (nb < 1) return LD_ERR_SHAPE;
-    return control_forward_checked(cn, x, sigma, 2 * nb, h, w, stream, true);
-}
-
-int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, void* stream) {
-    return abi_profile(cn, stream, [&] { return control_forward_checked(cn, x, sigma, n, h, w, stream, false); });
-}
-
-int ld_controlnet_profile_pair(ld_unet* cn, const float* x, const float* sigma, int nb, int h, int w, void* stream) {
-    if (nb < 1) return LD_ERR_SHAPE;
-    return abi_profile(cn, stream, [&] { return control_forward_checked(cn, x, sigma, 2 * nb, h, w, stream, true); });
+int ld_controlnet_profile(ld_unet* cn, const float* x, const float* sigma, int n, int h, int w, int flags, void* stream) {
+    return abi_profile(cn, stream, [&] { return control_forward_checked(cn, x, sigma, n, h, w, flags, stream); });
 }
 
 int ld_controlnet_read_hint(const ld_unet* cn, void* dst_f16, int* hb, int* h, int* w, int* C, void* stream) {
@@ -1151,42 +1144,14 @@ int ld_controlnet_fill_control(const ld_unet* cn, int r_n, float strength, ld_co
     return LD_OK;
 }
 
-int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int eps_only, void* stream) {
-    return forward_checked(u, x, sigma, out, n, h, w, eps_only, stream, false);
+int ld_unet_forward(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int flags, const ld_control* ctl, void* stream) {
+    return forward_checked(u, x, sigma, out, n, h, w, flags, ctl, stream);
 }
 
-int ld_unet_forward_pair(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, void* stream) {
-    if (nb < 1) return LD_ERR_SHAPE;
-    return forward_checked(u, x, sigma, out, 2 * nb, h, w, 0, stream, true);
-}
-
-static int profile_any(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6], double flops[6],
-                       int launches[6], bool pair, const ld_control* ctl = nullptr);
-
-int ld_unet_profile(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6],
-                    double flops[6], int launches[6]) {
-    return profile_any(u, x, sigma, out, n, h, w, stream, ms, flops, launches, false);
-}
-
-int ld_unet_profile_pair(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, void* stream, double ms[6],
-                         double flops[6], int launches[6]) {
-    return profile_any(u, x, sigma, out, 2 * nb, h, w, stream, ms, flops, launches, true);
-}
-
-int ld_unet_profile_control(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, const ld_control* ctl, void* stream,
-                            double ms[6], double flops[6], int launches[6]) {
-    return profile_any(u, x, sigma, out, n, h, w, stream, ms, flops, launches, false, ctl);
-}
-
-int ld_unet_profile_pair_control(ld_unet* u, const float* x, const float* sigma, float* out, int nb, int h, int w, const ld_control* ctl, void* stream,
-                                 double ms[6], double flops[6], int launches[6]) {
-    return profile_any(u, x, sigma, out, 2 * nb, h, w, stream, ms, flops, launches, true, ctl);
-}
-
-static int profile_any(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, void* stream, double ms[6], double flops[6],
-                       int launches[6], bool pair, const ld_control* ctl) {
+int ld_unet_profile(ld_unet* u, const float* x, const float* sigma, float* out, int n, int h, int w, int flags, const ld_control* ctl, void* stream,
+                    double ms[6], double flops[6], int launches[6]) {
     if (u == nullptr || ms == nullptr || flops == nullptr || launches == nullptr) return LD_ERR_ARG;
-    const int st = abi_profile(u, stream, [&] { return forward_checked(u, x, sigma, out, n, h, w, 0, stream, pair, ctl); });
+    const int st = abi_profile(u, stream, [&] { return forward_checked(u, x, sigma, out, n, h, w, flags, ctl, stream); });
     if (st != LD_OK) return st;
     for (int i = 0; i < KC_COUNT; ++i) {
         ms[i] = u->timing.ms[i];

@@ -4,7 +4,7 @@ One sampler step of the reference = `sampling_function` (LD.py:2609-2626): cat([
 the order [uncond, cond] → uncond + (cond - uncond) * cfg.  Here the B-sample input, sigma and the 2B-sample output live in
 static device buffers, the ~345 kernel launches of the forward plus the guidance mix are captured once into a hipGraph and
 replayed per step (sigma is read from device memory, so one graph serves every step).  The forward is the library's CFG-pair
-entry (`ld_unet_forward_pair`): both halves of the batch are the SAME latents, so the layers in front of the first
+form (`ld_unet_forward` with `LD_FWD_PAIR`): both halves of the batch are the SAME latents, so the layers in front of the first
 cross-attention — conv_in, the first ResBlock, the first transformer's self-attention — are evaluated once.
 """
 from __future__ import annotations
@@ -88,12 +88,12 @@ class CFGDenoiser:
 
     def _body(self) -> None:
         from ._lib import check, lib
+        ctl = None
         if self.control is not None:
             cn, strength = self.control
             cn.forward_pair(self.x1, self.sigma1)
-            self.unet.forward_pair_control(self.x1, self.sigma1, cn.control(strength), out=self.den2)
-        else:
-            self.unet.forward_pair(self.x1, self.sigma1, out=self.den2)
+            ctl = cn.control(strength)
+        self.unet.forward_pair(self.x1, self.sigma1, out=self.den2, control=ctl)
         check(lib().ld_op_cfg_combine(self.den2.data_ptr(), self.den.data_ptr(), self.cfg_scale, self.den.numel(),
                                       torch.cuda.current_stream().cuda_stream), "ld_op_cfg_combine")
 
@@ -119,7 +119,7 @@ class HookRunner:
     """The UNet forward behind the reference's `model_function_wrapper` seam (LD.py:2558-2567) as a replayed hipGraph on static
     buffers — what `enable_cuda_graph` does for the reference's own plugin on that seam (StableFastPatch, LD.py:9896-9933).
 
-    One runner per (N, h, w): `pair` replays the CFG-pair forward (`ld_unet_forward_pair`: the layers in front of the first
+    One runner per (N, h, w): `pair` replays the CFG-pair forward (`LD_FWD_PAIR`: the layers in front of the first
     cross-attention once for both halves of calc_cond_batch's cat([x_in, x_in]), LD.py:2515-2547), `plain` the forward on all N rows.
     Which one is valid for a call is decided ON THE DEVICE (`ld_op_hook_check`, flags in pinned host memory) and read after the
     speculative replay has been queued, so the GPU never waits for the host."""

@@ -57,7 +57,7 @@ def test_config3_through_the_wrapper_hook_at_batch16(sd15_unet):
     """The reference's own seam at config #3's size (UNet batch 16, 64 x 64): `MI355XUNet.__call__` replays captured hipGraphs.  Sixteen
     different samples under cond_or_uncond == [1, 0]: the speculative CFG-pair replay is found wrong ON THE DEVICE (halves differ) and the
     call itself replays the plain graph — every row must reproduce the reference golden of its sample.  Then the shape calc_cond_batch really
-    sends (one latent batch twice): the pair graph, bit for bit the eager `ld_unet_forward_pair`, and its cond rows against the golden."""
+    sends (one latent batch twice): the pair graph, bit for bit the eager `ld_unet_forward` with `LD_FWD_PAIR`, and its cond rows against the golden."""
     g = load_golden("unet_sd15_64x64")
     order = [0, 1, 1, 0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 1, 1, 0]
     x, s, ctx = _stack(g, order)
@@ -102,7 +102,7 @@ def test_config5_unet_128x128(sd15_unet, n):
 
 
 def test_config5_forward_pair_128x128_batch4(sd15_unet):
-    """The route bench.py times for config #5 (LD.py:10585-10603 through calc_cond_batch, LD.py:2515-2547): ld_unet_forward_pair at nb = 4 on 128x128
+    """The route bench.py times for config #5 (LD.py:10585-10603 through calc_cond_batch, LD.py:2515-2547): ld_unet_forward with LD_FWD_PAIR at nb = 4 on 128x128
     latents — conv_in, the first ResBlock and the first transformer's self-attention (L = 16384) evaluated once on 4 samples, the rest on 8.
     The golden's two samples carry different x, so pair i runs x_{o_i} twice against contexts [ctx_{1-o_i}, ctx_{o_i}]: the cond half must be the
     reference's denoised row o_i; with the golden's own context in BOTH halves the uncond half must be it too."""

@@ -1,4 +1,4 @@
-"""ControlNet on the device (csrc/unet.hip in control mode, ld_unet_forward_control) against chains of operator calls: the control branch
+"""ControlNet on the device (csrc/unet.hip in control mode, ld_unet_forward with an ld_control) against chains of operator calls: the control branch
 against tests/controlnet_chain.py's ControlChain, the controlled UNet against tests/unet_chain.py's UNetChain.forward(control=...), per launch
 and per bit; every stage of both chains element-wise against fp64.  Tiny configuration, and SD1.5's width at 16 x 16 (all 13 residuals at
 C = 320 / 640 / 1280, from 16 x 16 down to 2 x 2).  The full-size cases: tests/test_controlnet_chain_full_gpu.py.
@@ -6,8 +6,8 @@ C = 320 / 640 / 1280, from 16 x 16 down to 2 x 2).  The full-size cases: tests/t
 A case is (config, n or nb, (h, w), tokens, mode, hint batch, strength); mode "pair_rn2": the branch runs as `forward` on the nb latents
 against the first nb rows of the context, and its residuals join the 2 nb samples of the UNet's pair with r_n = nb (sample s reads s % nb).
 
-B1  same launches: the control chain's launch list equals the branch's launch table (ld_controlnet_profile / _pair), the controlled UNet
-    chain's equals ld_unet_profile_control / _pair_control's, entry by entry; and the controlled table IS the plain table with exactly one
+B1  same launches: the control chain's launch list equals the branch's launch table (ld_controlnet_profile), the controlled UNet
+    chain's equals that of ld_unet_profile with the ld_control, entry by entry; and the controlled table IS the plain table with exactly one
     control_add_kernel entry behind the middle block's last launch (asserted on the tables).  The hint encoder has no table of its own
     (ld_controlnet_set_hint is no forward): its eight launches are held as a count — last_launches == 8 behind set_hint — against the
     chain's eight hint_conv_kernel launches.
@@ -147,9 +147,9 @@ class Side:
         self.unet.set_context(ctx)
         ctl = self.cnet.control(strength)
         if is_pair(mode):
-            out = self.unet.forward_pair_control(x, sigma, ctl)
+            out = self.unet.forward_pair(x, sigma, control=ctl)
         else:
-            out = self.unet.forward_control(x, sigma, ctl, eps_only=mode == "eps")
+            out = self.unet.forward(x, sigma, control=ctl, eps_only=mode == "eps")
         return (enc, *res, out)
 
     def tables(self, name):
@@ -160,7 +160,7 @@ class Side:
         rows = {"branch": self.cnet.profile_launches()}
         self.unet.set_context(ctx)
         ctl = self.cnet.control(strength)
-        (self.unet.profile_pair_control if is_pair(mode) else self.unet.profile_control)(x, sigma, ctl)
+        (self.unet.profile_pair if is_pair(mode) else self.unet.profile)(x, sigma, control=ctl)
         rows["controlled_unet"] = self.unet.profile_launches()
         (self.unet.profile_pair if is_pair(mode) else self.unet.profile)(x, sigma)
         rows["plain_unet"] = self.unet.profile_launches()

@@ -83,13 +83,13 @@ def test_residuals_and_controlled_output_against_the_reference(unet, cnet, maste
     assert max(errs) < UNET_TOL, errs                              # each residual on its own
     unet.set_context(ctx)
     for strength in (1.0, 0.6):
-        out = unet.forward_control(x.to(DEV), s.to(DEV), cnet.control(strength)).cpu()
+        out = unet.forward(x.to(DEV), s.to(DEV), control=cnet.control(strength)).cpu()
         ref = R.apply_model(sd, CFG, ms, x, s, ctx, cn_sd, hint, strength)
         print("controlled output rel-L2 at strength", strength, "%.2e" % rel_l2(out, ref))
         assert rel_l2(out, ref) < UNET_TOL, (strength, rel_l2(out, ref))
     plain = unet.forward(x.to(DEV), s.to(DEV)).cpu()
     assert rel_l2(out, plain) > 10 * UNET_TOL                      # and control really moved it
-    eps = unet.forward_control(x.to(DEV), s.to(DEV), cnet.control(1.0), eps_only=True).cpu()
+    eps = unet.forward(x.to(DEV), s.to(DEV), control=cnet.control(1.0), eps_only=True).cpu()
     assert rel_l2(eps, R.apply_model(sd, CFG, ms, x, s, ctx, cn_sd, hint, 1.0, eps_only=True)) < UNET_TOL
 
 
@@ -103,13 +103,13 @@ def test_strength_zero_and_a_null_control_are_the_plain_forwards_bits(unet, cnet
     cnet.forward(x2, s2)
     unet.set_context(ctx)
     plain, n_plain = unet.forward(x2, s2).clone(), unet.last_launches
-    assert same_bits(unet.forward_control(x2, s2, cnet.control(0.0)), plain) and unet.last_launches == n_plain
-    assert same_bits(unet.forward_control(x2, s2, None), plain) and unet.last_launches == n_plain
-    assert not same_bits(unet.forward_control(x2, s2, cnet.control(1.0)), plain) and unet.last_launches == n_plain + 1      # ONE launch more
+    assert same_bits(unet.forward(x2, s2, control=cnet.control(0.0)), plain) and unet.last_launches == n_plain
+    assert same_bits(unet.forward(x2, s2, control=None), plain) and unet.last_launches == n_plain
+    assert not same_bits(unet.forward(x2, s2, control=cnet.control(1.0)), plain) and unet.last_launches == n_plain + 1      # ONE launch more
     pair, n_pair = unet.forward_pair(xd, sd_).clone(), unet.last_launches
-    assert same_bits(unet.forward_pair_control(xd, sd_, cnet.control(0.0)), pair) and unet.last_launches == n_pair
-    assert same_bits(unet.forward_pair_control(xd, sd_, None), pair) and unet.last_launches == n_pair
-    assert not same_bits(unet.forward_pair_control(xd, sd_, cnet.control(1.0)), pair) and unet.last_launches == n_pair + 1
+    assert same_bits(unet.forward_pair(xd, sd_, control=cnet.control(0.0)), pair) and unet.last_launches == n_pair
+    assert same_bits(unet.forward_pair(xd, sd_, control=None), pair) and unet.last_launches == n_pair
+    assert not same_bits(unet.forward_pair(xd, sd_, control=cnet.control(1.0)), pair) and unet.last_launches == n_pair + 1
 
 
 def test_all_zero_zero_convolutions_are_the_plain_forwards_bits(unet):
@@ -121,7 +121,7 @@ def test_all_zero_zero_convolutions_are_the_plain_forwards_bits(unet):
     assert all(float(r.abs().max()) == 0.0 for r in res)
     unet.set_context(ctx)
     plain = unet.forward(x.to(DEV), s.to(DEV)).clone()
-    assert same_bits(unet.forward_control(x.to(DEV), s.to(DEV), cn.control(1.0)), plain)
+    assert same_bits(unet.forward(x.to(DEV), s.to(DEV), control=cn.control(1.0)), plain)
 
 
 @pytest.mark.parametrize("b,h,w", CASES)
@@ -134,12 +134,12 @@ def test_pair_forms_equal_the_plain_forms_on_duplicated_inputs(unet, cnet, b, h,
     cnet.forward(x2, s2)
     full = cnet.residuals()
     unet.set_context(ctx)
-    out_full = unet.forward_control(x2, s2, cnet.control(1.0)).clone()
+    out_full = unet.forward(x2, s2, control=cnet.control(1.0)).clone()
     cnet.forward_pair(xd, sd_)
     pair = cnet.residuals()
     assert all(p.shape == f.shape and rel_l2(p.float().cpu(), f.float().cpu()) < 1e-3 for p, f in zip(pair, full))
     assert not torch.equal(pair[-1][:b], pair[-1][b:])             # the cond half saw the other context
-    unet_out = unet.forward_pair_control(xd, sd_, cnet.control(1.0))
+    unet_out = unet.forward_pair(xd, sd_, control=cnet.control(1.0))
     assert rel_l2(unet_out.cpu(), out_full.cpu()) < 1e-3
 
 
@@ -154,7 +154,7 @@ def test_a_wrong_count_shape_or_batch_is_refused_and_writes_nothing(unet, cnet):
 
     def status(ctl, xx=xd):
         with pytest.raises(LDError) as e:
-            unet.forward_control(xx, sd_, ctl, out=out)
+            unet.forward(xx, sd_, control=ctl, out=out)
         assert bool((out == 7.0).all())
         return e.value.status
 
@@ -178,8 +178,8 @@ def test_a_wrong_count_shape_or_batch_is_refused_and_writes_nothing(unet, cnet):
         cnet.forward(torch.zeros(2, 4, 8, 8, device=DEV), sd_)
     assert e.value.status == ERR_SHAPE
     from lightdiffusion_amd._lib import lib
-    assert lib().ld_controlnet_forward(unet._h, xd.data_ptr(), sd_.data_ptr(), 2, 8, 24, None) == ERR_ARG
-    assert lib().ld_unet_forward(cnet._h, xd.data_ptr(), sd_.data_ptr(), out.data_ptr(), 2, 8, 24, 0, None) == ERR_ARG
+    assert lib().ld_controlnet_forward(unet._h, xd.data_ptr(), sd_.data_ptr(), 2, 8, 24, 0, None) == ERR_ARG
+    assert lib().ld_unet_forward(cnet._h, xd.data_ptr(), sd_.data_ptr(), out.data_ptr(), 2, 8, 24, 0, None, None) == ERR_ARG
 
 
 def test_loaded_state_dict_reads_back(cnet):

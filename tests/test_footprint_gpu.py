@@ -393,7 +393,7 @@ def _rand(shape, seed):
 def test_unet_workspace_history(L, make):
     """Batch 4 at 16x16 with 154 context tokens on adverse inputs, then batch 1 at 7x9 with 77 tokens (63 self-attention keys, context rows
     77 .. Tp, ragged GroupNorm chunks, the counters of the row-resident convolution) and the CFG pair on it."""
-    from lightdiffusion_amd._lib import F32 as LD_F32, OK
+    from lightdiffusion_amd._lib import F32 as LD_F32, FWD_PAIR, OK
     fam = FAMILIES["unet"]
     handles = [make(fam, loaded=True) for _ in range(2)]
     for hd in handles:
@@ -404,14 +404,14 @@ def test_unet_workspace_history(L, make):
     def large(hd):
         out = torch.empty(4, 4, 16, 16, device=DEV)
         assert L.ld_unet_set_context(hd, cl.data_ptr(), LD_F32, 4, 154, stream()) == OK
-        assert L.ld_unet_forward(hd, xl.data_ptr(), sl.data_ptr(), out.data_ptr(), 4, 16, 16, 0, stream()) == OK
+        assert L.ld_unet_forward(hd, xl.data_ptr(), sl.data_ptr(), out.data_ptr(), 4, 16, 16, 0, None, stream()) == OK
 
     def small(hd):
         o1, o2 = torch.full((1, 4, 7, 9), float("nan"), device=DEV), torch.full((2, 4, 7, 9), float("nan"), device=DEV)
         assert L.ld_unet_set_context(hd, c1.data_ptr(), LD_F32, 1, 77, stream()) == OK
-        assert L.ld_unet_forward(hd, xs.data_ptr(), ss.data_ptr(), o1.data_ptr(), 1, 7, 9, 0, stream()) == OK
+        assert L.ld_unet_forward(hd, xs.data_ptr(), ss.data_ptr(), o1.data_ptr(), 1, 7, 9, 0, None, stream()) == OK
         assert L.ld_unet_set_context(hd, c2.data_ptr(), LD_F32, 2, 77, stream()) == OK
-        assert L.ld_unet_forward_pair(hd, xs.data_ptr(), ss.data_ptr(), o2.data_ptr(), 1, 7, 9, stream()) == OK
+        assert L.ld_unet_forward(hd, xs.data_ptr(), ss.data_ptr(), o2.data_ptr(), 1, 7, 9, FWD_PAIR, None, stream()) == OK
         return o1, o2
     _history("unet", handles, large, small)
 

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from lightdiffusion_amd import weights as W
-from lightdiffusion_amd._lib import ERR_ARG, ERR_SHAPE, ERR_STATE, F32, OK, ESRGANConfig, UNetConfig, VAEConfig, lib
+from lightdiffusion_amd._lib import ERR_ARG, ERR_SHAPE, ERR_STATE, F32, FWD_EPS_ONLY, FWD_PAIR, OK, ESRGANConfig, UNetConfig, VAEConfig, lib
 
 pytestmark = pytest.mark.gpu
 
@@ -83,18 +83,19 @@ class UNet(Family):
 
     def run(self, hd, ins, outs, b, h, w, profile=False):
         if not profile:
-            return lib().ld_unet_forward(hd, *ins, *outs, b, h, w, 0, stream())
+            return lib().ld_unet_forward(hd, *ins, *outs, b, h, w, 0, None, stream())
         ms, fl, self.class_launches = (C.c_double * 6)(), (C.c_double * 6)(), (C.c_int * 6)()
-        return lib().ld_unet_profile(hd, *ins, *outs, b, h, w, stream(), ms, fl, self.class_launches)
+        return lib().ld_unet_profile(hd, *ins, *outs, b, h, w, 0, None, stream(), ms, fl, self.class_launches)
 
     def null_runs(self):
         i, o = self.buffers(2, 8, 8)
         x, s, y = (t.data_ptr() for t in i + o)
         ms, fl, nl = (C.c_double * 6)(), (C.c_double * 6)(), (C.c_int * 6)()
         L = lib()
-        return {"forward": L.ld_unet_forward(None, x, s, y, 2, 8, 8, 0, stream()), "forward_pair": L.ld_unet_forward_pair(None, x, s, y, 1, 8, 8, stream()),
-                "profile": L.ld_unet_profile(None, x, s, y, 2, 8, 8, stream(), ms, fl, nl),
-                "profile_pair": L.ld_unet_profile_pair(None, x, s, y, 1, 8, 8, stream(), ms, fl, nl),
+        return {"forward": L.ld_unet_forward(None, x, s, y, 2, 8, 8, 0, None, stream()),
+                "forward_pair": L.ld_unet_forward(None, x, s, y, 1, 8, 8, FWD_PAIR, None, stream()),
+                "profile": L.ld_unet_profile(None, x, s, y, 2, 8, 8, 0, None, stream(), ms, fl, nl),
+                "profile_pair": L.ld_unet_profile(None, x, s, y, 1, 8, 8, FWD_PAIR, None, stream(), ms, fl, nl),
                 "set_context": L.ld_unet_set_context(None, x, F32, 1, 77, stream())}
 
 
@@ -311,6 +312,38 @@ def test_profile_fills_the_launch_table(fam, make):
     assert sum(float(r[5]) for r in rows) == flops > 0
     assert fam.fn("profile_launches")(hd, buf, 8) == ERR_ARG    # a buffer too small for the table
     assert fam.fn("profile_launches")(hd, None, 0) == ERR_ARG
+
+
+def test_forward_flags_are_checked_before_anything_is_launched():
+    """The flags of ld_unet_forward / ld_unet_profile and ld_controlnet_forward / ld_controlnet_profile on valid handles with their context
+    set: a bit that is no flag, eps of a pair and eps of a control branch are LD_ERR_ARG, a pair of no samples is LD_ERR_SHAPE — on the host:
+    nothing is launched (last_launches stays) and nothing is written."""
+    from lightdiffusion_amd.controlnet import synthetic_controlnet
+    from lightdiffusion_amd.unet import synthetic_unet
+    cfg = W.tiny_unet_config()
+    unet = synthetic_unet(cfg, max_batch=2, max_hw=(8, 8), max_tokens=77)
+    cnet = synthetic_controlnet(cfg, max_batch=2, max_hw=(8, 8), max_tokens=77)
+    ctx = torch.randn(2, 77, cfg["context_dim"], generator=torch.Generator().manual_seed(3))
+    unet.set_context(ctx)
+    cnet.set_context(ctx)
+    (x, s), (out,) = FAMILIES["unet"].buffers(2, 8, 8)
+    ms, fl, nl = (C.c_double * 6)(), (C.c_double * 6)(), (C.c_int * 6)()
+    L = lib()
+    forms = {
+        "ld_unet_forward": lambda n, flags: L.ld_unet_forward(unet._h, ptr(x), ptr(s), ptr(out), n, 8, 8, flags, None, stream()),
+        "ld_unet_profile": lambda n, flags: L.ld_unet_profile(unet._h, ptr(x), ptr(s), ptr(out), n, 8, 8, flags, None, stream(), ms, fl, nl),
+        "ld_controlnet_forward": lambda n, flags: L.ld_controlnet_forward(cnet._h, ptr(x), ptr(s), n, 8, 8, flags, stream()),
+        "ld_controlnet_profile": lambda n, flags: L.ld_controlnet_profile(cnet._h, ptr(x), ptr(s), n, 8, 8, flags, stream()),
+    }
+    before = (unet.last_launches, cnet.last_launches)
+    for name, call in forms.items():
+        assert call(2, 4) == ERR_ARG, name
+        assert call(1, FWD_PAIR | FWD_EPS_ONLY) == ERR_ARG, name
+        assert call(0, FWD_PAIR) == ERR_SHAPE, name
+        if "controlnet" in name:
+            assert call(2, FWD_EPS_ONLY) == ERR_ARG, name
+    assert (unet.last_launches, cnet.last_launches) == before
+    assert untouched([out])
 
 
 def test_vae_encode_needs_the_encoder(make):

@@ -49,7 +49,7 @@ def test_tiny_unet_batch4_matches_batch2(tiny_unet):
 
 
 def test_forward_pair_equals_forward_on_duplicated_inputs(tiny_unet):
-    """`ld_unet_forward_pair` (the CFG pair of a sampler step: the layers in front of the first cross-attention evaluated once for both halves)
+    """`ld_unet_forward` with `LD_FWD_PAIR` (the CFG pair of a sampler step: the layers in front of the first cross-attention evaluated once for both halves)
     against `ld_unet_forward` on cat([x, x]) — the same rows up to the rounding of tile / split choices that follow the row count — for the tiny
     net at B = 1 / 2 (two contexts per sample: the halves must differ) and, below, for the SD1.5 net against the reference golden."""
     g = load_golden("unet_tiny_16x16")

@@ -1,5 +1,5 @@
 """Per-shape launch table of the UNet forward (ld_unet_profile + LD_PROFILE_DUMP) with whatever library LD_MI355X_LIB names (no debug hooks needed):
-for same-box comparisons of two builds.  Usage: [LD_MI355X_LIB=...] python tools/launch_table.py [batch=1] [pair=0]"""
+for same-box comparisons of two builds (both with the flag form of ld_unet_forward / ld_unet_profile: the wrapper calls no other).  Usage: [LD_MI355X_LIB=...] python tools/launch_table.py [batch=1] [pair=0]"""
 import collections, os, re, sys, tempfile
 import torch
 sys.path.insert(0, '.')

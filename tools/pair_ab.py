@@ -1,4 +1,4 @@
-"""Same-process A/B: the plain forward on cat([x, x]) (N = 2B) against the CFG-pair forward (`ld_unet_forward_pair`: the layers in front of the first
+"""Same-process A/B: the plain forward on cat([x, x]) (N = 2B) against the CFG-pair forward (`ld_unet_forward` with `LD_FWD_PAIR`: the layers in front of the first
 cross-attention evaluated once), both graph-replayed.  Usage: python3 tools/pair_ab.py [B:hw ...]   (default 8:64 4:128 2:64 1:64)"""
 import statistics, sys, torch
 sys.path.insert(0, '.')
